@@ -26,6 +26,11 @@ names (strong scaling, speed-up against the same job on rank 0 alone measured in
     batchsolve_sharded.
 Inputs are resident in HBM when the timed region starts; all timing is bracketed by a barrier and a
 device synchronize on both sides; kernel durations come from HIP events on the library's stream.
+
+A plain run sets up, warms up, times the K steps of Phase A and prints the line with the primary metric.
+Everything else -- Phase B, the reference-layout leg, the fixed jobs above, the extras, the scaling model and the
+CPU baselines -- runs with `--full` only.  `--dump-outputs DIR` writes what the last timed step left in the rule
+(H(k), eigenvalues and the k-points of a fixed, seeded sample of the nodes) as float64 `DIR/<name>.npy`.
 """
 import argparse
 import ctypes
@@ -41,7 +46,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 measured copy)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec (6.29 measured copy)
 F64_PEAK_TFLOPS = 78.6  # f64 vector = f64 matrix peak (AMD spec, not in the local guide)
 
 
@@ -68,7 +73,28 @@ def parse_args():
     ap.add_argument("--no-scaling-model", action="store_true", help="skip the 8-GPU scaling model from one-GPU shard timings (N = 1; ~40 s)")
     ap.add_argument("--no-c5-shard", action="store_true", help="skip config 5 as one sharded solve (N > 1 only; ~11 s for its N = 1 leg)")
     ap.add_argument("--c5-abstol", type=float, default=1e-3, help="config 5 (16-band IAI) tolerance; SURVEY 8d: 1e-3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the primary metric, every other leg of the line: Phase B, the reference layout, the fixed jobs, "
+                         "the extras, the scaling model, the CPU baselines (the --no-* switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write H(k), eigenvalues and k-points of a fixed sample of the nodes after the last timed step, "
+                         "as float64 DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_NODES = 1 << 17  # nodes in the --dump-outputs sample: 24 doubles each, 25 MB in all
+
+
+def dump_outputs(path, rule):
+    """What a caller of the timed path gets back after its last step -- the rule's export: H(k) as full matrices, the
+    eigenvalues and the node coordinates -- at a fixed, seeded sample of the nodes (the whole 150^3 export is 0.6 GB)."""
+    os.makedirs(path, exist_ok=True)
+    ex = rule.export(x=True, w=False, H=True, eig=True)
+    nk = len(ex["eig"])
+    pick = np.arange(nk) if nk <= DUMP_NODES else np.sort(np.random.default_rng(0).choice(nk, DUMP_NODES, replace=False))
+    H = ex["H"][pick]
+    for name, v in (("k", ex["x"][pick]), ("H_re", H.real), ("H_im", H.imag), ("eig", ex["eig"][pick])):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def spawn_ranks(a):
@@ -352,6 +378,53 @@ def rank_main(a):
     eval_ms, eval_n = ctx.prof_read(L.K_EVAL)
     ctx.prof_enable(False)
     step_ms = np.diff([t0] + block_ms) * 1e3 if block_ms else np.array([tA * 1e3 / a.steps])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rule)
+
+    def primary(tA):
+        """The primary metric's part of the line (tA: the slowest rank's timed region); a plain run prints it alone."""
+        eval_avg_s = (eval_ms / max(eval_n, 1)) * 1e-3
+        achieved = nk * bpk / eval_avg_s / 1e9 if eval_avg_s > 0 else 0.0
+        return {
+            "metric": "k-point evals/sec (H(k)+eig)", "value": world * nk * P * a.steps / tA, "unit": "k-points/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * tA / a.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic PTR grid over the reference's svo_hr.dat example coefficients (device resident)",
+            "config": {"workload": f"BASELINE configs[3] per-GPU share: SVO 3-band Wannier H(k)+eig on a {npt}^3 PTR grid (FBZ) "
+                                   f"+ fused DOS sweep of {a.omegas_per_rank} omega per GPU (256 at 8 GPUs), eta={a.eta}; "
+                                   f"one step = {P} passes over the grid",
+                       "npt": npt, "nk_per_gpu": nk, "passes_per_step": P, "n_bands": 3, "n_R": 1331,
+                       "omegas_per_gpu": a.omegas_per_rank,
+                       "rule_layout": ("hermitian-compact: upper triangle of H(k) + eigenvalues, 96 B per k-point (the host mirror's default "
+                                       "for Hermitian series; exports and rule sums bit-identical to the full layout)") if compact else
+                                      "reference: full H(k) + eigenvalues, 168 B per k-point",
+                       "parallelism": f"omega-sharded x{world}, coefficient+rule replicas"},
+            "n_ranks_seen": n_ranks_seen, "backend": ("rccl(nccl)" if backend == "nccl" else backend) if distributed else None,
+            "rehearsal_ranks_share_one_gpu": bool(rehearsal),
+            "timed_region_seconds": tA, "ms_per_pass": 1e3 * tA / (a.steps * P),
+            "ms_per_step_min_median_max": [float(step_ms.min()), float(np.median(step_ms)), float(step_ms.max())],
+            "rule_buffer": {"base_address": hex(base_addr), "bytes": rule_bytes, "base_mod_2MiB": base_addr % (2 << 20),
+                            "base_mod_4KiB": base_addr % 4096},
+            # HIP events of the timed region itself (Fourier-eval kernel) and of the warm-up (contractions)
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(npt, compact),
+                         "kernel": "eval_grid_kernel<3> (Fourier-eval + fused eig)",
+                         "algorithmic_bytes_per_kpoint": bpk,
+                         "avg_launch_ms": eval_ms / max(eval_n, 1), "launches": eval_n,
+                         "contract_avg_ms": con_ms / max(con_n, 1)},
+        }
+
+    if not a.full:
+        if distributed:
+            tmax = torch.tensor([tA], dtype=torch.float64, device=cdev)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            tA = float(tmax.cpu()[0])
+        if rank == 0:
+            print(json.dumps(primary(tA)), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the same passes with H(k) in the reference's full SMatrix layout (168 B per k-point): the numbers of rounds 1-2
     ref_layout = None
@@ -579,31 +652,10 @@ def rank_main(a):
     tA, tB, tBe = (float(v) for v in times.cpu())
 
     if rank == 0:
-        kps = world * nk * P * a.steps / tA
-        eval_avg_s = (eval_ms / max(eval_n, 1)) * 1e-3
-        achieved = nk * bpk / eval_avg_s / 1e9 if eval_avg_s > 0 else 0.0
         build_ms = 1e3 * tA / (a.steps * P)
-        out = {
-            "metric": "k-point evals/sec (H(k)+eig)", "value": kps, "unit": "k-points/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * tA / a.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic PTR grid over the reference's svo_hr.dat example coefficients (device resident)",
-            "config": {"workload": f"BASELINE configs[3] per-GPU share: SVO 3-band Wannier H(k)+eig on a {npt}^3 PTR grid (FBZ) "
-                                   f"+ fused DOS sweep of {a.omegas_per_rank} omega per GPU (256 at 8 GPUs), eta={a.eta}; "
-                                   f"one step = {P} passes over the grid",
-                       "npt": npt, "nk_per_gpu": nk, "passes_per_step": P, "n_bands": 3, "n_R": 1331,
-                       "omegas_per_gpu": a.omegas_per_rank,
-                       "rule_layout": ("hermitian-compact: upper triangle of H(k) + eigenvalues, 96 B per k-point (the host mirror's default "
-                                       "for Hermitian series; exports and rule sums bit-identical to the full layout)") if compact else
-                                      "reference: full H(k) + eigenvalues, 168 B per k-point",
-                       "parallelism": f"omega-sharded x{world}, coefficient+rule replicas"},
-            "n_ranks_seen": n_ranks_seen, "backend": ("rccl(nccl)" if backend == "nccl" else backend) if distributed else None,
-            "rehearsal_ranks_share_one_gpu": bool(rehearsal),
+        out = primary(tA)
+        out.update({
             "value_reference_layout": ref_layout["value"] if ref_layout else None,  # the same metric with the full 168-B layout of rounds 1-2
-            "timed_region_seconds": tA, "ms_per_pass": build_ms,
-            "ms_per_step_min_median_max": [float(step_ms.min()), float(np.median(step_ms)), float(step_ms.max())],
-            "rule_buffer": {"base_address": hex(base_addr), "bytes": rule_bytes, "base_mod_2MiB": base_addr % (2 << 20),
-                            "base_mod_4KiB": base_addr % 4096},
             "dos_points_per_sec": world * len(mine) / tB,
             "dos_points_per_sec_eigcached": world * len(mine) / tBe,
             "ms_per_sweep": 1e3 * tB,
@@ -620,8 +672,8 @@ def rank_main(a):
             "speedup_vs_n1_fine_grid": (big_job or {}).get("k_sharded", {}).get("speedup_vs_n1") if isinstance(big_job, dict) else None,
             "iai_sweep_432_omega": iai_job,
             "iai_config5_sharded": c5_job,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(npt, compact),
+        })
+        out["roofline"].update({
                          "compute_floor_note": ("the same kernel storing eigenvalues only (no H planes) takes "
                                                 f"{ref_layout['eigenvalues_only_avg_launch_ms']:.4f} ms: with the compact layout the H stores are almost "
                                                 "hidden behind the Fourier sums and the eigensolves, the kernel sits between its f64-VALU floor and its HBM-write floor")
@@ -641,14 +693,9 @@ def rank_main(a):
                                                        "launch writes the 96 B a Hermitian matrix + its eigenvalues need, so `achieved` and `frac` "
                                                        "use 96 B (168 B x this rate would exceed the HBM peak and is not claimed); the reference "
                                                        "layout's own time and fraction are in `reference_layout`") if compact else None,
-                         "kernel": "eval_grid_kernel<3> (Fourier-eval + fused eig)",
-                         "algorithmic_bytes_per_kpoint": bpk,
-                         "avg_launch_ms": eval_ms / max(eval_n, 1), "launches": eval_n,
-                         "contract_avg_ms": con_ms / max(con_n, 1),
                          "reduce_avg_ms": red_ms / max(red_n, 1),
                          # Hermitian rule: the scan reads the upper triangle only, n^2 doubles per k-point
-                         "reduce_read_GBs": nk * (8 * n * n) / ((red_ms / max(red_n, 1)) * 1e-3) / 1e9 if red_n else None},
-        }
+                         "reduce_read_GBs": nk * (8 * n * n) / ((red_ms / max(red_n, 1)) * 1e-3) / 1e9 if red_n else None})
         if world > 1:
             # the measured speed-ups of this run beside the one-GPU model's predictions for 8 ranks (profiles/scaling_model_latest.json,
             # written by tools/save_scaling_model.py from an N = 1 line): the first real multi-GPU run reads as a check of the model

@@ -1,4 +1,4 @@
-"""profiles/scaling_model_latest.json from an N = 1 bench line (its `scaling_model` block): python tools/save_scaling_model.py bench.json"""
+"""profiles/scaling_model_latest.json from an N = 1 `bench.py --full` line (its `scaling_model` block): python tools/save_scaling_model.py bench.json"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 line = [l for l in open(sys.argv[1]).read().strip().splitlines() if l.startswith("{")][-1]
