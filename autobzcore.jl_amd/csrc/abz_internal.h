@@ -71,6 +71,7 @@ enum Switch {
     SW_EIG_SPLIT,        // ABZ_EIG_SPLIT       5...16-band eigenvalue builds: tridiagonal eigenvalues in a kernel of their own
     SW_IAI_LANES,        // ABZ_IAI_LANES       lanes (host thread + stream each) an IAI sweep is split over
     SW_IAI_LANE_MIN,     // ABZ_IAI_LANE_MIN    solves a lane needs before a sweep is split further
+    SW_CHAIN_FUSED,      // ABZ_CHAIN_FUSED     3-D full grids: variables 3 and 2 contracted in one launch (0: one launch per level)
     SW_COUNT
 };
 int abz_switch(Switch s);  // the switch's integer value from the environment, or its default
@@ -292,6 +293,11 @@ constexpr int ABZ_CONTRACT_GRID_MAXM = 16;
 int launch_contract_grid(abz_ctx* ctx, const double2* src, int64_t src_slot_elems, int64_t nparents, const double2* tab,
                          double2* out, int64_t L, int M, int first, int npt, bool deriv, int gbeg, int gcnt,
                          const double2* phs_table = nullptr);  // phs_table [npt][M]: scalar-phase kernel (no derivative)
+// 3-D full grids: variables 3 and 2 in one launch (the sums of the two launch_contract_grid levels, bit for bit).
+// src: the coefficient set [M3][M2][L]; phs3, phs2: the levels' phase tables [npt][M]; out[(k3 - gbeg) * npt + k2][l]
+bool contract_chain_fits(int64_t L, int M3, int M2, int npt, int gcnt);
+int launch_contract_chain(abz_ctx* ctx, const double2* src, const double2* phs3, const double2* phs2, double2* out,
+                          int64_t L, int M3, int M2, int npt, int gbeg, int gcnt);
 
 struct EvalSpec {
     int n;              // bands

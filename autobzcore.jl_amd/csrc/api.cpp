@@ -87,6 +87,7 @@ const SwitchDef g_switches[SW_COUNT] = {
     {"ABZ_EIG_SPLIT", 1, "0: eigenvalues of 5...16-band rules by bisection inside the grid kernel instead of the per-lane QR kernel"},
     {"ABZ_IAI_LANES", 4, "lanes (host thread + stream each) a sweep of independent IAI solves is split over; 1: off"},
     {"ABZ_IAI_LANE_MIN", 16, "solves per lane below which a sweep is not split further"},
+    {"ABZ_CHAIN_FUSED", 1, "0: 3-D full-grid chains contract variables 3 and 2 in two launches instead of contract_chain_kernel"},
 };
 }  // namespace
 
@@ -515,6 +516,20 @@ static int build_chain(abz_series* s, const Plan& p, const PlanDev& pd, const do
     }
     const double2* src = packed ? s->coef_pk.as<double2>() : s->coef;
     int64_t src_elems = elems_of(d);
+    // 3-D full grids down to level 1 without a derivative factor in the contractions: variables 3 and 2 in one
+    // launch (contract_chain_kernel), the very sums of the two scalar-phase launches of the loop below
+    if (d == 3 && last_level == 1 && p.full && deriv_dim != 2 && deriv_dim != 3 && pd.phg[2].p && pd.phg[1].p &&
+        contract_chain_fits(elems_of(1), s->dims[2], s->dims[1], p.npt, p.outer_n) && abz_switch(SW_CHAIN_FUSED)) {
+        const int64_t Lrow = elems_of(1);
+        DevBuf& ob = last_out ? *last_out : s->pool[1];
+        int rc = ob.reserve(sizeof(double2) * (size_t)std::max<int64_t>(p.nitems[1] * Lrow, 1));
+        if (rc) return rc;
+        rc = launch_contract_chain(ctx, src, pd.phg[2].as<double2>(), pd.phg[1].as<double2>(), ob.as<double2>(), Lrow,
+                                   s->dims[2], s->dims[1], p.npt, p.outer0, p.outer_n);
+        if (rc) return rc;
+        *level1 = ob.as<double2>();
+        return ABZ_OK;
+    }
     for (int L = d - 1; L >= last_level; --L) {  // last_level = 2: stop at the level-2 sets (fused last contraction)
         // contract variable L+1 (0-based dim index L)
         const int64_t B = p.nitems[L];

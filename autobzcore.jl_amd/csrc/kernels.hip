@@ -291,6 +291,126 @@ int launch_contract_grid(abz_ctx* ctx, const double2* src, int64_t src_slot_elem
     return ABZ_OK;
 }
 
+// Variables 3 and 2 of a 3-D full grid in one launch: the level-1 sets
+//   out[k3 * npt + k2][l] = sum_m2 phs2[k2][m2] S[m2][l],   S[m2][l] = sum_m3 phs3[gbeg + k3][m3] src[m3][m2][l]
+// (k3 relative to the slab), with the very fma sequences of contract_grid_s_kernel<M3> then <M2>: the sums are
+// bit-identical to the two launches.  A workgroup owns (64 columns l, one k3, a block of k2): it contracts
+// variable 3 for its columns and all M2 into LDS (the level-2 values never leave the CU), then every wave keeps
+// its lane's column of S in registers and sweeps a quarter of the k2 block with scalar phases.  The variable-3
+// work is repeated once per k2 block; its input (the whole coefficient set) is shared by every workgroup and
+// served by L2.  Level-1 lines go out as 16-B write-through (sc1) buffer stores through a per-plane descriptor
+// (32-bit offsets): 0.2-0.6 ms per bench step faster than the same stores without sc1.  The eval kernel
+// reads them after the kernel boundary.
+constexpr int CHAIN_COLS = 64;
+constexpr int CHAIN_THREADS = 256;
+
+template <int M2>
+__global__ __launch_bounds__(CHAIN_THREADS) void contract_chain_kernel(const double2* __restrict__ src,
+                                                                       const double2* __restrict__ phs3,
+                                                                       const double2* __restrict__ phs2,
+                                                                       double2* __restrict__ out, int L, int M3,
+                                                                       int npt, int gbeg, int kchunk) {
+    __shared__ double2 s2[M2 * CHAIN_COLS];
+    constexpr int NA = (M2 * CHAIN_COLS + CHAIN_THREADS - 1) / CHAIN_THREADS;  // level-2 values per thread
+    const int c0 = blockIdx.x * CHAIN_COLS;
+    const int k3 = blockIdx.y;
+    const int t = threadIdx.x;
+    const int64_t L2 = (int64_t)M2 * L;  // numbers per level-2 set (m2-major rows of L)
+    {
+        cptr_t p3 = as_const(phs3 + (int64_t)(gbeg + k3) * M3);
+        const double2* sp[NA];
+        bool ok[NA];
+        double ar[NA], ai[NA];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int i = t + j * CHAIN_THREADS, m2 = i / CHAIN_COLS, col = c0 + i % CHAIN_COLS;
+            ok[j] = i < M2 * CHAIN_COLS && col < L;
+            sp[j] = ok[j] ? src + (int64_t)m2 * L + col : src;  // idle slots load column 0: no branch around the loads
+            ar[j] = 0.0;
+            ai[j] = 0.0;
+        }
+#pragma unroll 4
+        for (int m3 = 0; m3 < M3; ++m3) {
+            const double px = p3[m3].x, py = p3[m3].y;  // scalar loads
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const double2 c = sp[j][m3 * L2];
+                ar[j] = fma(c.x, px, ar[j]);
+                ar[j] = fma(-c.y, py, ar[j]);
+                ai[j] = fma(c.x, py, ai[j]);
+                ai[j] = fma(c.y, px, ai[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NA; ++j)
+            if (ok[j]) s2[t + j * CHAIN_THREADS] = make_double2(ar[j], ai[j]);
+    }
+    __syncthreads();
+    const int lane = t % 64;
+    const int col = c0 + lane;
+    if (col >= L) return;
+    const int w = __builtin_amdgcn_readfirstlane(t / 64);  // wave-uniform: scalar phase loads below
+    double2 c[M2];
+#pragma unroll
+    for (int m = 0; m < M2; ++m) c[m] = s2[m * CHAIN_COLS + lane];
+    // this k3's plane of level-1 sets: npt * L numbers, < 2 GB (launch_contract_chain)
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        out + (int64_t)k3 * npt * L, 0, (int)(sizeof(double2) * (size_t)npt * L), 0x00020000);
+    const int kb1 = min(npt, (int)(blockIdx.z + 1) * kchunk);
+    for (int k2 = blockIdx.z * kchunk + w; k2 < kb1; k2 += CHAIN_THREADS / 64) {
+        cptr_t p = as_const(phs2 + (int64_t)k2 * M2);
+        double ar = 0.0, ai = 0.0;
+#pragma unroll
+        for (int m = 0; m < M2; ++m) {
+            const double px = p[m].x, py = p[m].y;  // scalar loads
+            ar = fma(c[m].x, px, ar);
+            ar = fma(-c[m].y, py, ar);
+            ai = fma(c[m].x, py, ai);
+            ai = fma(c[m].y, px, ai);
+        }
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const double2 v = make_double2(ar, ai);
+        u32x4 bits;
+        __builtin_memcpy(&bits, &v, sizeof(bits));
+        __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, (int)sizeof(double2) * (k2 * L + col), 0, 16);  // aux 16: sc1
+    }
+}
+
+bool contract_chain_fits(int64_t L, int M3, int M2, int npt, int gcnt) {
+    return L > 0 && M3 >= 1 && M3 <= ABZ_CONTRACT_GRID_MAXM && M2 >= 1 && M2 <= ABZ_CONTRACT_GRID_MAXM && gcnt > 0 &&
+           gcnt <= 65535 && (int64_t)sizeof(double2) * npt * L < ((int64_t)1 << 31) &&
+           (int64_t)M3 * M2 * L < ((int64_t)1 << 31);
+}
+
+int launch_contract_chain(abz_ctx* ctx, const double2* src, const double2* phs3, const double2* phs2, double2* out,
+                          int64_t L, int M3, int M2, int npt, int gbeg, int gcnt) {
+    if (!contract_chain_fits(L, M3, M2, npt, gcnt)) {
+        set_error("contract_chain: L = %lld, M = %d x %d, npt = %d", (long long)L, M3, M2, npt);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    ProfScope ps(ctx, ABZ_K_CONTRACT);
+    const int64_t gx = cdiv(L, CHAIN_COLS);
+    // k2 blocks: about two workgroups per CU.  Every block repeats the variable-3 work (and reads the whole coefficient
+    // set from L2); fewer, longer blocks leave each wave a longer serial sweep.  Measured at 150^3 (SVO): targets 256,
+    // 512, 1024, 2048 (300, 600, 1050, 2100 workgroups) -> 10.67, 10.41, 10.64, 11.02 ms per bench step.
+    const int64_t target_blocks = 512;
+    int64_t nz = std::max<int64_t>(1, std::min<int64_t>(cdiv(npt, 8), cdiv(target_blocks, gx * gcnt)));
+    const int kchunk = (int)cdiv(npt, nz);
+    nz = cdiv(npt, kchunk);
+#define CC(MM)                                                                                                         \
+    case MM:                                                                                                           \
+        hipLaunchKernelGGL(contract_chain_kernel<MM>, dim3((unsigned)gx, (unsigned)gcnt, (unsigned)nz),                \
+                           dim3(CHAIN_THREADS), 0, ctx->stream, src, phs3, phs2, out, (int)L, M3, npt, gbeg, kchunk);     \
+        break;
+    switch (M2) {
+        CC(1) CC(2) CC(3) CC(4) CC(5) CC(6) CC(7) CC(8) CC(9) CC(10) CC(11) CC(12) CC(13) CC(14) CC(15) CC(16)
+        default: set_error("contract_chain: M = %d", M2); return ABZ_ERR_UNSUPPORTED;
+    }
+#undef CC
+    ABZ_HIP(hipGetLastError());
+    return ABZ_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // innermost evaluation
 // ------------------------------------------------------------------------------------------
