@@ -1,5 +1,6 @@
 // Internal declarations shared by the HIP translation units of libabzhip.so (gfx950 only).
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -11,6 +12,7 @@
 #include "../../include/abzhip.h"
 
 namespace abz {
+struct ProfScope;
 
 void set_error(const char* fmt, ...);
 int catch_status() noexcept;  // status + abz_last_error message of the exception in flight
@@ -157,6 +159,7 @@ struct abz_ctx {
     hipStream_t stream = nullptr;
     bool owns_stream = true;  // false: borrowed from the caller (abz_ctx_create_on_stream)
     unsigned prof = 0;  // bit k set: record HIP events around launches of kernel id k
+    abz::ProfScope* prof_scope = nullptr;  // innermost active ProfScope: launch() binds its events
     abz::ProfSlot prof_slots[ABZ_K_COUNT];
     std::vector<hipEvent_t> event_pool;
     abz::DevBuf scratch[8];  // phases, partials, staging...
@@ -254,15 +257,34 @@ struct abz_rule {
 
 namespace abz {
 
-// RAII-ish profiling bracket around launches of one logical kernel.
+// RAII-ish profiling bracket around launches of one logical kernel.  Its two events are bound to the kernel dispatches
+// made by launch() inside it, not recorded on the stream: an event record is a packet of its own, with a system-scope
+// fence unless disabled, and those packets cost 0.5 ms per 128 bench passes.  Memsets and copies
+// inside a scope are not timed; a scope that launches nothing records nothing; of nested active scopes, the innermost
+// takes the launches.
 struct ProfScope {
     abz_ctx* ctx;
     int id;
     hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool started = false;  // e0 is bound to a launch
+    ProfScope* outer = nullptr;
     ProfScope(abz_ctx* c, int kernel_id);
     ~ProfScope();
 };
 int prof_collect(abz_ctx* ctx);
+
+// A kernel launch on the context's stream.  Inside an active ProfScope the scope's start event is bound to its first
+// dispatch and its stop event to the last one (hipExtLaunchKernelGGL): no packets besides the kernels themselves.
+template <class F, class... Args>
+inline void launch(abz_ctx* ctx, F kernel, dim3 grid, dim3 block, unsigned lds, Args... args) {
+    ProfScope* ps = ctx->prof_scope;
+    if (ps) {
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, ps->started ? nullptr : ps->e0, ps->e1, 0, args...);
+        ps->started = true;
+    } else {
+        hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
+    }
+}
 
 // ---- launchers (kernels.hip) ------------------------------------------------------------
 // phase table tab[i] = (cos, sin)(2 pi i / npt), computed on the host in long double

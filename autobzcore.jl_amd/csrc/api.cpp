@@ -317,19 +317,26 @@ ProfScope::ProfScope(abz_ctx* c, int kernel_id) : ctx(c), id(kernel_id) {
         if (!ctx->event_pool.empty()) {
             e = ctx->event_pool.back();
             ctx->event_pool.pop_back();
-        } else if (hipEventCreate(&e) != hipSuccess) {
+        } else if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) {
             e = nullptr;
         }
         return e;
     };
     e0 = get();
     e1 = get();
-    if (e0) (void)hipEventRecord(e0, ctx->stream);
+    if (!e0 || !e1) return;
+    outer = ctx->prof_scope;
+    ctx->prof_scope = this;
 }
 
 ProfScope::~ProfScope() {
-    if (!(ctx->prof & (1u << id)) || !e0 || !e1) return;
-    (void)hipEventRecord(e1, ctx->stream);
+    if (!(ctx->prof & (1u << id))) return;
+    if (e0 && e1) ctx->prof_scope = outer;
+    if (!e0 || !e1 || !started) {  // nothing launched (or no events): nothing to time
+        if (e0) ctx->event_pool.push_back(e0);
+        if (e1) ctx->event_pool.push_back(e1);
+        return;
+    }
     ctx->prof_slots[id].pending.emplace_back(e0, e1);
 }
 

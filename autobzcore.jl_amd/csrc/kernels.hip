@@ -126,7 +126,7 @@ int launch_phases(abz_ctx* ctx, const PhaseSpec& ps, double2* phs) {
     a.inv_period = 1.0 / ps.period;
     const int64_t total = ps.B * ps.M;
     if (total == 0) return ABZ_OK;
-    hipLaunchKernelGGL(phase_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, ctx->stream, a, phs);
+    launch(ctx, phase_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, a, phs);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -166,7 +166,7 @@ int launch_contract(abz_ctx* ctx, const double2* src, int64_t src_slot_elems, co
         set_error("contract: row length %lld too large", (long long)L);
         return ABZ_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(contract_kernel, dim3((unsigned)B, (unsigned)gy), dim3(bs), 0, ctx->stream, src,
+    launch(ctx, contract_kernel, dim3((unsigned)B, (unsigned)gy), dim3(bs), 0, src,
                        src_slot_elems, parents, per_parent > 0 ? per_parent : 1, phs, out, B, L, M);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -273,8 +273,8 @@ int launch_contract_grid(abz_ctx* ctx, const double2* src, int64_t src_slot_elem
     if (phs_table && !deriv) {
 #define CS(MM)                                                                                                         \
     case MM:                                                                                                           \
-        hipLaunchKernelGGL(contract_grid_s_kernel<MM>, dim3((unsigned)gx, (unsigned)nparents, (unsigned)nsplit), dim3(128), 0, \
-                           ctx->stream, src, src_slot_elems, phs_table, out, L, chunk, gbeg, gcnt);                    \
+        launch(ctx, contract_grid_s_kernel<MM>, dim3((unsigned)gx, (unsigned)nparents, (unsigned)nsplit), dim3(128), 0, \
+               src, src_slot_elems, phs_table, out, L, chunk, gbeg, gcnt);                                             \
         break;
         switch (M) {
             CS(1) CS(2) CS(3) CS(4) CS(5) CS(6) CS(7) CS(8) CS(9) CS(10) CS(11) CS(12) CS(13) CS(14) CS(15) CS(16)
@@ -284,8 +284,8 @@ int launch_contract_grid(abz_ctx* ctx, const double2* src, int64_t src_slot_elem
         ABZ_HIP(hipGetLastError());
         return ABZ_OK;
     }
-    hipLaunchKernelGGL(contract_grid_kernel, dim3((unsigned)gx, (unsigned)nparents, (unsigned)nsplit), dim3(128),
-                       sizeof(double2) * (size_t)chunk * M, ctx->stream, src, src_slot_elems, tab, out, L, M, first, npt,
+    launch(ctx, contract_grid_kernel, dim3((unsigned)gx, (unsigned)nparents, (unsigned)nsplit), dim3(128),
+                       sizeof(double2) * (size_t)chunk * M, src, src_slot_elems, tab, out, L, M, first, npt,
                        chunk, deriv ? 1 : 0, gbeg, gcnt);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -399,8 +399,8 @@ int launch_contract_chain(abz_ctx* ctx, const double2* src, const double2* phs3,
     nz = cdiv(npt, kchunk);
 #define CC(MM)                                                                                                         \
     case MM:                                                                                                           \
-        hipLaunchKernelGGL(contract_chain_kernel<MM>, dim3((unsigned)gx, (unsigned)gcnt, (unsigned)nz),                \
-                           dim3(CHAIN_THREADS), 0, ctx->stream, src, phs3, phs2, out, (int)L, M3, npt, gbeg, kchunk);     \
+        launch(ctx, contract_chain_kernel<MM>, dim3((unsigned)gx, (unsigned)gcnt, (unsigned)nz),                \
+                           dim3(CHAIN_THREADS), 0, src, phs3, phs2, out, (int)L, M3, npt, gbeg, kchunk);     \
         break;
     switch (M2) {
         CC(1) CC(2) CC(3) CC(4) CC(5) CC(6) CC(7) CC(8) CC(9) CC(10) CC(11) CC(12) CC(13) CC(14) CC(15) CC(16)
@@ -1090,13 +1090,13 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
     {                                                                                                                          \
         constexpr int OO = NN == 3 ? 3 : 2;                                                                                    \
         if (a.pk)                                                                                                              \
-            hipLaunchKernelGGL((eval_grid_kernel<NN, KK, true, false, OO, true>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); \
+            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, true>, dim3((unsigned)blocks), dim3(256), lds, a); \
         else if (a.U.base)                                                                                                     \
-            hipLaunchKernelGGL((eval_grid_kernel<NN, KK, false, true, 2>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);  \
+            launch(ctx, eval_grid_kernel<NN, KK, false, true, 2>, dim3((unsigned)blocks), dim3(256), lds, a);  \
         else if (a.herm)                                                                                                       \
-            hipLaunchKernelGGL((eval_grid_kernel<NN, KK, true, false, OO>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); \
+            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO>, dim3((unsigned)blocks), dim3(256), lds, a); \
         else                                                                                                                   \
-            hipLaunchKernelGGL((eval_grid_kernel<NN, KK, false, false, 2>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); \
+            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2>, dim3((unsigned)blocks), dim3(256), lds, a); \
     }
 #define FN(NN)                    \
     switch (kpl) {                \
@@ -1108,14 +1108,14 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
 #undef FN
 #undef LK
         } else {
-#define FN(NN) hipLaunchKernelGGL(eval_grid_kernel_scalar<NN>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a)
+#define FN(NN) launch(ctx, eval_grid_kernel_scalar<NN>, dim3((unsigned)blocks), dim3(256), 0, a)
             ABZ_DISPATCH_N(es.n, FN)
 #undef FN
         }
     } else {
         if (es.nk == 0) return ABZ_OK;
         const int64_t blocks = cdiv(es.nk, 256);
-#define FN(NN) hipLaunchKernelGGL(eval_node_kernel<NN>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a)
+#define FN(NN) launch(ctx, eval_node_kernel<NN>, dim3((unsigned)blocks), dim3(256), 0, a)
         ABZ_DISPATCH_N(es.n, FN)
 #undef FN
     }
@@ -1147,7 +1147,7 @@ __global__ __launch_bounds__(256) void eig_planes_kernel(PlaneView Hv, PlaneView
 int launch_eig_planes(abz_ctx* ctx, int n, PlaneView H, PlaneView E, PlaneView U, int64_t nk) {
     if (nk == 0) return ABZ_OK;
     ProfScope ps(ctx, ABZ_K_EIG);
-#define FN(NN) hipLaunchKernelGGL(eig_planes_kernel<NN>, dim3((unsigned)cdiv(nk, 256)), dim3(256), 0, ctx->stream, H, E, U, nk)
+#define FN(NN) launch(ctx, eig_planes_kernel<NN>, dim3((unsigned)cdiv(nk, 256)), dim3(256), 0, H, E, U, nk)
     ABZ_DISPATCH_N(n, FN)
 #undef FN
     ABZ_HIP(hipGetLastError());
@@ -1183,7 +1183,7 @@ __global__ __launch_bounds__(256) void velocity_kernel(PlaneView Uv, PlaneView D
 int launch_velocity(abz_ctx* ctx, int n, PlaneView U, PlaneView dH, PlaneView Vj, int64_t nk) {
     if (nk == 0) return ABZ_OK;
     if (n > 4) return launch_gen_velocity(ctx, n, U, dH, Vj, nk);
-#define FN(NN) hipLaunchKernelGGL(velocity_kernel<NN>, dim3((unsigned)cdiv(nk, 256)), dim3(256), 0, ctx->stream, U, dH, Vj, nk)
+#define FN(NN) launch(ctx, velocity_kernel<NN>, dim3((unsigned)cdiv(nk, 256)), dim3(256), 0, U, dH, Vj, nk)
     ABZ_DISPATCH_N(n, FN)
 #undef FN
     ABZ_HIP(hipGetLastError());
@@ -1689,13 +1689,13 @@ static int launch_dos3(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a0,
     const double pi = 3.14159265358979323846;
     const double scale = rs.scale * (mode == 0 ? -rs.params[0] / pi : rs.params[0] / pi);
     if (mode == 0)
-        hipLaunchKernelGGL((dos3_scan_kernel<kt, 0>), dim3((unsigned)nblocks, (unsigned)rows), dim3(256), lds, ctx->stream, a, 3.0, 6.0,
+        launch(ctx, (dos3_scan_kernel<kt, 0>), dim3((unsigned)nblocks, (unsigned)rows), dim3(256), lds, a, 3.0, 6.0,
                            ctx->scratch[1].as<double2>());
     else
-        hipLaunchKernelGGL((dos3_scan_kernel<kt, 1>), dim3((unsigned)nblocks, (unsigned)rows), dim3(256), lds, ctx->stream, a, 3.0, 6.0,
+        launch(ctx, (dos3_scan_kernel<kt, 1>), dim3((unsigned)nblocks, (unsigned)rows), dim3(256), lds, a, 3.0, 6.0,
                            ctx->scratch[1].as<double2>());
     ABZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, ctx->scratch[1].as<double2>(),
+    launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->scratch[1].as<double2>(),
                        nblocks, ncols, scale, rs.out_map_dev ? rs.out_map_dev : ctx->scratch[2].as<double2>());
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -1916,7 +1916,7 @@ __global__ __launch_bounds__(256, 2) void eval_sum_grid_kernel(EvalArgs a, SumAr
 }
 
 int launch_final_reduce(abz_ctx* ctx, const double2* partial, int64_t nblocks, int64_t ncols, double scale, double2* out) {
-    hipLaunchKernelGGL(final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, partial, nblocks, ncols, scale, out);
+    launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, partial, nblocks, ncols, scale, out);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -1985,7 +1985,7 @@ int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
         {
             ProfScope ps(ctx, ABZ_K_EVAL);
 #define SUMK(NN, KK, FF, WW) \
-    hipLaunchKernelGGL((eval_sum_grid_kernel<NN, KK, true, FF, WW>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a, q, partial)
+    launch(ctx, (eval_sum_grid_kernel<NN, KK, true, FF, WW>), dim3((unsigned)blocks), dim3(256), lds, a, q, partial)
 #define SUMN(NN, FF, WW)   \
     if (kpl == 2) {        \
         SUMK(NN, 2, FF, WW); \
@@ -2013,7 +2013,7 @@ int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
 #undef SUMK
             ABZ_HIP(hipGetLastError());
             const int64_t ncols = (int64_t)q.nw * ncomp;
-            hipLaunchKernelGGL(final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, partial, blocks, ncols,
+            launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, partial, blocks, ncols,
                                ss.scale, outd);
             ABZ_HIP(hipGetLastError());
         }
@@ -2065,10 +2065,10 @@ static int launch_reduce_h(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs&
     if (lds > 64 * 1024)
         ABZ_HIP(hipFuncSetAttribute((const void*)reduce_kernel<N, FID, KT, HERM>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)lds));
-    hipLaunchKernelGGL((reduce_kernel<N, FID, KT, HERM>), dim3((unsigned)nblocks, (unsigned)rows), dim3(256), lds, ctx->stream, a,
+    launch(ctx, (reduce_kernel<N, FID, KT, HERM>), dim3((unsigned)nblocks, (unsigned)rows), dim3(256), lds, a,
                        ctx->scratch[1].as<double2>());
     ABZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, ctx->scratch[1].as<double2>(),
+    launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->scratch[1].as<double2>(),
                        nblocks, ncols, rs.scale, rs.out_map_dev ? rs.out_map_dev : ctx->scratch[2].as<double2>());
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -2191,7 +2191,7 @@ int export_planes(abz_ctx* ctx, PlaneView v, int ncomp, int64_t nk, double* host
     int rc = ctx->scratch[3].reserve(bytes);
     if (rc) return rc;
     double* stg = ctx->scratch[3].as<double>();
-    hipLaunchKernelGGL(export_kernel, dim3((unsigned)cdiv(nk * ncomp, 256)), dim3(256), 0, ctx->stream, v, ncomp, nk, stg, row_major_n);
+    launch(ctx, export_kernel, dim3((unsigned)cdiv(nk * ncomp, 256)), dim3(256), 0, v, ncomp, nk, stg, row_major_n);
     ABZ_HIP(hipGetLastError());
     return stage_d2h(ctx, host_out, stg, bytes);  // large: through the pinned staging buffer
 }
@@ -2365,10 +2365,10 @@ int launch_node_integrand(abz_ctx* ctx, const NodeEvalSpec& ns, double2* values_
 #define CASE(FID)                                                                                                  \
     case FID:                                                                                                      \
         switch (ns.n) {                                                                                            \
-            case 1: hipLaunchKernelGGL((node_integrand_kernel<1, FID>), dim3(blocks), dim3(256), 0, ctx->stream, a, values_dev); break; \
-            case 2: hipLaunchKernelGGL((node_integrand_kernel<2, FID>), dim3(blocks), dim3(256), 0, ctx->stream, a, values_dev); break; \
-            case 3: hipLaunchKernelGGL((node_integrand_kernel<3, FID>), dim3(blocks), dim3(256), 0, ctx->stream, a, values_dev); break; \
-            case 4: hipLaunchKernelGGL((node_integrand_kernel<4, FID>), dim3(blocks), dim3(256), 0, ctx->stream, a, values_dev); break; \
+            case 1: launch(ctx, (node_integrand_kernel<1, FID>), dim3(blocks), dim3(256), 0, a, values_dev); break; \
+            case 2: launch(ctx, (node_integrand_kernel<2, FID>), dim3(blocks), dim3(256), 0, a, values_dev); break; \
+            case 3: launch(ctx, (node_integrand_kernel<3, FID>), dim3(blocks), dim3(256), 0, a, values_dev); break; \
+            case 4: launch(ctx, (node_integrand_kernel<4, FID>), dim3(blocks), dim3(256), 0, a, values_dev); break; \
             default:                                                                                               \
                 set_error("n = %d bands: only n <= 4 is built in this round", ns.n);                               \
                 return ABZ_ERR_UNSUPPORTED;                                                                        \
@@ -2948,7 +2948,7 @@ int launch_panel_contract(abz_ctx* ctx, const PanelNodesSpec& ps, const double2*
         set_error("panel_contract: row length %lld too large", (long long)Lrow);
         return ABZ_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(panel_contract_kernel, dim3((unsigned)(15 * ps.npanels), (unsigned)gy), dim3(bs), sizeof(double2) * (size_t)M, ctx->stream,
+    launch(ctx, panel_contract_kernel, dim3((unsigned)(15 * ps.npanels), (unsigned)gy), dim3(bs), sizeof(double2) * (size_t)M,
                        ps, src, slot_elems, M, first, 1.0 / period, out, Lrow);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -2973,7 +2973,7 @@ __global__ __launch_bounds__(256) void panel_rule_kernel(PanelRuleSpec a) {
 
 int launch_panel_rule(abz_ctx* ctx, const PanelRuleSpec& ps) {
     if (ps.npanels == 0) return ABZ_OK;
-    hipLaunchKernelGGL(panel_rule_kernel, dim3((unsigned)cdiv(ps.npanels, 256)), dim3(256), 0, ctx->stream, ps);
+    launch(ctx, panel_rule_kernel, dim3((unsigned)cdiv(ps.npanels, 256)), dim3(256), 0, ps);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -3039,13 +3039,13 @@ int launch_inner_adaptive(abz_ctx* ctx, const InnerSpec& is) {
         if (lds > 48 * 1024)                                                                                          \
             ABZ_HIP(hipFuncSetAttribute((const void*)inner_adaptive_kernel<NN, FID, HH>,                              \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                       \
-        hipLaunchKernelGGL((inner_adaptive_kernel<NN, FID, HH>), dim3(blocks), dim3(256), lds, ctx->stream, a);       \
+        launch(ctx, (inner_adaptive_kernel<NN, FID, HH>), dim3(blocks), dim3(256), lds, a);       \
     }
 #define LAUNCH_INNER2(NN, FID, HH)                                                                                    \
     {                                                                                                                 \
         if constexpr (NComp<FID>::template value<NN>() == 1) {                                                        \
             if (wave_state) {                                                                                         \
-                hipLaunchKernelGGL((inner_adaptive_wave_kernel<NN, FID, HH>), dim3(blocks), dim3(256), lds, ctx->stream, a); \
+                launch(ctx, (inner_adaptive_wave_kernel<NN, FID, HH>), dim3(blocks), dim3(256), lds, a); \
             } else                                                                                                    \
                 LAUNCH_INNER_LDS(NN, FID, HH)                                                                         \
         } else                                                                                                        \

@@ -910,13 +910,13 @@ int big_tridiag(abz_ctx* ctx, const BigWork& w, int n, int64_t cn, double2* keep
     const int64_t blocks = std::min<int64_t>(cn, 256 * 8);
     if (nw >= 4) {
         ABZ_HIP(hipFuncSetAttribute((const void*)big_tridiag_mw_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(big_tridiag_mw_kernel<4>, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, w.Hbuf, cn, n, tri, tri_nk, t0, keep);
+        launch(ctx, big_tridiag_mw_kernel<4>, dim3((unsigned)blocks), dim3(256), lds, w.Hbuf, cn, n, tri, tri_nk, t0, keep);
     } else if (nw >= 2) {
         ABZ_HIP(hipFuncSetAttribute((const void*)big_tridiag_mw_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(big_tridiag_mw_kernel<2>, dim3((unsigned)blocks), dim3(128), lds, ctx->stream, w.Hbuf, cn, n, tri, tri_nk, t0, keep);
+        launch(ctx, big_tridiag_mw_kernel<2>, dim3((unsigned)blocks), dim3(128), lds, w.Hbuf, cn, n, tri, tri_nk, t0, keep);
     } else {
         ABZ_HIP(hipFuncSetAttribute((const void*)big_tridiag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(big_tridiag_kernel, dim3((unsigned)blocks), dim3(64), lds, ctx->stream, w.Hbuf, cn, n, tri, tri_nk, t0, keep);
+        launch(ctx, big_tridiag_kernel, dim3((unsigned)blocks), dim3(64), lds, w.Hbuf, cn, n, tri, tri_nk, t0, keep);
     }
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -928,29 +928,29 @@ static int big_inverse(abz_ctx* ctx, BigInvArgs& ia, int64_t blocks) {
         blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (ia.nnodes + subs - 1) / subs));
     }
     if (ia.n <= 4)
-        hipLaunchKernelGGL((big_inverse_kernel<1, 8>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<1, 8>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 8)
-        hipLaunchKernelGGL((big_inverse_kernel<2, 8>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<2, 8>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 12)
-        hipLaunchKernelGGL((big_inverse_kernel<3, 4>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<3, 4>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 16)
-        hipLaunchKernelGGL((big_inverse_kernel<4, 4>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<4, 4>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 20)
-        hipLaunchKernelGGL((big_inverse_kernel<5, 2>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<5, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 24)
-        hipLaunchKernelGGL((big_inverse_kernel<6, 2>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<6, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 28)
-        hipLaunchKernelGGL((big_inverse_kernel<7, 2>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<7, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 32)
-        hipLaunchKernelGGL((big_inverse_kernel<8, 2>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<8, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 40)
-        hipLaunchKernelGGL((big_inverse_kernel<10, 1>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<10, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 48)
-        hipLaunchKernelGGL((big_inverse_kernel<12, 1>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<12, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else if (ia.n <= 56)
-        hipLaunchKernelGGL((big_inverse_kernel<14, 1>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<14, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
     else
-        hipLaunchKernelGGL((big_inverse_kernel<16, 1>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ia);
+        launch(ctx, (big_inverse_kernel<16, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -963,13 +963,13 @@ int big_series(abz_ctx* ctx, BigSeriesArgs& sa, int64_t c0, int64_t cn) {
         const int64_t lines = cn / sa.npt;
         if (abz_switch(SW_BIG_MFMA) && sa.M <= 64) {
             const int tpl = (sa.npt + 15) / 16;
-            hipLaunchKernelGGL(big_series_mfma_kernel, dim3((unsigned)(lines * tpl)), dim3(256), 0, ctx->stream, sa, tpl);
+            launch(ctx, big_series_mfma_kernel, dim3((unsigned)(lines * tpl)), dim3(256), 0, sa, tpl);
         } else {
             const int tpl = (sa.npt + BIG_TN - 1) / BIG_TN;
-            hipLaunchKernelGGL(big_series_kernel, dim3((unsigned)(lines * tpl)), dim3(256), 0, ctx->stream, sa, tpl);
+            launch(ctx, big_series_kernel, dim3((unsigned)(lines * tpl)), dim3(256), 0, sa, tpl);
         }
     } else {
-        hipLaunchKernelGGL(big_series_kernel, dim3((unsigned)cdivb(cn, BIG_TN)), dim3(256), 0, ctx->stream, sa, 0);
+        launch(ctx, big_series_kernel, dim3((unsigned)cdivb(cn, BIG_TN)), dim3(256), 0, sa, 0);
     }
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -1041,7 +1041,7 @@ int launch_big_ggr(abz_ctx* ctx, const GgrRowsSpec& gs) {
         {
             const size_t qlds = sizeof(double) * 2 * (size_t)(n + 2) * 64;
             ABZ_HIP(hipFuncSetAttribute((const void*)big_qr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qlds));
-            hipLaunchKernelGGL(big_qr_kernel, dim3((unsigned)cdivb(cn, 64)), dim3(64), qlds, ctx->stream, w.tri, w.tri_nk, c0, cn, n, gs.E);
+            launch(ctx, big_qr_kernel, dim3((unsigned)cdivb(cn, 64)), dim3(64), qlds, w.tri, w.tri_nk, c0, cn, n, gs.E);
             ABZ_HIP(hipGetLastError());
         }
         for (int j = 0; j < gs.d; ++j) {
@@ -1091,7 +1091,7 @@ int launch_big_nodes(abz_ctx* ctx, const GenSpec& gs) {
         const int64_t cn = std::min(w.chunk, gs.nnodes - c0);
         if ((rc = big_series(ctx, sa, c0, cn))) return rc;
         if (gs.Hplanes.base || gs.Haos) {
-            hipLaunchKernelGGL(big_store_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * gs.n * gs.n, 256), 256 * 16)), dim3(256), 0, ctx->stream,
+            launch(ctx, big_store_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * gs.n * gs.n, 256), 256 * 16)), dim3(256), 0,
                                w.Hbuf, c0, cn, gs.n, gs.Hplanes, gs.Haos);
             ABZ_HIP(hipGetLastError());
         }
@@ -1120,10 +1120,10 @@ int launch_big_nodes(abz_ctx* ctx, const GenSpec& gs) {
         if (gs.Eplanes.base && !gs.Eaos && (gs.n <= 56 || cn >= 64 * 512)) {
             const size_t qlds = sizeof(double) * 2 * (size_t)(gs.n + 2) * 64;
             ABZ_HIP(hipFuncSetAttribute((const void*)big_qr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qlds));
-            hipLaunchKernelGGL(big_qr_kernel, dim3((unsigned)cdivb(cn, 64)), dim3(64), qlds, ctx->stream, w.tri, w.tri_nk, c0, cn, gs.n, gs.Eplanes);
+            launch(ctx, big_qr_kernel, dim3((unsigned)cdivb(cn, 64)), dim3(64), qlds, w.tri, w.tri_nk, c0, cn, gs.n, gs.Eplanes);
             ABZ_HIP(hipGetLastError());
         } else if (gs.Eplanes.base || gs.Eaos) {
-            hipLaunchKernelGGL(big_bisect_kernel, dim3((unsigned)cdivb(cn, 4)), dim3(256), 0, ctx->stream, w.tri, w.tri_nk, (int64_t)0, c0, cn, gs.n,
+            launch(ctx, big_bisect_kernel, dim3((unsigned)cdivb(cn, 4)), dim3(256), 0, w.tri, w.tri_nk, (int64_t)0, c0, cn, gs.n,
                                gs.Eplanes, gs.Eaos);
             ABZ_HIP(hipGetLastError());
         }
@@ -1144,7 +1144,7 @@ int launch_big_nodes(abz_ctx* ctx, const GenSpec& gs) {
             ta.w = nullptr;
             ta.values = gs.values;
             ta.partial = nullptr;
-            hipLaunchKernelGGL(big_trace_kernel, dim3((unsigned)std::min<int64_t>(cdivb(cn, 256), 256 * 4)), dim3(256), 0, ctx->stream, ta);
+            launch(ctx, big_trace_kernel, dim3((unsigned)std::min<int64_t>(cdivb(cn, 256), 256 * 4)), dim3(256), 0, ta);
             ABZ_HIP(hipGetLastError());
         }
     }
@@ -1173,12 +1173,12 @@ static int big_sum_chunk(abz_ctx* ctx, const BigWork& w, int n, int64_t c0, int6
     ta.w = weights;
     ta.values = nullptr;
     ta.partial = ctx->scratch[1].as<double2>();
-    hipLaunchKernelGGL(big_trace_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ta);
+    launch(ctx, big_trace_kernel, dim3((unsigned)blocks), dim3(256), 0, ta);
     ABZ_HIP(hipGetLastError());
     double2* part = ta.partial + blocks * n_sweep;
     if ((rc = launch_final_reduce(ctx, ta.partial, blocks, n_sweep, 1.0, first ? total : part))) return rc;
     if (!first) {
-        hipLaunchKernelGGL(big_accumulate_kernel, dim3((unsigned)cdivb(n_sweep, 256)), dim3(256), 0, ctx->stream, total, part, n_sweep);
+        launch(ctx, big_accumulate_kernel, dim3((unsigned)cdivb(n_sweep, 256)), dim3(256), 0, total, part, n_sweep);
         ABZ_HIP(hipGetLastError());
     }
     return ABZ_OK;
@@ -1270,7 +1270,7 @@ int launch_big_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
         if ((rc = big_tridiag(ctx, w, ss.n, cn))) return rc;
         if ((rc = big_sum_chunk(ctx, w, ss.n, c0, cn, ss.integrand == ABZ_F_DOS, ss.params[0], sw, ss.n_sweep, nullptr, total, c0 == 0))) return rc;
     }
-    hipLaunchKernelGGL(big_scale_kernel, dim3((unsigned)cdivb(ss.n_sweep, 256)), dim3(256), 0, ctx->stream, total, ss.n_sweep, ss.scale);
+    launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(ss.n_sweep, 256)), dim3(256), 0, total, ss.n_sweep, ss.scale);
     ABZ_HIP(hipGetLastError());
     ABZ_HIP(hipMemcpyAsync(out_reim, total, sizeof(double2) * (size_t)ss.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
     ABZ_HIP(hipStreamSynchronize(ctx->stream));
@@ -1305,8 +1305,7 @@ int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
                 ABZ_HIP(hipMemsetAsync(partial, 0, sizeof(double2) * (size_t)(blocks * ns * ncomp), ctx->stream));
                 for (int64_t c0 = 0; c0 < rs.nk; c0 += w.chunk) {
                     const int64_t cn = std::min(w.chunk, rs.nk - c0);
-                    hipLaunchKernelGGL(big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * nn, 256), 256 * 16)), dim3(256), 0,
-                                       ctx->stream, w.Hbuf, c0, cn, rs.n, rs.H);
+                    launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * nn, 256), 256 * 16)), dim3(256), 0, w.Hbuf, c0, cn, rs.n, rs.H);
                     ABZ_HIP(hipGetLastError());
                     BigInvArgs ia;
                     ia.Hbuf = w.Hbuf;
@@ -1345,8 +1344,7 @@ int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
         if (*rs.tri_state == 0) {
             for (int64_t c0 = 0; c0 < rs.nk; c0 += w.chunk) {
                 const int64_t cn = std::min(w.chunk, rs.nk - c0);
-                hipLaunchKernelGGL(big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * rs.n * rs.n, 256), 256 * 16)), dim3(256), 0,
-                                   ctx->stream, w.Hbuf, c0, cn, rs.n, rs.H);
+                launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * rs.n * rs.n, 256), 256 * 16)), dim3(256), 0, w.Hbuf, c0, cn, rs.n, rs.H);
                 ABZ_HIP(hipGetLastError());
                 if ((rc = big_tridiag(ctx, w, rs.n, cn, nullptr, rs.tri_cache, rs.tri_nk, c0))) return rc;
             }
@@ -1356,20 +1354,20 @@ int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
         wc.tri = rs.tri_cache;
         wc.tri_nk = rs.tri_nk;
         if ((rc = big_sum_chunk(ctx, wc, rs.n, 0, rs.nk, rs.integrand == ABZ_F_DOS, rs.params[0], rs.sweep_dev, rs.n_sweep, rs.w, total, true))) return rc;
-        hipLaunchKernelGGL(big_scale_kernel, dim3((unsigned)cdivb(rs.n_sweep, 256)), dim3(256), 0, ctx->stream, total, rs.n_sweep, rs.scale);
+        launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(rs.n_sweep, 256)), dim3(256), 0, total, rs.n_sweep, rs.scale);
         ABZ_HIP(hipGetLastError());
     } else {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         for (int64_t c0 = 0; c0 < rs.nk; c0 += w.chunk) {
             const int64_t cn = std::min(w.chunk, rs.nk - c0);
-            hipLaunchKernelGGL(big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * rs.n * rs.n, 256), 256 * 16)), dim3(256), 0, ctx->stream,
+            launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * rs.n * rs.n, 256), 256 * 16)), dim3(256), 0,
                                w.Hbuf, c0, cn, rs.n, rs.H);
             ABZ_HIP(hipGetLastError());
             if ((rc = big_tridiag(ctx, w, rs.n, cn))) return rc;
             if ((rc = big_sum_chunk(ctx, w, rs.n, c0, cn, rs.integrand == ABZ_F_DOS, rs.params[0], rs.sweep_dev, rs.n_sweep, rs.w, total, c0 == 0)))
                 return rc;
         }
-        hipLaunchKernelGGL(big_scale_kernel, dim3((unsigned)cdivb(rs.n_sweep, 256)), dim3(256), 0, ctx->stream, total, rs.n_sweep, rs.scale);
+        launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(rs.n_sweep, 256)), dim3(256), 0, total, rs.n_sweep, rs.scale);
         ABZ_HIP(hipGetLastError());
     }
     if (rs.out_dev) {

@@ -565,7 +565,7 @@ int launch_big_vec(abz_ctx* ctx, const double* tri, int64_t tri_nk, const double
     a.E = E;
     a.V = V;
     const int64_t blocks = std::min<int64_t>(nnodes, 256 * 4 * 4);
-    hipLaunchKernelGGL(big_ggr_kernel, dim3((unsigned)blocks), dim3(128), 0, ctx->stream, tri, keep, Dm, a);
+    launch(ctx, big_ggr_kernel, dim3((unsigned)blocks), dim3(128), 0, tri, keep, Dm, a);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }

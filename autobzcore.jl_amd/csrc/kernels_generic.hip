@@ -374,7 +374,7 @@ int launch_gen_velocity(abz_ctx* ctx, int n, PlaneView U, PlaneView dH, PlaneVie
         ABZ_HIP(hipGetLastError());
         return ABZ_OK;
     }
-    hipLaunchKernelGGL(gen_velocity_kernel, dim3((unsigned)cdiv2(nk, 256), (unsigned)n), dim3(256), 0, ctx->stream, U, dH, Vj, nk, n);
+    launch(ctx, gen_velocity_kernel, dim3((unsigned)cdiv2(nk, 256), (unsigned)n), dim3(256), 0, U, dH, Vj, nk, n);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -823,7 +823,7 @@ int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
 #define ABZ_GS2(NPV, PV)                                                                                              \
     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_kernel<NPV, PV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds));                                                                           \
-    hipLaunchKernelGGL((gen_grid_sum_kernel<NPV, PV>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+    launch(ctx, (gen_grid_sum_kernel<NPV, PV>), dim3((unsigned)blocks), dim3(256), lds, a);
 #define ABZ_GS(NPV)   \
     if (pad) {        \
         ABZ_GS2(NPV, true) \
@@ -1283,26 +1283,26 @@ static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss, double* out_reim)
             if (np == 32) {  // 17...32 bands: two nodes per wave
                 if (pad) {
                     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_tri_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((gen_grid_sum_tri_kernel<32, true>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+                    launch(ctx, (gen_grid_sum_tri_kernel<32, true>), dim3((unsigned)blocks), dim3(256), lds, a);
                 } else {
                     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_tri_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((gen_grid_sum_tri_kernel<32, false>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+                    launch(ctx, (gen_grid_sum_tri_kernel<32, false>), dim3((unsigned)blocks), dim3(256), lds, a);
                 }
             } else if (np == 8) {
                 if (pad) {
                     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_tri_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((gen_grid_sum_tri_kernel<8, true>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+                    launch(ctx, (gen_grid_sum_tri_kernel<8, true>), dim3((unsigned)blocks), dim3(256), lds, a);
                 } else {
                     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_tri_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((gen_grid_sum_tri_kernel<8, false>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+                    launch(ctx, (gen_grid_sum_tri_kernel<8, false>), dim3((unsigned)blocks), dim3(256), lds, a);
                 }
             } else {
                 if (pad) {
                     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_tri_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((gen_grid_sum_tri_kernel<16, true>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+                    launch(ctx, (gen_grid_sum_tri_kernel<16, true>), dim3((unsigned)blocks), dim3(256), lds, a);
                 } else {
                     ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_sum_tri_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((gen_grid_sum_tri_kernel<16, false>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);
+                    launch(ctx, (gen_grid_sum_tri_kernel<16, false>), dim3((unsigned)blocks), dim3(256), lds, a);
                 }
             }
             ABZ_HIP(hipGetLastError());
@@ -1490,10 +1490,10 @@ __global__ __launch_bounds__(128) void gen_velocity_rows_kernel(PlaneView Uv, Pl
 static bool launch_gen_velocity_rows(abz_ctx* ctx, int n, PlaneView U, PlaneView dH, PlaneView Vj, int64_t nk) {
     if (n <= 4 || n > 16) return false;
     if (n <= 8)
-        hipLaunchKernelGGL(gen_velocity_rows_kernel<8>, dim3((unsigned)cdiv2(nk, 16)), dim3(128), sizeof(double2) * 2 * 16 * 64, ctx->stream, U, dH,
+        launch(ctx, gen_velocity_rows_kernel<8>, dim3((unsigned)cdiv2(nk, 16)), dim3(128), sizeof(double2) * 2 * 16 * 64, U, dH,
                            Vj, nk, n);
     else
-        hipLaunchKernelGGL(gen_velocity_rows_kernel<16>, dim3((unsigned)cdiv2(nk, 8)), dim3(128), sizeof(double2) * 2 * 8 * 256, ctx->stream, U, dH,
+        launch(ctx, gen_velocity_rows_kernel<16>, dim3((unsigned)cdiv2(nk, 8)), dim3(128), sizeof(double2) * 2 * 8 * 256, U, dH,
                            Vj, nk, n);
     return true;
 }
@@ -1845,7 +1845,7 @@ static int launch_gen_grid_eig(abz_ctx* ctx, const GenSpec& gs, int np, size_t l
     {                                                                                                                             \
         ABZ_HIP(hipFuncSetAttribute((const void*)gen_grid_eig_kernel<NPV, PV, VV, TV, SV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                     (int)lds));                                                                                   \
-        hipLaunchKernelGGL((gen_grid_eig_kernel<NPV, PV, VV, TV, SV>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);   \
+        launch(ctx, (gen_grid_eig_kernel<NPV, PV, VV, TV, SV>), dim3((unsigned)blocks), dim3(256), lds, a);   \
     }
 #define ABZ_GE3(NPV, PV, VV, TV) ABZ_GE4(NPV, PV, VV, TV, false)
     if (!vec && (split || !gs.Eplanes.base)) {  // (H only: the lean instance as well -- it never reaches the eigenvalue stage)
@@ -1871,11 +1871,11 @@ static int launch_gen_grid_eig(abz_ctx* ctx, const GenSpec& gs, int np, size_t l
     if (split) {
         const unsigned tb = (unsigned)cdiv2(gs.nnodes, 64);
         if (np == 8)
-            hipLaunchKernelGGL(tri_eig_kernel<8>, dim3(tb), dim3(64), 0, ctx->stream, a.tri, a.tri_nk, gs.nnodes, gs.n, gs.Eplanes);
+            launch(ctx, tri_eig_kernel<8>, dim3(tb), dim3(64), 0, a.tri, a.tri_nk, gs.nnodes, gs.n, gs.Eplanes);
         else if (np == 32)
-            hipLaunchKernelGGL(tri_eig_kernel<32>, dim3(tb), dim3(64), 0, ctx->stream, a.tri, a.tri_nk, gs.nnodes, gs.n, gs.Eplanes);
+            launch(ctx, tri_eig_kernel<32>, dim3(tb), dim3(64), 0, a.tri, a.tri_nk, gs.nnodes, gs.n, gs.Eplanes);
         else
-            hipLaunchKernelGGL(tri_eig_kernel<16>, dim3(tb), dim3(64), 0, ctx->stream, a.tri, a.tri_nk, gs.nnodes, gs.n, gs.Eplanes);
+            launch(ctx, tri_eig_kernel<16>, dim3(tb), dim3(64), 0, a.tri, a.tri_nk, gs.nnodes, gs.n, gs.Eplanes);
     }
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
@@ -1969,7 +1969,7 @@ int launch_gen_nodes(abz_ctx* ctx, const GenSpec& gs) {
 #define ABZ_PANEL2(NPV, PV)                                                                                                  \
     ABZ_HIP(hipFuncSetAttribute((const void*)gen_panel_kernel<NPV, PV>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
                                 (int)plds));                                                                               \
-    hipLaunchKernelGGL((gen_panel_kernel<NPV, PV>), dim3((unsigned)blocks), dim3(256), plds, ctx->stream, a);
+    launch(ctx, (gen_panel_kernel<NPV, PV>), dim3((unsigned)blocks), dim3(256), plds, a);
 #define ABZ_PANEL(NPV) \
     if (pad) {         \
         ABZ_PANEL2(NPV, true) \
@@ -1998,7 +1998,7 @@ int launch_gen_nodes(abz_ctx* ctx, const GenSpec& gs) {
     const int64_t blocks = std::min<int64_t>(cdiv2(gs.nnodes, wpb), 256 * 16);
     ProfScope ps(ctx, ABZ_K_EVAL);
     ABZ_HIP(hipFuncSetAttribute((const void*)gen_node_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(gen_node_kernel, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a, wpb);
+    launch(ctx, gen_node_kernel, dim3((unsigned)blocks), dim3(256), lds, a, wpb);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -2410,9 +2410,9 @@ static int launch_gen_rows_gloc(abz_ctx* ctx, const ReduceSpec& rs, double* out_
         {
             ProfScope ps(ctx, ABZ_K_REDUCE);
             if (np == 8)
-                hipLaunchKernelGGL(gen_rows_gloc_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+                launch(ctx, gen_rows_gloc_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, a);
             else
-                hipLaunchKernelGGL(gen_rows_gloc_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+                launch(ctx, gen_rows_gloc_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, a);
             ABZ_HIP(hipGetLastError());
             if ((rc = launch_final_reduce(ctx, a.partial, blocks, (int64_t)a.n_sweep * nn, rs.scale, outd))) return rc;
         }
@@ -2450,15 +2450,15 @@ static int launch_gen_rows_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* ou
         ProfScope ps(ctx, ABZ_K_REDUCE);
         const bool tri = (abz_switch(SW_GEN_SUM_TRI) && rs.n_sweep >= 3) || np == 32;  // sweeps: tridiagonalise once, p'/p per swept value
         if (np == 32)
-            hipLaunchKernelGGL(gen_rows_reduce_tri_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+            launch(ctx, gen_rows_reduce_tri_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, a);
         else if (tri && np == 8)
-            hipLaunchKernelGGL(gen_rows_reduce_tri_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+            launch(ctx, gen_rows_reduce_tri_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, a);
         else if (tri)
-            hipLaunchKernelGGL(gen_rows_reduce_tri_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+            launch(ctx, gen_rows_reduce_tri_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, a);
         else if (np == 8)
-            hipLaunchKernelGGL(gen_rows_reduce_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+            launch(ctx, gen_rows_reduce_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, a);
         else
-            hipLaunchKernelGGL(gen_rows_reduce_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+            launch(ctx, gen_rows_reduce_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, a);
         ABZ_HIP(hipGetLastError());
         if ((rc = launch_final_reduce(ctx, a.partial, blocks, rs.n_sweep, rs.scale, outd))) return rc;
     }
@@ -2547,7 +2547,7 @@ static int launch_gen_eig_dos(abz_ctx* ctx, const ReduceSpec& rs, double* out_re
     double2* outd = ctx->scratch[2].as<double2>();
     {
         ProfScope ps(ctx, ABZ_K_REDUCE);
-        hipLaunchKernelGGL(gen_eig_dos_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+        launch(ctx, gen_eig_dos_kernel, dim3((unsigned)blocks), dim3(256), 0, a);
         ABZ_HIP(hipGetLastError());
         if ((rc = launch_final_reduce(ctx, a.partial, blocks, rs.n_sweep, rs.scale, outd))) return rc;
     }
@@ -2608,9 +2608,9 @@ int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         const size_t lds = per * wpb;
         ABZ_HIP(hipFuncSetAttribute((const void*)gen_reduce_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(gen_reduce_kernel, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a, wpb, partial);
+        launch(ctx, gen_reduce_kernel, dim3((unsigned)blocks), dim3(256), lds, a, wpb, partial);
         ABZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(final_reduce2_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, partial, blocks * wpb,
+        launch(ctx, final_reduce2_kernel, dim3((unsigned)ncols), dim3(256), 0, partial, blocks * wpb,
                            ncols, rs.scale, outd);
         ABZ_HIP(hipGetLastError());
     }
@@ -2829,7 +2829,7 @@ int launch_gen_inner_adaptive(abz_ctx* ctx, const InnerSpec& is) {
     {                                                                                                                     \
         auto kfn = gen_inner_panel_kernel<NPV, PV, NTV, WV, ##__VA_ARGS__>;                                               \
         ABZ_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));            \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(NTV), plds, ctx->stream, a);                                 \
+        launch(ctx, kfn, dim3((unsigned)blocks), dim3(NTV), plds, a);                                 \
     }
     const bool fold = abz_switch(SW_IPANEL_FOLD) != 0, fmac = abz_switch(SW_IPANEL_FMAC) != 0;  // per call: tests compare the variants
     if (np == 16 && pad && a.herm && fold && fmac) {  // config 5's shape

@@ -652,10 +652,10 @@ int launch_pack_rows(abz_ctx* ctx, int n, int M, const double2* src, int64_t nro
     if (tot == 0) return ABZ_OK;
     const unsigned blocks = (unsigned)cdiv64(tot, 256);
     switch (n) {
-        case 1: hipLaunchKernelGGL(pack_rows_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, src, nrows, M, out); break;
-        case 2: hipLaunchKernelGGL(pack_rows_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, src, nrows, M, out); break;
-        case 3: hipLaunchKernelGGL(pack_rows_kernel<3>, dim3(blocks), dim3(256), 0, ctx->stream, src, nrows, M, out); break;
-        case 4: hipLaunchKernelGGL(pack_rows_kernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, src, nrows, M, out); break;
+        case 1: launch(ctx, pack_rows_kernel<1>, dim3(blocks), dim3(256), 0, src, nrows, M, out); break;
+        case 2: launch(ctx, pack_rows_kernel<2>, dim3(blocks), dim3(256), 0, src, nrows, M, out); break;
+        case 3: launch(ctx, pack_rows_kernel<3>, dim3(blocks), dim3(256), 0, src, nrows, M, out); break;
+        case 4: launch(ctx, pack_rows_kernel<4>, dim3(blocks), dim3(256), 0, src, nrows, M, out); break;
         default: set_error("packed rows exist for n <= 4"); return ABZ_ERR_UNSUPPORTED;
     }
     ABZ_HIP(hipGetLastError());
@@ -720,7 +720,7 @@ int launch_ggr_build(abz_ctx* ctx, const GgrBuildSpec& gs) {
     if (!gs.grid) {
         if (gs.nk == 0) return ABZ_OK;
         const unsigned blocks = (unsigned)cdiv64(gs.nk, 256);
-#define GN(NN, DD) hipLaunchKernelGGL((ggr_build_nodes_kernel<NN, DD>), dim3(blocks), dim3(256), 0, ctx->stream, a)
+#define GN(NN, DD) launch(ctx, (ggr_build_nodes_kernel<NN, DD>), dim3(blocks), dim3(256), 0, a)
 #define GND(NN)                    \
     switch (d) {                   \
         case 1: GN(NN, 1); break;  \
@@ -750,10 +750,10 @@ int launch_ggr_build(abz_ctx* ctx, const GgrBuildSpec& gs) {
         {
             const unsigned pb = (unsigned)nparents;
             switch (n) {
-                case 1: hipLaunchKernelGGL(ggr_pack2_kernel<1>, dim3(pb), dim3(256), 0, ctx->stream, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
-                case 2: hipLaunchKernelGGL(ggr_pack2_kernel<2>, dim3(pb), dim3(256), 0, ctx->stream, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
-                case 3: hipLaunchKernelGGL(ggr_pack2_kernel<3>, dim3(pb), dim3(256), 0, ctx->stream, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
-                default: hipLaunchKernelGGL(ggr_pack2_kernel<4>, dim3(pb), dim3(256), 0, ctx->stream, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
+                case 1: launch(ctx, ggr_pack2_kernel<1>, dim3(pb), dim3(256), 0, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
+                case 2: launch(ctx, ggr_pack2_kernel<2>, dim3(pb), dim3(256), 0, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
+                case 3: launch(ctx, ggr_pack2_kernel<3>, dim3(pb), dim3(256), 0, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
+                default: launch(ctx, ggr_pack2_kernel<4>, dim3(pb), dim3(256), 0, gs.src2[0], gs.src2[1], d - 1, gs.M, gs.M2, gs.pack2); break;
             }
             ABZ_HIP(hipGetLastError());
             a.src2[0] = gs.pack2;
@@ -772,7 +772,7 @@ int launch_ggr_build(abz_ctx* ctx, const GgrBuildSpec& gs) {
         auto kfn = ggr_build_fused_kernel<NN, DD, NT>;                                                                    \
         if (lds > 64 * 1024)                                                                                              \
             ABZ_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, ctx->stream, a);                                            \
+        launch(ctx, kfn, dim3(blocks), dim3(256), lds, a);                                            \
     } while (0)
 #define GF(NN, DD)        \
     if (a.nt)             \
@@ -800,9 +800,9 @@ int launch_ggr_build(abz_ctx* ctx, const GgrBuildSpec& gs) {
         const unsigned blocks = (unsigned)std::min<int64_t>(cdiv64(npairs, 4), 256 * 12);
 #define GL(NN, DD)                                                                                                      \
     if (a.nt)                                                                                                           \
-        hipLaunchKernelGGL((ggr_build_lines_kernel<NN, DD, true>), dim3(blocks), dim3(256), lds, ctx->stream, a);      \
+        launch(ctx, (ggr_build_lines_kernel<NN, DD, true>), dim3(blocks), dim3(256), lds, a);      \
     else                                                                                                                \
-        hipLaunchKernelGGL((ggr_build_lines_kernel<NN, DD, false>), dim3(blocks), dim3(256), lds, ctx->stream, a)
+        launch(ctx, (ggr_build_lines_kernel<NN, DD, false>), dim3(blocks), dim3(256), lds, a)
 #define GLD(NN)                    \
     switch (d) {                   \
         case 1: GL(NN, 1); break;  \
@@ -1031,9 +1031,9 @@ __global__ __launch_bounds__(256) void ggr_final_kernel(const double* __restrict
     } while (0)
 #define ABZ_GGR_D(KERNEL, NN, ...)                                                                              \
     switch (d) {                                                                                                \
-        case 1: hipLaunchKernelGGL((KERNEL<NN, 1>), grid, dim3(256), lds, ctx->stream, __VA_ARGS__); break;     \
-        case 2: hipLaunchKernelGGL((KERNEL<NN, 2>), grid, dim3(256), lds, ctx->stream, __VA_ARGS__); break;     \
-        default: hipLaunchKernelGGL((KERNEL<NN, 3>), grid, dim3(256), lds, ctx->stream, __VA_ARGS__); break;    \
+        case 1: launch(ctx, (KERNEL<NN, 1>), grid, dim3(256), lds, __VA_ARGS__); break;     \
+        case 2: launch(ctx, (KERNEL<NN, 2>), grid, dim3(256), lds, __VA_ARGS__); break;     \
+        default: launch(ctx, (KERNEL<NN, 3>), grid, dim3(256), lds, __VA_ARGS__); break;    \
     }
 
 int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, const double* w, int64_t nk,
@@ -1092,7 +1092,7 @@ int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, co
         const dim3 grid((unsigned)nblocks, (unsigned)brows);
         ABZ_GGR_ND(ggr_window_kernel, a, partial, nrows);
         ABZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ggr_final_kernel, dim3((unsigned)cnt), dim3(256), 0, ctx->stream, partial, nrows, outd + s0);
+        launch(ctx, ggr_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, outd + s0);
         ABZ_HIP(hipGetLastError());
     }
     if (!mb) ABZ_HIP(hipMemcpyAsync(res.data(), outd, sizeof(double) * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));

@@ -596,7 +596,7 @@ int launch_ggr_rows(abz_ctx* ctx, const GgrRowsSpec& gs) {
 #define ABZ_GR(NPV, PV)                                                                                                              \
     {                                                                                                                                \
         ABZ_HIP(hipFuncSetAttribute((const void*)ggr_rows_kernel<NPV, PV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   \
-        hipLaunchKernelGGL((ggr_rows_kernel<NPV, PV>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);                      \
+        launch(ctx, (ggr_rows_kernel<NPV, PV>), dim3((unsigned)blocks), dim3(256), lds, a);                      \
     }
     if (np == 8 && pad) ABZ_GR(8, true)
     else if (np == 8) ABZ_GR(8, false)

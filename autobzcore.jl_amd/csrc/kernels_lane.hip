@@ -428,7 +428,7 @@ int lane_launch_n(abz_ctx* ctx, const LaneArgs& a, int mode, size_t lds, int64_t
 #define ABZ_LN(MV)                                                                                                             \
     {                                                                                                                          \
         ABZ_HIP(hipFuncSetAttribute((const void*)lane_grid_kernel<N, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((lane_grid_kernel<N, MV>), dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a);                 \
+        launch(ctx, (lane_grid_kernel<N, MV>), dim3((unsigned)blocks), dim3(256), lds, a);                 \
     }
     if (mode == 1) ABZ_LN(1)
     else if (mode == 2) ABZ_LN(2)
@@ -555,10 +555,10 @@ int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
     {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         switch (rs.n) {
-            case 5: hipLaunchKernelGGL(lane_scan_kernel<5>, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); break;
-            case 6: hipLaunchKernelGGL(lane_scan_kernel<6>, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); break;
-            case 7: hipLaunchKernelGGL(lane_scan_kernel<7>, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); break;
-            default: hipLaunchKernelGGL(lane_scan_kernel<8>, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, a); break;
+            case 5: launch(ctx, lane_scan_kernel<5>, dim3((unsigned)blocks), dim3(256), lds, a); break;
+            case 6: launch(ctx, lane_scan_kernel<6>, dim3((unsigned)blocks), dim3(256), lds, a); break;
+            case 7: launch(ctx, lane_scan_kernel<7>, dim3((unsigned)blocks), dim3(256), lds, a); break;
+            default: launch(ctx, lane_scan_kernel<8>, dim3((unsigned)blocks), dim3(256), lds, a); break;
         }
         ABZ_HIP(hipGetLastError());
         if ((rc = launch_final_reduce(ctx, a.partial, blocks * 4, rs.n_sweep, rs.scale, outd))) return rc;

@@ -120,8 +120,9 @@ int abz_ctx_create_on_stream(int device, void* hip_stream, abz_ctx** out);
 int abz_ctx_destroy(abz_ctx* ctx);
 int abz_ctx_sync(abz_ctx* ctx);
 /* HIP-event timing of the library's own launches on the context's stream.  on = 0: off; 1: every
- * kernel id; otherwise a mask with bit (k+1) selecting ABZ_K_<k> (timing one kernel keeps the event
- * records out of the gaps between the others). */
+ * kernel id; otherwise a mask with bit (k+1) selecting ABZ_K_<k>.  The events are bound to the kernel
+ * dispatches themselves (no marker packets between launches): a timed call of several launches runs
+ * from the start of its first kernel to the end of its last; memsets and copies are not timed. */
 int abz_prof_enable(abz_ctx* ctx, int on);
 int abz_prof_reset(abz_ctx* ctx);
 int abz_prof_read(abz_ctx* ctx, int kernel_id, double* total_ms, int64_t* launches);
