@@ -48,6 +48,7 @@ PROTOTYPES = {
     "abz_rule_reduce_device": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "abz_rule_values_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p]),
     "abz_rule_ggr": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
+    "abz_rule_ltm": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_mem_info": (C.c_int, [C.c_void_p, c_i64p]),
     "abz_symptr_rule": (C.c_int, [C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
     "abz_symptr_rule_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
@@ -71,7 +72,8 @@ WANT_H_COMPACT = 8  # with WANT_H on a Hermitian series of n <= 4 bands: upper-t
 WANT_H_ROW_MAJOR = 16  # abz_eval_nodes: matrices row-major in H_out (numpy's order; abzhip.h)
 F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = range(7)
 LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = 0, 1, 2, 3
-K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD = range(6)
+K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
+LTM_DOS, LTM_STATES = 0, 1
 ERR_ARG, ERR_HIP, ERR_NOGPU, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 
 

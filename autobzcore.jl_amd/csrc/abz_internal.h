@@ -434,6 +434,9 @@ int launch_big_vec(abz_ctx* ctx, const double* tri, int64_t tri_nk, const double
                    int64_t nnodes, int n, int d, PlaneView E, PlaneView V);
 int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, const double* w, int64_t nk,
                const double* Es_host, int nE, double* out_host);
+// Linear tetrahedron scan (kernels_ltm.hip) over the eigenvalue planes of a whole periodic grid of npt^d nodes:
+// g(E) or, with `states`, N(E), per unit cell and summed over the n bands
+int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host);
 
 // tiled planar (ncomp planes of the view) -> AoS [nk][ncomp] on the host
 int export_planes(abz_ctx* ctx, PlaneView v, int ncomp, int64_t nk, double* host_out, int row_major_n = 0);

@@ -2005,6 +2005,26 @@ int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out) try {
     return launch_ggr(ctx, r->s->n, r->s->d, r->npt, r->E, r->V, r->w, r->nk, E, nE, out);
 } ABZ_CATCH_ALL
 
+int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) try {
+    int rc0 = check_rule(r);
+    if (rc0) return rc0;
+    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm: bad arguments");
+    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES, "abz_rule_ltm: what = %d is neither ABZ_LTM_DOS nor ABZ_LTM_STATES", what);
+    ABZ_REQUIRE(r->E.base, "LTM needs a rule built with ABZ_WANT_EIG");
+    const int d = r->s->d;
+    int64_t ngrid = 1;
+    for (int j = 0; j < d; ++j) ngrid *= r->npt;
+    if (!r->full || r->k_offset != 0 || r->nk != ngrid) {
+        // the simplices of a cell need all its 2^d corners: a slab lacks one halo plane, a list of irreducible nodes the mesh
+        set_error("abz_rule_ltm: the rule is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)",
+                  r->full ? "a slab of the outermost variable" : "irreducible nodes of a symmetric rule");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    return launch_ltm(ctx, r->s->n, d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out);
+} ABZ_CATCH_ALL
+
 // ---------------------------------------------------------------- arbitrary nodes
 int abz_eval_nodes(abz_series* s, const double* k, int64_t nk, int want, double* H_out, double* eig_out) try {
     int rc = check_series(s);

@@ -484,3 +484,15 @@ class DeviceRule:
         if self.h is not None:
             L.check(L.lib().abz_rule_ggr(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), out.ctypes.data_as(L.c_f64p)))
         return self._sum_over_ranks(out)
+
+    def ltm(self, Es, states=False):
+        """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
+        number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid."""
+        if self.shard and self.shard[1] > 1:
+            raise NotImplementedError("LTM on a k-sharded (slab) rule is not implemented: the simplices of a slab's last "
+                                      "plane need one halo plane from the next rank")
+        Es = np.ascontiguousarray(np.asarray(Es, dtype=np.float64).reshape(-1))
+        out = np.zeros(len(Es))
+        L.check(L.lib().abz_rule_ltm(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), L.LTM_STATES if states else L.LTM_DOS,
+                                     out.ctypes.data_as(L.c_f64p)))
+        return out

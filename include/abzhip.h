@@ -95,6 +95,7 @@ typedef struct abz_rule abz_rule;     /* device-resident cached rule values (Fou
 #define ABZ_K_GGR 3        /* GGR formula scan (sum_ggr)                             */
 #define ABZ_K_EIG 4        /* stand-alone Hermitian eigensolve                        */
 #define ABZ_K_GGRBUILD 5   /* fused GGR build: H, dH/dk, eig, velocities per node (get_ggr_data, ref src/dos_ggr.jl:14-44) */
+#define ABZ_K_LTM 6        /* linear tetrahedron scan over cached eigenvalues (abz_rule_ltm) */
 #define ABZ_K_COUNT 8
 
 /* The library's own view of its memory, for leak checks and capacity planning (no reference counterpart):
@@ -248,6 +249,18 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
 
 /* Replaces: sum_ggr / ggr_formula (src/dos_ggr.jl:58-104) for nE energies; rule must hold VEL. */
 int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out);
+
+/* Linear tetrahedron method (Bloechl, Jepsen, Andersen, PRB 49, 16223, no curvature correction) on the eigenvalues of a
+ * full-grid rule (needs ABZ_WANT_EIG; velocities not needed).  The periodic grid's cells are cut into d! simplices by the
+ * Kuhn split, band b of a simplex is the b-th ascending eigenvalue at each corner.  out [nE] receives, per unit cell and
+ * summed over bands, the density of states g(E) (what = ABZ_LTM_DOS, integral over E = n) or the number of states below
+ * E (ABZ_LTM_STATES, n above all bands, exactly 0 below them).  Rules that are not a whole periodic grid (irreducible
+ * nodes, symmetric rules, slabs) return ABZ_ERR_UNSUPPORTED.
+ * Replaces: nothing yet -- the reference plans "LTM" (src/dos_algorithms.jl:1-7); entry point added without a change
+ * of ABZ_VERSION. */
+#define ABZ_LTM_DOS 0
+#define ABZ_LTM_STATES 1
+int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out);
 
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.

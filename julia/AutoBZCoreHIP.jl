@@ -11,6 +11,7 @@
 #   * BatchIntegrand f!(y, x, p)                          src/batch.jl:1-38
 #   * batchsolve                                          src/interfaces.jl:199-243
 #   * DOSProblem + GGR                                    src/dos_ggr.jl:1-104
+#   * DOSProblem + LTM (planned there)                    src/dos_algorithms.jl:1-7
 module AutoBZCoreHIP
 
 using AutoBZCore
@@ -364,6 +365,22 @@ function ggr(h::FourierSeries{S,N}, bz::SymmetricBZ, Es::Vector{Float64}; npt=50
     r = rule!(hs, npt, bz.syms, WANT_EIG | WANT_VEL)
     out = similar(Es)
     check(ccall((:abz_rule_ggr, libabz), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}), r.h, Es, length(Es), out))
+    return out
+end
+
+# ---------------------------------------------------------------- LTM
+"""
+    ltm(h, Es; npt=50, cumulative=false)
+
+Linear tetrahedron DOS g(E) (or, with `cumulative`, the number of states N(E)) from the eigenvalues of the FULL `npt^d`
+grid (`abz_rule_ltm`); the reference plans this method (src/dos_algorithms.jl:1-7).
+"""
+function ltm(h::FourierSeries{S,N}, Es::Vector{Float64}; npt=50, cumulative::Bool=false) where {S,N}
+    hs = HIPSeries(h)
+    r = rule!(hs, npt, nothing, WANT_EIG)
+    out = similar(Es)
+    check(ccall((:abz_rule_ltm, libabz), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Float64}), r.h, Es, length(Es),
+        cumulative ? 1 : 0, out))
     return out
 end
 
