@@ -41,7 +41,7 @@ int catch_status() noexcept;  // status + abz_last_error message of the exceptio
     } while (0)
 
 // ---- environment switches -------------------------------------------------------------------------------------------
-// Every switch the library reads, in one table (api.cpp: name, default, meaning; DESIGN.md section 11 repeats it).  They
+// Every switch the library reads, in one table (api.cpp: name, default, meaning; DESIGN.md section 12 repeats it).  They
 // exist for two reasons only: a test compares two code paths that must agree (the switch selects the one that is not the
 // default), or an operator sizes a resource.  Values are read per call -- tests flip them at run time.
 enum Switch {
@@ -84,8 +84,51 @@ int abz_switch(Switch s);  // the switch's integer value from the environment, o
 // arrays took 15-27 ms; staged: < 2 ms).  Both calls return when the data has arrived.
 int stage_h2d(abz_ctx* ctx, void* dst_dev, const void* src_host, size_t bytes);
 int stage_d2h(abz_ctx* ctx, void* dst_host, const void* src_dev, size_t bytes);
-// the context's pinned, device-visible mailbox (ctx->mbox / mbox_dev / mbox_cap): small inputs and results of a call
+// the context's pinned, device-visible mailbox (ctx->mbox / mbox_dev / mbox_cap): small inputs and results of a call.  Inputs
+// take its first half, results its second.
 int mbox_reserve(abz_ctx* ctx);
+
+// Swept values of a call to the device (scratch[5]): through the first half of the mailbox (memcpy + an asynchronous copy on
+// the context's stream, no synchronising pageable copy) or, where they do not fit, the staged upload.  The mailbox copy may
+// still be in flight when this returns: a caller synchronises the stream before it returns to ITS caller, so that the next
+// call finds the mailbox free.  rule_reduce, launch_lane_sum and launch_big_sum all end in sum_deliver to a host array, which
+// synchronises (and abz_ptr_sum synchronises once more); device-io scans take their swept values from the caller instead.
+int sweep_to_device(abz_ctx* ctx, const double* host, int n, const double** dev);
+
+// Where the `ncols` complex sums of a call end up: `host` alone, `dev` alone, `host` by way of a mailbox view, or a mailbox
+// view alone.
+struct SumOut {
+    double* host = nullptr;  // pageable host array [ncols][2]: a copy and a stream synchronisation
+    double* dev = nullptr;   // device array [ncols][2]: a device-to-device copy on the context's stream, nothing is synchronised
+    // mailbox view (device / host address of the same pinned memory): the last kernel writes the sums there itself, no copy
+    // call.  With map_host the stream is synchronised and the sums are copied to `host`; without it the launcher returns at
+    // once and the caller synchronises itself, after enqueueing more work.
+    double2* map_dev = nullptr;
+    const double2* map_host = nullptr;
+};
+// where the last kernel of a launcher writes columns [col0, col0 + ncols): the mailbox view when there is one, else scratch[2]
+// (reserved here)
+int sum_target(abz_ctx* ctx, const SumOut& so, int64_t col0, int64_t ncols, double2** where);
+// columns [col0, col0 + ncols), which the last kernel left at `from` (sum_target's answer), to where `so` wants them
+int sum_deliver(abz_ctx* ctx, const SumOut& so, const double2* from, int64_t col0, int64_t ncols);
+
+// The energy list of a GGR / LTM scan: sorted ascending (stable order of equal ones) on the device, and the room for one real
+// result per energy.  Energies in and sums out go through the pinned mailbox where they fit its halves -- an asynchronous
+// copy in, the last kernel writes the sums into host memory itself, one stream synchronisation per call -- else by plain copies.
+struct EnergyList {
+    std::vector<int> perm;         // sorted position -> position in the caller's list
+    std::vector<double> Es, res;   // sorted energies; results when the mailbox is not used
+    const double* dev = nullptr;   // device [n]: the sorted energies
+    double* out = nullptr;         // device-visible [n]: result of sorted energy i
+    double* extra = nullptr;       // device [extra]: scratch of the launcher behind the two
+    const double* res_host = nullptr;
+    bool mbox = false;
+    double inv_step = 0.0;         // 1 / step of an equispaced list of >= 8 energies (`uniform`), else 0: a thread computes its
+                                   // window's first index instead of searching
+};
+int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform, size_t extra, EnergyList& el);
+// synchronises the stream; out_host[i] = result of the caller's energy i
+int energies_deliver(abz_ctx* ctx, EnergyList& el, double* out_host);
 struct SymTables;
 int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, SymTables& out);
 void preload_symptr_code();  // kernels_symptr.hip: force the lazy code-object load
@@ -374,14 +417,16 @@ struct ReduceSpec {
     double* tri_cache = nullptr;  // 33...64 bands: the rule's room for the tridiagonal forms of its nodes [2 x 64][tri_nk] ...
     int64_t tri_nk = 0;
     int* tri_state = nullptr;     // ... and whether it holds them (set by the scan that fills it)
-    double* out_dev = nullptr;  // device [n_sweep][ncomp][2]: leave the result in HBM, no host synchronisation
-    double2* out_map_dev = nullptr;         // host-io calls: device view of the pinned mailbox region the sums are written to ...
-    const double2* out_map_host = nullptr;  // ... and its host view (read after the stream synchronisation; null with
-                                            // out_map_dev set: the launch returns without synchronising, n <= 4)
+    SumOut out;  // [n_sweep][ncomp] sums
 };
 int integrand_ncomp(int integrand, int n, int d);
-// result: host out_reim [n_sweep][ncomp][2]
-int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim);
+inline bool integrand_swept(int integrand) {  // the integrand is evaluated for a list of swept values
+    return integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC || integrand == ABZ_F_DOS_EIG;
+}
+inline int integrand_nparams(int integrand) {  // parameters it needs
+    return (integrand == ABZ_F_LINEAR || integrand == ABZ_F_LINEAR_X) ? 2 : (integrand_swept(integrand) ? 1 : 0);
+}
+int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs);
 
 int launch_gen_velocity(abz_ctx* ctx, int n, PlaneView U, PlaneView dH, PlaneView Vj, int64_t nk);
 
@@ -573,33 +618,34 @@ struct SumSpec {
     double scale;
     bool herm = true;  // the series is Hermitian (a series that is not goes through the inverse of every node)
     bool force_inverse = false;  // n <= 4 without a closed-form store-free kernel for this case: the inverse of every node as well
+    SumOut out;  // [n_sweep][ncomp] sums, scale * sum over the nlines * npt nodes
 };
 
 bool eval_sum_supported(int n, int M, int npt, int integrand, bool herm);
-int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim);
+int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss);
 int launch_final_reduce(abz_ctx* ctx, const double2* partial, int64_t nblocks, int64_t ncols, double scale, double2* out);
 // the same for 5..32 bands (kernels_generic.hip): resolvent-trace integrands, one workgroup per grid line
 bool gen_sum_supported(int n, int M, int npt, int integrand, bool herm);
 // 5...16 bands: can a rule of a Hermitian series keep H(k) as its upper triangle (ABZ_WANT_H_COMPACT)?  True when the row
 // kernel gen_grid_eig_kernel fills it (and every scan of kernels_generic.hip reads either layout)
 bool gen_compact_supported(int n, int M, int npt);
-int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim);
+int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss);
 // 33...64 bands (kernels_big.hip): wave-per-node Householder with the matrix in LDS, eigenvalues by bisection, resolvent
 // traces from the tridiagonal
 // 5...8 bands on full grids, one node per lane (kernels_lane.hip)
 bool lane_grid_supported(const GenSpec& gs);
 int launch_lane_grid(abz_ctx* ctx, const GenSpec& gs);
 bool lane_sum_supported(int n, int M, int first, int npt, int integrand, int n_sweep);
-int launch_lane_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim);
+int launch_lane_sum(abz_ctx* ctx, const SumSpec& ss);
 bool lane_scan_supported(const ReduceSpec& rs);
-int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim);
+int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs);
 bool big_supported(int n);
 bool big_inverse_wanted(int n, int integrand, bool herm);  // 5...64 bands: G / traces through big_inverse_kernel (scans, node values)
 bool big_inverse_sum_wanted(int n, int integrand, bool herm);  // ... store-free sums
 bool big_sum_supported(int n, int M, int npt, int integrand, bool herm);
 int launch_big_nodes(abz_ctx* ctx, const GenSpec& gs);
-int launch_big_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim);
-int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim);
-int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim);
+int launch_big_sum(abz_ctx* ctx, const SumSpec& ss);
+int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs);
+int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs);
 
 }  // namespace abz

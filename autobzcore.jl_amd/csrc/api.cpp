@@ -3,6 +3,7 @@
 #include <atomic>
 #include <cstdarg>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -290,6 +291,93 @@ int stage_d2h(abz_ctx* ctx, void* dst, const void* src, size_t bytes) {
     return ABZ_OK;
 }
 
+// the halves of the mailbox: inputs of a call in the first, its results in the second
+static bool mbox_half_fits(abz_ctx* ctx, size_t bytes) { return mbox_reserve(ctx) == ABZ_OK && bytes <= ctx->mbox_cap / 2; }
+template <class T>
+static T* mbox_results(abz_ctx* ctx, bool device_view) {
+    return reinterpret_cast<T*>(static_cast<char*>(device_view ? ctx->mbox_dev : ctx->mbox) + ctx->mbox_cap / 2);
+}
+
+int sweep_to_device(abz_ctx* ctx, const double* host, int n, const double** dev) {
+    const size_t bytes = sizeof(double) * (size_t)n;
+    int rc = ctx->scratch[5].reserve(std::max(bytes, sizeof(double)));
+    if (rc) return rc;
+    if (mbox_half_fits(ctx, bytes)) {
+        std::memcpy(ctx->mbox, host, bytes);
+        ABZ_HIP(hipMemcpyAsync(ctx->scratch[5].p, ctx->mbox, bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else if ((rc = stage_h2d(ctx, ctx->scratch[5].p, host, bytes))) {
+        return rc;
+    }
+    *dev = ctx->scratch[5].as<double>();
+    return ABZ_OK;
+}
+
+int sum_target(abz_ctx* ctx, const SumOut& so, int64_t col0, int64_t ncols, double2** where) {
+    if (so.map_dev) {
+        *where = so.map_dev + col0;
+        return ABZ_OK;
+    }
+    int rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)ncols);
+    *where = ctx->scratch[2].as<double2>();
+    return rc;
+}
+
+int sum_deliver(abz_ctx* ctx, const SumOut& so, const double2* from, int64_t col0, int64_t ncols) {
+    const size_t bytes = sizeof(double2) * (size_t)ncols;
+    if (so.dev) {  // the sums stay in HBM (they feed a collective on the same stream); `from` is reused in stream order
+        ABZ_HIP(hipMemcpyAsync(so.dev + 2 * col0, from, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        return ABZ_OK;
+    }
+    if (so.map_dev) {  // the last kernel wrote the sums into the pinned mailbox: one synchronisation, no copy call
+        if (!so.map_host) return ABZ_OK;  // ... which the caller does itself, after enqueueing more work
+        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        std::memcpy(so.host + 2 * col0, so.map_host + col0, bytes);
+        return ABZ_OK;
+    }
+    ABZ_HIP(hipMemcpyAsync(so.host + 2 * col0, from, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ABZ_HIP(hipStreamSynchronize(ctx->stream));
+    return ABZ_OK;
+}
+
+int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform, size_t extra, EnergyList& el) {
+    el.perm.resize((size_t)n);
+    for (int i = 0; i < n; ++i) el.perm[(size_t)i] = i;
+    std::stable_sort(el.perm.begin(), el.perm.end(), [&](int x, int y) { return Es_host[x] < Es_host[y]; });
+    el.Es.resize((size_t)n);
+    for (int i = 0; i < n; ++i) el.Es[(size_t)i] = Es_host[el.perm[(size_t)i]];
+    const size_t bytes = sizeof(double) * (size_t)n;
+    int rc = ctx->scratch[2].reserve(2 * bytes + sizeof(double) * extra);
+    if (rc) return rc;
+    double* const Es_dev = ctx->scratch[2].as<double>();
+    el.dev = Es_dev;
+    el.extra = Es_dev + 2 * (size_t)n;
+    el.mbox = mbox_half_fits(ctx, bytes);
+    if (el.mbox) {
+        std::memcpy(ctx->mbox, el.Es.data(), bytes);
+        ABZ_HIP(hipMemcpyAsync(Es_dev, ctx->mbox, bytes, hipMemcpyHostToDevice, ctx->stream));
+        el.out = mbox_results<double>(ctx, true);
+        el.res_host = mbox_results<const double>(ctx, false);
+    } else {
+        ABZ_HIP(hipMemcpyAsync(Es_dev, el.Es.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        el.out = Es_dev + n;
+        el.res.resize((size_t)n);
+        el.res_host = el.res.data();
+    }
+    const double step = n >= 2 ? (el.Es[(size_t)n - 1] - el.Es[0]) / (double)(n - 1) : 0.0;
+    bool uni = uniform && n >= 8 && step > 0.0;
+    for (int i = 0; i < n && uni; ++i) uni = std::fabs(el.Es[(size_t)i] - (el.Es[0] + (double)i * step)) <= 1e-6 * step;
+    el.inv_step = uni ? 1.0 / step : 0.0;
+    return ABZ_OK;
+}
+
+int energies_deliver(abz_ctx* ctx, EnergyList& el, double* out_host) {
+    const size_t n = el.perm.size();
+    if (!el.mbox) ABZ_HIP(hipMemcpyAsync(el.res.data(), el.out, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    ABZ_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) out_host[el.perm[i]] = el.res_host[i];
+    return ABZ_OK;
+}
+
 int DevBuf::reserve(size_t bytes) {
     if (!view && bytes <= cap) return ABZ_OK;
     release();
@@ -489,6 +577,29 @@ static int plan_upload(abz_ctx* ctx, const Plan& p, PlanDev& pd) {
     if (!p.run_start.empty()) {
         int rc = upload(ctx, pd.runs, p.run_start.data(), p.run_start.size());
         if (rc) return rc;
+    }
+    return ABZ_OK;
+}
+
+// full grids: the phase tables [npt][M] of the contraction levels, for the scalar-phase contraction kernel
+static int level_phase_tables(abz_series* s, int npt, const double2* tab, PlanDev& pd) {
+    for (int L = 1; L < s->d; ++L) {
+        const int M = s->dims[L];
+        int rc = pd.phg[L].reserve(sizeof(double2) * (size_t)npt * M);
+        if (rc) return rc;
+        PhaseSpec ps;
+        ps.B = npt;
+        ps.M = M;
+        ps.first = s->first[L];
+        ps.gi = nullptr;
+        ps.x = nullptr;
+        ps.tab = tab;
+        ps.npt = npt;
+        ps.g0 = 0;
+        ps.gcnt = npt;
+        ps.period = s->period[L];
+        ps.deriv = false;
+        if ((rc = launch_phases(s->ctx, ps, pd.phg[L].as<double2>()))) return rc;
     }
     return ABZ_OK;
 }
@@ -1002,6 +1113,12 @@ static int rule_fill(abz_rule* r) {
         set_error("the rule keeps H(k) as an upper triangle (ABZ_WANT_H_COMPACT) and the series is no longer Hermitian: build a new rule");
         return ABZ_ERR_ARG;
     }
+    // level-1 families of the fused GGR builds: src[0] plain, src[j - 1] with the derivative factor on variable j >= 2
+    auto family_chains = [&](const double2** src) -> int {
+        int rc = build_chain(s, plan, rp->pd, tab, 0, &src[0]);
+        for (int j = 2; j <= d && !rc; ++j) rc = build_chain(s, plan, rp->pd, tab, j, &src[j - 1], 1, &rp->fam[j - 2]);
+        return rc;
+    };
     bool vel_done = false;
     if (rule_ggr_rows(r)) {
         // 5...32 bands: H, every dH/dk_j, eigenvalues, eigenvectors and velocities of a node in the registers of its lanes
@@ -1024,9 +1141,7 @@ static int rule_fill(abz_rule* r) {
             gs.nk = r->nk;
         }
         int rc;
-        if ((rc = build_chain(s, plan, rp->pd, tab, 0, &gs.src[0]))) return rc;
-        for (int j = 2; j <= d; ++j)
-            if ((rc = build_chain(s, plan, rp->pd, tab, j, &gs.src[j - 1], 1, &rp->fam[j - 2]))) return rc;
+        if ((rc = family_chains(gs.src))) return rc;
         if (!big_supported(n)) return launch_ggr_rows(ctx, gs);
         if ((rc = launch_big_ggr(ctx, gs)) || !(r->want & ABZ_WANT_H)) return rc;
         vel_done = true;  // the matrices as well: the plain build below, without its eigenvalues
@@ -1058,18 +1173,14 @@ static int rule_fill(abz_rule* r) {
                 const int64_t nparents = gs.nlines / std::max(gs.gcnt, 1);
                 if ((rc = rp->fam[0].reserve(sizeof(double2) * ggr_build_pack2_elems(n, d, gs.M, gs.M2, nparents)))) return rc;
                 gs.pack2 = rp->fam[0].as<double2>();
-            } else {
-                if ((rc = build_chain(s, plan, rp->pd, tab, 0, &gs.src[0]))) return rc;
-                for (int j = 2; j <= d; ++j)
-                    if ((rc = build_chain(s, plan, rp->pd, tab, j, &gs.src[j - 1], 1, &rp->fam[j - 2]))) return rc;
+            } else if ((rc = family_chains(gs.src))) {
+                return rc;
             }
         } else {
             gs.nk = r->nk;
             gs.parents = d == 1 ? nullptr : rp->pd.parent[0].as<int64_t>();
             gs.gi = rp->pd.gi[0].as<int32_t>();
-            if ((rc = build_chain(s, plan, rp->pd, tab, 0, &gs.src[0]))) return rc;
-            for (int j = 2; j <= d; ++j)
-                if ((rc = build_chain(s, plan, rp->pd, tab, j, &gs.src[j - 1], 1, &rp->fam[j - 2]))) return rc;
+            if ((rc = family_chains(gs.src))) return rc;
         }
         return launch_ggr_build(ctx, gs);
     }
@@ -1250,25 +1361,7 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
     lap("plan_upload");
     RULE_TRY(make_phase_table(ctx, npt, rp->tab));
     lap("phase_table");
-    if (r->full) {  // per-level phase tables [npt][M] for the scalar-phase contraction kernel
-        for (int L = 1; L < d; ++L) {
-            const int M = s->dims[L];
-            RULE_TRY(rp->pd.phg[L].reserve(sizeof(double2) * (size_t)npt * M));
-            PhaseSpec ps;
-            ps.B = npt;
-            ps.M = M;
-            ps.first = s->first[L];
-            ps.gi = nullptr;
-            ps.x = nullptr;
-            ps.tab = rp->tab.as<double2>();
-            ps.npt = npt;
-            ps.g0 = 0;
-            ps.gcnt = npt;
-            ps.period = s->period[L];
-            ps.deriv = false;
-            RULE_TRY(launch_phases(ctx, ps, rp->pd.phg[L].as<double2>()));
-        }
-    }
+    if (r->full) RULE_TRY(level_phase_tables(s, npt, rp->tab.as<double2>(), rp->pd));
     const size_t bytes = sizeof(double) * (size_t)(r->ntiles * (int64_t)r->planes * pitch);
     RULE_TRY(dev_alloc((void**)&r->vals, bytes, &r->vals_cap));
     // on the context's stream: it is non-blocking, a null-stream memset would not be ordered before the
@@ -1502,11 +1595,10 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
         ABZ_REQUIRE(r->E.base, "integrand needs cached eigenvalues: build the rule with ABZ_WANT_EIG");
     else if (integrand != ABZ_F_ONE)
         ABZ_REQUIRE(r->H.base, "integrand needs cached H(k): build the rule with ABZ_WANT_H");
-    const bool swept = integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC ||
-                       integrand == ABZ_F_DOS_EIG;
+    const bool swept = integrand_swept(integrand);
     int ns = swept ? n_sweep : 1;
     ABZ_REQUIRE(ns >= 1 && (!swept || sweep), "sweep values required for integrand %d", integrand);
-    const int need = (integrand == ABZ_F_LINEAR || integrand == ABZ_F_LINEAR_X) ? 2 : (swept ? 1 : 0);
+    const int need = integrand_nparams(integrand);
     ABZ_REQUIRE(nparams >= need && (need == 0 || params), "integrand %d needs %d parameters", integrand, need);
     ReduceSpec rs;
     rs.n = r->s->n;
@@ -1535,34 +1627,28 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
     if (swept && device_io) {
         rs.sweep_dev = sweep;
     } else if (swept) {
-        // through the pinned mailbox: an asynchronous copy on the context's stream (a pageable source is staged by the
-        // runtime and the small-copy path of upload() synchronises the stream before the first launch)
-        const size_t sb = sizeof(double) * (size_t)ns;
-        int rc = ctx->scratch[5].reserve(sb);
+        int rc = sweep_to_device(ctx, sweep, ns, &rs.sweep_dev);
         if (rc) return rc;
-        if (mbox_reserve(ctx) == ABZ_OK && sb <= ctx->mbox_cap / 2) {
-            std::memcpy(ctx->mbox, sweep, sb);
-            ABZ_HIP(hipMemcpyAsync(ctx->scratch[5].p, ctx->mbox, sb, hipMemcpyHostToDevice, ctx->stream));
-        } else if ((rc = upload(ctx, ctx->scratch[5], sweep, (size_t)ns))) {
-            return rc;
-        }
-        rs.sweep_dev = ctx->scratch[5].as<double>();
     }
     double vol = 1.0;
     for (int j = 0; j < rs.d; ++j) vol *= (double)r->npt;
     rs.scale = 1.0 / (vol * (double)nsyms);
+    // The mailbox is offered up to four bands only (and never allocated for the sums' sake): how many copy calls a scan makes
+    // is decided here, and a launcher that is handed a view uses it.
     if (device_io && map_dev && rs.n <= 4)
-        rs.out_map_dev = map_dev;
+        rs.out.map_dev = map_dev;
     else if (device_io)
-        rs.out_dev = out_reim;
+        rs.out.dev = out_reim;
+    else
+        rs.out.host = out_reim;
     if (!device_io && rs.n <= 4 && ctx->mbox) {  // sums land in the second half of the mailbox (zero copy)
         const int nc = integrand_ncomp(integrand, rs.n, rs.d);
         if (nc > 0 && sizeof(double2) * (size_t)ns * (size_t)nc <= ctx->mbox_cap / 2) {
-            rs.out_map_dev = reinterpret_cast<double2*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
-            rs.out_map_host = reinterpret_cast<const double2*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
+            rs.out.map_dev = mbox_results<double2>(ctx, true);
+            rs.out.map_host = mbox_results<const double2>(ctx, false);
         }
     }
-    return launch_reduce(ctx, rs, device_io ? nullptr : out_reim);
+    return launch_reduce(ctx, rs);
 }
 
 int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int integrand, const double* params, int nparams,
@@ -1586,9 +1672,9 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
         set_error("store-free sum not available for this series / grid / integrand (use a rule)");
         return ABZ_ERR_UNSUPPORTED;
     }
-    const bool swept = integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC || integrand == ABZ_F_DOS_EIG;
+    const bool swept = integrand_swept(integrand);
     ABZ_REQUIRE(!swept || (sweep && n_sweep >= 1), "sweep values required for integrand %d", integrand);
-    const int need = (integrand == ABZ_F_LINEAR || integrand == ABZ_F_LINEAR_X) ? 2 : (swept ? 1 : 0);
+    const int need = integrand_nparams(integrand);
     ABZ_REQUIRE(nparams >= need && (need == 0 || params), "integrand %d needs %d parameters", integrand, need);
     abz_ctx* ctx = s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
@@ -1602,23 +1688,7 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
         return code;
     };
     if ((rc = make_phase_table(ctx, npt, tab))) return done(rc);
-    for (int L = 1; L < d; ++L) {  // scalar-phase tables of the contraction levels
-        const int M = s->dims[L];
-        if ((rc = pd.phg[L].reserve(sizeof(double2) * (size_t)npt * M))) return done(rc);
-        PhaseSpec ps;
-        ps.B = npt;
-        ps.M = M;
-        ps.first = s->first[L];
-        ps.gi = nullptr;
-        ps.x = nullptr;
-        ps.tab = tab.as<double2>();
-        ps.npt = npt;
-        ps.g0 = 0;
-        ps.gcnt = npt;
-        ps.period = s->period[L];
-        ps.deriv = false;
-        if ((rc = launch_phases(ctx, ps, pd.phg[L].as<double2>()))) return done(rc);
-    }
+    if ((rc = level_phase_tables(s, npt, tab.as<double2>(), pd))) return done(rc);
     const double2* level1 = nullptr;
     // n <= 4: the store-free kernel takes packed Hermitian sets (eval_sum_supported requires a Hermitian series)
     if ((rc = build_chain(s, plan, pd, tab.as<double2>(), 0, &level1, 1, nullptr, !generic))) return done(rc);
@@ -1638,11 +1708,12 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
     ss.force_inverse = inv_small;
     ss.n_sweep = n_sweep;
     ss.sweep_host = sweep;
+    ss.out.host = out_reim;
     for (int i = 0; i < 4; ++i) ss.params[i] = (i < nparams && params) ? params[i] : 0.0;
     double vol = 1.0;
     for (int j = 0; j < d; ++j) vol *= (double)npt;
     ss.scale = 1.0 / (vol * (double)nsyms);
-    rc = inv_small ? launch_big_sum(ctx, ss, out_reim) : (generic ? launch_gen_sum(ctx, ss, out_reim) : launch_eval_sum(ctx, ss, out_reim));
+    rc = inv_small ? launch_big_sum(ctx, ss) : (generic ? launch_gen_sum(ctx, ss) : launch_eval_sum(ctx, ss));
     (void)hipStreamSynchronize(ctx->stream);
     return done(rc);
 } ABZ_CATCH_ALL
@@ -1713,7 +1784,7 @@ int abz_autoptr_solve_many(abz_series* s, const int32_t* syms, int nsyms, int in
     const int d = s->d, n = s->n;
     const int ncomp = integrand_ncomp(integrand, n, d);
     ABZ_REQUIRE(ncomp > 0, "unknown integrand id %d", integrand);
-    const bool swept = integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC || integrand == ABZ_F_DOS_EIG;
+    const bool swept = integrand_swept(integrand);
     ABZ_REQUIRE(!swept || sweeps, "sweep values required for integrand %d", integrand);
     ABZ_REQUIRE(swept || n_sweep == 1, "integrand %d has no swept parameter: n_sweep must be 1", integrand);
     abz_ctx* ctx = s->ctx;

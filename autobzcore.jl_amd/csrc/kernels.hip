@@ -1665,7 +1665,7 @@ __global__ __launch_bounds__(256, 3) void dos3_scan_kernel(ReduceArgs a, double 
 }
 
 // mode 0: ABZ_F_DOS on the H planes of a Hermitian rule; mode 1: ABZ_F_DOS_EIG on the eigenvalue planes
-static int launch_dos3(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a0, int mode) {
+static int launch_dos3(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a0, int mode, double2* outd) {
     ReduceArgs a = a0;
     // KT = 8 nodes per thread at 3 waves per SIMD (KT = 4 ... 7, and 6 or 4 at 4 waves per SIMD, measured the same to 3 % at
     // 150^3: the kernel is bound by VALU issue).  Small rules (one rank's slab of a k-sharded grid) split the SWEEP over
@@ -1696,7 +1696,7 @@ static int launch_dos3(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a0,
                            ctx->scratch[1].as<double2>());
     ABZ_HIP(hipGetLastError());
     launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->scratch[1].as<double2>(),
-                       nblocks, ncols, scale, rs.out_map_dev ? rs.out_map_dev : ctx->scratch[2].as<double2>());
+                       nblocks, ncols, scale, outd);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -1929,15 +1929,13 @@ bool eval_sum_supported(int n, int M, int npt, int integrand, bool herm) {
     return integrand >= ABZ_F_ONE && integrand <= ABZ_F_DOS_EIG;
 }
 
-// out_reim [n_sweep][ncomp][2] (host): scale * sum over the nlines * npt nodes
-int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
+int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss) {
     const int ncomp = integrand_ncomp(ss.integrand, ss.n, ss.d);
-    const bool swept = ss.integrand == ABZ_F_DOS || ss.integrand == ABZ_F_TRGLOC || ss.integrand == ABZ_F_GLOC ||
-                       ss.integrand == ABZ_F_DOS_EIG;
+    const bool swept = integrand_swept(ss.integrand);
     const int ns = swept ? ss.n_sweep : 1;
     if (ss.integrand == ABZ_F_ONE) {  // the sum of ones
-        out_reim[0] = ss.scale * (double)ss.nlines * (double)ss.npt;
-        out_reim[1] = 0.0;
+        ss.out.host[0] = ss.scale * (double)ss.nlines * (double)ss.npt;
+        ss.out.host[1] = 0.0;
         return ABZ_OK;
     }
     EvalArgs a{};
@@ -1971,9 +1969,7 @@ int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
     const int nwmax = (ss.integrand == ABZ_F_GLOC || ss.integrand == ABZ_F_LINEAR_X) ? 1 : 8;
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * nwmax * ncomp));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)(nwmax * ncomp)))) return rc;
     double2* partial = ctx->scratch[1].as<double2>();
-    double2* outd = ctx->scratch[2].as<double2>();
     for (int s0 = 0; s0 < ns; s0 += nwmax) {
         SumArgs q;
         q.fid = ss.integrand;
@@ -1982,6 +1978,9 @@ int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
         q.d = ss.d;
         for (int i = 0; i < 4; ++i) q.p[i] = ss.params[i];
         for (int w = 0; w < 8; ++w) q.sweep[w] = (swept && w < q.nw) ? ss.sweep_host[s0 + w] : 0.0;
+        const int64_t col0 = (int64_t)s0 * ncomp, ncols = (int64_t)q.nw * ncomp;
+        double2* outd = nullptr;
+        if ((rc = sum_target(ctx, ss.out, col0, ncols, &outd))) return rc;
         {
             ProfScope ps(ctx, ABZ_K_EVAL);
 #define SUMK(NN, KK, FF, WW) \
@@ -2012,14 +2011,11 @@ int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
 #undef SUMN
 #undef SUMK
             ABZ_HIP(hipGetLastError());
-            const int64_t ncols = (int64_t)q.nw * ncomp;
             launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, partial, blocks, ncols,
                                ss.scale, outd);
             ABZ_HIP(hipGetLastError());
         }
-        ABZ_HIP(hipMemcpyAsync(out_reim + 2 * (size_t)s0 * ncomp, outd, sizeof(double2) * (size_t)(q.nw * ncomp),
-                               hipMemcpyDeviceToHost, ctx->stream));
-        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = sum_deliver(ctx, ss.out, outd, col0, ncols))) return rc;
     }
     return ABZ_OK;
 }
@@ -2042,7 +2038,7 @@ constexpr int reduce_kt_of() {
 // 27 per swept value).  KT = 2 instead of 8 was measured too: 4x the blocks but 0.227 ms -- the per-value wave reduction
 // is then amortised over 2 nodes instead of 8.
 template <int N, int FID, bool HERM>
-static int launch_reduce_h(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a0) {
+static int launch_reduce_h(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a0, double2* outd) {
     constexpr int KT = reduce_kt_of<N, FID, HERM>();
     constexpr int NC = NComp<FID>::template value<N>();
     const int64_t nblocks = cdiv(rs.nk, 256 * KT);
@@ -2069,20 +2065,20 @@ static int launch_reduce_h(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs&
                        ctx->scratch[1].as<double2>());
     ABZ_HIP(hipGetLastError());
     launch(ctx, final_reduce_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->scratch[1].as<double2>(),
-                       nblocks, ncols, rs.scale, rs.out_map_dev ? rs.out_map_dev : ctx->scratch[2].as<double2>());
+                       nblocks, ncols, rs.scale, outd);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
 
 // Hermitian rules take the real-polynomial / adjugate paths where they exist
 template <int N, int FID>
-static int launch_reduce_t(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a) {
+static int launch_reduce_t(abz_ctx* ctx, const ReduceSpec& rs, const ReduceArgs& a, double2* outd) {
     constexpr bool canH = ((N == 2 || N == 3 || N == 4) && (FID == ABZ_F_DOS || FID == ABZ_F_TRGLOC)) || ((N == 3 || N == 4) && FID == ABZ_F_GLOC);
     if constexpr (N == 3 && (FID == ABZ_F_DOS || FID == ABZ_F_DOS_EIG)) {  // the sweep kernel of 3-band DOS scans
-        if (abz_switch(SW_DOS3_SCAN) && (FID == ABZ_F_DOS_EIG || rs.herm)) return launch_dos3(ctx, rs, a, FID == ABZ_F_DOS ? 0 : 1);
+        if (abz_switch(SW_DOS3_SCAN) && (FID == ABZ_F_DOS_EIG || rs.herm)) return launch_dos3(ctx, rs, a, FID == ABZ_F_DOS ? 0 : 1, outd);
     }
-    if (canH && rs.herm) return launch_reduce_h<N, FID, canH>(ctx, rs, a);
-    return launch_reduce_h<N, FID, false>(ctx, rs, a);
+    if (canH && rs.herm) return launch_reduce_h<N, FID, canH>(ctx, rs, a, outd);
+    return launch_reduce_h<N, FID, false>(ctx, rs, a, outd);
 }
 
 template <int FID>
@@ -2090,8 +2086,8 @@ static constexpr int reduce_kt(int n) {
     return (FID == ABZ_F_GLOC || n >= 4) ? 1 : 2;
 }
 
-int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
-    if (rs.n > 4) return launch_gen_reduce(ctx, rs, out_reim);
+int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs) {
+    if (rs.n > 4) return launch_gen_reduce(ctx, rs);
     const int ncomp = integrand_ncomp(rs.integrand, rs.n, rs.d);
     if (ncomp < 0) {
         set_error("unknown integrand id %d", rs.integrand);
@@ -2115,18 +2111,18 @@ int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
     a.ncomp = ncomp;
     for (int i = 0; i < 4; ++i) a.p[i] = rs.params[i];
     const int64_t ncols = (int64_t)rs.n_sweep * ncomp;
-    int rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)ncols);
+    double2* outd = nullptr;
+    int rc = sum_target(ctx, rs.out, 0, ncols, &outd);
     if (rc) return rc;
-    double2* outd = ctx->scratch[2].as<double2>();
     {
         ProfScope ps(ctx, ABZ_K_REDUCE);
 #define CASE(FID)                                                          \
     case FID:                                                              \
         switch (rs.n) {                                                    \
-            case 1: rc = launch_reduce_t<1, FID>(ctx, rs, a); break;       \
-            case 2: rc = launch_reduce_t<2, FID>(ctx, rs, a); break;       \
-            case 3: rc = launch_reduce_t<3, FID>(ctx, rs, a); break;       \
-            case 4: rc = launch_reduce_t<4, FID>(ctx, rs, a); break;       \
+            case 1: rc = launch_reduce_t<1, FID>(ctx, rs, a, outd); break; \
+            case 2: rc = launch_reduce_t<2, FID>(ctx, rs, a, outd); break; \
+            case 3: rc = launch_reduce_t<3, FID>(ctx, rs, a, outd); break; \
+            case 4: rc = launch_reduce_t<4, FID>(ctx, rs, a, outd); break; \
             default:                                                       \
                 set_error("n = %d bands: only n <= 4 is built in this round", rs.n); \
                 return ABZ_ERR_UNSUPPORTED;                                \
@@ -2144,19 +2140,7 @@ int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
 #undef CASE
         if (rc) return rc;
     }
-    if (rs.out_dev) {  // the sums stay in HBM (they feed a collective on the same stream)
-        ABZ_HIP(hipMemcpyAsync(rs.out_dev, outd, sizeof(double2) * (size_t)ncols, hipMemcpyDeviceToDevice, ctx->stream));
-        return ABZ_OK;
-    }
-    if (rs.out_map_dev) {  // the last kernel wrote the sums into the pinned mailbox: one synchronisation, no copy call
-        if (!rs.out_map_host) return ABZ_OK;  // ... which the caller does itself, after enqueueing more work
-        ABZ_HIP(hipStreamSynchronize(ctx->stream));
-        std::memcpy(out_reim, rs.out_map_host, sizeof(double2) * (size_t)ncols);
-        return ABZ_OK;
-    }
-    ABZ_HIP(hipMemcpyAsync(out_reim, outd, sizeof(double2) * (size_t)ncols, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, rs.out, outd, 0, ncols);
 }
 
 // ------------------------------------------------------------------------------------------

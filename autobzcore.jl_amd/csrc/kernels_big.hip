@@ -17,6 +17,7 @@
 // matrices or the eigenvalues), store-free PTR sums and the IAI node path; big_inverse_kernel (one workgroup per node, Gauss-
 // Jordan in registers) adds matrix-valued G and the traces of series that are not Hermitian; GGR builds (eigenvalues + band
 // velocities): launch_big_ggr below with kernels_big_vec.hip.  (The Hermitian-compact layout ends at 16 bands.)
+#include <optional>
 #include <utility>
 
 #include "abz_internal.h"
@@ -1198,17 +1199,105 @@ bool big_sum_supported(int n, int M, int npt, int integrand, bool herm) {
     return big_supported(n) && herm && (integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC);
 }
 
-// store-free PTR sums (abz_ptr_sum)
-int launch_big_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
-    const int64_t nnodes = ss.nlines * ss.npt;
-    BigWork w;
-    int rc = big_reserve(ctx, ss.n, ss.npt, nnodes, w);
+// What the store-free sums and the scans of cached matrices share: the same two algorithms over chunks of nodes, which differ in
+// how a chunk's matrices reach Hbuf (`fill(c0, cn)`: the series evaluated, or the rule's planes loaded), in the weights, in the
+// kernel id their time is booked under and in where the sums go.
+struct BigJob {
+    int n, integrand, n_sweep;
+    int64_t nnodes;
+    double eta, scale;
+    const double* sweep;    // device [n_sweep]
+    const double* weights;  // device [nnodes], null: 1
+    int prof_id;
+    const SumOut* out;
+};
+
+static int big_load_h(abz_ctx* ctx, const BigWork& w, int n, PlaneView H, int64_t c0, int64_t cn) {
+    launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * n * n, 256), 256 * 16)), dim3(256), 0, w.Hbuf, c0, cn, n, H);
+    ABZ_HIP(hipGetLastError());
+    return ABZ_OK;
+}
+
+static int big_scale(abz_ctx* ctx, double2* v, int n, double s) {
+    launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(n, 256)), dim3(256), 0, v, n, s);
+    ABZ_HIP(hipGetLastError());
+    return ABZ_OK;
+}
+
+// Matrix-valued G, or matrices that are not Hermitian: the inverse of every node (big_inverse_kernel), weighted sums in registers;
+// a group of swept values per pass so that the workgroups' partial sums stay under 256 MB, the chunks filled again per group.
+// One profiling scope per group, or one around all of them.
+template <class Fill>
+static int big_inverse_groups(abz_ctx* ctx, const BigWork& w, const BigJob& j, bool scope_per_group, Fill fill) {
+    const int nn = j.n * j.n, kind = big_inv_kind(j.integrand);
+    const int64_t ncomp = kind == 0 ? nn : 1;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(j.nnodes, 256 * 2));
+    const int group = (int)std::max<int64_t>(1, std::min<int64_t>(j.n_sweep, (256ll << 20) / (int64_t)(sizeof(double2) * blocks * ncomp)));
+    int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * group * ncomp));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)ss.n_sweep))) return rc;
-    if ((rc = ctx->scratch[5].reserve(sizeof(double) * (size_t)ss.n_sweep))) return rc;
-    double* sw = ctx->scratch[5].as<double>();
-    ABZ_HIP(hipMemcpyAsync(sw, ss.sweep_host, sizeof(double) * (size_t)ss.n_sweep, hipMemcpyHostToDevice, ctx->stream));
-    double2* total = ctx->scratch[2].as<double2>();
+    double2* partial = ctx->scratch[1].as<double2>();
+    std::optional<ProfScope> all, one;
+    if (!scope_per_group) all.emplace(ctx, j.prof_id);
+    for (int s0 = 0; s0 < j.n_sweep; s0 += group) {
+        const int ns = std::min(group, j.n_sweep - s0);
+        const int64_t col0 = s0 * ncomp, ncols = ns * ncomp;
+        double2* outd = nullptr;
+        if ((rc = sum_target(ctx, *j.out, col0, ncols, &outd))) return rc;
+        if (scope_per_group) one.emplace(ctx, j.prof_id);
+        ABZ_HIP(hipMemsetAsync(partial, 0, sizeof(double2) * (size_t)(blocks * ncols), ctx->stream));
+        for (int64_t c0 = 0; c0 < j.nnodes; c0 += w.chunk) {
+            const int64_t cn = std::min(w.chunk, j.nnodes - c0);
+            if ((rc = fill(c0, cn))) return rc;
+            BigInvArgs ia;
+            ia.Hbuf = w.Hbuf;
+            ia.node0 = c0;
+            ia.nnodes = cn;
+            ia.n = j.n;
+            ia.n_sweep = ns;
+            ia.kind = kind;
+            ia.eta = j.eta;
+            ia.sweep = j.sweep + s0;
+            ia.sweep_per_node = nullptr;
+            ia.sweep0 = 0.0;
+            ia.w = j.weights;
+            ia.values = nullptr;
+            ia.partial = partial;
+            ia.nodes_per_block = (int)cdivb(cn, blocks);
+            if ((rc = big_inverse(ctx, ia, cdivb(cn, ia.nodes_per_block)))) return rc;
+        }
+        if ((rc = launch_final_reduce(ctx, partial, blocks, ncols, j.scale, outd))) return rc;
+        one.reset();
+        if ((rc = sum_deliver(ctx, *j.out, outd, col0, ncols))) return rc;
+    }
+    return ABZ_OK;
+}
+
+// DOS / tr G of Hermitian matrices: tridiagonalise chunk by chunk and sum p'/p over the chunk's nodes
+template <class Fill>
+static int big_tridiag_chunks(abz_ctx* ctx, const BigWork& w, const BigJob& j, Fill fill) {
+    double2* total = nullptr;
+    int rc = sum_target(ctx, *j.out, 0, j.n_sweep, &total);
+    if (rc) return rc;
+    {
+        ProfScope ps(ctx, j.prof_id);
+        for (int64_t c0 = 0; c0 < j.nnodes; c0 += w.chunk) {
+            const int64_t cn = std::min(w.chunk, j.nnodes - c0);
+            if ((rc = fill(c0, cn))) return rc;
+            if ((rc = big_tridiag(ctx, w, j.n, cn))) return rc;
+            if ((rc = big_sum_chunk(ctx, w, j.n, c0, cn, j.integrand == ABZ_F_DOS, j.eta, j.sweep, j.n_sweep, j.weights, total, c0 == 0))) return rc;
+        }
+        if ((rc = big_scale(ctx, total, j.n_sweep, j.scale))) return rc;
+    }
+    return sum_deliver(ctx, *j.out, total, 0, j.n_sweep);
+}
+
+// store-free PTR sums (abz_ptr_sum)
+int launch_big_sum(abz_ctx* ctx, const SumSpec& ss) {
+    BigJob j{ss.n, ss.integrand, ss.n_sweep, ss.nlines * ss.npt, ss.params[0], ss.scale, nullptr, nullptr, ABZ_K_EVAL, &ss.out};
+    BigWork w;
+    int rc = big_reserve(ctx, ss.n, ss.npt, j.nnodes, w);
+    if (rc) return rc;
+    if ((rc = sweep_to_device(ctx, ss.sweep_host, ss.n_sweep, &j.sweep))) return rc;
     BigSeriesArgs sa;
     sa.src = ss.src;
     sa.parents = nullptr;
@@ -1222,130 +1311,36 @@ int launch_big_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
     sa.grid = 1;
     sa.inv_period = 1.0;
     sa.Hbuf = w.Hbuf;
-    if (big_inverse_sum_wanted(ss.n, ss.integrand, ss.herm) || (ss.force_inverse && big_inv_kind(ss.integrand) >= 0)) {
-        // matrix-valued G, or a series that is not Hermitian: H(k) of a chunk, the inverse of every node, weighted sums in registers;
-        // a group of swept values per pass (the workgroups' partial sums stay under 256 MB), the chunks re-evaluated per group
-        const int nn = ss.n * ss.n, kind = big_inv_kind(ss.integrand);
-        const int64_t ncomp = kind == 0 ? nn : 1;
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(nnodes, 256 * 2));
-        const int group = (int)std::max<int64_t>(1, std::min<int64_t>(ss.n_sweep, (256ll << 20) / (int64_t)(sizeof(double2) * blocks * ncomp)));
-        if ((rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * group * ncomp)))) return rc;
-        if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)(group * ncomp)))) return rc;
-        double2* partial = ctx->scratch[1].as<double2>();
-        double2* outd = ctx->scratch[2].as<double2>();
-        ProfScope ps(ctx, ABZ_K_EVAL);
-        for (int s0 = 0; s0 < ss.n_sweep; s0 += group) {
-            const int ns = std::min(group, ss.n_sweep - s0);
-            ABZ_HIP(hipMemsetAsync(partial, 0, sizeof(double2) * (size_t)(blocks * ns * ncomp), ctx->stream));
-            for (int64_t c0 = 0; c0 < nnodes; c0 += w.chunk) {
-                const int64_t cn = std::min(w.chunk, nnodes - c0);
-                if ((rc = big_series(ctx, sa, c0, cn))) return rc;
-                BigInvArgs ia;
-                ia.Hbuf = w.Hbuf;
-                ia.node0 = c0;
-                ia.nnodes = cn;
-                ia.n = ss.n;
-                ia.n_sweep = ns;
-                ia.kind = kind;
-                ia.eta = ss.params[0];
-                ia.sweep = sw + s0;
-                ia.sweep_per_node = nullptr;
-                ia.sweep0 = 0.0;
-                ia.w = nullptr;
-                ia.values = nullptr;
-                ia.partial = partial;
-                ia.nodes_per_block = (int)cdivb(cn, blocks);
-                if ((rc = big_inverse(ctx, ia, cdivb(cn, ia.nodes_per_block)))) return rc;
-            }
-            if ((rc = launch_final_reduce(ctx, partial, blocks, (int64_t)ns * ncomp, ss.scale, outd))) return rc;
-            ABZ_HIP(hipMemcpyAsync(out_reim + 2 * (size_t)s0 * ncomp, outd, sizeof(double2) * (size_t)ns * ncomp, hipMemcpyDeviceToHost, ctx->stream));
-            ABZ_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        return ABZ_OK;
-    }
-    ProfScope ps(ctx, ABZ_K_EVAL);
-    for (int64_t c0 = 0; c0 < nnodes; c0 += w.chunk) {
-        const int64_t cn = std::min(w.chunk, nnodes - c0);
-        if ((rc = big_series(ctx, sa, c0, cn))) return rc;
-        if ((rc = big_tridiag(ctx, w, ss.n, cn))) return rc;
-        if ((rc = big_sum_chunk(ctx, w, ss.n, c0, cn, ss.integrand == ABZ_F_DOS, ss.params[0], sw, ss.n_sweep, nullptr, total, c0 == 0))) return rc;
-    }
-    launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(ss.n_sweep, 256)), dim3(256), 0, total, ss.n_sweep, ss.scale);
-    ABZ_HIP(hipGetLastError());
-    ABZ_HIP(hipMemcpyAsync(out_reim, total, sizeof(double2) * (size_t)ss.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    auto fill = [&](int64_t c0, int64_t cn) { return big_series(ctx, sa, c0, cn); };
+    // matrix-valued G, or a series that is not Hermitian
+    if (big_inverse_sum_wanted(ss.n, ss.integrand, ss.herm) || (ss.force_inverse && big_inv_kind(ss.integrand) >= 0))
+        return big_inverse_groups(ctx, w, j, false, fill);
+    return big_tridiag_chunks(ctx, w, j, fill);
 }
 
 // scans of a cached rule: DOS / tr G from the matrices (tridiagonalised chunk by chunk); the eigenvalue form goes through
 // gen_eig_dos_kernel (kernels_generic.hip), which is generic in n
-int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
+int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs) {
     if (big_inv_kind(rs.integrand) < 0 || !rs.H.base || rs.H.compact) {
         set_error("n = %d bands: scans of a cached rule offer G, tr G and DOS from the matrices (full layout) and DOS from eigenvalues", rs.n);
         return ABZ_ERR_UNSUPPORTED;
     }
+    const BigJob j{rs.n, rs.integrand, rs.n_sweep, rs.nk, rs.params[0], rs.scale, rs.sweep_dev, rs.w, ABZ_K_REDUCE, &rs.out};
     BigWork w;
     int rc = big_reserve(ctx, rs.n, 0, rs.nk, w);
     if (rc) return rc;
-    if (rs.integrand == ABZ_F_GLOC || !rs.herm) {
-        // matrix-valued G, or matrices that are not Hermitian: the inverse of every node (big_inverse_kernel), a group of swept
-        // values per pass so that the workgroups' partial sums stay under 256 MB
-        const int nn = rs.n * rs.n, kind = big_inv_kind(rs.integrand);
-        const int64_t ncomp = kind == 0 ? nn : 1;
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(rs.nk, 256 * 2));
-        const int group = (int)std::max<int64_t>(1, std::min<int64_t>(rs.n_sweep, (256ll << 20) / (int64_t)(sizeof(double2) * blocks * ncomp)));
-        if ((rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * group * ncomp)))) return rc;
-        if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)(group * ncomp)))) return rc;
-        double2* partial = ctx->scratch[1].as<double2>();
-        double2* outd = ctx->scratch[2].as<double2>();
-        for (int s0 = 0; s0 < rs.n_sweep; s0 += group) {
-            const int ns = std::min(group, rs.n_sweep - s0);
-            {
-                ProfScope ps(ctx, ABZ_K_REDUCE);
-                ABZ_HIP(hipMemsetAsync(partial, 0, sizeof(double2) * (size_t)(blocks * ns * ncomp), ctx->stream));
-                for (int64_t c0 = 0; c0 < rs.nk; c0 += w.chunk) {
-                    const int64_t cn = std::min(w.chunk, rs.nk - c0);
-                    launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * nn, 256), 256 * 16)), dim3(256), 0, w.Hbuf, c0, cn, rs.n, rs.H);
-                    ABZ_HIP(hipGetLastError());
-                    BigInvArgs ia;
-                    ia.Hbuf = w.Hbuf;
-                    ia.node0 = c0;
-                    ia.nnodes = cn;
-                    ia.n = rs.n;
-                    ia.n_sweep = ns;
-                    ia.kind = kind;
-                    ia.eta = rs.params[0];
-                    ia.sweep = rs.sweep_dev + s0;
-                    ia.sweep_per_node = nullptr;
-                    ia.sweep0 = 0.0;
-                    ia.w = rs.w;
-                    ia.values = nullptr;
-                    ia.partial = partial;
-                    ia.nodes_per_block = (int)cdivb(cn, blocks);
-                    if ((rc = big_inverse(ctx, ia, cdivb(cn, ia.nodes_per_block)))) return rc;
-                }
-                if ((rc = launch_final_reduce(ctx, partial, blocks, (int64_t)ns * ncomp, rs.scale, outd))) return rc;
-            }
-            if (rs.out_dev) {
-                ABZ_HIP(hipMemcpyAsync(rs.out_dev + 2 * (size_t)s0 * ncomp, outd, sizeof(double2) * (size_t)ns * ncomp, hipMemcpyDeviceToDevice,
-                                       ctx->stream));
-                continue;
-            }
-            ABZ_HIP(hipMemcpyAsync(out_reim + 2 * (size_t)s0 * ncomp, outd, sizeof(double2) * (size_t)ns * ncomp, hipMemcpyDeviceToHost, ctx->stream));
-            ABZ_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        return ABZ_OK;
-    }
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)rs.n_sweep))) return rc;
-    double2* total = ctx->scratch[2].as<double2>();
-    if (rs.tri_cache && rs.tri_state) {
-        // the rule keeps the tridiagonal forms of its nodes: tridiagonalise once per fill of the rule, then every scan is the p'/p pass
+    auto fill = [&](int64_t c0, int64_t cn) { return big_load_h(ctx, w, rs.n, rs.H, c0, cn); };
+    if (rs.integrand == ABZ_F_GLOC || !rs.herm) return big_inverse_groups(ctx, w, j, true, fill);
+    if (!(rs.tri_cache && rs.tri_state)) return big_tridiag_chunks(ctx, w, j, fill);
+    // the rule keeps the tridiagonal forms of its nodes: tridiagonalise once per fill of the rule, then every scan is the p'/p pass
+    double2* total = nullptr;
+    if ((rc = sum_target(ctx, rs.out, 0, rs.n_sweep, &total))) return rc;
+    {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         if (*rs.tri_state == 0) {
             for (int64_t c0 = 0; c0 < rs.nk; c0 += w.chunk) {
                 const int64_t cn = std::min(w.chunk, rs.nk - c0);
-                launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * rs.n * rs.n, 256), 256 * 16)), dim3(256), 0, w.Hbuf, c0, cn, rs.n, rs.H);
-                ABZ_HIP(hipGetLastError());
+                if ((rc = fill(c0, cn))) return rc;
                 if ((rc = big_tridiag(ctx, w, rs.n, cn, nullptr, rs.tri_cache, rs.tri_nk, c0))) return rc;
             }
             *rs.tri_state = 1;
@@ -1354,29 +1349,9 @@ int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
         wc.tri = rs.tri_cache;
         wc.tri_nk = rs.tri_nk;
         if ((rc = big_sum_chunk(ctx, wc, rs.n, 0, rs.nk, rs.integrand == ABZ_F_DOS, rs.params[0], rs.sweep_dev, rs.n_sweep, rs.w, total, true))) return rc;
-        launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(rs.n_sweep, 256)), dim3(256), 0, total, rs.n_sweep, rs.scale);
-        ABZ_HIP(hipGetLastError());
-    } else {
-        ProfScope ps(ctx, ABZ_K_REDUCE);
-        for (int64_t c0 = 0; c0 < rs.nk; c0 += w.chunk) {
-            const int64_t cn = std::min(w.chunk, rs.nk - c0);
-            launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * rs.n * rs.n, 256), 256 * 16)), dim3(256), 0,
-                               w.Hbuf, c0, cn, rs.n, rs.H);
-            ABZ_HIP(hipGetLastError());
-            if ((rc = big_tridiag(ctx, w, rs.n, cn))) return rc;
-            if ((rc = big_sum_chunk(ctx, w, rs.n, c0, cn, rs.integrand == ABZ_F_DOS, rs.params[0], rs.sweep_dev, rs.n_sweep, rs.w, total, c0 == 0)))
-                return rc;
-        }
-        launch(ctx, big_scale_kernel, dim3((unsigned)cdivb(rs.n_sweep, 256)), dim3(256), 0, total, rs.n_sweep, rs.scale);
-        ABZ_HIP(hipGetLastError());
+        if ((rc = big_scale(ctx, total, rs.n_sweep, rs.scale))) return rc;
     }
-    if (rs.out_dev) {
-        ABZ_HIP(hipMemcpyAsync(rs.out_dev, total, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToDevice, ctx->stream));
-        return ABZ_OK;
-    }
-    ABZ_HIP(hipMemcpyAsync(out_reim, total, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, rs.out, total, 0, rs.n_sweep);
 }
 
 }  // namespace abz

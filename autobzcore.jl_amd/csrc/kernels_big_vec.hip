@@ -22,11 +22,17 @@
 //       FMAs, every one misses the 16-KB scalar cache, and ~100 SGPRs hold too few of them in flight: 1.8 ms per 1 152 nodes
 //       of 64 bands, nine times the issue time of its instructions.)
 // Only (e, v) reach the rule; nothing of U is stored.
-#include <cstdlib>
 #include <utility>
 
 #include "abz_internal.h"
 #include "rows_device.h"
+
+// Timing experiments only (-DABZ_BIG_VEC_PHASES=n): which parts of big_ggr_kernel run -- bit 0 inverse iteration, 1
+// back-transformation, 2 quadratic forms.  Anything below 7 yields wrong velocities.
+#ifndef ABZ_BIG_VEC_PHASES
+#define ABZ_BIG_VEC_PHASES 7
+#endif
+static_assert(ABZ_BIG_VEC_PHASES >= 0 && ABZ_BIG_VEC_PHASES <= 7, "ABZ_BIG_VEC_PHASES is a mask of three bits");
 
 namespace abz {
 
@@ -558,10 +564,7 @@ int launch_big_vec(abz_ctx* ctx, const double* tri, int64_t tri_nk, const double
     a.dstride = dstride;
     a.n = n;
     a.d = d;
-    {
-        const char* ph = getenv("ABZ_BIG_VEC_PHASES");
-        a.phases = ph ? atoi(ph) : 7;
-    }
+    a.phases = ABZ_BIG_VEC_PHASES;
     a.E = E;
     a.V = V;
     const int64_t blocks = std::min<int64_t>(nnodes, 256 * 4 * 4);

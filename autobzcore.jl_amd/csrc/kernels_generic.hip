@@ -784,13 +784,13 @@ bool gen_sum_supported(int n, int M, int npt, int integrand, bool herm) {
 }
 
 static bool gen_sum_tri_wanted(const SumSpec& ss);
-static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss, double* out_reim);
+static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss);
 
-int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
-    if (big_supported(ss.n) || big_inverse_sum_wanted(ss.n, ss.integrand, ss.herm)) return launch_big_sum(ctx, ss, out_reim);
-    if (lane_sum_supported(ss.n, ss.M, ss.first, ss.npt, ss.integrand, ss.n_sweep)) return launch_lane_sum(ctx, ss, out_reim);
+int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss) {
+    if (big_supported(ss.n) || big_inverse_sum_wanted(ss.n, ss.integrand, ss.herm)) return launch_big_sum(ctx, ss);
+    if (lane_sum_supported(ss.n, ss.M, ss.first, ss.npt, ss.integrand, ss.n_sweep)) return launch_lane_sum(ctx, ss);
     if (gen_sum_tri_wanted(ss)) {
-        const int rc = launch_gen_sum_tri(ctx, ss, out_reim);
+        const int rc = launch_gen_sum_tri(ctx, ss);
         if (rc != ABZ_ERR_UNSUPPORTED) return rc;
     }
     const int n = ss.n, M = ss.M;
@@ -803,7 +803,6 @@ int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
     const int64_t blocks = std::min<int64_t>(ss.nlines, 256 * 2);
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * 4));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * 4))) return rc;
     GenSumArgs a;
     a.src = ss.src;
     a.tab = ss.tab;
@@ -818,6 +817,8 @@ int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
     for (int s0 = 0; s0 < ss.n_sweep; s0 += 4) {
         a.nw = std::min(4, ss.n_sweep - s0);
         for (int q = 0; q < 4; ++q) a.sweep[q] = q < a.nw ? ss.sweep_host[s0 + q] : 0.0;
+        double2* outd = nullptr;
+        if ((rc = sum_target(ctx, ss.out, s0, a.nw, &outd))) return rc;
         {
             ProfScope ps(ctx, ABZ_K_EVAL);
 #define ABZ_GS2(NPV, PV)                                                                                              \
@@ -840,12 +841,10 @@ int launch_gen_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
 #undef ABZ_GS
 #undef ABZ_GS2
             ABZ_HIP(hipGetLastError());
-            rc = launch_final_reduce(ctx, a.partial, blocks, a.nw, ss.scale, ctx->scratch[2].as<double2>());
+            rc = launch_final_reduce(ctx, a.partial, blocks, a.nw, ss.scale, outd);
             if (rc) return rc;
         }
-        ABZ_HIP(hipMemcpyAsync(out_reim + 2 * (size_t)s0, ctx->scratch[2].p, sizeof(double2) * (size_t)a.nw, hipMemcpyDeviceToHost,
-                               ctx->stream));
-        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = sum_deliver(ctx, ss.out, outd, s0, a.nw))) return rc;
     }
     return ABZ_OK;
 }
@@ -1244,7 +1243,7 @@ static bool gen_sum_tri_wanted(const SumSpec& ss) {
     return abz_switch(SW_GEN_SUM_TRI) && ss.n > 4 && ss.n <= 32 && (ss.n_sweep >= 3 || ss.n > 16 || !whole);
 }
 
-static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
+static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss) {
     const int n = ss.n, M = ss.M;
     const int np = n <= 8 ? 8 : (n <= 16 ? 16 : 32);
     const size_t rest = sizeof(double2) * (size_t)256;  // [SLOTS][NP] partial sums
@@ -1262,7 +1261,6 @@ static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss, double* out_reim)
     const int64_t blocks = std::min<int64_t>(ss.nlines, 256 * 4);
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * 32));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * 32))) return rc;
     GenSumTriArgs a;
     a.src = ss.src;
     a.tab = ss.tab;
@@ -1278,6 +1276,8 @@ static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss, double* out_reim)
     for (int s0 = 0; s0 < ss.n_sweep; s0 += np) {
         a.nw = std::min(np, ss.n_sweep - s0);
         for (int q = 0; q < 32; ++q) a.sweep[q] = q < a.nw ? ss.sweep_host[s0 + q] : 0.0;
+        double2* outd = nullptr;
+        if ((rc = sum_target(ctx, ss.out, s0, a.nw, &outd))) return rc;
         {
             ProfScope ps(ctx, ABZ_K_EVAL);
             if (np == 32) {  // 17...32 bands: two nodes per wave
@@ -1306,12 +1306,10 @@ static int launch_gen_sum_tri(abz_ctx* ctx, const SumSpec& ss, double* out_reim)
                 }
             }
             ABZ_HIP(hipGetLastError());
-            rc = launch_final_reduce(ctx, a.partial, blocks, a.nw, ss.scale, ctx->scratch[2].as<double2>());
+            rc = launch_final_reduce(ctx, a.partial, blocks, a.nw, ss.scale, outd);
             if (rc) return rc;
         }
-        ABZ_HIP(hipMemcpyAsync(out_reim + 2 * (size_t)s0, ctx->scratch[2].p, sizeof(double2) * (size_t)a.nw, hipMemcpyDeviceToHost,
-                               ctx->stream));
-        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = sum_deliver(ctx, ss.out, outd, s0, a.nw))) return rc;
     }
     return ABZ_OK;
 }
@@ -2387,14 +2385,13 @@ static bool gen_rows_reduce_supported(const ReduceSpec& rs) {
                        : (rs.n <= 32 && !rs.H.compact && (rs.integrand == ABZ_F_DOS || rs.integrand == ABZ_F_TRGLOC)));
 }
 
-static int launch_gen_rows_gloc(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
+static int launch_gen_rows_gloc(abz_ctx* ctx, const ReduceSpec& rs) {
     const int np = rs.n <= 8 ? 8 : 16, nn = rs.n * rs.n;
     const int64_t blocks = std::min<int64_t>(cdiv2(rs.nk, 256 / np), 256);
     // swept values per launch: partial sums of at most 64 MB
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(rs.n_sweep, (64ll << 20) / (int64_t)(sizeof(double2) * blocks * nn)));
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * chunk * nn));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)chunk * nn))) return rc;
     GenRowsReduceArgs a;
     a.H = rs.H;
     a.w = rs.w;
@@ -2403,10 +2400,12 @@ static int launch_gen_rows_gloc(abz_ctx* ctx, const ReduceSpec& rs, double* out_
     a.n = rs.n;
     a.is_dos = 0;
     a.eta = rs.params[0];
-    double2* outd = ctx->scratch[2].as<double2>();
     for (int s0 = 0; s0 < rs.n_sweep; s0 += chunk) {
         a.n_sweep = std::min(chunk, rs.n_sweep - s0);
         a.sweep = rs.sweep_dev + s0;
+        const int64_t col0 = (int64_t)s0 * nn, ncols = (int64_t)a.n_sweep * nn;
+        double2* outd = nullptr;
+        if ((rc = sum_target(ctx, rs.out, col0, ncols, &outd))) return rc;
         {
             ProfScope ps(ctx, ABZ_K_REDUCE);
             if (np == 8)
@@ -2414,27 +2413,21 @@ static int launch_gen_rows_gloc(abz_ctx* ctx, const ReduceSpec& rs, double* out_
             else
                 launch(ctx, gen_rows_gloc_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, a);
             ABZ_HIP(hipGetLastError());
-            if ((rc = launch_final_reduce(ctx, a.partial, blocks, (int64_t)a.n_sweep * nn, rs.scale, outd))) return rc;
+            if ((rc = launch_final_reduce(ctx, a.partial, blocks, ncols, rs.scale, outd))) return rc;
         }
-        if (rs.out_dev) {  // chunk results stay in HBM; the next chunk reuses `outd` in stream order
-            ABZ_HIP(hipMemcpyAsync(rs.out_dev + 2 * (size_t)s0 * nn, outd, sizeof(double2) * (size_t)a.n_sweep * nn,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-            continue;
-        }
-        ABZ_HIP(hipMemcpyAsync(out_reim + 2 * (size_t)s0 * nn, outd, sizeof(double2) * (size_t)a.n_sweep * nn, hipMemcpyDeviceToHost,
-                               ctx->stream));
-        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = sum_deliver(ctx, rs.out, outd, col0, ncols))) return rc;
     }
     return ABZ_OK;
 }
 
-static int launch_gen_rows_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
-    if (rs.integrand == ABZ_F_GLOC) return launch_gen_rows_gloc(ctx, rs, out_reim);
+static int launch_gen_rows_reduce(abz_ctx* ctx, const ReduceSpec& rs) {
+    if (rs.integrand == ABZ_F_GLOC) return launch_gen_rows_gloc(ctx, rs);
     const int np = rs.n <= 8 ? 8 : (rs.n <= 16 ? 16 : 32);
     const int64_t blocks = std::min<int64_t>(cdiv2(rs.nk, 256 / np), 256 * 2);
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * rs.n_sweep));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)rs.n_sweep))) return rc;
+    double2* outd = nullptr;
+    if ((rc = sum_target(ctx, rs.out, 0, rs.n_sweep, &outd))) return rc;
     GenRowsReduceArgs a;
     a.H = rs.H;
     a.w = rs.w;
@@ -2445,7 +2438,6 @@ static int launch_gen_rows_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* ou
     a.n_sweep = rs.n_sweep;
     a.is_dos = rs.integrand == ABZ_F_DOS ? 1 : 0;
     a.eta = rs.params[0];
-    double2* outd = ctx->scratch[2].as<double2>();
     {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         const bool tri = (abz_switch(SW_GEN_SUM_TRI) && rs.n_sweep >= 3) || np == 32;  // sweeps: tridiagonalise once, p'/p per swept value
@@ -2462,13 +2454,7 @@ static int launch_gen_rows_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* ou
         ABZ_HIP(hipGetLastError());
         if ((rc = launch_final_reduce(ctx, a.partial, blocks, rs.n_sweep, rs.scale, outd))) return rc;
     }
-    if (rs.out_dev) {
-        ABZ_HIP(hipMemcpyAsync(rs.out_dev, outd, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToDevice, ctx->stream));
-        return ABZ_OK;
-    }
-    ABZ_HIP(hipMemcpyAsync(out_reim, outd, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, rs.out, outd, 0, rs.n_sweep);
 }
 
 // DOS from CACHED EIGENVALUES for more than four bands: sum_k w_k sum_b (eta / pi) / ((omega - e_b(k))^2 + eta^2).
@@ -2530,11 +2516,12 @@ __global__ __launch_bounds__(256) void gen_eig_dos_kernel(GenEigDosArgs a) {
     }
 }
 
-static int launch_gen_eig_dos(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
+static int launch_gen_eig_dos(abz_ctx* ctx, const ReduceSpec& rs) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(cdiv2(rs.nk, 256), 256 * 4));
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * rs.n_sweep));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)rs.n_sweep))) return rc;
+    double2* outd = nullptr;
+    if ((rc = sum_target(ctx, rs.out, 0, rs.n_sweep, &outd))) return rc;
     GenEigDosArgs a;
     a.E = rs.E;
     a.w = rs.w;
@@ -2544,28 +2531,21 @@ static int launch_gen_eig_dos(abz_ctx* ctx, const ReduceSpec& rs, double* out_re
     a.n = rs.n;
     a.n_sweep = rs.n_sweep;
     a.eta = rs.params[0];
-    double2* outd = ctx->scratch[2].as<double2>();
     {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         launch(ctx, gen_eig_dos_kernel, dim3((unsigned)blocks), dim3(256), 0, a);
         ABZ_HIP(hipGetLastError());
         if ((rc = launch_final_reduce(ctx, a.partial, blocks, rs.n_sweep, rs.scale, outd))) return rc;
     }
-    if (rs.out_dev) {
-        ABZ_HIP(hipMemcpyAsync(rs.out_dev, outd, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToDevice, ctx->stream));
-        return ABZ_OK;
-    }
-    ABZ_HIP(hipMemcpyAsync(out_reim, outd, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, rs.out, outd, 0, rs.n_sweep);
 }
 
-int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
-    if (lane_scan_supported(rs)) return launch_lane_scan(ctx, rs, out_reim);  // 5...8 bands, DOS / tr G: one node per lane
-    if (gen_rows_reduce_supported(rs)) return launch_gen_rows_reduce(ctx, rs, out_reim);
-    if (rs.integrand == ABZ_F_DOS_EIG && rs.E.base && rs.sweep_dev && rs.n_sweep >= 1) return launch_gen_eig_dos(ctx, rs, out_reim);
-    if (big_supported(rs.n)) return launch_big_reduce(ctx, rs, out_reim);  // 33...64 bands: kernels_big.hip
-    if (big_inverse_wanted(rs.n, rs.integrand, rs.herm) && rs.H.base && !rs.H.compact) return launch_big_reduce(ctx, rs, out_reim);
+int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs) {
+    if (lane_scan_supported(rs)) return launch_lane_scan(ctx, rs);  // 5...8 bands, DOS / tr G: one node per lane
+    if (gen_rows_reduce_supported(rs)) return launch_gen_rows_reduce(ctx, rs);
+    if (rs.integrand == ABZ_F_DOS_EIG && rs.E.base && rs.sweep_dev && rs.n_sweep >= 1) return launch_gen_eig_dos(ctx, rs);
+    if (big_supported(rs.n)) return launch_big_reduce(ctx, rs);  // 33...64 bands: kernels_big.hip
+    if (big_inverse_wanted(rs.n, rs.integrand, rs.herm) && rs.H.base && !rs.H.compact) return launch_big_reduce(ctx, rs);
     const int ncomp = integrand_ncomp(rs.integrand, rs.n, rs.d);
     if (ncomp < 0 || rs.integrand == ABZ_F_LINEAR || rs.integrand == ABZ_F_LINEAR_X) {
         set_error("integrand %d is not available for n = %d bands", rs.integrand, rs.n);
@@ -2587,10 +2567,9 @@ int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
     const int64_t blocks = cdiv2(nwaves, wpb);
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * wpb * ncols));
     if (rc) return rc;
-    rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)ncols);
-    if (rc) return rc;
+    double2* outd = nullptr;
+    if ((rc = sum_target(ctx, rs.out, 0, ncols, &outd))) return rc;
     double2* partial = ctx->scratch[1].as<double2>();
-    double2* outd = ctx->scratch[2].as<double2>();
     ABZ_HIP(hipMemsetAsync(partial, 0, sizeof(double2) * (size_t)(blocks * wpb * ncols), ctx->stream));
     GenReduceArgs a;
     a.Hplanes = rs.H;
@@ -2614,13 +2593,7 @@ int launch_gen_reduce(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
                            ncols, rs.scale, outd);
         ABZ_HIP(hipGetLastError());
     }
-    if (rs.out_dev) {
-        ABZ_HIP(hipMemcpyAsync(rs.out_dev, outd, sizeof(double2) * (size_t)ncols, hipMemcpyDeviceToDevice, ctx->stream));
-        return ABZ_OK;
-    }
-    ABZ_HIP(hipMemcpyAsync(out_reim, outd, sizeof(double2) * (size_t)ncols, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, rs.out, outd, 0, ncols);
 }
 
 // ------------------------------------------------------------------------------------------

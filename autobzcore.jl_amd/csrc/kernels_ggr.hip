@@ -1048,57 +1048,28 @@ int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, co
     a.d = d;
     a.vstride = n;
     a.b = 1.0 / (2.0 * (double)npt);
-    // ascending energies (stable order of equal ones), results go back through the permutation
-    std::vector<int> perm((size_t)nE);
-    for (int i = 0; i < nE; ++i) perm[(size_t)i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return Es_host[x] < Es_host[y]; });
-    std::vector<double> Es((size_t)nE), res((size_t)nE);
-    for (int i = 0; i < nE; ++i) Es[(size_t)i] = Es_host[perm[(size_t)i]];
     constexpr int CH = 1024;  // energies per launch: 5 x 8 KB of LDS
     const int64_t nblocks = std::min<int64_t>(cdiv64(nk, 256), 256 * 8);
     const int64_t nrows = nblocks * brows;
     int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)(nrows * std::min(nE, CH)));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double) * (size_t)nE * 2))) return rc;
     double* partial = ctx->scratch[1].as<double>();
-    double* Es_dev = ctx->scratch[2].as<double>();
-    double* outd = Es_dev + nE;
-    // energies in and sums out through the pinned mailbox: an asynchronous copy, the last kernel writes the sums into
-    // host memory itself, one stream synchronisation per call
-    const bool mb = mbox_reserve(ctx) == ABZ_OK && sizeof(double) * (size_t)nE <= ctx->mbox_cap / 2;
-    const double* res_host = res.data();
-    if (mb) {
-        std::memcpy(ctx->mbox, Es.data(), sizeof(double) * (size_t)nE);
-        ABZ_HIP(hipMemcpyAsync(Es_dev, ctx->mbox, sizeof(double) * (size_t)nE, hipMemcpyHostToDevice, ctx->stream));
-        outd = reinterpret_cast<double*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
-        res_host = reinterpret_cast<const double*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
-    } else {
-        ABZ_HIP(hipMemcpyAsync(Es_dev, Es.data(), sizeof(double) * (size_t)nE, hipMemcpyHostToDevice, ctx->stream));
-    }
-    // an equispaced list (the usual linspace sweep) lets a thread compute its window's first index instead of searching
-    {
-        const bool off = !abz_switch(SW_GGR_UNIFORM);  // per call: tests compare both
-        const double step = nE >= 2 ? (Es[(size_t)nE - 1] - Es[0]) / (double)(nE - 1) : 0.0;
-        bool uni = !off && nE >= 8 && step > 0.0;
-        for (int i = 0; i < nE && uni; ++i) uni = std::fabs(Es[(size_t)i] - (Es[0] + (double)i * step)) <= 1e-6 * step;
-        a.inv_step = uni ? 1.0 / step : 0.0;
-    }
+    EnergyList el;
+    if ((rc = energies_to_device(ctx, Es_host, nE, abz_switch(SW_GGR_UNIFORM) != 0, 0, el))) return rc;  // (per call: tests compare both)
+    a.inv_step = el.inv_step;
     for (int s0 = 0; s0 < nE; s0 += CH) {
         const int cnt = std::min(CH, nE - s0);
-        a.Es = Es_dev + s0;
+        a.Es = el.dev + s0;
         a.nE = cnt;
         ProfScope ps(ctx, ABZ_K_GGR);
         const size_t lds = sizeof(double) * 5 * (size_t)cnt;
         const dim3 grid((unsigned)nblocks, (unsigned)brows);
         ABZ_GGR_ND(ggr_window_kernel, a, partial, nrows);
         ABZ_HIP(hipGetLastError());
-        launch(ctx, ggr_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, outd + s0);
+        launch(ctx, ggr_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, el.out + s0);
         ABZ_HIP(hipGetLastError());
     }
-    if (!mb) ABZ_HIP(hipMemcpyAsync(res.data(), outd, sizeof(double) * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < nE; ++i) out_host[perm[(size_t)i]] = res_host[(size_t)i];
-    return ABZ_OK;
+    return energies_deliver(ctx, el, out_host);
 }
 #undef ABZ_GGR_D
 #undef ABZ_GGR_ND

@@ -496,15 +496,15 @@ bool lane_sum_supported(int n, int M, int first, int npt, int integrand, int n_s
     return 4 * lane_wave_bytes(n, M, 4, n_sweep) <= 150 * 1024;
 }
 
-int launch_lane_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
+int launch_lane_sum(abz_ctx* ctx, const SumSpec& ss) {
     const int64_t units = ss.nlines * ((ss.npt + 63) / 64);
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 256 * 8));
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * 4 * ss.n_sweep));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)ss.n_sweep))) return rc;
-    if ((rc = ctx->scratch[5].reserve(sizeof(double) * (size_t)ss.n_sweep))) return rc;
-    double* sw = ctx->scratch[5].as<double>();
-    ABZ_HIP(hipMemcpyAsync(sw, ss.sweep_host, sizeof(double) * (size_t)ss.n_sweep, hipMemcpyHostToDevice, ctx->stream));
+    double2* outd = nullptr;
+    if ((rc = sum_target(ctx, ss.out, 0, ss.n_sweep, &outd))) return rc;
+    const double* sw = nullptr;
+    if ((rc = sweep_to_device(ctx, ss.sweep_host, ss.n_sweep, &sw))) return rc;
     LaneArgs a;
     a.src = ss.src;
     a.tab = ss.tab;
@@ -523,11 +523,9 @@ int launch_lane_sum(abz_ctx* ctx, const SumSpec& ss, double* out_reim) {
     {
         ProfScope ps(ctx, ABZ_K_EVAL);
         if ((rc = lane_launch(ctx, ss.n, a, 4, lds, blocks))) return rc;
-        if ((rc = launch_final_reduce(ctx, a.partial, blocks * 4, ss.n_sweep, ss.scale, ctx->scratch[2].as<double2>()))) return rc;
+        if ((rc = launch_final_reduce(ctx, a.partial, blocks * 4, ss.n_sweep, ss.scale, outd))) return rc;
     }
-    ABZ_HIP(hipMemcpyAsync(out_reim, ctx->scratch[2].p, sizeof(double2) * (size_t)ss.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, ss.out, outd, 0, ss.n_sweep);
 }
 
 bool lane_scan_supported(const ReduceSpec& rs) {
@@ -535,12 +533,13 @@ bool lane_scan_supported(const ReduceSpec& rs) {
            (rs.integrand == ABZ_F_DOS || rs.integrand == ABZ_F_TRGLOC) && sizeof(double2) * 4 * (size_t)rs.n_sweep <= 60 * 1024;
 }
 
-int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
+int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs) {
     const int64_t units = (rs.nk + 63) / 64;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 256 * 8));
     int rc = ctx->scratch[1].reserve(sizeof(double2) * (size_t)(blocks * 4 * rs.n_sweep));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double2) * (size_t)rs.n_sweep))) return rc;
+    double2* outd = nullptr;
+    if ((rc = sum_target(ctx, rs.out, 0, rs.n_sweep, &outd))) return rc;
     LaneScanArgs a;
     a.H = rs.H;
     a.w = rs.w;
@@ -551,7 +550,6 @@ int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
     a.eta = rs.params[0];
     a.partial = ctx->scratch[1].as<double2>();
     const size_t lds = sizeof(double2) * 4 * (size_t)rs.n_sweep;
-    double2* outd = ctx->scratch[2].as<double2>();
     {
         ProfScope ps(ctx, ABZ_K_REDUCE);
         switch (rs.n) {
@@ -563,13 +561,7 @@ int launch_lane_scan(abz_ctx* ctx, const ReduceSpec& rs, double* out_reim) {
         ABZ_HIP(hipGetLastError());
         if ((rc = launch_final_reduce(ctx, a.partial, blocks * 4, rs.n_sweep, rs.scale, outd))) return rc;
     }
-    if (rs.out_dev) {
-        ABZ_HIP(hipMemcpyAsync(rs.out_dev, outd, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToDevice, ctx->stream));
-        return ABZ_OK;
-    }
-    ABZ_HIP(hipMemcpyAsync(out_reim, outd, sizeof(double2) * (size_t)rs.n_sweep, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    return ABZ_OK;
+    return sum_deliver(ctx, rs.out, outd, 0, rs.n_sweep);
 }
 
 }  // namespace abz

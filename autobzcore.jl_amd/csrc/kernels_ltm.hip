@@ -342,12 +342,6 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
     a.ncell = 1;
     for (int j = 0; j < d; ++j) a.ncell *= npt;
     const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);
-    // ascending energies (stable order of equal ones), results go back through the permutation
-    std::vector<int> perm((size_t)nE);
-    for (int i = 0; i < nE; ++i) perm[(size_t)i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return Es_host[x] < Es_host[y]; });
-    std::vector<double> Es((size_t)nE), res((size_t)nE);
-    for (int i = 0; i < nE; ++i) Es[(size_t)i] = Es_host[perm[(size_t)i]];
     // energies per launch: (1 + 4) x 8 KB of LDS for g, (1 + 8) x 4 KB for N (+ 1 KB of queue).  Chunks are independent: the steps of all
     // simplices below a chunk's first energy land on its index 0.
     const int CH = states ? 512 : 1024;
@@ -358,33 +352,14 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
     const int chmax = std::min(nE, CH);
     int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)(nrows * chmax * ncol));
     if (rc) return rc;
-    if ((rc = ctx->scratch[2].reserve(sizeof(double) * ((size_t)nE * 2 + 2 * (size_t)CH)))) return rc;
     double* partial = ctx->scratch[1].as<double>();
-    double* Es_dev = ctx->scratch[2].as<double>();
-    double* outd = Es_dev + nE;
-    double* col = Es_dev + 2 * (size_t)nE;  // states: column sums of a chunk [cnt sums | cnt steps]
-    // energies in and sums out through the pinned mailbox: an asynchronous copy, the last kernel writes the sums into
-    // host memory itself, one stream synchronisation per call
-    const bool mb = mbox_reserve(ctx) == ABZ_OK && sizeof(double) * (size_t)nE <= ctx->mbox_cap / 2;
-    const double* res_host = res.data();
-    if (mb) {
-        std::memcpy(ctx->mbox, Es.data(), sizeof(double) * (size_t)nE);
-        ABZ_HIP(hipMemcpyAsync(Es_dev, ctx->mbox, sizeof(double) * (size_t)nE, hipMemcpyHostToDevice, ctx->stream));
-        outd = reinterpret_cast<double*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
-        res_host = reinterpret_cast<const double*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
-    } else {
-        ABZ_HIP(hipMemcpyAsync(Es_dev, Es.data(), sizeof(double) * (size_t)nE, hipMemcpyHostToDevice, ctx->stream));
-    }
-    // an equispaced list (the usual linspace sweep) lets a thread compute its window's first index instead of searching
-    {
-        const double stp = nE >= 2 ? (Es[(size_t)nE - 1] - Es[0]) / (double)(nE - 1) : 0.0;
-        bool uni = nE >= 8 && stp > 0.0;
-        for (int i = 0; i < nE && uni; ++i) uni = std::fabs(Es[(size_t)i] - (Es[0] + (double)i * stp)) <= 1e-6 * stp;
-        a.inv_step = uni ? 1.0 / stp : 0.0;
-    }
+    EnergyList el;
+    if ((rc = energies_to_device(ctx, Es_host, nE, true, 2 * (size_t)CH, el))) return rc;
+    double* col = el.extra;  // states: column sums of a chunk [cnt sums | cnt steps]
+    a.inv_step = el.inv_step;
     for (int s0 = 0; s0 < nE; s0 += CH) {
         const int cnt = std::min(CH, nE - s0);
-        a.Es = Es_dev + s0;
+        a.Es = el.dev + s0;
         a.nE = cnt;
         ProfScope ps(ctx, ABZ_K_LTM);
         const size_t lds = sizeof(double) * (states ? 9 : 5) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
@@ -394,18 +369,15 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
             ABZ_HIP(hipGetLastError());
             launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
             ABZ_HIP(hipGetLastError());
-            launch(ctx, ltm_prefix_kernel, dim3(1), dim3(256), 0, col, cnt, weight, outd + s0);
+            launch(ctx, ltm_prefix_kernel, dim3(1), dim3(256), 0, col, cnt, weight, el.out + s0);
         } else {
             ABZ_LTM_D(false);
             ABZ_HIP(hipGetLastError());
-            launch(ctx, ltm_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, weight, outd + s0);
+            launch(ctx, ltm_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, weight, el.out + s0);
         }
         ABZ_HIP(hipGetLastError());
     }
-    if (!mb) ABZ_HIP(hipMemcpyAsync(res.data(), outd, sizeof(double) * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < nE; ++i) out_host[perm[(size_t)i]] = res_host[(size_t)i];
-    return ABZ_OK;
+    return energies_deliver(ctx, el, out_host);
 }
 #undef ABZ_LTM_D
 
