@@ -49,6 +49,9 @@ PROTOTYPES = {
     "abz_rule_values_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p]),
     "abz_rule_ggr": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
     "abz_rule_ltm": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int, c_f64p]),
+    "abz_rule_ltm_elements": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
+    "abz_rule_ltm_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
+    "abz_rule_ltm_fermi": (C.c_int, [C.c_void_p, C.c_double, C.c_double, c_f64p, c_f64p]),
     "abz_mem_info": (C.c_int, [C.c_void_p, c_i64p]),
     "abz_symptr_rule": (C.c_int, [C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
     "abz_symptr_rule_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
@@ -74,6 +77,8 @@ F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = range(7)
 LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = 0, 1, 2, 3
 K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
 LTM_DOS, LTM_STATES = 0, 1
+LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
+LTM_MAX_COMP = 16
 ERR_ARG, ERR_HIP, ERR_NOGPU, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 
 

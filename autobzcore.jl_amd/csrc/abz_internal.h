@@ -112,8 +112,8 @@ int sum_target(abz_ctx* ctx, const SumOut& so, int64_t col0, int64_t ncols, doub
 // columns [col0, col0 + ncols), which the last kernel left at `from` (sum_target's answer), to where `so` wants them
 int sum_deliver(abz_ctx* ctx, const SumOut& so, const double2* from, int64_t col0, int64_t ncols);
 
-// The energy list of a GGR / LTM scan: sorted ascending (stable order of equal ones) on the device, and the room for one real
-// result per energy.  Energies in and sums out go through the pinned mailbox where they fit its halves -- an asynchronous
+// The energy list of a GGR / LTM scan: sorted ascending (stable order of equal ones) on the device, and the room for `width`
+// real results per energy (1, or the components of a weighted LTM scan: device layout [width][n], delivered as [n][width]).  Energies in and sums out go through the pinned mailbox where they fit its halves -- an asynchronous
 // copy in, the last kernel writes the sums into host memory itself, one stream synchronisation per call -- else by plain copies.
 struct EnergyList {
     std::vector<int> perm;         // sorted position -> position in the caller's list
@@ -123,11 +123,12 @@ struct EnergyList {
     double* extra = nullptr;       // device [extra]: scratch of the launcher behind the two
     const double* res_host = nullptr;
     bool mbox = false;
+    int width = 1;
     double inv_step = 0.0;         // 1 / step of an equispaced list of >= 8 energies (`uniform`), else 0: a thread computes its
                                    // window's first index instead of searching
 };
-int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform, size_t extra, EnergyList& el);
-// synchronises the stream; out_host[i] = result of the caller's energy i
+int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform, size_t extra, EnergyList& el, int width = 1);
+// synchronises the stream; out_host[i * width + c] = result c of the caller's energy i
 int energies_deliver(abz_ctx* ctx, EnergyList& el, double* out_host);
 struct SymTables;
 int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, SymTables& out);
@@ -292,6 +293,10 @@ struct abz_rule {
     size_t vals_cap = 0, w_cap = 0, idx_cap = 0;  // block sizes as handed out by dev_alloc
     int planes = 0;
     abz::PlaneView H, E, V;  // views into vals (base == nullptr when absent)
+    double* ltm_elems = nullptr;  // matrix elements of abz_rule_ltm_elements: [ntiles][ltm_ncomp * n planes][row]
+    size_t ltm_elems_cap = 0;
+    int ltm_ncomp = 0;
+    abz::PlaneView A;        // view of ltm_elems
     double* w = nullptr;   // [nk] weights (symmetric rules)
     int32_t* idx = nullptr;  // [d][nk] grid indices (symmetric rules)
     void* plan = nullptr;    // abz::RulePlan (api.cpp): contraction plan + phase table, device resident
@@ -482,6 +487,13 @@ int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, co
 // Linear tetrahedron scan (kernels_ltm.hip) over the eigenvalue planes of a whole periodic grid of npt^d nodes:
 // g(E) or, with `states`, N(E), per unit cell and summed over the n bands
 int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host);
+// ... with matrix elements A (ncomp n planes tiled like E, plane c n + b: component c of band b): out_host [nE][ncomp]
+int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
+                        bool states, double* out_host);
+// one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
+int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
+// Fermi level by repeated N(E) scans of 512 energies between the smallest and largest eigenvalue (abz_rule_ltm_fermi)
+int ltm_fermi(abz_ctx* ctx, int n, int d, int npt, PlaneView E, int64_t nk, double nstates, double tol, double* E_F, double* N_F);
 
 // tiled planar (ncomp planes of the view) -> AoS [nk][ncomp] on the host
 int export_planes(abz_ctx* ctx, PlaneView v, int ncomp, int64_t nk, double* host_out, int row_major_n = 0);

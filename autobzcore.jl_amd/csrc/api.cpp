@@ -339,19 +339,20 @@ int sum_deliver(abz_ctx* ctx, const SumOut& so, const double2* from, int64_t col
     return ABZ_OK;
 }
 
-int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform, size_t extra, EnergyList& el) {
+int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform, size_t extra, EnergyList& el, int width) {
+    el.width = width;
     el.perm.resize((size_t)n);
     for (int i = 0; i < n; ++i) el.perm[(size_t)i] = i;
     std::stable_sort(el.perm.begin(), el.perm.end(), [&](int x, int y) { return Es_host[x] < Es_host[y]; });
     el.Es.resize((size_t)n);
     for (int i = 0; i < n; ++i) el.Es[(size_t)i] = Es_host[el.perm[(size_t)i]];
     const size_t bytes = sizeof(double) * (size_t)n;
-    int rc = ctx->scratch[2].reserve(2 * bytes + sizeof(double) * extra);
+    int rc = ctx->scratch[2].reserve((1 + (size_t)width) * bytes + sizeof(double) * extra);
     if (rc) return rc;
     double* const Es_dev = ctx->scratch[2].as<double>();
     el.dev = Es_dev;
-    el.extra = Es_dev + 2 * (size_t)n;
-    el.mbox = mbox_half_fits(ctx, bytes);
+    el.extra = Es_dev + (1 + (size_t)width) * (size_t)n;
+    el.mbox = mbox_half_fits(ctx, bytes * (size_t)width);
     if (el.mbox) {
         std::memcpy(ctx->mbox, el.Es.data(), bytes);
         ABZ_HIP(hipMemcpyAsync(Es_dev, ctx->mbox, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -360,7 +361,7 @@ int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform,
     } else {
         ABZ_HIP(hipMemcpyAsync(Es_dev, el.Es.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
         el.out = Es_dev + n;
-        el.res.resize((size_t)n);
+        el.res.resize((size_t)n * (size_t)width);
         el.res_host = el.res.data();
     }
     const double step = n >= 2 ? (el.Es[(size_t)n - 1] - el.Es[0]) / (double)(n - 1) : 0.0;
@@ -371,10 +372,15 @@ int energies_to_device(abz_ctx* ctx, const double* Es_host, int n, bool uniform,
 }
 
 int energies_deliver(abz_ctx* ctx, EnergyList& el, double* out_host) {
-    const size_t n = el.perm.size();
-    if (!el.mbox) ABZ_HIP(hipMemcpyAsync(el.res.data(), el.out, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t n = el.perm.size(), width = (size_t)el.width;
+    if (!el.mbox) ABZ_HIP(hipMemcpyAsync(el.res.data(), el.out, sizeof(double) * n * width, hipMemcpyDeviceToHost, ctx->stream));
     ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; ++i) out_host[el.perm[i]] = el.res_host[i];
+    if (width == 1) {
+        for (size_t i = 0; i < n; ++i) out_host[el.perm[i]] = el.res_host[i];
+    } else {
+        for (size_t c = 0; c < width; ++c)
+            for (size_t i = 0; i < n; ++i) out_host[(size_t)el.perm[i] * width + c] = el.res_host[c * n + i];
+    }
     return ABZ_OK;
 }
 
@@ -1045,8 +1051,17 @@ struct RulePlan {
 };
 }  // namespace abz
 
+static void rule_drop_ltm_elements(abz_rule* r) {
+    dev_free(r->ltm_elems, r->ltm_elems_cap);
+    r->ltm_elems = nullptr;
+    r->ltm_elems_cap = 0;
+    r->ltm_ncomp = 0;
+    r->A = PlaneView();
+}
+
 static void rule_free(abz_rule* r) {
     if (!r) return;
+    rule_drop_ltm_elements(r);
     dev_free(r->vals, r->vals_cap);
     if (!r->tables_view) {
         dev_free(r->w, r->w_cap);
@@ -1491,6 +1506,10 @@ int abz_rule_rebuild(abz_rule* r) try {
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     RulePlan* rp = static_cast<RulePlan*>(r->plan);
+    if (r->ltm_elems) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
+        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        rule_drop_ltm_elements(r);
+    }
     if ((r->want & ABZ_WANT_VEL) && !rule_ggr_fused(r)) {
         const size_t tb = sizeof(double) * (size_t)(r->ntiles * 2 * r->s->n * r->s->n * r->E.row);
         int rc = rp->tmpU.reserve(tb);
@@ -2094,6 +2113,92 @@ int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) tr
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     return launch_ltm(ctx, r->s->n, d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out);
+} ABZ_CATCH_ALL
+
+// the rule is a whole periodic grid with eigenvalues (the test and the wording of abz_rule_ltm)
+static int ltm_check_grid(const abz_rule* r, const char* who) {
+    if (!r->E.base) {
+        set_error("LTM needs a rule built with ABZ_WANT_EIG");
+        return ABZ_ERR_ARG;
+    }
+    int64_t ngrid = 1;
+    for (int j = 0; j < r->s->d; ++j) ngrid *= r->npt;
+    if (!r->full || r->k_offset != 0 || r->nk != ngrid) {
+        set_error("%s: the rule is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)", who,
+                  r->full ? "a slab of the outermost variable" : "irreducible nodes of a symmetric rule");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    return ABZ_OK;
+}
+
+int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE((A == nullptr) == (ncomp == 0), "abz_rule_ltm_elements: elements and ncomp = %d do not go together (drop with NULL, 0)", ncomp);
+    ABZ_REQUIRE(ncomp >= 0 && ncomp <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_elements: ncomp = %d outside 1..%d", ncomp, ABZ_LTM_MAX_COMP);
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_elements"))) return rc;
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    ABZ_HIP(hipStreamSynchronize(ctx->stream));
+    rule_drop_ltm_elements(r);
+    if (!A) return ABZ_OK;
+    const int n = r->s->n;
+    const int planes = ncomp * n;
+    const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
+    if ((rc = dev_alloc((void**)&r->ltm_elems, bytes, &r->ltm_elems_cap))) return rc;
+    r->ltm_ncomp = ncomp;
+    r->A = r->E;  // the tiling of the eigenvalue planes: same rows, same lines, ncomp n planes per tile
+    r->A.base = r->ltm_elems;
+    r->A.tile = (int64_t)planes * r->E.row;
+    r->A.pitch = r->E.row;
+    r->A.compact = 0;
+    DevBuf stage;  // one component at a time in the host's order
+    const size_t cbytes = sizeof(double) * (size_t)r->nk * (size_t)n;
+    rc = stage.reserve(cbytes);
+    if (!rc && hipMemsetAsync(r->ltm_elems, 0, bytes, ctx->stream) != hipSuccess) {  // the padding columns hold finite numbers
+        set_error("abz_rule_ltm_elements: hipMemsetAsync failed");
+        rc = ABZ_ERR_HIP;
+    }
+    for (int c = 0; c < ncomp && !rc; ++c) {
+        rc = stage_h2d(ctx, stage.p, A + (size_t)c * (size_t)r->nk * (size_t)n, cbytes);
+        if (!rc) rc = launch_ltm_repack(ctx, stage.as<double>(), r->A, c * n, n, r->nk);
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_elements: the upload failed");
+        rc = ABZ_ERR_HIP;
+    }
+    stage.release();
+    if (rc) rule_drop_ltm_elements(r);
+    return rc;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int what, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm_weighted: bad arguments");
+    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES, "abz_rule_ltm_weighted: what = %d is neither ABZ_LTM_DOS nor ABZ_LTM_STATES", what);
+    ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
+                "abz_rule_ltm_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_weighted"))) return rc;
+    ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems,
+                "abz_rule_ltm_weighted: no matrix elements are attached (abz_rule_ltm_elements; abz_rule_rebuild drops them)");
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const bool energy = source == ABZ_LTM_A_ENERGY;
+    return launch_ltm_weighted(ctx, r->s->n, r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, E, nE,
+                               what == ABZ_LTM_STATES, out);
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(E_F, "abz_rule_ltm_fermi: null E_F");
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_fermi"))) return rc;
+    ABZ_REQUIRE(nstates > 0.0 && nstates < (double)r->s->n, "abz_rule_ltm_fermi: nstates = %g outside (0, %d)", nstates, r->s->n);
+    ABZ_REQUIRE(tol > 0.0, "abz_rule_ltm_fermi: tol = %g is not positive", tol);
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    return ltm_fermi(ctx, r->s->n, r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
 } ABZ_CATCH_ALL
 
 // ---------------------------------------------------------------- arbitrary nodes

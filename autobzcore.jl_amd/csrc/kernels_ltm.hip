@@ -36,6 +36,24 @@
 //    N(above all bands) = d! npt^d n * weight = n to one rounding, and N(below all bands) is exactly 0.
 //  * Locals are plain scalars and fully unrolled constant-index arrays: nothing goes to scratch (DESIGN section 4e has
 //    the compiler's resource report).
+//  * Matrix elements (wltm_window_kernel).  With a quantity A_b(k) per node and band, interpolated linearly inside a
+//    simplex like the energy, the same scan gives g_A(E) = sum_b int A_b delta(E - e_b) and N_A(E) = sum_b int A_b
+//    theta(E - e_b).  The compare-exchange network that sorts the corner energies swaps the corners' A values along; per
+//    (simplex, energy) the d + 1 corner weights w_c are formed from the energies alone and every component adds
+//    sum_c w_c A_c.  With t_ij = (E - e_i) / (e_j - e_i), s_j = (e_last - E) / (e_last - e_j), unit = one simplex:
+//      d = 3, e1 <= E < e2: q = t12 t13 t14 / 4, N: w_j = q t_1j, w_1 = 4 q - sum;  g: q = t13 t14 / e21, w_j = q t_1j,
+//             w_1 = 3 q - sum
+//             e2 <= E < e3: the part below E is a prism cut into the tetrahedra (1, P13, P14, 2) (P13, P14, 2, P23)
+//             (P14, 2, P23, P24) of volumes v1 = t13 t14, v2 = t14 t23 (1 - t13), v3 = (1 - t14) t23 t24, each giving
+//             a quarter of its volume to its vertices; the cut is the triangles (P13, P14, P23) (P14, P23, P24) with
+//             densities 3 t13 (1 - t23) / e41 and 3 t23 (1 - t24) / e41, each giving a third to its vertices; a vertex
+//             P_ij hands (1 - t_ij, t_ij) of its share to the corners i, j
+//             e3 <= E < e4: the mirror image of the first region from corner 4, N: w = 1/4 - (that)
+//      d = 2, d = 1: the same with one and two corners fewer (wltm_simplex2, wltm_simplex1)
+//    A simplex wholly below E adds the mean of its corners' A to the step histogram, which is therefore no longer
+//    integer; its prefix sum keeps a fixed order.  The elements live in ncomp n planes tiled like the eigenvalue
+//    planes (plane c n + b: component c of band b); a launch carries 1, 2 or 4 components, so that the corners of a
+//    cell (8 energies + 8 NC elements) stay in registers, and a call walks the grid once per group of components.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -326,6 +344,408 @@ __global__ __launch_bounds__(256) void ltm_prefix_kernel(const double* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Matrix elements: g_A(E), N_A(E)
+// ---------------------------------------------------------------------------------------------------------------------
+struct WLtmArgs {
+    PlaneView E, A;
+    const double* Es;  // device, ascending
+    int64_t ncell;     // npt^d
+    int64_t acomp;     // doubles from a band's plane of one component to its plane of the next: n * A.pitch
+    int npt, nE;
+    int aplane0;       // first element plane of this launch: (its first component) * n
+    double inv_step = 0.0;
+};
+
+template <int NC>
+struct LtmVec {
+    double v[NC];
+};
+
+// compare-exchange of two corners: the energies, and the elements with them
+template <int NC>
+__device__ __forceinline__ void ltm_cx(double& ea, double& eb, LtmVec<NC>& Aa, LtmVec<NC>& Ab) {
+    const bool sw = eb < ea;
+    const double lo = sw ? eb : ea, hi = sw ? ea : eb;
+    ea = lo;
+    eb = hi;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const double x = sw ? Ab.v[c] : Aa.v[c], y = sw ? Aa.v[c] : Ab.v[c];
+        Aa.v[c] = x;
+        Ab.v[c] = y;
+    }
+}
+
+// One tetrahedron, corners in any order.  hist / step: [NC][nE] of the wave.
+template <bool STATES, int NC>
+__device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, double e4, LtmVec<NC> A1, LtmVec<NC> A2, LtmVec<NC> A3,
+                                              LtmVec<NC> A4, const double* Esl, int nE, int i0, double* hist, double* step) {
+    ltm_cx(e1, e2, A1, A2);
+    ltm_cx(e3, e4, A3, A4);
+    ltm_cx(e1, e3, A1, A3);
+    ltm_cx(e2, e4, A2, A4);
+    ltm_cx(e2, e3, A2, A3);
+    int i = i0;
+    if (i < nE && Esl[i] < e4) {
+        // an unselected region may have zero width: its reciprocal is then inf and never read
+        const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r41 = 1.0 / (e4 - e1), r32 = 1.0 / (e3 - e2), r42 = 1.0 / (e4 - e2),
+                     r43 = 1.0 / (e4 - e3);
+        for (; i < nE; ++i) {
+            const double En = Esl[i];
+            if (!(En < e4)) break;
+            if (En >= e1) {
+                double w1, w2, w3, w4;
+                if (En < e2) {
+                    const double x = En - e1, t2 = x * r21, t3 = x * r31, t4 = x * r41;
+                    const double q = STATES ? 0.25 * (t2 * t3 * t4) : t3 * t4 * r21;
+                    w2 = q * t2;
+                    w3 = q * t3;
+                    w4 = q * t4;
+                    w1 = (STATES ? 4.0 : 3.0) * q - (w2 + w3 + w4);
+                } else if (En < e3) {
+                    const double x1 = En - e1, x2 = En - e2;
+                    const double t13 = x1 * r31, t14 = x1 * r41, t23 = x2 * r32, t24 = x2 * r42;
+                    // shares of the vertices P13, P14, P23, P24 and of the corners 1, 2 themselves
+                    double p13, p14, p23, p24, c1, c2;
+                    if (STATES) {
+                        const double v1 = 0.25 * (t13 * t14), v2 = 0.25 * (t14 * t23 * (1.0 - t13)), v3 = 0.25 * ((1.0 - t14) * t23 * t24);
+                        p13 = v1 + v2;
+                        p14 = v1 + v2 + v3;
+                        p23 = v2 + v3;
+                        p24 = v3;
+                        c1 = v1;
+                        c2 = p14;
+                    } else {
+                        const double ga = t13 * (1.0 - t23) * r41, gb = t23 * (1.0 - t24) * r41;
+                        p13 = ga;
+                        p14 = ga + gb;
+                        p23 = p14;
+                        p24 = gb;
+                        c1 = 0.0;
+                        c2 = 0.0;
+                    }
+                    w1 = c1 + p13 * (1.0 - t13) + p14 * (1.0 - t14);
+                    w2 = c2 + p23 * (1.0 - t23) + p24 * (1.0 - t24);
+                    w3 = p13 * t13 + p23 * t23;
+                    w4 = p14 * t14 + p24 * t24;
+                } else {
+                    const double y = e4 - En, s1 = y * r41, s2 = y * r42, s3 = y * r43;
+                    const double q = STATES ? 0.25 * (s1 * s2 * s3) : s1 * s2 * r43;
+                    const double u1 = q * s1, u2 = q * s2, u3 = q * s3, u4 = (STATES ? 4.0 : 3.0) * q - (u1 + u2 + u3);
+                    w1 = STATES ? 0.25 - u1 : u1;
+                    w2 = STATES ? 0.25 - u2 : u2;
+                    w3 = STATES ? 0.25 - u3 : u3;
+                    w4 = STATES ? 0.25 - u4 : u4;
+                }
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const double f = (w1 * A1.v[c] + w2 * A2.v[c]) + (w3 * A3.v[c] + w4 * A4.v[c]);
+                    if (f != 0.0) ltm_add(hist + (size_t)c * nE + i, f);
+                }
+            }
+        }
+    }
+    if (STATES && i < nE) {  // i: first energy >= e4
+#pragma unroll
+        for (int c = 0; c < NC; ++c) ltm_add(step + (size_t)c * nE + i, 0.25 * ((A1.v[c] + A2.v[c]) + (A3.v[c] + A4.v[c])));
+    }
+}
+
+template <bool STATES, int NC>
+__device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, LtmVec<NC> A1, LtmVec<NC> A2, LtmVec<NC> A3,
+                                              const double* Esl, int nE, int i0, double* hist, double* step) {
+    ltm_cx(e1, e2, A1, A2);
+    ltm_cx(e2, e3, A2, A3);
+    ltm_cx(e1, e2, A1, A2);
+    constexpr double third = 1.0 / 3.0;
+    int i = i0;
+    if (i < nE && Esl[i] < e3) {
+        const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r32 = 1.0 / (e3 - e2);
+        for (; i < nE; ++i) {
+            const double En = Esl[i];
+            if (!(En < e3)) break;
+            if (En >= e1) {
+                double w1, w2, w3;
+                if (En < e2) {
+                    const double x = En - e1, t2 = x * r21, t3 = x * r31;
+                    const double q = STATES ? third * (t2 * t3) : t3 * r21;
+                    w2 = q * t2;
+                    w3 = q * t3;
+                    w1 = (STATES ? 3.0 : 2.0) * q - (w2 + w3);
+                } else {
+                    const double y = e3 - En, s1 = y * r31, s2 = y * r32;
+                    const double q = STATES ? third * (s1 * s2) : s1 * r32;
+                    const double u1 = q * s1, u2 = q * s2, u3 = (STATES ? 3.0 : 2.0) * q - (u1 + u2);
+                    w1 = STATES ? third - u1 : u1;
+                    w2 = STATES ? third - u2 : u2;
+                    w3 = STATES ? third - u3 : u3;
+                }
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const double f = (w1 * A1.v[c] + w2 * A2.v[c]) + w3 * A3.v[c];
+                    if (f != 0.0) ltm_add(hist + (size_t)c * nE + i, f);
+                }
+            }
+        }
+    }
+    if (STATES && i < nE) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) ltm_add(step + (size_t)c * nE + i, third * ((A1.v[c] + A2.v[c]) + A3.v[c]));
+    }
+}
+
+template <bool STATES, int NC>
+__device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A1, LtmVec<NC> A2, const double* Esl, int nE, int i0,
+                                              double* hist, double* step) {
+    ltm_cx(e1, e2, A1, A2);
+    int i = i0;
+    if (i < nE && Esl[i] < e2) {
+        const double r21 = 1.0 / (e2 - e1);
+        for (; i < nE; ++i) {
+            const double En = Esl[i];
+            if (!(En < e2)) break;
+            if (En >= e1) {
+                const double t = (En - e1) * r21;
+                const double w2 = STATES ? 0.5 * t * t : t * r21, w1 = STATES ? t - w2 : r21 - w2;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const double f = w1 * A1.v[c] + w2 * A2.v[c];
+                    if (f != 0.0) ltm_add(hist + (size_t)c * nE + i, f);
+                }
+            }
+        }
+    }
+    if (STATES && i < nE) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) ltm_add(step + (size_t)c * nE + i, 0.5 * (A1.v[c] + A2.v[c]));
+    }
+}
+
+// ltm_window_kernel with NC components of matrix elements.
+// partial [(STATES ? 2 : 1) NC nE][nrows]: columns c nE + i the formula sums of component c, NC nE + c nE + i its steps
+template <int D, bool STATES, int NC>
+__global__ __launch_bounds__(256) void wltm_window_kernel(WLtmArgs a, double* __restrict__ partial, int64_t nrows) {
+    // [nE] energies | [4 waves][NC][nE] sums | STATES: [4 waves][NC][nE] steps | [256] queue of a pass | [2][4] per-wave counts
+    extern __shared__ __attribute__((aligned(16))) double ldsl[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int nE = a.nE;
+    constexpr int NH = (STATES ? 8 : 4) * NC;
+    constexpr int NS = D == 3 ? 6 : (D == 2 ? 2 : 1);  // simplices per cell
+    constexpr int NV = 1 << D;                         // corners per cell
+    const double* const Esl = ldsl;
+    double* const hist = ldsl + (size_t)(1 + wave * NC) * nE;
+    double* const step = ldsl + (size_t)(1 + (4 + wave) * NC) * nE;  // STATES only
+    uint32_t* const queue = reinterpret_cast<uint32_t*>(ldsl + (size_t)(1 + NH) * nE);
+    uint32_t* const wcount = queue + 256;
+    for (int i = threadIdx.x; i < nE; i += 256) ldsl[i] = a.Es[i];
+    for (int i = threadIdx.x; i < NH * nE; i += 256) ldsl[nE + i] = 0.0;
+    __syncthreads();
+    const int npt = a.npt;
+    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
+    const double* __restrict__ const Ab = a.A.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.A.pitch;
+    const int64_t tileE = a.E.tile, tileA = a.A.tile, acomp = a.acomp;
+    // corner `bits` (bit j: +1 along variable j+1, wrapped) of cell (i1, i2, i3): its grid line and its place in the line
+    auto wrap = [&](int& i1, int& i2, int& i3, int bits) {
+        if ((bits & 1) && ++i1 == npt) i1 = 0;
+        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
+        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
+    };
+    auto cornerE = [&](int i1, int i2, int i3, int bits) -> double {
+        wrap(i1, i2, i3, bits);
+        return Eb[((int64_t)i3 * npt + i2) * tileE + i1];
+    };
+    auto cornerA = [&](int i1, int i2, int i3, int bits) -> LtmVec<NC> {
+        wrap(i1, i2, i3, bits);
+        const double* __restrict__ const p = Ab + ((int64_t)i3 * npt + i2) * tileA + i1;
+        LtmVec<NC> r;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) r.v[c] = p[(int64_t)c * acomp];
+        return r;
+    };
+    unsigned pass = 0;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
+        const int64_t k = base + threadIdx.x;
+        bool active = false;
+        int i0 = 0, i1 = 0, i2 = 0, i3 = 0;
+        double c[NV];
+        if (k < a.ncell) {
+            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
+            i1 = (int)(k - line * npt);
+            i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
+            i2 = (int)line - i3 * npt;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) c[j] = cornerE(i1, i2, i3, j);
+            double cmin = c[0], cmax = c[0];
+#pragma unroll
+            for (int j = 1; j < NV; ++j) {
+                cmin = fmin(cmin, c[j]);
+                cmax = fmax(cmax, c[j]);
+            }
+            i0 = ltm_first(Esl, nE, a.inv_step, cmin);
+            if (i0 < nE) {  // else every energy lies below the cell
+                if (Esl[i0] < cmax) {
+                    active = true;
+                } else if (STATES) {
+                    // no energy inside the window: all simplices step at the same index, by the sum of their means in one
+                    // add per component.  Corner 0 and corner (1..1) belong to all d! simplices, every other corner to
+                    // d! / d of them... d = 3: (6 (A0 + A7) + 2 sum others) / 4, d = 2: (2 (A0 + A3) + A1 + A2) / 3
+                    LtmVec<NC> m;
+#pragma unroll
+                    for (int cc = 0; cc < NC; ++cc) m.v[cc] = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) {
+                        const LtmVec<NC> Aj = cornerA(i1, i2, i3, j);
+                        const bool ends = j == 0 || j == NV - 1;
+                        const double wj = D == 3 ? (ends ? 1.5 : 0.5) : (D == 2 ? (ends ? 2.0 / 3.0 : 1.0 / 3.0) : 0.5);
+#pragma unroll
+                        for (int cc = 0; cc < NC; ++cc) m.v[cc] += wj * Aj.v[cc];
+                    }
+#pragma unroll
+                    for (int cc = 0; cc < NC; ++cc) ltm_add(step + (size_t)cc * nE + i0, m.v[cc]);
+                }
+            }
+        }
+        const unsigned long long mask = __ballot(active);
+        uint32_t* const wc = wcount + 4 * (pass & 1);  // two sets in turn, as in ltm_window_kernel
+        ++pass;
+        if (lane == 0) wc[wave] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        uint32_t off = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t cw = wc[w];
+            off += w < wave ? cw : 0u;
+            total += cw;
+        }
+        if (total > LTM_QUEUE_MAX) {
+            // the direct walk: the energies of the corners are held, their elements are loaded now
+            if (active) {
+                LtmVec<NC> Av[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) Av[j] = cornerA(i1, i2, i3, j);
+                if constexpr (D == 3) {
+                    wltm_simplex3<STATES, NC>(c[0], c[1], c[3], c[7], Av[0], Av[1], Av[3], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC>(c[0], c[1], c[5], c[7], Av[0], Av[1], Av[5], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC>(c[0], c[2], c[3], c[7], Av[0], Av[2], Av[3], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC>(c[0], c[2], c[6], c[7], Av[0], Av[2], Av[6], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC>(c[0], c[4], c[5], c[7], Av[0], Av[4], Av[5], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC>(c[0], c[4], c[6], c[7], Av[0], Av[4], Av[6], Av[7], Esl, nE, i0, hist, step);
+                } else if constexpr (D == 2) {
+                    wltm_simplex2<STATES, NC>(c[0], c[1], c[3], Av[0], Av[1], Av[3], Esl, nE, i0, hist, step);
+                    wltm_simplex2<STATES, NC>(c[0], c[2], c[3], Av[0], Av[2], Av[3], Esl, nE, i0, hist, step);
+                } else {
+                    wltm_simplex1<STATES, NC>(c[0], c[1], Av[0], Av[1], Esl, nE, i0, hist, step);
+                }
+            }
+            continue;
+        }
+        if (active) queue[off + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((uint32_t)i0 << 8) | threadIdx.x;
+        __syncthreads();  // the next pass writes the queue after its own first barrier
+        for (uint32_t p = threadIdx.x; p < NS * total; p += 256) {
+            const uint32_t cell = p / NS, t = p - cell * NS;
+            const uint32_t q = queue[cell];
+            const int64_t kq = base + (q & 255u);
+            const int j0 = (int)(q >> 8);
+            const int64_t line = kq <= 0xffffffffll ? (int64_t)((uint32_t)kq / (uint32_t)npt) : kq / npt;
+            const int q1 = (int)(kq - line * npt);
+            const int q3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
+            const int q2 = (int)line - q3 * npt;
+            const double c0 = cornerE(q1, q2, q3, 0), c1 = cornerE(q1, q2, q3, NV - 1);
+            const LtmVec<NC> A0 = cornerA(q1, q2, q3, 0), A1 = cornerA(q1, q2, q3, NV - 1);
+            if constexpr (D == 3) {
+                // the permutation (A, B, C) of the axes: corners 0, e_A, e_A + e_B, (1,1,1)
+                const int X = (int)(t >> 1), Y = (X + 1 + (int)(t & 1)) % 3;
+                const int ba = 1 << X, bb = (1 << X) | (1 << Y);
+                wltm_simplex3<STATES, NC>(c0, cornerE(q1, q2, q3, ba), cornerE(q1, q2, q3, bb), c1, A0, cornerA(q1, q2, q3, ba),
+                                          cornerA(q1, q2, q3, bb), A1, Esl, nE, j0, hist, step);
+            } else if constexpr (D == 2) {
+                wltm_simplex2<STATES, NC>(c0, cornerE(q1, q2, q3, 1 << t), c1, A0, cornerA(q1, q2, q3, 1 << t), A1, Esl, nE, j0, hist, step);
+            } else {
+                wltm_simplex1<STATES, NC>(c0, c1, A0, A1, Esl, nE, j0, hist, step);
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const double* h = ldsl + nE;
+    // transposed partials [column][row]; column c nE + t sits at the same place in every wave's block
+    for (int t = threadIdx.x; t < NC * nE; t += 256) {
+        const size_t w = (size_t)NC * nE;  // from one wave's histograms to the next
+        partial[(int64_t)t * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
+        if (STATES) partial[((int64_t)NC * nE + t) * nrows + prow] = (h[4 * w + t] + h[5 * w + t]) + (h[6 * w + t] + h[7 * w + t]);
+    }
+}
+
+// ltm_final_kernel for a group of components: block (c, i) -> out[c * ostride + i]
+__global__ __launch_bounds__(256) void wltm_final_kernel(const double* __restrict__ partial, int64_t nrows, double scale, int cnt,
+                                                         int64_t ostride, double* __restrict__ out) {
+    __shared__ double red[256];
+    const double* __restrict__ p = partial + (int64_t)blockIdx.x * nrows;
+    double s = 0.0;
+    for (int64_t r = threadIdx.x; r < nrows; r += 256) s += p[r];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const int c = (int)blockIdx.x / cnt, i = (int)blockIdx.x - c * cnt;
+    if (threadIdx.x == 0) out[(int64_t)c * ostride + i] = scale * red[0];
+}
+
+// ltm_prefix_kernel, one block per component: col = [NC][nE] sums | [NC][nE] steps, nE <= 512.  The steps are means of
+// elements, not integers: the prefix sum runs in index order, the same at every call.
+__global__ __launch_bounds__(256) void wltm_prefix_kernel(const double* __restrict__ col, int nE, int nc, double weight, int64_t ostride,
+                                                          double* __restrict__ out) {
+    __shared__ double st[512];
+    const int c = (int)blockIdx.x;
+    for (int i = threadIdx.x; i < nE; i += 256) st[i] = col[(size_t)(nc + c) * nE + i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < nE; i += 256) {
+        double run = 0.0;
+        for (int j = 0; j <= i; ++j) run += st[j];
+        out[(int64_t)c * ostride + i] = weight * (col[(size_t)c * nE + i] + run);
+    }
+}
+
+// host array of one component [nk][n] -> its n planes: plane0 + b, node k
+__global__ __launch_bounds__(256) void ltm_repack_kernel(const double* __restrict__ src, PlaneView A, int plane0, int n, int64_t nk) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nk * n) return;
+    const int64_t k = t / n;
+    const int b = (int)(t - k * n);
+    const int64_t line = k / A.line_len;
+    A.base[line * A.tile + (int64_t)(plane0 + b) * A.pitch + (k - line * A.line_len)] = src[t];
+}
+
+// smallest and largest eigenvalue of the n planes (padding excluded): out[2 block + {0, 1}]
+__global__ __launch_bounds__(256) void ltm_minmax_kernel(PlaneView E, int n, int64_t nk, double* __restrict__ out) {
+    __shared__ double lo[256], hi[256];
+    double mn = INFINITY, mx = -INFINITY;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nk * n; t += (int64_t)gridDim.x * 256) {
+        const int64_t b = t / nk, k = t - b * nk;
+        const int64_t line = k / E.line_len;
+        const double v = E.base[line * E.tile + b * E.pitch + (k - line * E.line_len)];
+        mn = fmin(mn, v);
+        mx = fmax(mx, v);
+    }
+    lo[threadIdx.x] = mn;
+    hi[threadIdx.x] = mx;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            lo[threadIdx.x] = fmin(lo[threadIdx.x], lo[threadIdx.x + w]);
+            hi[threadIdx.x] = fmax(hi[threadIdx.x], hi[threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[2 * blockIdx.x] = lo[0];
+        out[2 * blockIdx.x + 1] = hi[0];
+    }
+}
+
 }  // namespace
 
 #define ABZ_LTM_D(ST)                                                                                         \
@@ -380,5 +800,193 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
     return energies_deliver(ctx, el, out_host);
 }
 #undef ABZ_LTM_D
+
+namespace {
+template <int D, bool ST, int NC>
+void wltm_launch(abz_ctx* ctx, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
+    launch(ctx, (wltm_window_kernel<D, ST, NC>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
+}
+template <bool ST, int NC>
+void wltm_launch_d(abz_ctx* ctx, int d, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
+    switch (d) {
+        case 1: wltm_launch<1, ST, NC>(ctx, grid, lds, a, partial, nrows); break;
+        case 2: wltm_launch<2, ST, NC>(ctx, grid, lds, a, partial, nrows); break;
+        default: wltm_launch<3, ST, NC>(ctx, grid, lds, a, partial, nrows); break;
+    }
+}
+template <bool ST>
+void wltm_launch_nc(abz_ctx* ctx, int d, int nc, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
+    switch (nc) {
+        case 1: wltm_launch_d<ST, 1>(ctx, d, grid, lds, a, partial, nrows); break;
+        case 2: wltm_launch_d<ST, 2>(ctx, d, grid, lds, a, partial, nrows); break;
+        default: wltm_launch_d<ST, 4>(ctx, d, grid, lds, a, partial, nrows); break;
+    }
+}
+// dynamic LDS of the shipped scans: 5 x 1024 (g) energies x 8 B + queue and counts; the weighted scans stay within it
+constexpr size_t LTM_LDS_MAX = sizeof(double) * 5 * 1024 + sizeof(uint32_t) * (256 + 8);
+}  // namespace
+
+int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
+                        bool states, double* out_host) {
+    WLtmArgs a;
+    a.E = E;
+    a.A = A;
+    a.acomp = (int64_t)n * A.pitch;
+    a.npt = npt;
+    a.ncell = 1;
+    for (int j = 0; j < d; ++j) a.ncell *= npt;
+    const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);
+    const int ncol = states ? 2 : 1;
+    // Energies per launch of NC components: 8 (1 + 4 NC ncol) B of LDS each, within LTM_LDS_MAX, and at most 512 where the
+    // prefix kernel holds a chunk's steps: g 1024 / 568 / 301, N 512 / 301 / 155 for NC = 1 / 2 / 4.
+    auto chunk = [&](int nc) {
+        const size_t fit = (LTM_LDS_MAX - sizeof(uint32_t) * (256 + 8)) / (sizeof(double) * (size_t)(1 + 4 * nc * ncol));
+        return (int)std::min<size_t>(fit, states ? 512 : 1024);
+    };
+    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
+    const int64_t nrows = nblocks * n;
+    size_t pmax = 0;
+    for (int nc : {1, 2, 4})
+        if (nc <= ncomp) pmax = std::max(pmax, (size_t)std::min(nE, chunk(nc)) * (size_t)(nc * ncol));
+    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax);
+    if (rc) return rc;
+    double* partial = ctx->scratch[1].as<double>();
+    EnergyList el;
+    if ((rc = energies_to_device(ctx, Es_host, nE, true, 2 * 4 * (size_t)512, el, ncomp))) return rc;
+    double* col = el.extra;  // states: column sums of a launch [nc][cnt] sums | [nc][cnt] steps
+    a.inv_step = el.inv_step;
+    const dim3 grid((unsigned)nblocks, (unsigned)n);
+    // groups of 4 components, then 2, then 1; every group walks the grid once per chunk of energies
+    for (int c0 = 0; c0 < ncomp;) {
+        const int nc = ncomp - c0 >= 4 ? 4 : (ncomp - c0 >= 2 ? 2 : 1);
+        const int CH = chunk(nc);
+        a.aplane0 = c0 * n;
+        for (int s0 = 0; s0 < nE; s0 += CH) {
+            const int cnt = std::min(CH, nE - s0);
+            a.Es = el.dev + s0;
+            a.nE = cnt;
+            ProfScope ps(ctx, ABZ_K_LTM);
+            const size_t lds = sizeof(double) * (size_t)(1 + 4 * nc * ncol) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
+            double* const o = el.out + (size_t)c0 * nE + s0;  // results [ncomp][nE] in sorted order
+            if (states) {
+                wltm_launch_nc<true>(ctx, d, nc, grid, lds, a, partial, nrows);
+                ABZ_HIP(hipGetLastError());
+                launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
+                ABZ_HIP(hipGetLastError());
+                launch(ctx, wltm_prefix_kernel, dim3((unsigned)nc), dim3(256), 0, col, cnt, nc, weight, (int64_t)nE, o);
+            } else {
+                wltm_launch_nc<false>(ctx, d, nc, grid, lds, a, partial, nrows);
+                ABZ_HIP(hipGetLastError());
+                launch(ctx, wltm_final_kernel, dim3((unsigned)(nc * cnt)), dim3(256), 0, partial, nrows, weight, cnt, (int64_t)nE, o);
+            }
+            ABZ_HIP(hipGetLastError());
+        }
+        c0 += nc;
+    }
+    return energies_deliver(ctx, el, out_host);
+}
+
+int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk) {
+    ProfScope ps(ctx, ABZ_K_LTM);
+    launch(ctx, ltm_repack_kernel, dim3((unsigned)cdiv64(nk * n, 256)), dim3(256), 0, src_dev, A, plane0, n, nk);
+    ABZ_HIP(hipGetLastError());
+    return ABZ_OK;
+}
+
+int launch_ltm_minmax(abz_ctx* ctx, int n, PlaneView E, int64_t nk, double* emin, double* emax) {
+    const int nb = (int)std::min<int64_t>(256, cdiv64(nk * n, 256));
+    int rc = ctx->scratch[1].reserve(sizeof(double) * 2 * (size_t)nb);
+    if (rc) return rc;
+    double* part = ctx->scratch[1].as<double>();
+    {
+        ProfScope ps(ctx, ABZ_K_LTM);
+        launch(ctx, ltm_minmax_kernel, dim3((unsigned)nb), dim3(256), 0, E, n, nk, part);
+        ABZ_HIP(hipGetLastError());
+    }
+    std::vector<double> h(2 * (size_t)nb);
+    ABZ_HIP(hipMemcpyAsync(h.data(), part, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    ABZ_HIP(hipStreamSynchronize(ctx->stream));
+    double mn = h[0], mx = h[1];
+    for (int b = 1; b < nb; ++b) {
+        mn = std::min(mn, h[2 * (size_t)b]);
+        mx = std::max(mx, h[2 * (size_t)b + 1]);
+    }
+    *emin = mn;
+    *emax = mx;
+    return ABZ_OK;
+}
+
+int ltm_fermi(abz_ctx* ctx, int n, int d, int npt, PlaneView E, int64_t nk, double nstates, double tol, double* E_F, double* N_F) {
+    double lo = 0.0, hi = 0.0;
+    int rc = launch_ltm_minmax(ctx, n, E, nk, &lo, &hi);
+    if (rc) return rc;
+    const double hi_all = hi;
+    const double target = nstates * (1.0 - 1e-12);
+    constexpr int M = 512;
+    std::vector<double> Es(M), N(M);
+    double Nhi = (double)n;
+    // every scan keeps the sub-interval (E_{i-1}, E_i] of its M samples with N(E_{i-1}) < target <= N(E_i): 511 times
+    // narrower per launch
+    for (int it = 0; it < 64; ++it) {
+        const double width = hi - lo;
+        int m = M;
+        if (!(width > 0.0)) m = 1;
+        for (int i = 0; i < m; ++i) Es[(size_t)i] = i == m - 1 ? hi : lo + width * ((double)i / (double)(M - 1));
+        if ((rc = launch_ltm(ctx, n, d, npt, E, Es.data(), m, true, N.data()))) return rc;
+        int i = 0;
+        while (i < m - 1 && !(N[(size_t)i] >= target)) ++i;  // the upper end stands for "none": N(hi) >= target was seen before
+        Nhi = N[(size_t)i];
+        const double nlo = i > 0 ? Es[(size_t)i - 1] : lo, nhi = Es[(size_t)i];
+        if (i == 0) {  // already the lower end holds the states (first scan: a flat band at the bottom)
+            hi = nhi;
+            break;
+        }
+        const bool shrunk = nhi - nlo < width;
+        lo = nlo;
+        hi = nhi;
+        if (hi - lo <= tol || !shrunk) break;
+    }
+    // Below a gap the search stops short of the band top: under a 3-D maximum N(top - x) = 1 - c x^3 reaches the target a
+    // distance (1e-12 / c)^(1/3), about 1e-4, below it, and in f64 N cannot tell x < 1e-5 from 0.  The DOS can: g(E) is
+    // exactly 0 where no simplex straddles E (nothing is added to its sum) and positive below the top.  So if g vanishes
+    // at a sample above `hi` while N there is still nstates to the same slack -- a gap, not the next band edge of a
+    // metal -- the same 511-fold narrowing on "g == 0" finds the lowest such energy, the band top, to within tol.
+    const double emax = hi_all, upper = nstates * (1.0 + 1e-12);
+    if (emax > hi) {
+        std::vector<double>& G = N;
+        double a = hi, b = emax;
+        bool gap = false;
+        for (int it = 0; it < 64; ++it) {
+            const double width = b - a;
+            for (int i = 0; i < M; ++i) Es[(size_t)i] = i == M - 1 ? b : a + width * ((double)i / (double)(M - 1));
+            if ((rc = launch_ltm(ctx, n, d, npt, E, Es.data(), M, false, G.data()))) return rc;
+            int i = 0;
+            while (i < M - 1 && G[(size_t)i] != 0.0) ++i;
+            if (it == 0) {
+                if (G[(size_t)i] != 0.0 || i == 0) break;  // no zero of g above hi, or hi itself already has one
+                double Nz = 0.0;
+                if ((rc = launch_ltm(ctx, n, d, npt, E, &Es[(size_t)i], 1, true, &Nz))) return rc;
+                if (Nz > upper) break;  // states in between: the zero belongs to a higher gap
+                gap = true;
+            }
+            if (i == 0) {  // (rounding: the lower end had g > 0 in the scan before)
+                b = a;
+                break;
+            }
+            const double na = Es[(size_t)i - 1], nb = Es[(size_t)i];
+            const bool shrunk = nb - na < width;
+            a = na;
+            b = nb;
+            if (b - a <= tol || !shrunk) break;
+        }
+        if (gap) {
+            hi = b;
+            if ((rc = launch_ltm(ctx, n, d, npt, E, &hi, 1, true, &Nhi))) return rc;
+        }
+    }
+    *E_F = hi;
+    if (N_F) *N_F = Nhi;
+    return ABZ_OK;
+}
 
 }  // namespace abz

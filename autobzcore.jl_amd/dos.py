@@ -24,11 +24,23 @@ class GGR(DOSAlgorithm):
 class LTM(DOSAlgorithm):
     """Linear tetrahedron method (Bloechl, Jepsen, Andersen, PRB 49, 16223; no curvature correction) on the eigenvalues of
     the full periodic `npt^d` grid, cells cut by the Kuhn split.  `cumulative=True` returns the number of states N(E)
-    below E instead of the DOS g(E).  The reference plans it: src/dos_algorithms.jl:1-7."""
+    below E instead of the DOS g(E).  The reference plans it: src/dos_algorithms.jl:1-7.
 
-    def __init__(self, npt=50, cumulative=False):
+    `elements` weighs every band with a matrix element A_b(k), interpolated linearly inside a simplex like the energy:
+    the solution is g_A(E) = sum_b int A_b delta(E - e_b) (or N_A with `cumulative`), `u` of shape [nE, ncomp]
+    ([ncomp] for a scalar domain).
+      "energy"    A = e itself, one component: E g(E), and the band energy as N_A;
+      "orbitals"  the orbital-projected DOS, A_{a,b}(k) = |U_ab(k)|^2, ncomp = n.  A host-side companion, not a
+                  performance path: the rule is built with H(k) as well, exported, and diagonalised by numpy.linalg.eigh;
+      callable    f(x [nk, d], eig [nk, n]) -> [ncomp, nk, n] on the rule's exported nodes and eigenvalues.
+    The elements are computed again whenever the cache rebuilds its eigenvalues."""
+
+    def __init__(self, npt=50, cumulative=False, elements=None):
         self.npt = int(npt)
         self.cumulative = bool(cumulative)
+        if not (elements is None or callable(elements) or elements in ("energy", "orbitals")):
+            raise ValueError(f"LTM: elements = {elements!r} is neither 'energy', 'orbitals' nor a callable")
+        self.elements = elements
 
 
 @dataclass
@@ -55,6 +67,7 @@ class DOSCache:
         object.__setattr__(self, "H", H)
         self.domain, self.p, self.alg, self.cacheval, self.kwargs = domain, p, alg, cacheval, kwargs
         self.isfresh = False
+        self.elements = _ltm_elements(cacheval, alg)
 
     def __setattr__(self, name, value):
         if name == "H":
@@ -78,8 +91,42 @@ def _init_cacheval(h, domain, p, alg):
     if isinstance(alg, LTM):
         # eigenvalues only, on the FULL grid whatever the zone's symmetries: the DOS is a scalar, so the full-zone sum is the
         # answer for every zone kind (a symmetry-reduced tetrahedron mesh is not implemented)
-        return h.device().rule(alg.npt, None, L.WANT_EIG)
+        return h.device().rule(alg.npt, None, (L.WANT_H | L.WANT_EIG) if alg.elements == "orbitals" else L.WANT_EIG)
     return h.device().rule(alg.npt, p.syms, L.WANT_EIG | L.WANT_VEL)
+
+
+def _ltm_elements(rule, alg):
+    """What an LTM cache hands DeviceRule.ltm as `elements`: None, "energy", or the host array [ncomp, nk, n] computed
+    from the rule's current values."""
+    if not isinstance(alg, LTM) or alg.elements is None or rule is None:
+        return None
+    if alg.elements == "energy":
+        return "energy"
+    if alg.elements == "orbitals":
+        ex = rule.export(x=False, w=False, H=True)
+        H = ex["H"]
+        if H.ndim == 1:  # scalar series
+            return np.ones((1, len(H), 1))
+        _, U = np.linalg.eigh(H)  # ascending, the order of the rule's eigenvalue planes
+        return np.ascontiguousarray((np.abs(U) ** 2).transpose(1, 0, 2))  # [a, k, b]
+    ex = rule.export(x=True, w=False, eig=True)
+    A = np.asarray(alg.elements(ex["x"], ex["eig"]), dtype=np.float64)
+    if A.ndim == 2:
+        A = A[None]
+    if A.ndim != 3 or A.shape[1:] != ex["eig"].shape:
+        raise ValueError(f"LTM: elements(x, eig) returned shape {A.shape}, expected [ncomp, {ex['eig'].shape[0]}, {ex['eig'].shape[1]}]")
+    return np.ascontiguousarray(A)
+
+
+def _ltm_solve(c, Es):
+    rule, el = c.cacheval, c.elements
+    if el is None or isinstance(el, str):
+        return rule.ltm(Es, states=c.alg.cumulative, elements=el)
+    rule.h  # a stale rule refills here and loses its elements
+    if rule._ltm_ncomp == 0 or getattr(rule, "_ltm_owner", None) is not el:  # (another cache on the same rule attached its own)
+        rule.ltm_elements(el)
+        rule._ltm_owner = el
+    return rule.ltm(Es, states=c.alg.cumulative, elements="attached")
 
 
 def init(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):
@@ -92,6 +139,7 @@ def solve_(c: DOSCache):
     """solve!(cache).  ref: src/dos_interfaces.jl:104-112, dos_solve src/dos_ggr.jl:46-56."""
     if c.isfresh:
         c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     if not isinstance(c.alg, (GGR, LTM)):
         raise ValueError("unknown DOS algorithm")
@@ -99,8 +147,23 @@ def solve_(c: DOSCache):
     if not scalar and not isinstance(c.domain, (list, tuple, np.ndarray)):
         raise ValueError(f"{type(c.alg).__name__} supports domains of individual eigenvalues")
     Es = np.atleast_1d(np.asarray(c.domain, dtype=np.float64))
-    u = c.cacheval.ltm(Es, states=c.alg.cumulative) if isinstance(c.alg, LTM) else c.cacheval.ggr(Es)
+    u = _ltm_solve(c, Es) if isinstance(c.alg, LTM) else c.cacheval.ggr(Es)
+    if u.ndim == 2:
+        return DOSSolution(u[0].copy() if scalar else u, None, True, -1)
     return DOSSolution(float(u[0]) if scalar else u, None, True, -1)
+
+
+def fermi_level(prob_or_cache, nstates, tol=1e-10):
+    """(E_F, N(E_F)) of `nstates` states per unit cell (0 < nstates < n) from the eigenvalues of an LTM cache, or of a
+    DOSProblem (solved with LTM()): E_F is the upper end of an interval no wider than `tol` that N crosses `nstates` in."""
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    if not isinstance(c.alg, LTM):
+        raise ValueError("fermi_level needs an LTM cache")
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    return c.cacheval.ltm_fermi(nstates, tol)
 
 
 def solve(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):

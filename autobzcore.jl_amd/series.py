@@ -365,6 +365,7 @@ class DeviceRule:
                                                    w.ctypes.data_as(L.c_i64p), want, C.byref(h)))
         self._h = h if h.value else None
         self._closed = False
+        self._ltm_ncomp = 0  # components of the matrix elements attached by ltm_elements
         self.generation = dev.generation
         if self._h is not None and want & L.WANT_H_COMPACT:  # the library drops the bit when the layout does not apply
             got = C.c_int(0)
@@ -382,6 +383,7 @@ class DeviceRule:
             raise L.AbzError("DeviceRule was closed")
         if self._h is not None and self.generation != self.dev.generation:
             self.generation = self.dev.generation
+            self._ltm_ncomp = 0  # the library drops attached matrix elements with the old eigenstates
             L.check(L.lib().abz_rule_rebuild(self._h))
         return self._h
 
@@ -412,6 +414,7 @@ class DeviceRule:
             raise L.AbzError("DeviceRule was closed")
         if self._h is not None:
             self.generation = self.dev.generation
+            self._ltm_ncomp = 0
             L.check(L.lib().abz_rule_rebuild(self._h))
 
     def reduce(self, fid, params=(), sweep=None, nsyms=None):
@@ -485,14 +488,63 @@ class DeviceRule:
             L.check(L.lib().abz_rule_ggr(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), out.ctypes.data_as(L.c_f64p)))
         return self._sum_over_ranks(out)
 
-    def ltm(self, Es, states=False):
-        """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
-        number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid."""
+    def _ltm_refuse_shard(self):
         if self.shard and self.shard[1] > 1:
             raise NotImplementedError("LTM on a k-sharded (slab) rule is not implemented: the simplices of a slab's last "
                                       "plane need one halo plane from the next rank")
+
+    def ltm_elements(self, A):
+        """Attach matrix elements A [ncomp, nk, n] (node and band order of export()'s eig [nk, n]) to the rule for
+        weighted tetrahedron scans (abz_rule_ltm_elements); `None` drops them.  They stay on the device until replaced,
+        dropped, or the rule is rebuilt."""
+        self._ltm_refuse_shard()
+        if A is None:
+            L.check(L.lib().abz_rule_ltm_elements(self.h, None, 0))
+            self._ltm_ncomp = 0
+            return
+        s = self.dev.s
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+        if A.ndim == 2:
+            A = A[None]
+        if A.ndim != 3 or A.shape[1:] != (self.nk, s.n):
+            raise ValueError(f"ltm_elements: elements of shape {A.shape}, expected [ncomp, {self.nk}, {s.n}]")
+        L.check(L.lib().abz_rule_ltm_elements(self.h, A.ctypes.data_as(L.c_f64p), A.shape[0]))
+        self._ltm_ncomp = A.shape[0]
+
+    def ltm(self, Es, states=False, elements=None):
+        """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
+        number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid.
+
+        `elements`: matrix elements A_b(k), interpolated linearly inside a simplex like the energy; the result is then
+        g_A(E) = sum_b int A_b delta(E - e_b) or N_A(E) = sum_b int A_b theta(E - e_b) as [nE, ncomp]
+        (abz_rule_ltm_weighted).  "energy": A = e itself (one component); "attached": what ltm_elements attached; an
+        array [ncomp, nk, n]: attached first."""
+        self._ltm_refuse_shard()
         Es = np.ascontiguousarray(np.asarray(Es, dtype=np.float64).reshape(-1))
-        out = np.zeros(len(Es))
-        L.check(L.lib().abz_rule_ltm(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), L.LTM_STATES if states else L.LTM_DOS,
-                                     out.ctypes.data_as(L.c_f64p)))
+        what = L.LTM_STATES if states else L.LTM_DOS
+        if elements is None:
+            out = np.zeros(len(Es))
+            L.check(L.lib().abz_rule_ltm(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
+            return out
+        if isinstance(elements, str):
+            if elements not in ("energy", "attached"):
+                raise ValueError(f"ltm: elements = {elements!r} is neither 'energy' nor 'attached'")
+        else:
+            self.ltm_elements(elements)
+            elements = "attached"
+        h = self.h  # (a stale rule is refilled here, which drops the attached elements)
+        ncomp = 1 if elements == "energy" else self._ltm_ncomp
+        if ncomp < 1:
+            raise ValueError("ltm: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
+        out = np.zeros((len(Es), ncomp))
+        L.check(L.lib().abz_rule_ltm_weighted(h, L.LTM_A_ENERGY if elements == "energy" else L.LTM_A_ELEMENTS,
+                                              Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
         return out
+
+    def ltm_fermi(self, nstates, tol=1e-10):
+        """(E_F, N(E_F)): the Fermi level of `nstates` states per unit cell, 0 < nstates < n, to within `tol`
+        (abz_rule_ltm_fermi: a few N(E) scans of 512 energies each, no host bisection)."""
+        self._ltm_refuse_shard()
+        ef, nf = C.c_double(0.0), C.c_double(0.0)
+        L.check(L.lib().abz_rule_ltm_fermi(self.h, float(nstates), float(tol), C.byref(ef), C.byref(nf)))
+        return ef.value, nf.value

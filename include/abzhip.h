@@ -262,6 +262,25 @@ int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out);
 #define ABZ_LTM_STATES 1
 int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out);
 
+/* Tetrahedron method with matrix elements, and the Fermi level.  The same whole periodic grids as abz_rule_ltm, the same
+ * refusals (ABZ_ERR_UNSUPPORTED for slabs and irreducible nodes, ABZ_ERR_ARG without eigenvalues).
+ * Replaces: nothing yet -- the reference plans LTM for "any function or H_R" (src/dos_algorithms.jl:5-7). */
+#define ABZ_LTM_MAX_COMP 16
+/* Attach matrix elements to a full-grid rule that holds eigenvalues: A [ncomp][nk][n] host doubles, node order and band
+ * order those of abz_rule_export's eig [nk][n] (i_1 fastest, bands ascending).  They stay resident in HBM in the layout of the
+ * eigenvalue planes until replaced, dropped (A = NULL, ncomp = 0), abz_rule_rebuild (they described the old eigenstates) or
+ * abz_rule_destroy. */
+int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp);
+#define ABZ_LTM_A_ELEMENTS 0   /* the attached elements, ncomp components */
+#define ABZ_LTM_A_ENERGY 1     /* A_b(k) = e_b(k) itself, 1 component, nothing attached needed */
+/* out [nE][ncomp]: g_A(E) (ABZ_LTM_DOS) or N_A(E) (ABZ_LTM_STATES), per unit cell, summed over bands; A is interpolated
+ * linearly inside each simplex like the band energy. */
+int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int what, double* out);
+/* Fermi level: E_F with N(E_F) >= nstates (1 - 1e-12) and N(E) below that for every sampled E <= E_F - tol;
+ * 0 < nstates < n.  N_F (nullable) receives N(E_F).  Below a gap (g = 0 exactly from some energy on while N is still
+ * nstates to 1e-12) E_F is moved up to the lowest energy with g(E_F) = 0, the top of the band, to within tol. */
+int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F);
+
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.
  * First call with irr_idx = NULL to get *nirr; then with buffers irr_idx [nirr][d], wsym [nirr]. */

@@ -384,6 +384,47 @@ function ltm(h::FourierSeries{S,N}, Es::Vector{Float64}; npt=50, cumulative::Boo
     return out
 end
 
+"""
+    ltm_elements!(r, A)
+
+Attach matrix elements `A[b, k, c]` (band, node, component: the memory order of the C array `[ncomp][nk][n]`, nodes and
+bands as `export_rule` orders the eigenvalues) to a full-grid rule with eigenvalues (`abz_rule_ltm_elements`);
+`nothing` drops them.  A rebuild of the rule drops them too.
+"""
+function ltm_elements!(r::HIPRule, A::Union{Nothing,Array{Float64,3}})
+    if A === nothing
+        check(ccall((:abz_rule_ltm_elements, libabz), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), r.h, C_NULL, 0))
+    else
+        check(ccall((:abz_rule_ltm_elements, libabz), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), r.h, A, size(A, 3)))
+    end
+    return r
+end
+
+"""
+    ltm_weighted(r, Es; ncomp, energy=false, cumulative=false)
+
+`g_A(E)` (or `N_A(E)` with `cumulative`) of the attached elements, `ncomp` of them, or with `energy` of `A = e` itself
+(`abz_rule_ltm_weighted`): a matrix `[ncomp, nE]`.
+"""
+function ltm_weighted(r::HIPRule, Es::Vector{Float64}; ncomp::Integer=1, energy::Bool=false, cumulative::Bool=false)
+    out = Matrix{Float64}(undef, energy ? 1 : ncomp, length(Es))
+    check(ccall((:abz_rule_ltm_weighted, libabz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cint, Ptr{Float64}), r.h,
+        energy ? 1 : 0, Es, length(Es), cumulative ? 1 : 0, out))
+    return out
+end
+
+"""
+    ltm_fermi(r, nstates; tol=1e-10)
+
+`(E_F, N(E_F))` of `nstates` states per unit cell, `0 < nstates < n`, to within `tol` (`abz_rule_ltm_fermi`).
+"""
+function ltm_fermi(r::HIPRule, nstates::Real; tol::Real=1e-10)
+    ef = Ref{Float64}(0.0); nf = Ref{Float64}(0.0)
+    check(ccall((:abz_rule_ltm_fermi, libabz), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}), r.h,
+        Float64(nstates), Float64(tol), ef, nf))
+    return ef[], nf[]
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
