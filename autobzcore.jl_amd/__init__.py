@@ -19,7 +19,7 @@ from .io_sweep import SweepArchive, batchsolve_archive
 from .h5lite import read_h5_to_nt, write_nt_to_h5
 from .generic import fourier_batch
 from .synthetic import synthetic_wannier, tb_integer, splitmix64_uniform
-from .series import DeviceRule, DeviceSeries, FourierSeries, symptr_rule
+from .series import DeviceRule, DeviceSeries, FourierSeries, UnfoldedRule, symptr_rule
 from .solver import (IAI, PTR, TAI, PTR_IAI, AutoPTR_IAI, HCubatureJL, ContQuadGKJL, MeroQuadGKJL, InplaceIntegrand, QuadratureFunction, trapz, AbsoluteEstimate, AutoPTR, AutoSymPTRJL, AuxQuadGKJL, AuxValue, QuadGKJL, BatchIntegrand, DOSIntegrand, DeviceIntegrand,
                      EvalCounter, FourierIntegrand, FourierValue, GlocIntegrand, IntegralProblem, IntegralSolution,
                      IntegralSolver, LinearIntegrand, LinearXIntegrand, MixedParameters, MonkhorstPack, NestedBatchIntegrand, NestedQuad,

@@ -301,6 +301,11 @@ struct abz_rule {
     int32_t* idx = nullptr;  // [d][nk] grid indices (symmetric rules)
     void* plan = nullptr;    // abz::RulePlan (api.cpp): contraction plan + phase table, device resident
     bool tables_view = false;  // w and idx point into the plan's copy of the symmetric-rule tables
+    // a full-grid rule whose eigenvalue planes abz_rule_ltm_unfold gathers from the irreducible nodes of another rule:
+    int32_t* node_of = nullptr;  // [npt^d] the source node in the orbit of every grid point (the orbit map)
+    size_t node_of_cap = 0;
+    int64_t unfold_nk = 0;       // nodes of the source rule the map was made for
+    std::vector<int32_t> unfold_syms;  // the symmetries the map was made under [nsyms][d][d]
 };
 
 namespace abz {
@@ -492,6 +497,12 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
                         bool states, double* out_host);
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
+// Orbit map of an unfolded rule: node_of[x] = the node k of the list idx [d][nk] that is x or its first image under syms that
+// is a node; rank [npt^d] is scratch; *missing_dev counts the points without one (their node_of is -1).  Launches only.
+int launch_ltm_orbit_map(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, const int32_t* idx, int64_t nk, int32_t* rank,
+                         int32_t* node_of, int* missing_dev);
+// dst (the n eigenvalue planes of the whole grid, padding included) <- src at node_of; a point without a node gets zeros
+int launch_ltm_unfold(abz_ctx* ctx, PlaneView src, PlaneView dst, const int32_t* node_of, int n, int npt, int64_t nlines);
 // Fermi level by repeated N(E) scans of 512 energies between the smallest and largest eigenvalue (abz_rule_ltm_fermi)
 int ltm_fermi(abz_ctx* ctx, int n, int d, int npt, PlaneView E, int64_t nk, double nstates, double tol, double* E_F, double* N_F);
 

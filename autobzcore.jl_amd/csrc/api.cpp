@@ -1063,6 +1063,7 @@ static void rule_free(abz_rule* r) {
     if (!r) return;
     rule_drop_ltm_elements(r);
     dev_free(r->vals, r->vals_cap);
+    dev_free(r->node_of, r->node_of_cap);
     if (!r->tables_view) {
         dev_free(r->w, r->w_cap);
         dev_free(r->idx, r->idx_cap);
@@ -1503,6 +1504,11 @@ int abz_ptr_rule_build_slab(abz_series* s, int npt, int outer_begin, int outer_e
 int abz_rule_rebuild(abz_rule* r) try {
     int rc0 = check_rule(r);
     if (rc0) return rc0;
+    if (r->node_of) {
+        set_error("abz_rule_rebuild: the rule holds eigenvalues unfolded from another rule and no plan of its own; rebuild the source "
+                  "and call abz_rule_ltm_unfold(src, syms, nsyms, &rule) again");
+        return ABZ_ERR_UNSUPPORTED;
+    }
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     RulePlan* rp = static_cast<RulePlan*>(r->plan);
@@ -2199,6 +2205,98 @@ int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, dou
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     return ltm_fermi(ctx, r->s->n, r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
+} ABZ_CATCH_ALL
+
+// One eigenvalue per band is a scalar that the zone's symmetries leave alone, e_b(S k) = e_b(k): the planes of the whole grid
+// are a gather from the irreducible nodes.  The orbit map depends on (npt, d, syms, node list) only and stays with the rule.
+int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule** out) try {
+    int rc = check_rule(src);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_unfold: null out");
+    ABZ_REQUIRE(syms && nsyms >= 1, "abz_rule_ltm_unfold: no symmetries (syms = %s, nsyms = %d)", syms ? "given" : "NULL", nsyms);
+    ABZ_REQUIRE(src->E.base, "abz_rule_ltm_unfold: the source rule holds no eigenvalues (build it with ABZ_WANT_EIG)");
+    if (src->full) {
+        set_error("abz_rule_ltm_unfold: the source rule is %s, not a list of irreducible nodes: there is nothing to unfold",
+                  src->node_of ? "an unfolded grid" : "a full grid or a slab of one");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    abz_series* s = src->s;
+    abz_ctx* ctx = s->ctx;
+    const int d = s->d, n = s->n, npt = src->npt;
+    int64_t N = 1;
+    for (int j = 0; j < d; ++j) N *= npt;
+    if (N >= ((int64_t)1 << 31)) {
+        set_error("abz_rule_ltm_unfold: a grid of %lld points does not fit the 32-bit orbit map", (long long)N);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    ABZ_HIP(hipSetDevice(ctx->device));
+    abz_rule* r = *out;
+    if (r) {  // gather again through the map the rule has
+        if ((rc = check_rule(r))) return rc;
+        ABZ_REQUIRE(r->node_of && r != src, "abz_rule_ltm_unfold: *out is not a rule made by abz_rule_ltm_unfold (pass NULL to create one)");
+        ABZ_REQUIRE(r->s == s && r->npt == npt && r->unfold_nk == src->nk,
+                    "abz_rule_ltm_unfold: *out was unfolded from another geometry (series, npt = %d, %lld nodes; the source has npt = %d, %lld nodes)",
+                    r->npt, (long long)r->unfold_nk, npt, (long long)src->nk);
+        ABZ_REQUIRE(r->unfold_syms.size() == (size_t)nsyms * d * d && std::equal(r->unfold_syms.begin(), r->unfold_syms.end(), syms),
+                    "abz_rule_ltm_unfold: *out was unfolded under another symmetry set (its orbit map does not fit these %d matrices)", nsyms);
+        if (r->ltm_elems) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
+            ABZ_HIP(hipStreamSynchronize(ctx->stream));
+            rule_drop_ltm_elements(r);
+        }
+        r->herm = src->herm;
+        if ((rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of, n, npt, r->ntiles))) return rc;
+        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        return ABZ_OK;
+    }
+    r = new abz_rule();
+    r->plan = new RulePlan();  // empty: an unfolded rule has no contraction plan (abz_rule_rebuild refuses it)
+    r->s = s;
+    r->npt = npt;
+    r->want = ABZ_WANT_EIG;
+    r->full = true;
+    r->herm = src->herm;
+    r->nk = N;
+    r->ntiles = N / npt;
+    r->planes = n;
+    r->unfold_nk = src->nk;
+    r->unfold_syms.assign(syms, syms + (size_t)nsyms * d * d);
+    const int row = (npt + 15) / 16 * 16;
+    r->E.tile = (int64_t)n * row;
+    r->E.pitch = row;
+    r->E.line_len = npt;
+    r->E.row = row;
+    int32_t* rank = nullptr;  // scratch: [N] node of a point, then the counter of points without one
+    size_t rank_cap = 0;
+    int missing = 0;
+    rc = dev_alloc((void**)&r->vals, sizeof(double) * (size_t)r->ntiles * (size_t)n * (size_t)row, &r->vals_cap);
+    if (!rc) rc = dev_alloc((void**)&r->node_of, sizeof(int32_t) * (size_t)N, &r->node_of_cap);
+    if (!rc) rc = dev_alloc((void**)&rank, sizeof(int32_t) * ((size_t)N + 1), &rank_cap);
+    if (!rc) {
+        r->E.base = r->vals;
+        int* const missing_dev = reinterpret_cast<int*>(rank + N);
+        rc = launch_ltm_orbit_map(ctx, npt, d, syms, nsyms, src->idx, src->nk, rank, r->node_of, missing_dev);
+        if (!rc) rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of, n, npt, r->ntiles);
+        // the call's one synchronisation: the counter, the map and the planes have arrived
+        hipError_t e = hipMemcpyAsync(&missing, missing_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess && !rc) {
+            set_error("abz_rule_ltm_unfold: %s", hipGetErrorString(e));
+            rc = ABZ_ERR_HIP;
+        }
+    }
+    dev_free(rank, rank_cap);
+    if (!rc && missing != 0) {
+        set_error("abz_rule_ltm_unfold: %d of the %lld grid points have no image under the %d symmetries among the %lld nodes of the source rule "
+                  "(the node list does not cover every orbit)", missing, (long long)N, nsyms, (long long)src->nk);
+        rc = ABZ_ERR_ARG;
+    }
+    if (rc) {
+        rule_free(r);
+        return rc;
+    }
+    s->refs += 1;
+    *out = r;
+    return ABZ_OK;
 } ABZ_CATCH_ALL
 
 // ---------------------------------------------------------------- arbitrary nodes

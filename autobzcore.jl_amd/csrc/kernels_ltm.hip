@@ -54,6 +54,11 @@
 //    integer; its prefix sum keeps a fixed order.  The elements live in ncomp n planes tiled like the eigenvalue
 //    planes (plane c n + b: component c of band b); a launch carries 1, 2 or 4 components, so that the corners of a
 //    cell (8 energies + 8 NC elements) stay in registers, and a call walks the grid once per group of components.
+//  * Symmetric zones (abz_rule_ltm_unfold).  The scans always walk the whole grid; the eigenvalues they read are invariant
+//    under the zone's symmetries, e_b(S k) = e_b(k), so a full-grid rule's planes can be a gather from the irreducible
+//    nodes of another rule.  ltm_rank_kernel scatters the node numbers into a table over the grid, ltm_orbit_kernel finds
+//    for every grid point the node among its images (the orbit map, 4 B per point, kept by the rule), ltm_unfold_kernel
+//    copies: one wave per 64 columns of a padded line, 512 contiguous bytes per plane and store instruction.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,6 +67,8 @@
 #include <vector>
 
 #include "abz_internal.h"
+#include "rows_device.h"
+#include "sym_image.h"
 
 namespace abz {
 
@@ -746,6 +753,67 @@ __global__ __launch_bounds__(256) void ltm_minmax_kernel(PlaneView E, int n, int
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Eigenvalues of the whole grid from those of the irreducible nodes (abz_rule_ltm_unfold): e_b(S k) = e_b(k)
+// ---------------------------------------------------------------------------------------------------------------------
+// rank[flat index of node k] = k.  idx [d][nk] holds grid indices inside 0 .. npt-1 (device-built lists by construction,
+// explicit lists are checked when their rule is built); a list that names a point twice leaves either of the two.
+__global__ __launch_bounds__(256) void ltm_rank_kernel(const int32_t* __restrict__ idx, int64_t nk, int d, int npt, int64_t N,
+                                                       int32_t* __restrict__ rank) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nk) return;
+    int64_t lin = 0, mul = 1;
+    for (int j = 0; j < d; ++j) {
+        lin += (int64_t)idx[(int64_t)j * nk + k] * mul;
+        mul *= npt;
+    }
+    if (lin >= 0 && lin < N) rank[lin] = (int32_t)k;
+}
+
+// One thread per grid point: the node it is, or the node among its images (sym_image: the integer matrices on grid
+// indices mod npt) that comes first in the set's order.  Which image of an orbit the list keeps does not matter.
+__global__ __launch_bounds__(256) void ltm_orbit_kernel(SymArgs a, const int32_t* __restrict__ rank, int32_t* __restrict__ node_of,
+                                                        int* __restrict__ missing) {
+    const int64_t lin = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (lin >= a.N) return;
+    int32_t k = rank[lin];
+    if (k < 0) {
+        int v[3] = {0, 0, 0};
+        int64_t r = lin;
+        for (int j = 0; j < a.d; ++j) {
+            v[j] = (int)(r % a.npt);
+            r /= a.npt;
+        }
+        for (int s = 0; s < a.nsyms && k < 0; ++s) {
+            const int64_t img = sym_image(a, v, s);  // inside 0 .. N-1: every coordinate is reduced mod npt
+            k = rank[img];
+        }
+        if (k < 0) atomicAdd(missing, 1);
+    }
+    node_of[lin] = k;
+}
+
+// One wave per 64 consecutive columns of a padded grid line: each lane reads its point's node once and copies the n
+// eigenvalues of that node (a source of a few MB at most: it stays in L2) into the n planes; the stores of a wave are
+// 512 contiguous bytes per plane, the rows the builders write.  Padding columns npt .. row-1 get zeros.
+__global__ __launch_bounds__(256) void ltm_unfold_kernel(PlaneView src, PlaneView dst, const int32_t* __restrict__ node_of, int n,
+                                                         int npt, int chunks, int64_t nunits) {
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= nunits) return;
+    const int64_t line = u / chunks;
+    const int i = (int)(u - line * chunks) * 64 + (int)(threadIdx.x & 63);
+    if (i >= dst.row) return;
+    double* __restrict__ const out = dst.base + line * dst.tile + i;
+    const int32_t k = i < npt ? node_of[line * npt + i] : -1;
+    if (k < 0) {
+        for (int b = 0; b < n; ++b) out[(int64_t)b * dst.pitch] = 0.0;
+        return;
+    }
+    const double* __restrict__ const in = src.base + view_off(src, k);
+#pragma unroll 4
+    for (int b = 0; b < n; ++b) out[(int64_t)b * dst.pitch] = in[(int64_t)b * src.pitch];
+}
+
 }  // namespace
 
 #define ABZ_LTM_D(ST)                                                                                         \
@@ -913,6 +981,33 @@ int launch_ltm_minmax(abz_ctx* ctx, int n, PlaneView E, int64_t nk, double* emin
     }
     *emin = mn;
     *emax = mx;
+    return ABZ_OK;
+}
+
+int launch_ltm_orbit_map(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, const int32_t* idx, int64_t nk, int32_t* rank,
+                         int32_t* node_of, int* missing_dev) {
+    if (nsyms > 48 || d > 3 || d < 1) {
+        set_error("abz_rule_ltm_unfold: at most 48 symmetries of a <= 3-d lattice");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    SymArgs a;
+    sym_args_init(a, npt, d, syms, nsyms);
+    ABZ_HIP(hipMemsetAsync(rank, 0xff, sizeof(int32_t) * (size_t)a.N, ctx->stream));  // -1: not a node
+    ABZ_HIP(hipMemsetAsync(missing_dev, 0, sizeof(int), ctx->stream));
+    ProfScope ps(ctx, ABZ_K_LTM);
+    launch(ctx, ltm_rank_kernel, dim3((unsigned)cdiv64(nk, 256)), dim3(256), 0, idx, nk, d, npt, a.N, rank);
+    ABZ_HIP(hipGetLastError());
+    launch(ctx, ltm_orbit_kernel, dim3((unsigned)cdiv64(a.N, 256)), dim3(256), 0, a, (const int32_t*)rank, node_of, missing_dev);
+    ABZ_HIP(hipGetLastError());
+    return ABZ_OK;
+}
+
+int launch_ltm_unfold(abz_ctx* ctx, PlaneView src, PlaneView dst, const int32_t* node_of, int n, int npt, int64_t nlines) {
+    const int chunks = (dst.row + 63) / 64;
+    const int64_t nunits = nlines * chunks;
+    ProfScope ps(ctx, ABZ_K_LTM);
+    launch(ctx, ltm_unfold_kernel, dim3((unsigned)cdiv64(nunits, 4)), dim3(256), 0, src, dst, node_of, n, npt, chunks, nunits);
+    ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
 

@@ -6,6 +6,7 @@
 //   compaction      order-preserving stream compaction of the representatives (block counts ->
 //                   exclusive scan -> scatter), so the list comes out in column-major order.
 #include "abz_internal.h"
+#include "sym_image.h"
 
 #include <algorithm>
 #include <chrono>
@@ -14,49 +15,6 @@
 #include <cstdlib>
 
 namespace abz {
-
-struct SymArgs {
-    int npt, d, nsyms;
-    int small;  // every |S v| < 2^31: 32-bit arithmetic (a 64-bit modulo costs ~4x more)
-    int perm;   // every matrix is a signed permutation (cubic / inversion groups in the lattice basis): no modulo at all
-    int group;  // the set is closed under multiplication (a group): orbit size = nsyms / |stabiliser|
-    int64_t N;
-    int S[48 * 9];  // up to 48 symmetries of a 3-d lattice, row-major
-};
-
-__device__ __forceinline__ int64_t sym_image(const SymArgs& a, const int* v, int s) {
-    int64_t img = 0, mul = 1;
-    if (a.perm) {  // row r has one entry +-1, in column c: the image coordinate is v[c] or (npt - v[c]) mod npt
-        for (int r = 0; r < a.d; ++r) {
-            int t = 0;
-            for (int c = 0; c < a.d; ++c) {
-                const int e = a.S[(s * a.d + r) * a.d + c];
-                t = e > 0 ? v[c] : (e < 0 ? (v[c] == 0 ? 0 : a.npt - v[c]) : t);
-            }
-            img += (int64_t)t * mul;
-            mul *= a.npt;
-        }
-        return img;
-    }
-    for (int r = 0; r < a.d; ++r) {
-        int64_t t;
-        if (a.small) {
-            int t32 = 0;
-            for (int c = 0; c < a.d; ++c) t32 += a.S[(s * a.d + r) * a.d + c] * v[c];
-            t32 %= a.npt;
-            if (t32 < 0) t32 += a.npt;
-            t = t32;
-        } else {
-            t = 0;
-            for (int c = 0; c < a.d; ++c) t += (int64_t)a.S[(s * a.d + r) * a.d + c] * v[c];
-            t %= a.npt;
-            if (t < 0) t += a.npt;
-        }
-        img += t * mul;
-        mul *= a.npt;
-    }
-    return img;
-}
 
 __global__ __launch_bounds__(256) void symptr_flag_kernel(SymArgs a, int* __restrict__ wflag) {
     const int64_t lin = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,28 +82,7 @@ int symptr_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, 
         return ABZ_ERR_UNSUPPORTED;
     }
     SymArgs a;
-    a.npt = npt;
-    a.d = d;
-    a.nsyms = nsyms;
-    a.N = 1;
-    for (int j = 0; j < d; ++j) a.N *= npt;
-    int64_t smax = 1;
-    for (int i = 0; i < nsyms * d * d; ++i) {
-        a.S[i] = syms[i];
-        smax = std::max<int64_t>(smax, std::llabs((long long)syms[i]));
-    }
-    a.small = (smax * d * (int64_t)npt < ((int64_t)1 << 30)) ? 1 : 0;
-    a.perm = 1;
-    a.group = 0;
-    for (int sidx = 0; sidx < nsyms && a.perm; ++sidx)
-        for (int r = 0; r < d && a.perm; ++r) {
-            int nz = 0;
-            for (int c = 0; c < d; ++c) {
-                const int e = syms[(sidx * d + r) * d + c];
-                if (e != 0) nz += (e == 1 || e == -1) ? 1 : 2;
-            }
-            if (nz != 1) a.perm = 0;
-        }
+    sym_args_init(a, npt, d, syms, nsyms);
     const int64_t nb = (a.N + 255) / 256;
     DevBuf flag, counts, offs, didx, dw;
     int rc;
@@ -426,27 +363,7 @@ int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsy
         return ABZ_ERR_UNSUPPORTED;
     }
     SymArgs a;
-    a.npt = npt;
-    a.d = d;
-    a.nsyms = nsyms;
-    a.N = 1;
-    for (int j = 0; j < d; ++j) a.N *= npt;
-    int64_t smax = 1;
-    for (int i = 0; i < nsyms * d * d; ++i) {
-        a.S[i] = syms[i];
-        smax = std::max<int64_t>(smax, std::llabs((long long)syms[i]));
-    }
-    a.small = (smax * d * (int64_t)npt < ((int64_t)1 << 30)) ? 1 : 0;
-    a.perm = 1;
-    for (int sidx = 0; sidx < nsyms && a.perm; ++sidx)
-        for (int r = 0; r < d && a.perm; ++r) {
-            int nz = 0;
-            for (int c = 0; c < d; ++c) {
-                const int e = syms[(sidx * d + r) * d + c];
-                if (e != 0) nz += (e == 1 || e == -1) ? 1 : 2;
-            }
-            if (nz != 1) a.perm = 0;
-        }
+    sym_args_init(a, npt, d, syms, nsyms);
     a.group = syms_closed(d, syms, nsyms) ? 1 : 0;
     const int64_t nlines = a.N / npt, nplanes = d >= 3 ? nlines / npt : 0;
     // one block for all temporaries (every allocation and every return to the allocator costs a driver call or a

@@ -33,11 +33,18 @@ class LTM(DOSAlgorithm):
       "orbitals"  the orbital-projected DOS, A_{a,b}(k) = |U_ab(k)|^2, ncomp = n.  A host-side companion, not a
                   performance path: the rule is built with H(k) as well, exported, and diagonalised by numpy.linalg.eigh;
       callable    f(x [nk, d], eig [nk, n]) -> [ncomp, nk, n] on the rule's exported nodes and eigenvalues.
-    The elements are computed again whenever the cache rebuilds its eigenvalues."""
+    The elements are computed again whenever the cache rebuilds its eigenvalues.
 
-    def __init__(self, npt=50, cumulative=False, elements=None):
+    `symmetric=True` solves the eigenproblem at the irreducible nodes of the zone only and fills the full grid's eigenvalues
+    from them on the device (e_b(S k) = e_b(k), DeviceRule.unfold); the tetrahedron sum still runs over the whole grid.  The
+    zone's symmetries must be symmetries of H, the contract GGR and PTR have.  With one symmetry (FBZ) it is the plain full
+    grid.  "energy" and a callable work as before, at every full-grid node; "orbitals" is refused: |U_ab|^2 is not
+    invariant under operations that permute orbitals, and no H(k) is stored."""
+
+    def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False):
         self.npt = int(npt)
         self.cumulative = bool(cumulative)
+        self.symmetric = bool(symmetric)
         if not (elements is None or callable(elements) or elements in ("energy", "orbitals")):
             raise ValueError(f"LTM: elements = {elements!r} is neither 'energy', 'orbitals' nor a callable")
         self.elements = elements
@@ -87,10 +94,17 @@ def _init_cacheval(h, domain, p, alg):
         raise ValueError(f"{name} supports BZ parameters from load_bz")
     if p.ndim != h.d:
         raise ValueError(f"{name}: BZ and series dimensions differ")
+    if isinstance(alg, LTM) and alg.symmetric and alg.elements == "orbitals":
+        raise ValueError('LTM: elements = "orbitals" needs symmetric=False (orbital weights are not invariant under the zone\'s '
+                         "symmetries, and an unfolded rule stores no H(k))")
     h.invalidate()  # coefficients may have been mutated in place (test/dos.jl:123): re-upload, rules refill lazily
+    if isinstance(alg, LTM) and alg.symmetric and p.syms is not None and len(p.syms) > 1:
+        # eigensolves at the irreducible nodes only; the full grid's eigenvalue planes are a gather from them
+        return h.device().rule(alg.npt, p.syms, L.WANT_EIG).unfold()
     if isinstance(alg, LTM):
         # eigenvalues only, on the FULL grid whatever the zone's symmetries: the DOS is a scalar, so the full-zone sum is the
-        # answer for every zone kind (a symmetry-reduced tetrahedron mesh is not implemented)
+        # answer for every zone kind (symmetric=True above fills the same grid from the irreducible nodes; a symmetry-
+        # reduced tetrahedron MESH is not implemented)
         return h.device().rule(alg.npt, None, (L.WANT_H | L.WANT_EIG) if alg.elements == "orbitals" else L.WANT_EIG)
     return h.device().rule(alg.npt, p.syms, L.WANT_EIG | L.WANT_VEL)
 

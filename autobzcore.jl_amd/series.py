@@ -363,10 +363,7 @@ class DeviceRule:
             if len(w):
                 L.check(L.lib().abz_ptr_rule_build(dev.h, self.npt, len(w), idx.ctypes.data_as(L.c_i32p),
                                                    w.ctypes.data_as(L.c_i64p), want, C.byref(h)))
-        self._h = h if h.value else None
-        self._closed = False
-        self._ltm_ncomp = 0  # components of the matrix elements attached by ltm_elements
-        self.generation = dev.generation
+        self._adopt(h)
         if self._h is not None and want & L.WANT_H_COMPACT:  # the library drops the bit when the layout does not apply
             got = C.c_int(0)
             L.check(L.lib().abz_rule_info(self._h, None, None, None, None, C.byref(got)))
@@ -374,6 +371,13 @@ class DeviceRule:
         per = ((n * n if want & L.WANT_H_COMPACT else 2 * n * n) if want & L.WANT_H else 0) + (n if want & (L.WANT_EIG | L.WANT_VEL) else 0) + \
               (d * n if want & L.WANT_VEL else 0)
         self.nbytes = 8 * per * self.nk_local
+
+    def _adopt(self, h):
+        """The state every rule object keeps about its handle (subclasses that make the handle another way call this too)."""
+        self._h = h if h.value else None
+        self._closed = False
+        self._ltm_ncomp = 0  # components of the matrix elements attached by ltm_elements
+        self.generation = self.dev.generation
         self._fin = weakref.finalize(self, DeviceRule._destroy, self._h)
 
     @property
@@ -548,3 +552,74 @@ class DeviceRule:
         ef, nf = C.c_double(0.0), C.c_double(0.0)
         L.check(L.lib().abz_rule_ltm_fermi(self.h, float(nstates), float(tol), C.byref(ef), C.byref(nf)))
         return ef.value, nf.value
+
+    def unfold(self):
+        """The full-grid eigenvalue rule of this symmetric rule (abz_rule_ltm_unfold): every grid point gets the
+        eigenvalues of the irreducible node in its orbit, e_b(S k) = e_b(k), by a gather on the device instead of npt^d
+        eigensolves.  The symmetries must be symmetries of H (the contract GGR and PTR have on a symmetric zone).  The
+        result serves `ltm`, `ltm_elements`, `ltm_fermi` and `export`, follows the series like any rule; while it is alive this
+        rule hands out the same object."""
+        self._ltm_refuse_shard()
+        if self.syms is None:
+            raise ValueError("unfold: the rule is a full grid already (no symmetries to unfold)")
+        if not (self.want & L.WANT_EIG):
+            raise ValueError("unfold: the rule holds no eigenvalues (want lacked WANT_EIG)")
+        ref = getattr(self, "_unfolded", None)  # a weak reference: the unfolded rule holds this one, not the other way round
+        u = ref() if ref is not None else None
+        if u is None or u._closed:
+            u = UnfoldedRule(self)
+            self._unfolded = weakref.ref(u)
+        return u
+
+
+class UnfoldedRule(DeviceRule):
+    """Whole periodic grid of eigenvalues gathered from the irreducible nodes of a symmetric DeviceRule
+    (DeviceRule.unfold, abz_rule_ltm_unfold).  It holds eigenvalues only -- no H(k), no velocities -- and an orbit map of
+    4 B per grid point; `ltm`, `ltm_elements`, `ltm_fermi`, `export(eig=True)`, `npt`, `nk = npt^d` and `close` are those
+    of a full-grid rule."""
+
+    def __init__(self, source: DeviceRule):
+        dev = self.dev = source.dev
+        d, n = dev.s.d, dev.s.n
+        self.source = source
+        self.npt = source.npt
+        self.want = L.WANT_EIG
+        self.syms = None  # a full grid to every reader
+        self.nsyms = 1
+        self.shard = None
+        self.nk = self.nk_local = self.npt ** d
+        self._S = np.ascontiguousarray(np.rint(np.asarray(source.syms)).astype(np.int32).reshape(-1, d, d))
+        self._hbox = C.c_void_p()
+        src = source.h  # (a stale source is refilled here)
+        L.check(L.lib().abz_rule_ltm_unfold(src, self._S.ctypes.data_as(L.c_i32p), len(self._S), C.byref(self._hbox)))
+        self._adopt(self._hbox)
+        self.nbytes = (8 * n + 4) * self.nk
+
+    def _source(self):
+        if self.source._closed:  # the series' rule cache let it go: the same nodes again
+            self.source = self.dev.rule(self.npt, self.source.syms, self.source.want)
+        return self.source
+
+    def _gather(self):
+        self._source()
+        self.generation = self.dev.generation
+        self._ltm_ncomp = 0  # the library drops attached matrix elements with the old eigenstates
+        L.check(L.lib().abz_rule_ltm_unfold(self.source.h, self._S.ctypes.data_as(L.c_i32p), len(self._S), C.byref(self._hbox)))
+
+    @property
+    def h(self):
+        """The abz_rule handle; when the series moved on, the source is refilled and the planes are gathered again."""
+        if self._closed:
+            raise L.AbzError("DeviceRule was closed")
+        if self.generation != self.dev.generation:
+            self._gather()
+        return self._h
+
+    def rebuild(self):
+        if self._closed:
+            raise L.AbzError("DeviceRule was closed")
+        self._source().rebuild()
+        self._gather()
+
+    def unfold(self):
+        raise ValueError("unfold: the rule is a full grid already (no symmetries to unfold)")

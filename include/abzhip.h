@@ -280,6 +280,22 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
  * 0 < nstates < n.  N_F (nullable) receives N(E_F).  Below a gap (g = 0 exactly from some energy on while N is still
  * nstates to 1e-12) E_F is moved up to the lowest energy with g(E_F) = 0, the top of the band, to within tol. */
 int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F);
+/* Full-grid eigenvalue rule filled from the irreducible nodes of `src` (built with ABZ_WANT_EIG by abz_ptr_rule_build_sym or
+ * from an explicit node list) under syms [nsyms][d][d]: node x of the grid gets the eigenvalues of the node of `src` in its
+ * orbit.  *out == NULL: creates the rule; *out != NULL (a rule this function made for the same src geometry): gathers again
+ * into it, reusing its orbit map -- what a caller does after abz_rule_rebuild(src).
+ * The map addresses the nodes of `src` by their position in its list: a refresh must come with the same symmetries (checked)
+ * and a source whose nodes stand in the same ORDER as when the map was made (only their count is checked) -- the same handle
+ * rebuilt, or a rule built the same way.
+ * The symmetries must be symmetries of H, H(S k) = H(k) up to a unitary: then e_b(S k) = e_b(k) and the gather is exact.  The
+ * result is a whole periodic grid with eigenvalues only: abz_rule_ltm, _elements, _weighted, _fermi, abz_rule_export (x, w,
+ * eig), abz_rule_info and abz_rule_destroy take it like a rule of abz_ptr_rule_build(s, npt, 0, NULL, NULL, ABZ_WANT_EIG, ...);
+ * abz_rule_rebuild answers ABZ_ERR_UNSUPPORTED (rebuild src and unfold again; that drops attached matrix elements).  It
+ * keeps its series alive and does not hold `src`.  ABZ_ERR_ARG: src without eigenvalues, nsyms < 1 or syms NULL, *out not
+ * an unfolded rule of the same series, npt, node count and symmetries, or a node list that does not hold a node of every orbit (the
+ * message counts the uncovered points).  ABZ_ERR_UNSUPPORTED: src is a full grid or a slab, or npt^d >= 2^31.  Costs 4 B
+ * per grid point for the orbit map beside the n planes. */
+int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule** out);
 
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.

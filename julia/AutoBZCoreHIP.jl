@@ -425,6 +425,29 @@ function ltm_fermi(r::HIPRule, nstates::Real; tol::Real=1e-10)
     return ef[], nf[]
 end
 
+"""
+    ltm_unfold(r, syms, ::Val{d})            -> HIPRule
+    ltm_unfold!(u, r, syms, ::Val{d})        -> u
+
+Full-grid eigenvalue rule filled from the irreducible nodes of the symmetric rule `r` (built with `WANT_EIG` under `syms`) by a
+gather on the device, `e_b(S k) = e_b(k)` (`abz_rule_ltm_unfold`); the symmetries must be symmetries of `H`.  The result serves
+`ltm_weighted`, `ltm_elements!`, `ltm_fermi` and `export_rule` like a rule of `rule!(hs, npt, nothing, WANT_EIG)`.  After new
+coefficients and a rebuild of `r`, `ltm_unfold!` gathers again into `u` through the orbit map it already holds.
+"""
+function ltm_unfold(r::HIPRule, syms, ::Val{d}) where {d}
+    S = Cint[round(Int, M[a, b]) for M in syms for a in 1:d for b in 1:d]   # row-major per matrix
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:abz_rule_ltm_unfold, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint, Ptr{Ptr{Cvoid}}), r.h, S, length(syms), ref))
+    u = HIPRule(ref[], r.npt^d, r.npt, 1)
+    finalizer(x -> ccall((:abz_rule_destroy, libabz), Cint, (Ptr{Cvoid},), x.h), u)
+end
+function ltm_unfold!(u::HIPRule, r::HIPRule, syms, ::Val{d}) where {d}
+    S = Cint[round(Int, M[a, b]) for M in syms for a in 1:d for b in 1:d]
+    ref = Ref{Ptr{Cvoid}}(u.h)
+    check(ccall((:abz_rule_ltm_unfold, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint, Ptr{Ptr{Cvoid}}), r.h, S, length(syms), ref))
+    return u
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
