@@ -974,6 +974,7 @@ int abz_series_update(abz_series* s, const double* coef_reim) try {
     s->hermitian = detect_hermitian(s, coef_reim);
     s->coef_pk_valid = false;
     s->generation += 1;  // rules kept by the series refill themselves at their next use
+    for (int64_t& u : s->iai_used) u = 0;  // sets contracted from the old coefficients (abz_contract_nodes) are dead
     for (abz_series* v : s->lanes) {
         v->hermitian = s->hermitian;
         v->coef_pk_valid = false;

@@ -1470,6 +1470,9 @@ static int iai_solve_lane(abz_series* s, int lims_kind, const double* lim_a, con
     }
     ABZ_REQUIRE(nparams >= 0 && nparams <= 4, "nparams = %d not in 0..4", nparams);
     ABZ_HIP(hipSetDevice(s->ctx->device));
+    // the solve lays its own sets (packed rows for Hermitian series of n <= 4) over the pools: slots that abz_contract_nodes handed out
+    // die here, and a client that keeps one is refused afterwards instead of reading this solve's sets
+    for (int64_t& u : s->iai_used) u = 0;
     IaiDriver drv;
     drv.s = s;
     drv.ctx = s->ctx;
@@ -1648,10 +1651,31 @@ int abz_iai_solve(abz_series* s, int lims_kind, const double* lim_a, const doubl
 } ABZ_CATCH_ALL
 
 // ---- building blocks for a host-language (Julia) adaptive loop -------------------------------
+// parents of a node-list call are checked on the host before anything is launched: a slot the library does not hold (one a
+// client kept across abz_release_level or a solve) would otherwise be read from wherever it points in device memory
+static int check_node_parents(const char* who, const abz_series* s, int level, const int64_t* parents, int64_t nnodes) {
+    const int64_t live = level == s->d ? 1 : s->iai_used[level];
+    for (int64_t i = 0; i < nnodes; ++i) {
+        if (parents[i] >= 0 && parents[i] < live) continue;
+        if (level == s->d)
+            set_error("%s: parents[%lld] = %lld, but level %d is the series itself: its only slot is 0 (1 live slot)", who, (long long)i,
+                      (long long)parents[i], level);
+        else
+            set_error("%s: parents[%lld] = %lld is not a live level-%d slot (%lld live slots)", who, (long long)i, (long long)parents[i],
+                      level, (long long)live);
+        return ABZ_ERR_ARG;
+    }
+    return ABZ_OK;
+}
+
 int abz_contract_nodes(abz_series* s, int src_level, const int64_t* parents, const double* x, int64_t nnodes,
                        int64_t* slots_out) try {
     ABZ_REQUIRE(s && s->ctx && !s->closed && !s->ctx->closed && parents && x && slots_out, "abz_contract_nodes: null argument");
     ABZ_REQUIRE(src_level >= 2 && src_level <= s->d, "src_level = %d must be in 2..d", src_level);
+    ABZ_REQUIRE(nnodes >= 0, "abz_contract_nodes: nnodes = %lld is negative", (long long)nnodes);
+    if (nnodes == 0) return ABZ_OK;
+    int rc_par = check_node_parents("abz_contract_nodes", s, src_level, parents, nnodes);
+    if (rc_par) return rc_par;
     ABZ_HIP(hipSetDevice(s->ctx->device));
     IaiDriver drv;
     drv.s = s;
@@ -1688,7 +1712,7 @@ int abz_eval_line_nodes(abz_series* s, const int64_t* parents, const double* x, 
                         int integrand, const double* params, int nparams, double sweep, double* values_reim) try {
     ABZ_REQUIRE(s && s->ctx && !s->closed && !s->ctx->closed && parents && x && values_reim, "abz_eval_line_nodes: null argument");
     ABZ_REQUIRE(nparams >= 0 && nparams <= 4, "nparams = %d not in 0..4", nparams);
-    ABZ_HIP(hipSetDevice(s->ctx->device));
+    ABZ_REQUIRE(nnodes >= 0, "abz_eval_line_nodes: nnodes = %lld is negative", (long long)nnodes);
     IaiDriver drv;
     drv.s = s;
     drv.ctx = s->ctx;
@@ -1697,7 +1721,12 @@ int abz_eval_line_nodes(abz_series* s, const int64_t* parents, const double* x, 
     drv.integrand = integrand;
     drv.ncomp = integrand_ncomp(integrand, s->n, s->d);
     ABZ_REQUIRE(drv.ncomp > 0, "unknown integrand id %d", integrand);
+    ABZ_REQUIRE((integrand != ABZ_F_LINEAR && integrand != ABZ_F_LINEAR_X) || s->n == 1, "ABZ_F_LINEAR(_X) needs a scalar (n = 1) series");
     ABZ_REQUIRE(integrand != ABZ_F_LINEAR_X || s->d == 1 || tail, "ABZ_F_LINEAR_X needs the outer coordinates (tail)");
+    if (nnodes == 0) return ABZ_OK;
+    int rc_par = check_node_parents("abz_eval_line_nodes", s, 1, parents, nnodes);
+    if (rc_par) return rc_par;
+    ABZ_HIP(hipSetDevice(s->ctx->device));
     for (int i = 0; i < 4; ++i) drv.params[i] = (i < nparams && params) ? params[i] : 0.0;
     drv.sweep = sweep;
     drv.h_parents.assign(parents, parents + nnodes);

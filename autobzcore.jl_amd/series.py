@@ -178,6 +178,50 @@ class DeviceSeries:
             out.append(E)
         return out[0] if len(out) == 1 else tuple(out)
 
+    # ---- IAI building blocks: what abz_iai_solve is built from, for a caller that keeps its own adaptive loop (the
+    # semantics of julia/AutoBZCoreHIP.jl's contract_nodes / eval_line_nodes / release_level!)
+    def contract_nodes(self, src_level, parents, x):
+        """Contract the outermost remaining variable of the level-`src_level` sets `parents` (slot 0 at level d = the
+        series itself) at the coordinates `x`, one parent per node (abz_contract_nodes).  Returns the slots of the new
+        level-(src_level - 1) sets: consecutive numbers from the level's current count; they stay valid until
+        release_level, an IAI solve or update()."""
+        parents = np.ascontiguousarray(np.asarray(parents, dtype=np.int64).reshape(-1))
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+        if len(parents) != len(x):
+            raise ValueError("contract_nodes: one parent per node")
+        slots = np.empty(len(x), dtype=np.int64)
+        L.check(L.lib().abz_contract_nodes(self.h, int(src_level), parents.ctypes.data_as(L.c_i64p), x.ctypes.data_as(L.c_f64p),
+                                           len(x), slots.ctypes.data_as(L.c_i64p)))
+        return slots
+
+    def eval_line_nodes(self, parents, x, integrand, params, sweep, tail=None):
+        """Values of the built-in integrand `integrand` at the innermost nodes `x` of the level-1 sets `parents` (all 0
+        for d = 1) as complex [nnodes, ncomp] (abz_eval_line_nodes); F_GLOC's n x n matrix comes column-major like
+        everywhere in the ABI.  `tail` [nnodes, d - 1]: the outer coordinates x_2..x_d of every node's line, read by
+        F_LINEAR_X only."""
+        s = self.s
+        parents = np.ascontiguousarray(np.asarray(parents, dtype=np.int64).reshape(-1))
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+        if len(parents) != len(x):
+            raise ValueError("eval_line_nodes: one parent per node")
+        ptail = None
+        if tail is not None and s.d > 1:
+            tail = np.ascontiguousarray(np.asarray(tail, dtype=np.float64).reshape(-1, s.d - 1))
+            if len(tail) != len(x):
+                raise ValueError(f"eval_line_nodes: tail of shape {tail.shape}, expected [{len(x)}, {s.d - 1}]")
+            ptail = tail.ctypes.data_as(L.c_f64p)
+        ncomp = {L.F_GLOC: s.n * s.n, L.F_LINEAR_X: s.d}.get(integrand, 1)
+        params = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+        vals = np.empty((len(x), ncomp, 2))
+        L.check(L.lib().abz_eval_line_nodes(self.h, parents.ctypes.data_as(L.c_i64p), x.ctypes.data_as(L.c_f64p), ptail, len(x),
+                                            int(integrand), params.ctypes.data_as(L.c_f64p) if len(params) else None, len(params),
+                                            float(0.0 if sweep is None else sweep), vals.ctypes.data_as(L.c_f64p)))
+        return vals.view(np.complex128).reshape(len(x), ncomp)
+
+    def release_level(self, level):
+        """Drop every contracted set below `level` (abz_release_level): their slots are invalid from here on."""
+        L.check(L.lib().abz_release_level(self.h, int(level)))
+
     # ---- store-free rule values
     stream_above_bytes = 32 << 30  # rules beyond this many bytes are summed on the fly instead of being cached
 

@@ -311,18 +311,31 @@ int abz_symptr_rule_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, in
 
 /* ---------------------------------------------------------------- IAI building blocks + driver
  * Replaces: workspace_contract!(w, x) on a batch of nodes (src/fourier.jl:468,478):
- * contracts the outermost remaining variable of `src_level` coefficient sets.  The library keeps
- * contracted sets in its own device pool; `slots_out[i]` identifies the set made from parent slot
- * `parents[i]` (slot 0 at level d = the series itself) at coordinate x[i]. */
+ * contracts the outermost remaining variable of `src_level` coefficient sets (src_level = 2..d).  The
+ * library keeps contracted sets in its own device pool; `slots_out[i]` identifies the set made from parent
+ * slot `parents[i]` (slot 0 at level d = the series itself) at coordinate x[i].
+ * Slots are numbered consecutively per level from the level's current count: a call with nnodes nodes while
+ * the level below src_level holds c sets returns c .. c + nnodes - 1 and keeps the sets made before it.
+ * Slots are invalidated by abz_release_level, abz_iai_solve*, and abz_series_update (the counts go back to 0).
+ * nnodes < 0 is ABZ_ERR_ARG; nnodes == 0 is ABZ_OK with nothing launched and the counts unchanged.
+ * Every parents[i] must be 0 when src_level == d, otherwise a live slot of level src_level, 0 <= parents[i] <
+ * its count: anything else is ABZ_ERR_ARG before any device work (the message names the first bad index, its
+ * value and the number of live slots), with slots_out and the counts untouched. */
 int abz_contract_nodes(abz_series* s, int src_level, const int64_t* parents, const double* x,
                        int64_t nnodes, int64_t* slots_out);
 /* Replaces: workspace_evaluate!(w, x) + integrand at a batch of innermost nodes
  * (src/fourier.jl:445-446,454-455): values_reim [nnodes][ncomp][2].  tail [nnodes][d-1] gives the
- * outer coordinates (x_2..x_d) of each node's line (needed by ABZ_F_LINEAR_X only; may be NULL). */
+ * outer coordinates (x_2..x_d) of each node's line (needed by ABZ_F_LINEAR_X only; may be NULL).
+ * nnodes < 0 is ABZ_ERR_ARG; nnodes == 0 is ABZ_OK with nothing launched.
+ * Every parents[i] must be 0 for d = 1, otherwise a live level-1 slot, 0 <= parents[i] < the level's count:
+ * anything else is ABZ_ERR_ARG before any device work.  Every refused call (these, or an integrand that is not
+ * built for the series' band count) leaves values_reim untouched. */
 int abz_eval_line_nodes(abz_series* s, const int64_t* parents, const double* x, const double* tail,
                         int64_t nnodes, int integrand, const double* params, int nparams,
                         double sweep, double* values_reim);
-int abz_release_level(abz_series* s, int level); /* drop all contracted sets below `level` */
+/* Drop all contracted sets below `level` (1..d): their slots are invalid from here on and the next
+ * abz_contract_nodes into those levels numbers from 0 again. */
+int abz_release_level(abz_series* s, int level);
 
 /* Whole IAI solve with the adaptive GK(7,15) loops on the host and every node batch on the GPU.
  * Replaces: do_solve(::FourierIntegrand, lims, p, ::NestedQuad, cacheval) (src/fourier.jl:493-510)

@@ -505,7 +505,11 @@ function gk15_batch(ab::Matrix{Float64}, values::Array{ComplexF64,3})
     return I, E
 end
 
-"Contract the outermost remaining variable of the level-`src_level` sets `parents` (slot 0 at level d = the series) at `x`: slots of the new sets."
+"""
+Contract the outermost remaining variable of the level-`src_level` sets `parents` (slot 0 at level d = the series) at `x`: slots of the new sets.
+Slots are numbered consecutively per level from the level's current count and stay valid until `release_level!`, an IAI solve or
+`update!` of the series; a parent that is not a live slot is an `ArgumentError` (checked by the library before any device work).
+"""
 function contract_nodes(hs::HIPSeries, src_level::Integer, parents::Vector{Int64}, x::Vector{Float64})
     length(parents) == length(x) || throw(ArgumentError("contract_nodes: one parent per node"))
     slots = Vector{Int64}(undef, length(x))
