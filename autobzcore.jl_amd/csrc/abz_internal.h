@@ -497,6 +497,11 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
                         bool states, double* out_host);
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
+// Orbital weights as matrix elements (kernels_ltm_orb.hip): plane c n + b of A (ncomp n planes tiled like the eigenvalue planes,
+// padding columns included) <- |U_{orb[c], b}|^2 from the H planes of the same whole grid (full or compact); orb == nullptr:
+// orbital c.  1...32 bands.  Launches only, under ABZ_K_EIG.
+bool ltm_orbitals_supported(int n);
+int launch_ltm_orbitals(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, PlaneView A, const int32_t* orb, int ncomp);
 // Orbit map of an unfolded rule: node_of[x] = the node k of the list idx [d][nk] that is x or its first image under syms that
 // is a node; rank [npt^d] is scratch; *missing_dev counts the points without one (their node_of is -1).  Launches only.
 int launch_ltm_orbit_map(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, const int32_t* idx, int64_t nk, int32_t* rank,

@@ -2179,6 +2179,90 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
     return rc;
 } ABZ_CATCH_ALL
 
+// The same block filled on the device with |U_ab(k)|^2 (kernels_ltm_orb.hip).  H(k) comes from the rule's own planes or, for a
+// rule of eigenvalues only, from a transient H-only rule of the same grid that lives for this call.  Whatever was attached
+// stays in place until the new block is complete: a refusal or a failure leaves it untouched.
+int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_orbitals"))) return rc;
+    if (r->node_of) {
+        set_error("abz_rule_ltm_orbitals: the rule's eigenvalues were unfolded from irreducible nodes; eigenvectors at every grid "
+                  "point are what such a rule avoids (build a full-grid rule with abz_ptr_rule_build)");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    const abz_series* s = r->s;
+    const int n = s->n;
+    if (!ltm_orbitals_supported(n)) {
+        set_error("abz_rule_ltm_orbitals: %d bands; orbital weights are computed for 1...32", n);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if (orb) {
+        ABZ_REQUIRE(norb >= 1 && norb <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: norb = %d outside 1..%d", norb, ABZ_LTM_MAX_COMP);
+        for (int c = 0; c < norb; ++c)
+            ABZ_REQUIRE(orb[c] >= 0 && orb[c] < n, "abz_rule_ltm_orbitals: orb[%d] = %d outside 0..%d", c, orb[c], n - 1);
+    } else {
+        ABZ_REQUIRE(n <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: all %d orbitals are more than %d components; select some (orb, norb)", n,
+                    ABZ_LTM_MAX_COMP);
+    }
+    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
+                "abz_rule_ltm_orbitals: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
+    const int ncomp = orb ? norb : n;
+    abz_ctx* ctx = s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    abz_rule* tmp = nullptr;  // H(k) of a rule that keeps eigenvalues only (one band: the weight is 1, no H needed)
+    if (!r->H.base && n > 1) {
+        if ((rc = rule_build(r->s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &tmp, nullptr, false))) return rc;
+    }
+    const int planes = ncomp * n;
+    const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
+    double* block = nullptr;
+    size_t cap = 0;
+    rc = dev_alloc((void**)&block, bytes, &cap);
+    PlaneView A = r->E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements)
+    A.base = block;
+    A.tile = (int64_t)planes * r->E.row;
+    A.pitch = r->E.row;
+    A.compact = 0;
+    if (!rc) rc = launch_ltm_orbitals(ctx, n, r->npt, r->ntiles, tmp ? tmp->H : r->H, A, orb, ncomp);
+    // the one synchronisation of the call: the block is complete, nothing reads the old one or the transient rule any more
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_orbitals: the weight kernel failed");
+        rc = ABZ_ERR_HIP;
+    }
+    if (tmp) {
+        rule_free(tmp);
+        series_release(r->s);
+    }
+    if (rc) {
+        dev_free(block, cap);
+        return rc;
+    }
+    rule_drop_ltm_elements(r);
+    r->ltm_elems = block;
+    r->ltm_elems_cap = cap;
+    r->ltm_ncomp = ncomp;
+    r->A = A;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(ncomp, "abz_rule_ltm_elements_export: null ncomp");
+    *ncomp = r->ltm_elems ? r->ltm_ncomp : 0;
+    if (!A || !r->ltm_elems) return ABZ_OK;
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = r->s->n;
+    for (int c = 0; c < r->ltm_ncomp; ++c) {  // one component [nk][n] at a time, the order they came in
+        PlaneView v = r->A;
+        v.base += (int64_t)c * n * v.pitch;
+        if ((rc = export_planes(ctx, v, n, r->nk, A + (size_t)c * (size_t)r->nk * (size_t)n))) return rc;
+    }
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int what, double* out) try {
     int rc = check_rule(r);
     if (rc) return rc;

@@ -30,8 +30,13 @@ class LTM(DOSAlgorithm):
     the solution is g_A(E) = sum_b int A_b delta(E - e_b) (or N_A with `cumulative`), `u` of shape [nE, ncomp]
     ([ncomp] for a scalar domain).
       "energy"    A = e itself, one component: E g(E), and the band energy as N_A;
-      "orbitals"  the orbital-projected DOS, A_{a,b}(k) = |U_ab(k)|^2, ncomp = n.  A host-side companion, not a
-                  performance path: the rule is built with H(k) as well, exported, and diagonalised by numpy.linalg.eigh;
+      "orbitals"  the orbital-projected DOS, A_{a,b}(k) = |U_ab(k)|^2, ncomp = n.  With eigenvectors="host" (the default) a
+                  host-side companion, not a performance path: the rule is built with H(k) as well, exported, and
+                  diagonalised by numpy.linalg.eigh.  With eigenvectors="device" the rule keeps eigenvalues only and the
+                  weights are computed on the GPU straight into the resident element block (DeviceRule.ltm_orbitals,
+                  1...32 bands, Hermitian series); `orbitals`, a sequence of orbital indices (at most 16, needed above 16
+                  bands), then selects the columns of `u`.  At a degenerate level either route weighs with some
+                  orthonormal basis of the eigenspace: sums over the level agree, single weights need not;
       callable    f(x [nk, d], eig [nk, n]) -> [ncomp, nk, n] on the rule's exported nodes and eigenvalues.
     The elements are computed again whenever the cache rebuilds its eigenvalues.
 
@@ -41,13 +46,27 @@ class LTM(DOSAlgorithm):
     grid.  "energy" and a callable work as before, at every full-grid node; "orbitals" is refused: |U_ab|^2 is not
     invariant under operations that permute orbitals, and no H(k) is stored."""
 
-    def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False):
+    def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None):
         self.npt = int(npt)
         self.cumulative = bool(cumulative)
         self.symmetric = bool(symmetric)
         if not (elements is None or callable(elements) or elements in ("energy", "orbitals")):
             raise ValueError(f"LTM: elements = {elements!r} is neither 'energy', 'orbitals' nor a callable")
         self.elements = elements
+        if not (isinstance(eigenvectors, str) and eigenvectors in ("host", "device")):
+            raise ValueError(f"LTM: eigenvectors = {eigenvectors!r} is neither 'host' nor 'device'")
+        device = eigenvectors == "device"
+        if device and not (isinstance(elements, str) and elements == "orbitals"):
+            raise ValueError('LTM: eigenvectors = "device" computes orbital weights: it needs elements = "orbitals"')
+        if orbitals is not None:
+            if not device:
+                raise ValueError('LTM: a selection of orbitals needs elements = "orbitals" with eigenvectors = "device"')
+            sel = np.asarray(orbitals).reshape(-1)
+            if sel.size < 1 or not np.issubdtype(sel.dtype, np.integer):
+                raise ValueError(f"LTM: orbitals = {orbitals!r} is not a sequence of orbital indices")
+            orbitals = tuple(int(a) for a in sel)
+        self.eigenvectors = eigenvectors
+        self.orbitals = orbitals
 
 
 @dataclass
@@ -105,17 +124,27 @@ def _init_cacheval(h, domain, p, alg):
         # eigenvalues only, on the FULL grid whatever the zone's symmetries: the DOS is a scalar, so the full-zone sum is the
         # answer for every zone kind (symmetric=True above fills the same grid from the irreducible nodes; a symmetry-
         # reduced tetrahedron MESH is not implemented)
-        return h.device().rule(alg.npt, None, (L.WANT_H | L.WANT_EIG) if alg.elements == "orbitals" else L.WANT_EIG)
+        host_vectors = alg.elements == "orbitals" and alg.eigenvectors == "host"  # numpy diagonalises the exported H(k)
+        return h.device().rule(alg.npt, None, (L.WANT_H | L.WANT_EIG) if host_vectors else L.WANT_EIG)
     return h.device().rule(alg.npt, p.syms, L.WANT_EIG | L.WANT_VEL)
 
 
+class _DeviceOrbitals:
+    """Orbital weights the rule computes itself (DeviceRule.ltm_orbitals); one object per refresh of a cache: the owner mark."""
+
+    def __init__(self, orbitals):
+        self.orbitals = orbitals
+
+
 def _ltm_elements(rule, alg):
-    """What an LTM cache hands DeviceRule.ltm as `elements`: None, "energy", or the host array [ncomp, nk, n] computed
-    from the rule's current values."""
+    """What an LTM cache hands DeviceRule.ltm as `elements`: None, "energy", the host array [ncomp, nk, n] computed
+    from the rule's current values, or the request for orbital weights made on the device."""
     if not isinstance(alg, LTM) or alg.elements is None or rule is None:
         return None
     if alg.elements == "energy":
         return "energy"
+    if alg.elements == "orbitals" and alg.eigenvectors == "device":
+        return _DeviceOrbitals(alg.orbitals)
     if alg.elements == "orbitals":
         ex = rule.export(x=False, w=False, H=True)
         H = ex["H"]
@@ -138,7 +167,10 @@ def _ltm_solve(c, Es):
         return rule.ltm(Es, states=c.alg.cumulative, elements=el)
     rule.h  # a stale rule refills here and loses its elements
     if rule._ltm_ncomp == 0 or getattr(rule, "_ltm_owner", None) is not el:  # (another cache on the same rule attached its own)
-        rule.ltm_elements(el)
+        if isinstance(el, _DeviceOrbitals):
+            rule.ltm_orbitals(el.orbitals)
+        else:
+            rule.ltm_elements(el)
         rule._ltm_owner = el
     return rule.ltm(Es, states=c.alg.cumulative, elements="attached")
 

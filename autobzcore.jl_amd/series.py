@@ -559,6 +559,37 @@ class DeviceRule:
         L.check(L.lib().abz_rule_ltm_elements(self.h, A.ctypes.data_as(L.c_f64p), A.shape[0]))
         self._ltm_ncomp = A.shape[0]
 
+    def ltm_orbitals(self, orbitals=None):
+        """Attach the orbital weights |U_ab(k)|^2 as matrix elements, computed on the device from H(k)
+        (abz_rule_ltm_orbitals): component c is orbital `orbitals[c]` (None: all n <= 16 of them), bands ascending as in
+        export()'s eig.  H(k) comes from the rule, or from a transient rule when it keeps eigenvalues only.  At a degenerate
+        level the weights belong to some orthonormal basis of the eigenspace.  `ltm(Es, elements="attached")` scans them."""
+        self._ltm_refuse_shard()
+        h = self.h  # (a stale rule is refilled here)
+        if orbitals is None:
+            L.check(L.lib().abz_rule_ltm_orbitals(h, None, 0))
+            self._ltm_ncomp = self.dev.s.n
+            return
+        orb = np.ascontiguousarray(np.asarray(orbitals).reshape(-1))
+        if orb.size and not np.issubdtype(orb.dtype, np.integer):
+            raise ValueError(f"ltm_orbitals: orbitals = {orbitals!r} are not integer indices")
+        orb = orb.astype(np.int32)
+        L.check(L.lib().abz_rule_ltm_orbitals(h, orb.ctypes.data_as(L.c_i32p), len(orb)))
+        self._ltm_ncomp = len(orb)
+
+    def ltm_elements_export(self):
+        """The attached matrix elements [ncomp, nk, n] back on the host (abz_rule_ltm_elements_export), in the order
+        ltm_elements takes them; None when nothing is attached."""
+        self._ltm_refuse_shard()
+        h = self.h  # (a stale rule is refilled here, which drops the attached elements)
+        nc = C.c_int(0)
+        L.check(L.lib().abz_rule_ltm_elements_export(h, C.byref(nc), None))
+        if nc.value == 0:
+            return None
+        A = np.empty((nc.value, self.nk, self.dev.s.n))
+        L.check(L.lib().abz_rule_ltm_elements_export(h, C.byref(nc), A.ctypes.data_as(L.c_f64p)))
+        return A
+
     def ltm(self, Es, states=False, elements=None):
         """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
         number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid.

@@ -271,6 +271,20 @@ int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out);
  * eigenvalue planes until replaced, dropped (A = NULL, ncomp = 0), abz_rule_rebuild (they described the old eigenstates) or
  * abz_rule_destroy. */
 int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp);
+/* Orbital weights as LTM matrix elements, computed on the device: component c, band b, node k gets
+ * |U_{orb[c], b}(k)|^2, U(k) = orthonormal eigenvectors of Hermitian(H(k)) (upper triangle), bands ascending as in
+ * the rule's eigenvalue planes.  orb == NULL: all n orbitals (norb ignored, n <= ABZ_LTM_MAX_COMP).  The result is
+ * attached exactly like abz_rule_ltm_elements would attach it (replaces what was attached; dropped by the same events).
+ * 1...32 bands, Hermitian series.  H(k) is read from the rule when it holds it (either layout), else from a transient rule of
+ * the series' CURRENT coefficients that lives for the call: rebuild a stale rule first.  At a degenerate level the weights
+ * are those of some orthonormal basis of the eigenspace: their sum over the level and sum_a = sum_b = 1 are defined, no more.
+ * ABZ_ERR_UNSUPPORTED: not a whole periodic grid, a rule of abz_rule_ltm_unfold, more than 32 bands.  ABZ_ERR_ARG: no
+ * eigenvalues, norb outside 1..ABZ_LTM_MAX_COMP, an index outside 0..n-1 (duplicates are fine), orb == NULL with
+ * n > ABZ_LTM_MAX_COMP, a series that is not Hermitian.  A refusal or failure leaves attached elements as they were. */
+int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb);
+/* Attached elements back to the host: *ncomp (0 if none), and, if A != NULL, A [ncomp][nk][n] in the order
+ * abz_rule_ltm_elements takes them. */
+int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A);
 #define ABZ_LTM_A_ELEMENTS 0   /* the attached elements, ncomp components */
 #define ABZ_LTM_A_ENERGY 1     /* A_b(k) = e_b(k) itself, 1 component, nothing attached needed */
 /* out [nE][ncomp]: g_A(E) (ABZ_LTM_DOS) or N_A(E) (ABZ_LTM_STATES), per unit cell, summed over bands; A is interpolated

@@ -401,6 +401,39 @@ function ltm_elements!(r::HIPRule, A::Union{Nothing,Array{Float64,3}})
 end
 
 """
+    ltm_orbitals!(r; orbitals=nothing)        -> number of components
+
+Attach the orbital weights `|U[a, b](k)|^2` of the listed orbitals (1-based; `nothing`: all `n <= 16`) as matrix elements,
+computed on the device from `H(k)` (`abz_rule_ltm_orbitals`): the orbital-projected DOS is then `ltm_weighted(r, Es; ncomp)`.
+"""
+function ltm_orbitals!(r::HIPRule; orbitals::Union{Nothing,AbstractVector{<:Integer}}=nothing)
+    if orbitals === nothing
+        check(ccall((:abz_rule_ltm_orbitals, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint), r.h, C_NULL, 0))
+    else
+        o = Cint[a - 1 for a in orbitals]
+        check(ccall((:abz_rule_ltm_orbitals, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint), r.h, o, length(o)))
+    end
+    nc = Ref{Cint}(0)
+    check(ccall((:abz_rule_ltm_elements_export, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Float64}), r.h, nc, C_NULL))
+    return Int(nc[])
+end
+
+"""
+    ltm_elements_export(r, n)                 -> A[b, k, c] or nothing
+
+The attached matrix elements back on the host, in the order `ltm_elements!` takes them (`abz_rule_ltm_elements_export`);
+`n`: the number of bands.
+"""
+function ltm_elements_export(r::HIPRule, n::Integer)
+    nc = Ref{Cint}(0)
+    check(ccall((:abz_rule_ltm_elements_export, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Float64}), r.h, nc, C_NULL))
+    nc[] == 0 && return nothing
+    A = Array{Float64,3}(undef, n, r.nk, Int(nc[]))
+    check(ccall((:abz_rule_ltm_elements_export, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Float64}), r.h, nc, A))
+    return A
+end
+
+"""
     ltm_weighted(r, Es; ncomp, energy=false, cumulative=false)
 
 `g_A(E)` (or `N_A(E)` with `cumulative`) of the attached elements, `ncomp` of them, or with `energy` of `A = e` itself
