@@ -492,9 +492,10 @@ int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, co
 // Linear tetrahedron scan (kernels_ltm.hip) over the eigenvalue planes of a whole periodic grid of npt^d nodes:
 // g(E) or, with `states`, N(E), per unit cell and summed over the n bands
 int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host);
-// ... with matrix elements A (ncomp n planes tiled like E, plane c n + b: component c of band b): out_host [nE][ncomp]
+// ... with matrix elements A (ncomp n planes tiled like E, plane c n + b: component c of band b): out_host [nE][ncomp];
+// what: ABZ_LTM_DOS, ABZ_LTM_STATES or ABZ_LTM_STATES_CORRECTED (N_A with the curvature correction)
 int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
-                        bool states, double* out_host);
+                        int what, double* out_host);
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
 // Orbital weights as matrix elements (kernels_ltm_orb.hip): plane c n + b of A (ncomp n planes tiled like the eigenvalue planes,

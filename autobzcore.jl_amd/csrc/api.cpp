@@ -2267,7 +2267,8 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
     int rc = check_rule(r);
     if (rc) return rc;
     ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm_weighted: bad arguments");
-    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES, "abz_rule_ltm_weighted: what = %d is neither ABZ_LTM_DOS nor ABZ_LTM_STATES", what);
+    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES || what == ABZ_LTM_STATES_CORRECTED,
+                "abz_rule_ltm_weighted: what = %d is neither ABZ_LTM_DOS, ABZ_LTM_STATES nor ABZ_LTM_STATES_CORRECTED", what);
     ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
                 "abz_rule_ltm_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_weighted"))) return rc;
@@ -2277,7 +2278,7 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
     ABZ_HIP(hipSetDevice(ctx->device));
     const bool energy = source == ABZ_LTM_A_ENERGY;
     return launch_ltm_weighted(ctx, r->s->n, r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, E, nE,
-                               what == ABZ_LTM_STATES, out);
+                               what, out);
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {

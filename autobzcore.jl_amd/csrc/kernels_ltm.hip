@@ -1,7 +1,7 @@
 // Linear tetrahedron method (gfx950 only): DOS g(E) and state count N(E) from the cached eigenvalues of a full grid.
 //
-// Bloechl, Jepsen, Andersen, PRB 49, 16223 (1994), without the curvature correction.  The reference has no
-// counterpart: src/dos_algorithms.jl:1-7 names "LTM" as planned.
+// Bloechl, Jepsen, Andersen, PRB 49, 16223 (1994); the curvature correction (eq. 22) is a mode of the weighted state sum,
+// see "Curvature correction" below.  The reference has no counterpart: src/dos_algorithms.jl:1-7 names "LTM" as planned.
 //
 //  * Geometry.  The grid is periodic; cell (i_1..i_d) has the corners i + {0,1}^d, indices wrapped mod npt, and is
 //    cut into d! simplices by the Kuhn (Freudenthal) split: one simplex per permutation of the axes, each walking
@@ -54,6 +54,17 @@
 //    integer; its prefix sum keeps a fixed order.  The elements live in ncomp n planes tiled like the eigenvalue
 //    planes (plane c n + b: component c of band b); a launch carries 1, 2 or 4 components, so that the corners of a
 //    cell (8 energies + 8 NC elements) stay in registers, and a call walks the grid once per group of components.
+//  * Curvature correction (wltm_window_kernel<D, true, NC, true>, ABZ_LTM_STATES_CORRECTED).  Linear interpolation misplaces
+//    the weight inside a simplex by the band's curvature; to leading order (eq. 22 of the paper for d = 3)
+//      N_A^corr(E) = N_A(E) + w sum_T g_T(E) kappa_T,   kappa_T = f_d sum_i A_i (sum_l e_l - (d+1) e_i),   f_d = 1 / (2 (d+1)(d+2)),
+//    f_3 = 1/40, f_2 = 1/24, f_1 = 1/12; g_T is the simplex's own DOS, unit = one simplex: the g formulas above.  Window:
+//    only a simplex with e_1 <= E < e_{d+1} contributes, the half-open regions of N_A itself, so nothing divides by zero; a
+//    flat simplex and one wholly below E give nothing, and the step histogram and pass 1's shortcut are those of N_A.
+//    kappa_T is formed once per simplex and component after the sort, g_T per energy from the reciprocals at hand
+//    (d = 3: 3 t13 t14 / e21 | 3 [t13 (1 - t23) + t23 (1 - t24)] / e41 | 3 s1 s2 / e43), and g_T kappa_T joins the value that
+//    goes into the histogram: no new histogram, launch or atomic.  For A = 1 kappa_T = 0: the state count and the Fermi
+//    level have no correction.  The correction removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING, at the
+//    Fermi level of the same grid; at a fixed energy the misplaced Fermi surface leaves an error of that order.
 //  * Symmetric zones (abz_rule_ltm_unfold).  The scans always walk the whole grid; the eigenvalues they read are invariant
 //    under the zone's symmetries, e_b(S k) = e_b(k), so a full-grid rule's planes can be a gather from the irreducible
 //    nodes of another rule.  ltm_rank_kernel scatters the node numbers into a table over the grid, ltm_orbit_kernel finds
@@ -385,7 +396,8 @@ __device__ __forceinline__ void ltm_cx(double& ea, double& eb, LtmVec<NC>& Aa, L
 }
 
 // One tetrahedron, corners in any order.  hist / step: [NC][nE] of the wave.
-template <bool STATES, int NC>
+// CORR (with STATES): the curvature correction, g_T(E) kappa_T added to the sum of the selected region.
+template <bool STATES, int NC, bool CORR = false>
 __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, double e4, LtmVec<NC> A1, LtmVec<NC> A2, LtmVec<NC> A3,
                                               LtmVec<NC> A4, const double* Esl, int nE, int i0, double* hist, double* step) {
     ltm_cx(e1, e2, A1, A2);
@@ -398,14 +410,23 @@ __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, d
         // an unselected region may have zero width: its reciprocal is then inf and never read
         const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r41 = 1.0 / (e4 - e1), r32 = 1.0 / (e3 - e2), r42 = 1.0 / (e4 - e2),
                      r43 = 1.0 / (e4 - e3);
+        LtmVec<NC> kap;  // CORR only
+        if constexpr (CORR) {
+            const double es = (e1 + e2) + (e3 + e4);
+            const double d1 = es - 4.0 * e1, d2 = es - 4.0 * e2, d3 = es - 4.0 * e3, d4 = es - 4.0 * e4;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) kap.v[c] = 0.025 * ((A1.v[c] * d1 + A2.v[c] * d2) + (A3.v[c] * d3 + A4.v[c] * d4));
+        }
         for (; i < nE; ++i) {
             const double En = Esl[i];
             if (!(En < e4)) break;
             if (En >= e1) {
                 double w1, w2, w3, w4;
+                double gT = 0.0;  // CORR only: the simplex's own g(E), unit = one simplex
                 if (En < e2) {
                     const double x = En - e1, t2 = x * r21, t3 = x * r31, t4 = x * r41;
                     const double q = STATES ? 0.25 * (t2 * t3 * t4) : t3 * t4 * r21;
+                    if constexpr (CORR) gT = 3.0 * (t3 * t4 * r21);
                     w2 = q * t2;
                     w3 = q * t3;
                     w4 = q * t4;
@@ -423,6 +444,7 @@ __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, d
                         p24 = v3;
                         c1 = v1;
                         c2 = p14;
+                        if constexpr (CORR) gT = 3.0 * ((t13 * (1.0 - t23) + t23 * (1.0 - t24)) * r41);
                     } else {
                         const double ga = t13 * (1.0 - t23) * r41, gb = t23 * (1.0 - t24) * r41;
                         p13 = ga;
@@ -439,6 +461,7 @@ __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, d
                 } else {
                     const double y = e4 - En, s1 = y * r41, s2 = y * r42, s3 = y * r43;
                     const double q = STATES ? 0.25 * (s1 * s2 * s3) : s1 * s2 * r43;
+                    if constexpr (CORR) gT = 3.0 * (s1 * s2 * r43);
                     const double u1 = q * s1, u2 = q * s2, u3 = q * s3, u4 = (STATES ? 4.0 : 3.0) * q - (u1 + u2 + u3);
                     w1 = STATES ? 0.25 - u1 : u1;
                     w2 = STATES ? 0.25 - u2 : u2;
@@ -447,7 +470,8 @@ __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, d
                 }
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const double f = (w1 * A1.v[c] + w2 * A2.v[c]) + (w3 * A3.v[c] + w4 * A4.v[c]);
+                    double f = (w1 * A1.v[c] + w2 * A2.v[c]) + (w3 * A3.v[c] + w4 * A4.v[c]);
+                    if constexpr (CORR) f += gT * kap.v[c];
                     if (f != 0.0) ltm_add(hist + (size_t)c * nE + i, f);
                 }
             }
@@ -459,7 +483,7 @@ __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, d
     }
 }
 
-template <bool STATES, int NC>
+template <bool STATES, int NC, bool CORR = false>
 __device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, LtmVec<NC> A1, LtmVec<NC> A2, LtmVec<NC> A3,
                                               const double* Esl, int nE, int i0, double* hist, double* step) {
     ltm_cx(e1, e2, A1, A2);
@@ -469,20 +493,30 @@ __device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, L
     int i = i0;
     if (i < nE && Esl[i] < e3) {
         const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r32 = 1.0 / (e3 - e2);
+        LtmVec<NC> kap;  // CORR only
+        if constexpr (CORR) {
+            const double es = (e1 + e2) + e3;
+            const double d1 = es - 3.0 * e1, d2 = es - 3.0 * e2, d3 = es - 3.0 * e3;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) kap.v[c] = (1.0 / 24.0) * ((A1.v[c] * d1 + A2.v[c] * d2) + A3.v[c] * d3);
+        }
         for (; i < nE; ++i) {
             const double En = Esl[i];
             if (!(En < e3)) break;
             if (En >= e1) {
                 double w1, w2, w3;
+                double gT = 0.0;  // CORR only
                 if (En < e2) {
                     const double x = En - e1, t2 = x * r21, t3 = x * r31;
                     const double q = STATES ? third * (t2 * t3) : t3 * r21;
+                    if constexpr (CORR) gT = 2.0 * (t3 * r21);
                     w2 = q * t2;
                     w3 = q * t3;
                     w1 = (STATES ? 3.0 : 2.0) * q - (w2 + w3);
                 } else {
                     const double y = e3 - En, s1 = y * r31, s2 = y * r32;
                     const double q = STATES ? third * (s1 * s2) : s1 * r32;
+                    if constexpr (CORR) gT = 2.0 * (s1 * r32);
                     const double u1 = q * s1, u2 = q * s2, u3 = (STATES ? 3.0 : 2.0) * q - (u1 + u2);
                     w1 = STATES ? third - u1 : u1;
                     w2 = STATES ? third - u2 : u2;
@@ -490,7 +524,8 @@ __device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, L
                 }
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const double f = (w1 * A1.v[c] + w2 * A2.v[c]) + w3 * A3.v[c];
+                    double f = (w1 * A1.v[c] + w2 * A2.v[c]) + w3 * A3.v[c];
+                    if constexpr (CORR) f += gT * kap.v[c];
                     if (f != 0.0) ltm_add(hist + (size_t)c * nE + i, f);
                 }
             }
@@ -502,13 +537,18 @@ __device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, L
     }
 }
 
-template <bool STATES, int NC>
+template <bool STATES, int NC, bool CORR = false>
 __device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A1, LtmVec<NC> A2, const double* Esl, int nE, int i0,
                                               double* hist, double* step) {
     ltm_cx(e1, e2, A1, A2);
     int i = i0;
     if (i < nE && Esl[i] < e2) {
         const double r21 = 1.0 / (e2 - e1);
+        LtmVec<NC> kap;  // CORR only: g_T = r21 at every energy of the window, folded in here
+        if constexpr (CORR) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) kap.v[c] = (1.0 / 12.0) * ((A1.v[c] - A2.v[c]) * (e2 - e1)) * r21;
+        }
         for (; i < nE; ++i) {
             const double En = Esl[i];
             if (!(En < e2)) break;
@@ -517,7 +557,8 @@ __device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A
                 const double w2 = STATES ? 0.5 * t * t : t * r21, w1 = STATES ? t - w2 : r21 - w2;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const double f = w1 * A1.v[c] + w2 * A2.v[c];
+                    double f = w1 * A1.v[c] + w2 * A2.v[c];
+                    if constexpr (CORR) f += kap.v[c];
                     if (f != 0.0) ltm_add(hist + (size_t)c * nE + i, f);
                 }
             }
@@ -531,7 +572,8 @@ __device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A
 
 // ltm_window_kernel with NC components of matrix elements.
 // partial [(STATES ? 2 : 1) NC nE][nrows]: columns c nE + i the formula sums of component c, NC nE + c nE + i its steps
-template <int D, bool STATES, int NC>
+// CORR (with STATES only): N_A with the curvature correction; same histograms, same launches.
+template <int D, bool STATES, int NC, bool CORR = false>
 __global__ __launch_bounds__(256) void wltm_window_kernel(WLtmArgs a, double* __restrict__ partial, int64_t nrows) {
     // [nE] energies | [4 waves][NC][nE] sums | STATES: [4 waves][NC][nE] steps | [256] queue of a pass | [2][4] per-wave counts
     extern __shared__ __attribute__((aligned(16))) double ldsl[];
@@ -632,17 +674,17 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(WLtmArgs a, double* __
 #pragma unroll
                 for (int j = 0; j < NV; ++j) Av[j] = cornerA(i1, i2, i3, j);
                 if constexpr (D == 3) {
-                    wltm_simplex3<STATES, NC>(c[0], c[1], c[3], c[7], Av[0], Av[1], Av[3], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC>(c[0], c[1], c[5], c[7], Av[0], Av[1], Av[5], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC>(c[0], c[2], c[3], c[7], Av[0], Av[2], Av[3], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC>(c[0], c[2], c[6], c[7], Av[0], Av[2], Av[6], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC>(c[0], c[4], c[5], c[7], Av[0], Av[4], Av[5], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC>(c[0], c[4], c[6], c[7], Av[0], Av[4], Av[6], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC, CORR>(c[0], c[1], c[3], c[7], Av[0], Av[1], Av[3], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC, CORR>(c[0], c[1], c[5], c[7], Av[0], Av[1], Av[5], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC, CORR>(c[0], c[2], c[3], c[7], Av[0], Av[2], Av[3], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC, CORR>(c[0], c[2], c[6], c[7], Av[0], Av[2], Av[6], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC, CORR>(c[0], c[4], c[5], c[7], Av[0], Av[4], Av[5], Av[7], Esl, nE, i0, hist, step);
+                    wltm_simplex3<STATES, NC, CORR>(c[0], c[4], c[6], c[7], Av[0], Av[4], Av[6], Av[7], Esl, nE, i0, hist, step);
                 } else if constexpr (D == 2) {
-                    wltm_simplex2<STATES, NC>(c[0], c[1], c[3], Av[0], Av[1], Av[3], Esl, nE, i0, hist, step);
-                    wltm_simplex2<STATES, NC>(c[0], c[2], c[3], Av[0], Av[2], Av[3], Esl, nE, i0, hist, step);
+                    wltm_simplex2<STATES, NC, CORR>(c[0], c[1], c[3], Av[0], Av[1], Av[3], Esl, nE, i0, hist, step);
+                    wltm_simplex2<STATES, NC, CORR>(c[0], c[2], c[3], Av[0], Av[2], Av[3], Esl, nE, i0, hist, step);
                 } else {
-                    wltm_simplex1<STATES, NC>(c[0], c[1], Av[0], Av[1], Esl, nE, i0, hist, step);
+                    wltm_simplex1<STATES, NC, CORR>(c[0], c[1], Av[0], Av[1], Esl, nE, i0, hist, step);
                 }
             }
             continue;
@@ -664,12 +706,12 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(WLtmArgs a, double* __
                 // the permutation (A, B, C) of the axes: corners 0, e_A, e_A + e_B, (1,1,1)
                 const int X = (int)(t >> 1), Y = (X + 1 + (int)(t & 1)) % 3;
                 const int ba = 1 << X, bb = (1 << X) | (1 << Y);
-                wltm_simplex3<STATES, NC>(c0, cornerE(q1, q2, q3, ba), cornerE(q1, q2, q3, bb), c1, A0, cornerA(q1, q2, q3, ba),
+                wltm_simplex3<STATES, NC, CORR>(c0, cornerE(q1, q2, q3, ba), cornerE(q1, q2, q3, bb), c1, A0, cornerA(q1, q2, q3, ba),
                                           cornerA(q1, q2, q3, bb), A1, Esl, nE, j0, hist, step);
             } else if constexpr (D == 2) {
-                wltm_simplex2<STATES, NC>(c0, cornerE(q1, q2, q3, 1 << t), c1, A0, cornerA(q1, q2, q3, 1 << t), A1, Esl, nE, j0, hist, step);
+                wltm_simplex2<STATES, NC, CORR>(c0, cornerE(q1, q2, q3, 1 << t), c1, A0, cornerA(q1, q2, q3, 1 << t), A1, Esl, nE, j0, hist, step);
             } else {
-                wltm_simplex1<STATES, NC>(c0, c1, A0, A1, Esl, nE, j0, hist, step);
+                wltm_simplex1<STATES, NC, CORR>(c0, c1, A0, A1, Esl, nE, j0, hist, step);
             }
         }
     }
@@ -870,24 +912,24 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
 #undef ABZ_LTM_D
 
 namespace {
-template <int D, bool ST, int NC>
+template <int D, bool ST, int NC, bool CORR>
 void wltm_launch(abz_ctx* ctx, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
-    launch(ctx, (wltm_window_kernel<D, ST, NC>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
+    launch(ctx, (wltm_window_kernel<D, ST, NC, CORR>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
 }
-template <bool ST, int NC>
+template <bool ST, int NC, bool CORR>
 void wltm_launch_d(abz_ctx* ctx, int d, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
     switch (d) {
-        case 1: wltm_launch<1, ST, NC>(ctx, grid, lds, a, partial, nrows); break;
-        case 2: wltm_launch<2, ST, NC>(ctx, grid, lds, a, partial, nrows); break;
-        default: wltm_launch<3, ST, NC>(ctx, grid, lds, a, partial, nrows); break;
+        case 1: wltm_launch<1, ST, NC, CORR>(ctx, grid, lds, a, partial, nrows); break;
+        case 2: wltm_launch<2, ST, NC, CORR>(ctx, grid, lds, a, partial, nrows); break;
+        default: wltm_launch<3, ST, NC, CORR>(ctx, grid, lds, a, partial, nrows); break;
     }
 }
-template <bool ST>
+template <bool ST, bool CORR = false>
 void wltm_launch_nc(abz_ctx* ctx, int d, int nc, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
     switch (nc) {
-        case 1: wltm_launch_d<ST, 1>(ctx, d, grid, lds, a, partial, nrows); break;
-        case 2: wltm_launch_d<ST, 2>(ctx, d, grid, lds, a, partial, nrows); break;
-        default: wltm_launch_d<ST, 4>(ctx, d, grid, lds, a, partial, nrows); break;
+        case 1: wltm_launch_d<ST, 1, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
+        case 2: wltm_launch_d<ST, 2, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
+        default: wltm_launch_d<ST, 4, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
     }
 }
 // dynamic LDS of the shipped scans: 5 x 1024 (g) energies x 8 B + queue and counts; the weighted scans stay within it
@@ -895,7 +937,8 @@ constexpr size_t LTM_LDS_MAX = sizeof(double) * 5 * 1024 + sizeof(uint32_t) * (2
 }  // namespace
 
 int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
-                        bool states, double* out_host) {
+                        int what, double* out_host) {
+    const bool states = what != ABZ_LTM_DOS, corrected = what == ABZ_LTM_STATES_CORRECTED;
     WLtmArgs a;
     a.E = E;
     a.A = A;
@@ -937,7 +980,8 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
             const size_t lds = sizeof(double) * (size_t)(1 + 4 * nc * ncol) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
             double* const o = el.out + (size_t)c0 * nE + s0;  // results [ncomp][nE] in sorted order
             if (states) {
-                wltm_launch_nc<true>(ctx, d, nc, grid, lds, a, partial, nrows);
+                if (corrected) wltm_launch_nc<true, true>(ctx, d, nc, grid, lds, a, partial, nrows);
+                else wltm_launch_nc<true>(ctx, d, nc, grid, lds, a, partial, nrows);
                 ABZ_HIP(hipGetLastError());
                 launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
                 ABZ_HIP(hipGetLastError());

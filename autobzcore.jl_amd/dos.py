@@ -22,7 +22,7 @@ class GGR(DOSAlgorithm):
 
 
 class LTM(DOSAlgorithm):
-    """Linear tetrahedron method (Bloechl, Jepsen, Andersen, PRB 49, 16223; no curvature correction) on the eigenvalues of
+    """Linear tetrahedron method (Bloechl, Jepsen, Andersen, PRB 49, 16223) on the eigenvalues of
     the full periodic `npt^d` grid, cells cut by the Kuhn split.  `cumulative=True` returns the number of states N(E)
     below E instead of the DOS g(E).  The reference plans it: src/dos_algorithms.jl:1-7.
 
@@ -44,15 +44,26 @@ class LTM(DOSAlgorithm):
     from them on the device (e_b(S k) = e_b(k), DeviceRule.unfold); the tetrahedron sum still runs over the whole grid.  The
     zone's symmetries must be symmetries of H, the contract GGR and PTR have.  With one symmetry (FBZ) it is the plain full
     grid.  "energy" and a callable work as before, at every full-grid node; "orbitals" is refused: |U_ab|^2 is not
-    invariant under operations that permute orbitals, and no H(k) is stored."""
+    invariant under operations that permute orbitals, and no H(k) is stored.
 
-    def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None):
+    `correction=True` (with `cumulative=True` and `elements`) adds Bloechl's curvature correction (eq. 22 of the paper)
+    to N_A on every route above.  It removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING, i.e. at the Fermi
+    level of the same grid (`fermi_level`, `band_energy`); at a fixed energy the misplaced Fermi surface leaves an error
+    of the same order.  The plain state count and the DOS have no correction."""
+
+    def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None,
+                 correction=False):
         self.npt = int(npt)
         self.cumulative = bool(cumulative)
         self.symmetric = bool(symmetric)
         if not (elements is None or callable(elements) or elements in ("energy", "orbitals")):
             raise ValueError(f"LTM: elements = {elements!r} is neither 'energy', 'orbitals' nor a callable")
         self.elements = elements
+        self.correction = bool(correction)
+        if self.correction and not self.cumulative:
+            raise ValueError("LTM: correction=True corrects the state sum N_A: it needs cumulative=True (the DOS has no correction)")
+        if self.correction and elements is None:
+            raise ValueError("LTM: correction=True needs elements (the correction of the unweighted state count is zero)")
         if not (isinstance(eigenvectors, str) and eigenvectors in ("host", "device")):
             raise ValueError(f"LTM: eigenvectors = {eigenvectors!r} is neither 'host' nor 'device'")
         device = eigenvectors == "device"
@@ -164,7 +175,7 @@ def _ltm_elements(rule, alg):
 def _ltm_solve(c, Es):
     rule, el = c.cacheval, c.elements
     if el is None or isinstance(el, str):
-        return rule.ltm(Es, states=c.alg.cumulative, elements=el)
+        return rule.ltm(Es, states=c.alg.cumulative, elements=el, correction=c.alg.correction)
     rule.h  # a stale rule refills here and loses its elements
     if rule._ltm_ncomp == 0 or getattr(rule, "_ltm_owner", None) is not el:  # (another cache on the same rule attached its own)
         if isinstance(el, _DeviceOrbitals):
@@ -172,7 +183,7 @@ def _ltm_solve(c, Es):
         else:
             rule.ltm_elements(el)
         rule._ltm_owner = el
-    return rule.ltm(Es, states=c.alg.cumulative, elements="attached")
+    return rule.ltm(Es, states=c.alg.cumulative, elements="attached", correction=c.alg.correction)
 
 
 def init(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):
@@ -210,6 +221,17 @@ def fermi_level(prob_or_cache, nstates, tol=1e-10):
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     return c.cacheval.ltm_fermi(nstates, tol)
+
+
+def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):
+    """(E_band, E_F): the band energy sum_b int e_b theta(E_F - e_b) of `nstates` states per unit cell.  E_F is
+    `fermi_level`'s on the same grid; one single-energy scan with the energy as the element follows, with Bloechl's
+    curvature correction unless `correction=False`.  The correction is made for exactly this use -- a sum at the grid's own
+    Fermi level: it removes the leading O(1/npt^2) error of the linear interpolation."""
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    E_F, _ = fermi_level(c, nstates, tol)
+    u = c.cacheval.ltm(np.array([E_F]), states=True, elements="energy", correction=bool(correction))
+    return float(u[0, 0]), E_F
 
 
 def solve(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):

@@ -590,17 +590,28 @@ class DeviceRule:
         L.check(L.lib().abz_rule_ltm_elements_export(h, C.byref(nc), A.ctypes.data_as(L.c_f64p)))
         return A
 
-    def ltm(self, Es, states=False, elements=None):
+    def ltm(self, Es, states=False, elements=None, correction=False):
         """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
         number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid.
 
         `elements`: matrix elements A_b(k), interpolated linearly inside a simplex like the energy; the result is then
         g_A(E) = sum_b int A_b delta(E - e_b) or N_A(E) = sum_b int A_b theta(E - e_b) as [nE, ncomp]
         (abz_rule_ltm_weighted).  "energy": A = e itself (one component); "attached": what ltm_elements attached; an
-        array [ncomp, nk, n]: attached first."""
+        array [ncomp, nk, n]: attached first.
+
+        `correction` (with `states` and `elements`): N_A with Bloechl's curvature correction (ABZ_LTM_STATES_CORRECTED),
+        N_A + w sum_T g_T(E) kappa_T, kappa_T = sum_i A_i (sum_l e_l - (d+1) e_i) / (2 (d+1)(d+2)), in the same launches.  It
+        removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING -- at the level `ltm_fermi` finds on the same
+        grid; at a fixed energy the misplaced Fermi surface leaves an error of that order.  The plain state count has no
+        correction (kappa_T = 0 for A = 1)."""
         self._ltm_refuse_shard()
+        if correction:
+            if not states:
+                raise ValueError("ltm: correction=True corrects the state sum N_A: it needs states=True (the DOS has no correction)")
+            if elements is None:
+                raise ValueError("ltm: correction=True needs elements (the correction of the unweighted state count is zero)")
         Es = np.ascontiguousarray(np.asarray(Es, dtype=np.float64).reshape(-1))
-        what = L.LTM_STATES if states else L.LTM_DOS
+        what = L.LTM_STATES_CORRECTED if correction else (L.LTM_STATES if states else L.LTM_DOS)
         if elements is None:
             out = np.zeros(len(Es))
             L.check(L.lib().abz_rule_ltm(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))

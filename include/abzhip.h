@@ -250,12 +250,14 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
 /* Replaces: sum_ggr / ggr_formula (src/dos_ggr.jl:58-104) for nE energies; rule must hold VEL. */
 int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out);
 
-/* Linear tetrahedron method (Bloechl, Jepsen, Andersen, PRB 49, 16223, no curvature correction) on the eigenvalues of a
+/* Linear tetrahedron method (Bloechl, Jepsen, Andersen, PRB 49, 16223) on the eigenvalues of a
  * full-grid rule (needs ABZ_WANT_EIG; velocities not needed).  The periodic grid's cells are cut into d! simplices by the
  * Kuhn split, band b of a simplex is the b-th ascending eigenvalue at each corner.  out [nE] receives, per unit cell and
  * summed over bands, the density of states g(E) (what = ABZ_LTM_DOS, integral over E = n) or the number of states below
  * E (ABZ_LTM_STATES, n above all bands, exactly 0 below them).  Rules that are not a whole periodic grid (irreducible
- * nodes, symmetric rules, slabs) return ABZ_ERR_UNSUPPORTED.
+ * nodes, symmetric rules, slabs) return ABZ_ERR_UNSUPPORTED.  The curvature correction of the paper (eq. 22) of an
+ * unweighted count is zero, so `what` is one of these two here and ABZ_LTM_STATES_CORRECTED (abz_rule_ltm_weighted) is
+ * refused with ABZ_ERR_ARG.
  * Replaces: nothing yet -- the reference plans "LTM" (src/dos_algorithms.jl:1-7); entry point added without a change
  * of ABZ_VERSION. */
 #define ABZ_LTM_DOS 0
@@ -288,7 +290,14 @@ int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A);
 #define ABZ_LTM_A_ELEMENTS 0   /* the attached elements, ncomp components */
 #define ABZ_LTM_A_ENERGY 1     /* A_b(k) = e_b(k) itself, 1 component, nothing attached needed */
 /* out [nE][ncomp]: g_A(E) (ABZ_LTM_DOS) or N_A(E) (ABZ_LTM_STATES), per unit cell, summed over bands; A is interpolated
- * linearly inside each simplex like the band energy. */
+ * linearly inside each simplex like the band energy.
+ * ABZ_LTM_STATES_CORRECTED: N_A(E) with Bloechl's curvature correction, for both sources and in the same launches:
+ *   N_A^corr(E) = N_A(E) + w sum_T g_T(E) kappa_T,   kappa_T = f_d sum_i A_i (sum_l e_l - (d+1) e_i),   f_d = 1 / (2 (d+1)(d+2))
+ * over the simplices T with e_1 <= E < e_{d+1}, g_T the simplex's own DOS, w = 1 / (d! npt^d); f_3 = 1/40 is eq. 22 of
+ * the paper, f_2 = 1/24, f_1 = 1/12.  It removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING, i.e. at
+ * the Fermi level of the same grid (abz_rule_ltm_fermi: for A = 1 the correction vanishes, the level has none); at a
+ * fixed energy the misplaced Fermi surface leaves an error of the same order.  Any other `what`: ABZ_ERR_ARG. */
+#define ABZ_LTM_STATES_CORRECTED 2
 int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int what, double* out);
 /* Fermi level: E_F with N(E_F) >= nstates (1 - 1e-12) and N(E) below that for every sampled E <= E_F - tol;
  * 0 < nstates < n.  N_F (nullable) receives N(E_F).  Below a gap (g = 0 exactly from some energy on while N is still

@@ -31,6 +31,7 @@ const WANT_H_ROW_MAJOR = Cint(16)  # abz_eval_nodes: row-major matrices (not for
 const WANT_HC = WANT_H | WANT_H_COMPACT
 const F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = Cint.(0:6)
 const LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = Cint(0), Cint(1), Cint(2), Cint(3)
+const LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = Cint(0), Cint(1), Cint(2)  # `what` of abz_rule_ltm / abz_rule_ltm_weighted
 
 # (kind, lim_a, lim_b) of the reference's limits types for abz_iai_solve(_many); the SymmetryReduceBZ
 # extension's Polyhedron3 travels as packed faces [nv, x y z ...] with lim_b = [length(lim_a)]
@@ -434,15 +435,19 @@ function ltm_elements_export(r::HIPRule, n::Integer)
 end
 
 """
-    ltm_weighted(r, Es; ncomp, energy=false, cumulative=false)
+    ltm_weighted(r, Es; ncomp, energy=false, cumulative=false, correction=false)
 
 `g_A(E)` (or `N_A(E)` with `cumulative`) of the attached elements, `ncomp` of them, or with `energy` of `A = e` itself
-(`abz_rule_ltm_weighted`): a matrix `[ncomp, nE]`.
+(`abz_rule_ltm_weighted`): a matrix `[ncomp, nE]`.  `correction` (with `cumulative`): `N_A` with Bloechl's curvature
+correction (`LTM_STATES_CORRECTED`), which removes the leading `O(1/npt^2)` error of a sum taken at fixed filling, i.e.
+at the level `ltm_fermi` finds on the same grid; at a fixed energy an error of that order remains.
 """
-function ltm_weighted(r::HIPRule, Es::Vector{Float64}; ncomp::Integer=1, energy::Bool=false, cumulative::Bool=false)
+function ltm_weighted(r::HIPRule, Es::Vector{Float64}; ncomp::Integer=1, energy::Bool=false, cumulative::Bool=false,
+        correction::Bool=false)
+    correction && !cumulative && throw(ArgumentError("ltm_weighted: correction corrects N_A: it needs cumulative=true"))
     out = Matrix{Float64}(undef, energy ? 1 : ncomp, length(Es))
     check(ccall((:abz_rule_ltm_weighted, libabz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cint, Ptr{Float64}), r.h,
-        energy ? 1 : 0, Es, length(Es), cumulative ? 1 : 0, out))
+        energy ? 1 : 0, Es, length(Es), correction ? LTM_STATES_CORRECTED : (cumulative ? 1 : 0), out))
     return out
 end
 
