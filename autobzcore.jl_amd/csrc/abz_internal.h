@@ -306,6 +306,10 @@ struct abz_rule {
     size_t node_of_cap = 0;
     int64_t unfold_nk = 0;       // nodes of the source rule the map was made for
     std::vector<int32_t> unfold_syms;  // the symmetries the map was made under [nsyms][d][d]
+    // a slab rule made scannable by abz_rule_ltm_halo: the eigenvalue-only rule of the one plane behind the slab,
+    // plane (outer_end mod npt) of the grid.  Owned by this rule (freed with it, refilled with it); holds no reference of
+    // its own on the series.
+    abz_rule* ltm_halo = nullptr;
 };
 
 namespace abz {
@@ -490,12 +494,21 @@ int launch_big_vec(abz_ctx* ctx, const double* tri, int64_t tri_nk, const double
 int launch_ggr(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView V, const double* w, int64_t nk,
                const double* Es_host, int nE, double* out_host);
 // Linear tetrahedron scan (kernels_ltm.hip) over the eigenvalue planes of a whole periodic grid of npt^d nodes:
-// g(E) or, with `states`, N(E), per unit cell and summed over the n bands
-int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host);
+// g(E) or, with `states`, N(E), per unit cell and summed over the n bands.
+// `slab` (d >= 2): E holds nz planes of the outermost variable only and slab->E the one plane behind them (the halo of
+// abz_rule_ltm_halo, planes tiled like a rule of one plane; slab->A: its element planes, weighted scans).  The scan walks
+// the cells of those nz planes with the whole grid's weight: the slabs of a partition add up to the grid's value.
+struct LtmSlab {
+    PlaneView E, A;
+    int nz = 0;
+};
+int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host,
+               const LtmSlab* slab = nullptr);
 // ... with matrix elements A (ncomp n planes tiled like E, plane c n + b: component c of band b): out_host [nE][ncomp];
 // what: ABZ_LTM_DOS, ABZ_LTM_STATES or ABZ_LTM_STATES_CORRECTED (N_A with the curvature correction)
+// (a slab: one component only)
 int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
-                        int what, double* out_host);
+                        int what, double* out_host, const LtmSlab* slab = nullptr);
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
 // Orbital weights as matrix elements (kernels_ltm_orb.hip): plane c n + b of A (ncomp n planes tiled like the eigenvalue planes,

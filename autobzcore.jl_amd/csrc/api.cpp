@@ -1062,6 +1062,8 @@ static void rule_drop_ltm_elements(abz_rule* r) {
 
 static void rule_free(abz_rule* r) {
     if (!r) return;
+    rule_free(r->ltm_halo);  // the halo plane of abz_rule_ltm_halo goes with its slab (it holds no reference on the series)
+    r->ltm_halo = nullptr;
     rule_drop_ltm_elements(r);
     dev_free(r->vals, r->vals_cap);
     dev_free(r->node_of, r->node_of_cap);
@@ -1523,7 +1525,45 @@ int abz_rule_rebuild(abz_rule* r) try {
         if (rc) return rc;
         if ((rc = rp->tmpD.reserve(tb))) return rc;
     }
-    return rule_fill(r);
+    int rc = rule_fill(r);
+    // the halo plane of abz_rule_ltm_halo belongs to the same values: behind the slab on the same stream, launches only
+    if (!rc && r->ltm_halo) rc = rule_fill(r->ltm_halo);
+    return rc;
+} ABZ_CATCH_ALL
+
+// One halo plane for the tetrahedron scans of a slab: the simplices of the cells of the slab's last plane reach into plane
+// outer_end (mod npt), which the next slab holds -- or this rule itself, as an eigenvalue-only rule of that one plane from
+// the same builder, 1 / npt of the grid.  No exchange between ranks, and the slabs' partial sums add up.
+int abz_rule_ltm_halo(abz_rule* r) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    if (!r->full) {
+        set_error("abz_rule_ltm_halo: the rule holds irreducible nodes (a node list or a symmetric rule), not a slab of a full grid: "
+                  "its simplices lack the mesh, not a plane");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if (r->node_of) {
+        set_error("abz_rule_ltm_halo: the rule was unfolded from irreducible nodes (abz_rule_ltm_unfold): it is a whole grid and has no "
+                  "plan to build a plane from; unfolding into a slab is not implemented");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    abz_series* s = r->s;
+    const Plan& plan = static_cast<RulePlan*>(r->plan)->plan;
+    ABZ_REQUIRE(!(plan.outer0 == 0 && plan.outer_n == r->npt), "abz_rule_ltm_halo: the rule is a whole periodic grid: nothing to attach");
+    ABZ_REQUIRE(r->E.base, "abz_rule_ltm_halo: the rule holds no eigenvalues (build the slab with ABZ_WANT_EIG)");
+    abz_ctx* ctx = s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    if (r->ltm_halo) {  // a second call: the same plane from the series' current coefficients
+        if ((rc = rule_fill(r->ltm_halo))) return rc;
+        ABZ_HIP(hipStreamSynchronize(ctx->stream));
+        return ABZ_OK;
+    }
+    abz_rule* halo = nullptr;
+    const int z = (plan.outer0 + plan.outer_n) % r->npt;
+    if ((rc = rule_build(s, r->npt, 0, nullptr, nullptr, ABZ_WANT_EIG, z, 1, &halo))) return rc;  // (waits for the fill)
+    s->refs -= 1;  // the slab's reference covers its halo
+    r->ltm_halo = halo;
+    return ABZ_OK;
 } ABZ_CATCH_ALL
 
 int abz_rule_info(const abz_rule* r, int64_t* nk, int* n, int* d, int* npt, int* want) try {
@@ -2102,28 +2142,10 @@ int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out) try {
     return launch_ggr(ctx, r->s->n, r->s->d, r->npt, r->E, r->V, r->w, r->nk, E, nE, out);
 } ABZ_CATCH_ALL
 
-int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) try {
-    int rc0 = check_rule(r);
-    if (rc0) return rc0;
-    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm: bad arguments");
-    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES, "abz_rule_ltm: what = %d is neither ABZ_LTM_DOS nor ABZ_LTM_STATES", what);
-    ABZ_REQUIRE(r->E.base, "LTM needs a rule built with ABZ_WANT_EIG");
-    const int d = r->s->d;
-    int64_t ngrid = 1;
-    for (int j = 0; j < d; ++j) ngrid *= r->npt;
-    if (!r->full || r->k_offset != 0 || r->nk != ngrid) {
-        // the simplices of a cell need all its 2^d corners: a slab lacks one halo plane, a list of irreducible nodes the mesh
-        set_error("abz_rule_ltm: the rule is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)",
-                  r->full ? "a slab of the outermost variable" : "irreducible nodes of a symmetric rule");
-        return ABZ_ERR_UNSUPPORTED;
-    }
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    return launch_ltm(ctx, r->s->n, d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out);
-} ABZ_CATCH_ALL
-
-// the rule is a whole periodic grid with eigenvalues (the test and the wording of abz_rule_ltm)
-static int ltm_check_grid(const abz_rule* r, const char* who) {
+// The rule is a whole periodic grid with eigenvalues -- or, where the caller scans slabs (`slab_ok`: abz_rule_ltm and the
+// energy-weighted abz_rule_ltm_weighted), a slab with its halo plane attached.  The simplices of a cell need all its 2^d
+// corners: a slab lacks one halo plane, a list of irreducible nodes the mesh.
+static int ltm_check_grid(const abz_rule* r, const char* who, bool slab_ok = false) {
     if (!r->E.base) {
         set_error("LTM needs a rule built with ABZ_WANT_EIG");
         return ABZ_ERR_ARG;
@@ -2131,12 +2153,41 @@ static int ltm_check_grid(const abz_rule* r, const char* who) {
     int64_t ngrid = 1;
     for (int j = 0; j < r->s->d; ++j) ngrid *= r->npt;
     if (!r->full || r->k_offset != 0 || r->nk != ngrid) {
-        set_error("%s: the rule is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)", who,
-                  r->full ? "a slab of the outermost variable" : "irreducible nodes of a symmetric rule");
+        if (r->full && r->ltm_halo) {
+            if (slab_ok) return ABZ_OK;
+            set_error("%s: the rule is not a whole periodic grid (a slab of the outermost variable; its halo plane serves abz_rule_ltm and "
+                      "abz_rule_ltm_weighted with ABZ_LTM_A_ENERGY only: attached elements, orbital weights, the Fermi level and unfolding "
+                      "are not implemented on slabs); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)", who);
+            return ABZ_ERR_UNSUPPORTED;
+        }
+        set_error("%s: the rule is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)%s", who,
+                  r->full ? "a slab of the outermost variable" : "irreducible nodes of a symmetric rule",
+                  r->full && slab_ok ? ", or give the slab its halo plane: attach it with abz_rule_ltm_halo" : "");
         return ABZ_ERR_UNSUPPORTED;
     }
     return ABZ_OK;
 }
+
+// the slab arguments of a scan when the rule is a slab with its halo (ltm_check_grid let it through), else false
+static bool ltm_slab_of(const abz_rule* r, LtmSlab& slab) {
+    if (!r->ltm_halo) return false;
+    slab.E = slab.A = r->ltm_halo->E;  // (the energy is the only element of a slab scan)
+    slab.nz = static_cast<const RulePlan*>(r->plan)->plan.outer_n;
+    return true;
+}
+
+int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) try {
+    int rc0 = check_rule(r);
+    if (rc0) return rc0;
+    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm: bad arguments");
+    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES, "abz_rule_ltm: what = %d is neither ABZ_LTM_DOS nor ABZ_LTM_STATES", what);
+    int rc = ltm_check_grid(r, "abz_rule_ltm", true);
+    if (rc) return rc;
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    LtmSlab slab;
+    return launch_ltm(ctx, r->s->n, r->s->d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out, ltm_slab_of(r, slab) ? &slab : nullptr);
+} ABZ_CATCH_ALL
 
 int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
     int rc = check_rule(r);
@@ -2250,6 +2301,8 @@ int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {
     int rc = check_rule(r);
     if (rc) return rc;
     ABZ_REQUIRE(ncomp, "abz_rule_ltm_elements_export: null ncomp");
+    // a slab made scannable by abz_rule_ltm_halo names its limit here too (any other rule without elements answers 0 components)
+    if (r->ltm_halo && (rc = ltm_check_grid(r, "abz_rule_ltm_elements_export"))) return rc;
     *ncomp = r->ltm_elems ? r->ltm_ncomp : 0;
     if (!A || !r->ltm_elems) return ABZ_OK;
     abz_ctx* ctx = r->s->ctx;
@@ -2271,14 +2324,15 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
                 "abz_rule_ltm_weighted: what = %d is neither ABZ_LTM_DOS, ABZ_LTM_STATES nor ABZ_LTM_STATES_CORRECTED", what);
     ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
                 "abz_rule_ltm_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_weighted"))) return rc;
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_weighted", source == ABZ_LTM_A_ENERGY))) return rc;
     ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems,
                 "abz_rule_ltm_weighted: no matrix elements are attached (abz_rule_ltm_elements; abz_rule_rebuild drops them)");
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     const bool energy = source == ABZ_LTM_A_ENERGY;
+    LtmSlab slab;
     return launch_ltm_weighted(ctx, r->s->n, r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, E, nE,
-                               what, out);
+                               what, out, ltm_slab_of(r, slab) ? &slab : nullptr);
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {

@@ -75,6 +75,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "abz_internal.h"
@@ -93,6 +94,13 @@ struct LtmArgs {
     int64_t ncell;     // npt^d
     int npt, nE;
     double inv_step = 0.0;  // > 0: the energies are equispaced: Es[i] = Es[0] + i / inv_step to rounding
+};
+
+// A slab of the outermost variable (abz_rule_ltm_halo): E holds the slab's nz planes, `halo` the one plane behind them
+// (plane outer_end mod npt of the grid, a rule of its own); ncell = nz npt^(d-1) and npt stays the grid's.
+struct LtmSlabArgs : LtmArgs {
+    PlaneView halo;
+    int nz = 0;
 };
 
 // first index i with Es[i] >= x (nE if none)
@@ -209,8 +217,12 @@ __device__ __forceinline__ void ltm_simplex1(double a, double b, const double* E
 constexpr unsigned LTM_QUEUE_MAX = 128;
 
 // partial [STATES ? 2 nE : nE][nrows]: columns 0 .. nE-1 the formula sums, nE .. 2 nE-1 the step counts
-template <int D, bool STATES>
-__global__ __launch_bounds__(256) void ltm_window_kernel(LtmArgs a, double* __restrict__ partial, int64_t nrows) {
+// SLAB (d >= 2): the cells of a slab of the outermost variable, whose index does not wrap: the step past the slab's last
+// plane reads the halo plane.  Everything else, and the whole-grid instantiations, are as without it.
+template <int D, bool STATES, bool SLAB = false>
+__global__ __launch_bounds__(256) void ltm_window_kernel(std::conditional_t<SLAB, LtmSlabArgs, LtmArgs> a, double* __restrict__ partial,
+                                                         int64_t nrows) {
+    static_assert(!SLAB || D >= 2, "a slab needs at least two variables");
     // [nE] energies | [4 waves][nE] sums | STATES: [4 waves][nE] steps | [256] queue of a pass | [2][4] per-wave counts
     extern __shared__ __attribute__((aligned(16))) double ldsl[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -228,11 +240,29 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(LtmArgs a, double* __re
     const int npt = a.npt;
     const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
     const int64_t tile = a.E.tile;
+    [[maybe_unused]] const double* __restrict__ Hb = nullptr;  // SLAB: this band's plane of the halo, its line stride, the slab's planes
+    [[maybe_unused]] int64_t htile = 0;
+    [[maybe_unused]] int nz = 0;
+    if constexpr (SLAB) {
+        Hb = a.halo.base + (int64_t)blockIdx.y * a.halo.pitch;
+        htile = a.halo.tile;
+        nz = a.nz;
+    }
     // eigenvalue at corner `bits` (bit j: +1 along variable j+1, wrapped) of cell k
     auto corner = [&](int i1, int i2, int i3, int bits) -> double {
         if ((bits & 1) && ++i1 == npt) i1 = 0;
-        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
-        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
+        if constexpr (SLAB) {
+            // the outermost index is local to the slab and does not wrap: behind plane nz - 1 lies the halo, line i_2 of it (d = 2: its only line)
+            if constexpr (D == 3) {
+                if ((bits & 2) && ++i2 == npt) i2 = 0;
+                if ((bits & 4) && ++i3 == nz) return Hb[(int64_t)i2 * htile + i1];
+            } else {
+                if ((bits & 2) && ++i2 == nz) return Hb[i1];
+            }
+        } else {
+            if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
+            if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
+        }
         return Eb[((int64_t)i3 * npt + i2) * tile + i1];
     };
     // Two passes over 256 cells at a time (the trip count is the block's, so the barriers are uniform).  Pass 1, one cell
@@ -373,6 +403,12 @@ struct WLtmArgs {
     int npt, nE;
     int aplane0;       // first element plane of this launch: (its first component) * n
     double inv_step = 0.0;
+};
+
+// LtmSlabArgs of the weighted scan: the halo's eigenvalue planes and its element planes (tiled alike, strides of their own)
+struct WLtmSlabArgs : WLtmArgs {
+    PlaneView haloE, haloA;
+    int nz = 0;
 };
 
 template <int NC>
@@ -573,8 +609,11 @@ __device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A
 // ltm_window_kernel with NC components of matrix elements.
 // partial [(STATES ? 2 : 1) NC nE][nrows]: columns c nE + i the formula sums of component c, NC nE + c nE + i its steps
 // CORR (with STATES only): N_A with the curvature correction; same histograms, same launches.
-template <int D, bool STATES, int NC, bool CORR = false>
-__global__ __launch_bounds__(256) void wltm_window_kernel(WLtmArgs a, double* __restrict__ partial, int64_t nrows) {
+// SLAB: as in ltm_window_kernel, for the energies and the elements alike.
+template <int D, bool STATES, int NC, bool CORR = false, bool SLAB = false>
+__global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLAB, WLtmSlabArgs, WLtmArgs> a, double* __restrict__ partial,
+                                                          int64_t nrows) {
+    static_assert(!SLAB || D >= 2, "a slab needs at least two variables");
     // [nE] energies | [4 waves][NC][nE] sums | STATES: [4 waves][NC][nE] steps | [256] queue of a pass | [2][4] per-wave counts
     extern __shared__ __attribute__((aligned(16))) double ldsl[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -600,13 +639,45 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(WLtmArgs a, double* __
         if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
         if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
     };
+    [[maybe_unused]] const double* __restrict__ EHb = nullptr;  // SLAB: this band's planes of the halo, their line strides, the slab's planes
+    [[maybe_unused]] const double* __restrict__ AHb = nullptr;
+    [[maybe_unused]] int64_t htileE = 0, htileA = 0;
+    [[maybe_unused]] int nz = 0;
+    if constexpr (SLAB) {
+        EHb = a.haloE.base + (int64_t)blockIdx.y * a.haloE.pitch;
+        AHb = a.haloA.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.haloA.pitch;
+        htileE = a.haloE.tile;
+        htileA = a.haloA.tile;
+        nz = a.nz;
+    }
+    // SLAB: the same step with a local outermost index that does not wrap; true: the corner lies in the halo plane, at
+    // (i1, line i2) of it for d = 3, (i1, line 0) for d = 2
+    [[maybe_unused]] auto wrap_slab = [&](int& i1, int& i2, int& i3, int bits) -> bool {
+        if ((bits & 1) && ++i1 == npt) i1 = 0;
+        if constexpr (D == 3) {
+            if ((bits & 2) && ++i2 == npt) i2 = 0;
+            return (bits & 4) && ++i3 == nz;
+        } else {
+            if ((bits & 2) && ++i2 == nz) {
+                i2 = 0;
+                return true;
+            }
+            return false;
+        }
+    };
     auto cornerE = [&](int i1, int i2, int i3, int bits) -> double {
-        wrap(i1, i2, i3, bits);
+        if constexpr (SLAB) {
+            if (wrap_slab(i1, i2, i3, bits)) return EHb[(int64_t)i2 * htileE + i1];
+        } else {
+            wrap(i1, i2, i3, bits);
+        }
         return Eb[((int64_t)i3 * npt + i2) * tileE + i1];
     };
     auto cornerA = [&](int i1, int i2, int i3, int bits) -> LtmVec<NC> {
-        wrap(i1, i2, i3, bits);
-        const double* __restrict__ const p = Ab + ((int64_t)i3 * npt + i2) * tileA + i1;
+        bool halo = false;
+        if constexpr (SLAB) halo = wrap_slab(i1, i2, i3, bits);
+        else wrap(i1, i2, i3, bits);
+        const double* __restrict__ const p = SLAB && halo ? AHb + (int64_t)i2 * htileA + i1 : Ab + ((int64_t)i3 * npt + i2) * tileA + i1;
         LtmVec<NC> r;
 #pragma unroll
         for (int c = 0; c < NC; ++c) r.v[c] = p[(int64_t)c * acomp];
@@ -860,18 +931,35 @@ __global__ __launch_bounds__(256) void ltm_unfold_kernel(PlaneView src, PlaneVie
 
 #define ABZ_LTM_D(ST)                                                                                         \
     switch (d) {                                                                                              \
-        case 1: launch(ctx, (ltm_window_kernel<1, ST>), grid, dim3(256), lds, a, partial, nrows); break;      \
-        case 2: launch(ctx, (ltm_window_kernel<2, ST>), grid, dim3(256), lds, a, partial, nrows); break;      \
-        default: launch(ctx, (ltm_window_kernel<3, ST>), grid, dim3(256), lds, a, partial, nrows); break;     \
+        case 1: launch(ctx, (ltm_window_kernel<1, ST>), grid, dim3(256), lds, ag, partial, nrows); break;      \
+        case 2: launch(ctx, (ltm_window_kernel<2, ST>), grid, dim3(256), lds, ag, partial, nrows); break;      \
+        default: launch(ctx, (ltm_window_kernel<3, ST>), grid, dim3(256), lds, ag, partial, nrows); break;     \
     }
 
-int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host) {
-    LtmArgs a;
+// the slab kernels take the same grid, block and LDS
+#define ABZ_LTM_SLAB_D(ST)                                                                                          \
+    if (d == 2) launch(ctx, (ltm_window_kernel<2, ST, true>), grid, dim3(256), lds, a, partial, nrows);             \
+    else launch(ctx, (ltm_window_kernel<3, ST, true>), grid, dim3(256), lds, a, partial, nrows);
+
+int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host,
+               const LtmSlab* slab) {
+    LtmSlabArgs a;
+    const LtmArgs& ag = a;  // what the whole-grid kernels take
     a.E = E;
     a.npt = npt;
     a.ncell = 1;
     for (int j = 0; j < d; ++j) a.ncell *= npt;
+    // the weight of a simplex is the whole grid's: the partial sums of the slabs of a partition add up to the grid's value
     const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);
+    if (slab) {
+        if (d < 2 || slab->nz < 1 || slab->nz > npt || !slab->E.base) {
+            set_error("launch_ltm: a slab of %d planes of a %d-d grid of %d points", slab->nz, d, npt);
+            return ABZ_ERR_INTERNAL;
+        }
+        a.halo = slab->E;
+        a.nz = slab->nz;
+        a.ncell = a.ncell / npt * slab->nz;
+    }
     // energies per launch: (1 + 4) x 8 KB of LDS for g, (1 + 8) x 4 KB for N (+ 1 KB of queue).  Chunks are independent: the steps of all
     // simplices below a chunk's first energy land on its index 0.
     const int CH = states ? 512 : 1024;
@@ -895,13 +983,21 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
         const size_t lds = sizeof(double) * (states ? 9 : 5) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
         const dim3 grid((unsigned)nblocks, (unsigned)n);
         if (states) {
-            ABZ_LTM_D(true);
+            if (slab) {
+                ABZ_LTM_SLAB_D(true);
+            } else {
+                ABZ_LTM_D(true);
+            }
             ABZ_HIP(hipGetLastError());
             launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
             ABZ_HIP(hipGetLastError());
             launch(ctx, ltm_prefix_kernel, dim3(1), dim3(256), 0, col, cnt, weight, el.out + s0);
         } else {
-            ABZ_LTM_D(false);
+            if (slab) {
+                ABZ_LTM_SLAB_D(false);
+            } else {
+                ABZ_LTM_D(false);
+            }
             ABZ_HIP(hipGetLastError());
             launch(ctx, ltm_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, weight, el.out + s0);
         }
@@ -910,6 +1006,7 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
     return energies_deliver(ctx, el, out_host);
 }
 #undef ABZ_LTM_D
+#undef ABZ_LTM_SLAB_D
 
 namespace {
 template <int D, bool ST, int NC, bool CORR>
@@ -932,21 +1029,37 @@ void wltm_launch_nc(abz_ctx* ctx, int d, int nc, dim3 grid, size_t lds, const WL
         default: wltm_launch_d<ST, 4, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
     }
 }
+// a slab: the energy as the element (one component), with or without the correction
+template <bool ST, bool CORR = false>
+void wltm_launch_slab(abz_ctx* ctx, int d, dim3 grid, size_t lds, const WLtmSlabArgs& a, double* partial, int64_t nrows) {
+    if (d == 2) launch(ctx, (wltm_window_kernel<2, ST, 1, CORR, true>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
+    else launch(ctx, (wltm_window_kernel<3, ST, 1, CORR, true>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
+}
 // dynamic LDS of the shipped scans: 5 x 1024 (g) energies x 8 B + queue and counts; the weighted scans stay within it
 constexpr size_t LTM_LDS_MAX = sizeof(double) * 5 * 1024 + sizeof(uint32_t) * (256 + 8);
 }  // namespace
 
 int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
-                        int what, double* out_host) {
+                        int what, double* out_host, const LtmSlab* slab) {
     const bool states = what != ABZ_LTM_DOS, corrected = what == ABZ_LTM_STATES_CORRECTED;
-    WLtmArgs a;
+    WLtmSlabArgs a;  // (the whole-grid kernels take its WLtmArgs part)
     a.E = E;
     a.A = A;
     a.acomp = (int64_t)n * A.pitch;
     a.npt = npt;
     a.ncell = 1;
     for (int j = 0; j < d; ++j) a.ncell *= npt;
-    const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);
+    const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);  // the whole grid's, as in launch_ltm
+    if (slab) {
+        if (d < 2 || slab->nz < 1 || slab->nz > npt || !slab->E.base || !slab->A.base || ncomp != 1) {
+            set_error("launch_ltm_weighted: a slab of %d planes of a %d-d grid of %d points with %d components", slab->nz, d, npt, ncomp);
+            return ABZ_ERR_INTERNAL;
+        }
+        a.haloE = slab->E;
+        a.haloA = slab->A;
+        a.nz = slab->nz;
+        a.ncell = a.ncell / npt * slab->nz;
+    }
     const int ncol = states ? 2 : 1;
     // Energies per launch of NC components: 8 (1 + 4 NC ncol) B of LDS each, within LTM_LDS_MAX, and at most 512 where the
     // prefix kernel holds a chunk's steps: g 1024 / 568 / 301, N 512 / 301 / 155 for NC = 1 / 2 / 4.
@@ -980,14 +1093,17 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
             const size_t lds = sizeof(double) * (size_t)(1 + 4 * nc * ncol) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
             double* const o = el.out + (size_t)c0 * nE + s0;  // results [ncomp][nE] in sorted order
             if (states) {
-                if (corrected) wltm_launch_nc<true, true>(ctx, d, nc, grid, lds, a, partial, nrows);
+                if (slab && corrected) wltm_launch_slab<true, true>(ctx, d, grid, lds, a, partial, nrows);
+                else if (slab) wltm_launch_slab<true>(ctx, d, grid, lds, a, partial, nrows);
+                else if (corrected) wltm_launch_nc<true, true>(ctx, d, nc, grid, lds, a, partial, nrows);
                 else wltm_launch_nc<true>(ctx, d, nc, grid, lds, a, partial, nrows);
                 ABZ_HIP(hipGetLastError());
                 launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
                 ABZ_HIP(hipGetLastError());
                 launch(ctx, wltm_prefix_kernel, dim3((unsigned)nc), dim3(256), 0, col, cnt, nc, weight, (int64_t)nE, o);
             } else {
-                wltm_launch_nc<false>(ctx, d, nc, grid, lds, a, partial, nrows);
+                if (slab) wltm_launch_slab<false>(ctx, d, grid, lds, a, partial, nrows);
+                else wltm_launch_nc<false>(ctx, d, nc, grid, lds, a, partial, nrows);
                 ABZ_HIP(hipGetLastError());
                 launch(ctx, wltm_final_kernel, dim3((unsigned)(nc * cnt)), dim3(256), 0, partial, nrows, weight, cnt, (int64_t)nE, o);
             }

@@ -79,12 +79,15 @@ class kshard:
     ref: SURVEY 8e (2) -- the recursion of fourier_ptr! is independent per outer index
     (src/fourier.jl:148-164), so rank r builds and scans only its slab of the outermost variable of a
     full grid (or its block of the irreducible nodes of a symmetric rule); every rule value
-    (abz_rule_reduce, abz_rule_ggr) is then one all-reduce(sum) of a few doubles.  The convergence
+    (abz_rule_reduce, abz_rule_ggr, abz_rule_ltm) is then one all-reduce(sum) of a few doubles.  LTM's
+    simplices reach one plane past a slab: every rank computes that halo plane itself (DeviceRule.ltm_halo,
+    1/npt of the grid, no exchange) and dos.solve(..., LTM()) does so for elements None or "energy"; orbital
+    and callable elements, symmetric=True, fermi_level and band_energy are not k-sharded.  The convergence
     test of AutoPTR runs redundantly on every rank on the same summed numbers, so all ranks take the
     same decisions.  IAI is not k-sharded (its panels are sharded by omega instead).
 
         with kshard(h, group):                      # h: FourierSeries (or its DeviceSeries)
-            u = solver(omega)                       # PTR / AutoPTR / GGR as usual, same value on all ranks
+            u = solver(omega)                       # PTR / AutoPTR / GGR / LTM as usual, same value on all ranks
     """
 
     def __init__(self, series, group=None, device=None, force=False):

@@ -49,7 +49,12 @@ class LTM(DOSAlgorithm):
     `correction=True` (with `cumulative=True` and `elements`) adds Bloechl's curvature correction (eq. 22 of the paper)
     to N_A on every route above.  It removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING, i.e. at the Fermi
     level of the same grid (`fermi_level`, `band_energy`); at a fixed energy the misplaced Fermi surface leaves an error
-    of the same order.  The plain state count and the DOS have no correction."""
+    of the same order.  The plain state count and the DOS have no correction.
+
+    On a k-sharded series (dist.kshard) every rank builds its slab of the grid and the one halo plane behind it
+    (DeviceRule.ltm_halo), scans the cells of its slab, and the partial sums are summed over the ranks: `elements` None or
+    "energy", with or without `cumulative` and `correction`.  "orbitals", a callable, `symmetric=True` on a symmetric zone,
+    `fermi_level` and `band_energy` raise NotImplementedError there."""
 
     def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None,
                  correction=False):
@@ -128,6 +133,17 @@ def _init_cacheval(h, domain, p, alg):
         raise ValueError('LTM: elements = "orbitals" needs symmetric=False (orbital weights are not invariant under the zone\'s '
                          "symmetries, and an unfolded rule stores no H(k))")
     h.invalidate()  # coefficients may have been mutated in place (test/dos.jl:123): re-upload, rules refill lazily
+    if isinstance(alg, LTM) and _ksharded(h.device()):
+        # slabs of the full grid, each with its halo plane; what needs more than a sum of partial scans is refused here
+        if alg.elements is not None and alg.elements != "energy":
+            raise NotImplementedError('LTM on a k-sharded series: elements = "orbitals" or a callable are not implemented (a slab '
+                                      'scans elements None or "energy")')
+        if alg.symmetric and p.syms is not None and len(p.syms) > 1:
+            raise NotImplementedError("LTM on a k-sharded series: symmetric=True on a symmetric zone is not implemented (no "
+                                      "unfolding into a slab)")
+        rule = h.device().rule(alg.npt, None, L.WANT_EIG)
+        rule.ltm_halo()
+        return rule
     if isinstance(alg, LTM) and alg.symmetric and p.syms is not None and len(p.syms) > 1:
         # eigensolves at the irreducible nodes only; the full grid's eigenvalue planes are a gather from them
         return h.device().rule(alg.npt, p.syms, L.WANT_EIG).unfold()
@@ -138,6 +154,10 @@ def _init_cacheval(h, domain, p, alg):
         host_vectors = alg.elements == "orbitals" and alg.eigenvectors == "host"  # numpy diagonalises the exported H(k)
         return h.device().rule(alg.npt, None, (L.WANT_H | L.WANT_EIG) if host_vectors else L.WANT_EIG)
     return h.device().rule(alg.npt, p.syms, L.WANT_EIG | L.WANT_VEL)
+
+
+def _ksharded(dev):
+    return bool(dev.kshard and dev.kshard[1] > 1)
 
 
 class _DeviceOrbitals:
@@ -213,6 +233,10 @@ def solve_(c: DOSCache):
 def fermi_level(prob_or_cache, nstates, tol=1e-10):
     """(E_F, N(E_F)) of `nstates` states per unit cell (0 < nstates < n) from the eigenvalues of an LTM cache, or of a
     DOSProblem (solved with LTM()): E_F is the upper end of an interval no wider than `tol` that N crosses `nstates` in."""
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+        raise NotImplementedError("fermi_level / band_energy on a k-sharded series are not implemented: the search for the level "
+                                  "needs an all-reduce inside it")
     c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
     if not isinstance(c.alg, LTM):
         raise ValueError("fermi_level needs an LTM cache")

@@ -421,12 +421,14 @@ class DeviceRule:
         self._h = h if h.value else None
         self._closed = False
         self._ltm_ncomp = 0  # components of the matrix elements attached by ltm_elements
+        self._ltm_halo = False  # a k-sharded rule: ltm_halo() made its slab scannable
         self.generation = self.dev.generation
         self._fin = weakref.finalize(self, DeviceRule._destroy, self._h)
 
     @property
     def h(self):
-        """The abz_rule handle (None for an empty k-shard); a stale rule is refilled first."""
+        """The abz_rule handle (None for an empty k-shard); a stale rule is refilled first, and an attached halo plane
+        (ltm_halo) with it: abz_rule_rebuild does both."""
         if self._closed:
             raise L.AbzError("DeviceRule was closed")
         if self._h is not None and self.generation != self.dev.generation:
@@ -536,16 +538,39 @@ class DeviceRule:
             L.check(L.lib().abz_rule_ggr(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), out.ctypes.data_as(L.c_f64p)))
         return self._sum_over_ranks(out)
 
-    def _ltm_refuse_shard(self):
+    def _ltm_refuse_shard(self, what=None):
+        """Everything of LTM but the scans of `ltm` refuses a k-sharded rule; `what` names the caller once a halo is there."""
         if self.shard and self.shard[1] > 1:
+            if self._ltm_halo and what:
+                raise NotImplementedError(f"{what} on a k-sharded (slab) rule is not implemented: with its halo plane a slab serves "
+                                          "ltm(Es) and ltm(Es, elements='energy') only")
             raise NotImplementedError("LTM on a k-sharded (slab) rule is not implemented: the simplices of a slab's last "
                                       "plane need one halo plane from the next rank")
+
+    def ltm_halo(self):
+        """Make this rank's slab of a k-sharded full-grid rule scannable by `ltm` (abz_rule_ltm_halo): the rule computes the
+        one plane behind its slab itself, eigenvalues only, 1/npt of the grid and no exchange between ranks.  The plane
+        belongs to the rule: it is refilled with it when the series changes and goes with it.  Nothing to do on a rank whose
+        slab is empty; ValueError on a rule that is not sharded."""
+        if not (self.shard and self.shard[1] > 1):
+            raise ValueError("ltm_halo: the rule is not k-sharded (a whole grid needs no halo plane)")
+        if self.syms is not None:
+            raise NotImplementedError("ltm_halo: a k-sharded symmetric rule holds a block of irreducible nodes, not a slab of the grid")
+        h = self.h  # (a stale rule is refilled here)
+        if h is not None:
+            L.check(L.lib().abz_rule_ltm_halo(h))
+            if not self._ltm_halo:
+                add = 8 * self.dev.s.n * self.npt ** (self.dev.s.d - 1)
+                self.nbytes += add
+                if any(r is self for r in self.dev.rules.values()):
+                    self.dev.rule_bytes += add
+        self._ltm_halo = True
 
     def ltm_elements(self, A):
         """Attach matrix elements A [ncomp, nk, n] (node and band order of export()'s eig [nk, n]) to the rule for
         weighted tetrahedron scans (abz_rule_ltm_elements); `None` drops them.  They stay on the device until replaced,
         dropped, or the rule is rebuilt."""
-        self._ltm_refuse_shard()
+        self._ltm_refuse_shard("ltm_elements")
         if A is None:
             L.check(L.lib().abz_rule_ltm_elements(self.h, None, 0))
             self._ltm_ncomp = 0
@@ -564,7 +589,7 @@ class DeviceRule:
         (abz_rule_ltm_orbitals): component c is orbital `orbitals[c]` (None: all n <= 16 of them), bands ascending as in
         export()'s eig.  H(k) comes from the rule, or from a transient rule when it keeps eigenvalues only.  At a degenerate
         level the weights belong to some orthonormal basis of the eigenspace.  `ltm(Es, elements="attached")` scans them."""
-        self._ltm_refuse_shard()
+        self._ltm_refuse_shard("ltm_orbitals")
         h = self.h  # (a stale rule is refilled here)
         if orbitals is None:
             L.check(L.lib().abz_rule_ltm_orbitals(h, None, 0))
@@ -580,7 +605,7 @@ class DeviceRule:
     def ltm_elements_export(self):
         """The attached matrix elements [ncomp, nk, n] back on the host (abz_rule_ltm_elements_export), in the order
         ltm_elements takes them; None when nothing is attached."""
-        self._ltm_refuse_shard()
+        self._ltm_refuse_shard("ltm_elements_export")
         h = self.h  # (a stale rule is refilled here, which drops the attached elements)
         nc = C.c_int(0)
         L.check(L.lib().abz_rule_ltm_elements_export(h, C.byref(nc), None))
@@ -592,7 +617,9 @@ class DeviceRule:
 
     def ltm(self, Es, states=False, elements=None, correction=False):
         """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
-        number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid.
+        number of states N(E) below E, per unit cell and summed over bands.  The rule must be a whole periodic grid, or a
+        k-sharded one after `ltm_halo()`: every rank scans the cells of its slab and the partial sums are summed over the
+        ranks (`elements` None or "energy" only).
 
         `elements`: matrix elements A_b(k), interpolated linearly inside a simplex like the energy; the result is then
         g_A(E) = sum_b int A_b delta(E - e_b) or N_A(E) = sum_b int A_b theta(E - e_b) as [nE, ncomp]
@@ -604,7 +631,11 @@ class DeviceRule:
         removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING -- at the level `ltm_fermi` finds on the same
         grid; at a fixed energy the misplaced Fermi surface leaves an error of that order.  The plain state count has no
         correction (kappa_T = 0 for A = 1)."""
-        self._ltm_refuse_shard()
+        sharded = bool(self.shard and self.shard[1] > 1)
+        if sharded and not self._ltm_halo:
+            self._ltm_refuse_shard()
+        if sharded and not (elements is None or (isinstance(elements, str) and elements == "energy")):
+            self._ltm_refuse_shard("ltm with attached elements")
         if correction:
             if not states:
                 raise ValueError("ltm: correction=True corrects the state sum N_A: it needs states=True (the DOS has no correction)")
@@ -614,8 +645,10 @@ class DeviceRule:
         what = L.LTM_STATES_CORRECTED if correction else (L.LTM_STATES if states else L.LTM_DOS)
         if elements is None:
             out = np.zeros(len(Es))
-            L.check(L.lib().abz_rule_ltm(self.h, Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
-            return out
+            h = self.h
+            if h is not None:  # (an empty slab adds nothing)
+                L.check(L.lib().abz_rule_ltm(h, Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
+            return self._sum_over_ranks(out)
         if isinstance(elements, str):
             if elements not in ("energy", "attached"):
                 raise ValueError(f"ltm: elements = {elements!r} is neither 'energy' nor 'attached'")
@@ -627,14 +660,15 @@ class DeviceRule:
         if ncomp < 1:
             raise ValueError("ltm: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
         out = np.zeros((len(Es), ncomp))
-        L.check(L.lib().abz_rule_ltm_weighted(h, L.LTM_A_ENERGY if elements == "energy" else L.LTM_A_ELEMENTS,
-                                              Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
-        return out
+        if h is not None:
+            L.check(L.lib().abz_rule_ltm_weighted(h, L.LTM_A_ENERGY if elements == "energy" else L.LTM_A_ELEMENTS,
+                                                  Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
+        return self._sum_over_ranks(out)
 
     def ltm_fermi(self, nstates, tol=1e-10):
         """(E_F, N(E_F)): the Fermi level of `nstates` states per unit cell, 0 < nstates < n, to within `tol`
         (abz_rule_ltm_fermi: a few N(E) scans of 512 energies each, no host bisection)."""
-        self._ltm_refuse_shard()
+        self._ltm_refuse_shard("ltm_fermi (it needs an all-reduce inside the search)")
         ef, nf = C.c_double(0.0), C.c_double(0.0)
         L.check(L.lib().abz_rule_ltm_fermi(self.h, float(nstates), float(tol), C.byref(ef), C.byref(nf)))
         return ef.value, nf.value
@@ -645,7 +679,7 @@ class DeviceRule:
         eigensolves.  The symmetries must be symmetries of H (the contract GGR and PTR have on a symmetric zone).  The
         result serves `ltm`, `ltm_elements`, `ltm_fermi` and `export`, follows the series like any rule; while it is alive this
         rule hands out the same object."""
-        self._ltm_refuse_shard()
+        self._ltm_refuse_shard("unfold")
         if self.syms is None:
             raise ValueError("unfold: the rule is a full grid already (no symmetries to unfold)")
         if not (self.want & L.WANT_EIG):

@@ -255,7 +255,7 @@ int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out);
  * Kuhn split, band b of a simplex is the b-th ascending eigenvalue at each corner.  out [nE] receives, per unit cell and
  * summed over bands, the density of states g(E) (what = ABZ_LTM_DOS, integral over E = n) or the number of states below
  * E (ABZ_LTM_STATES, n above all bands, exactly 0 below them).  Rules that are not a whole periodic grid (irreducible
- * nodes, symmetric rules, slabs) return ABZ_ERR_UNSUPPORTED.  The curvature correction of the paper (eq. 22) of an
+ * nodes, symmetric rules, slabs) return ABZ_ERR_UNSUPPORTED; a slab is taken once abz_rule_ltm_halo gave it its halo plane.  The curvature correction of the paper (eq. 22) of an
  * unweighted count is zero, so `what` is one of these two here and ABZ_LTM_STATES_CORRECTED (abz_rule_ltm_weighted) is
  * refused with ABZ_ERR_ARG.
  * Replaces: nothing yet -- the reference plans "LTM" (src/dos_algorithms.jl:1-7); entry point added without a change
@@ -319,6 +319,20 @@ int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, dou
  * message counts the uncovered points).  ABZ_ERR_UNSUPPORTED: src is a full grid or a slab, or npt^d >= 2^31.  Costs 4 B
  * per grid point for the orbit map beside the n planes. */
 int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule** out);
+/* Tetrahedron scans on a slab: attach the halo plane.  r: a rule of abz_ptr_rule_build_slab over [outer_begin, outer_end) that
+ * holds eigenvalues (other `want` bits are fine).  The simplices of the cells of the slab's last plane reach into plane
+ * outer_end mod npt; this builds that one plane, eigenvalues only, with the builder of the slab itself (1 / npt of the grid, no
+ * exchange between ranks) and hands it to r: it is freed by abz_rule_destroy(r), counted by abz_mem_info, refilled by a second
+ * call and by abz_rule_rebuild(r) (same call, same stream), and is not a rule of its own to the caller.
+ * With the halo, abz_rule_ltm (DOS, STATES) and abz_rule_ltm_weighted with ABZ_LTM_A_ENERGY (DOS, STATES, STATES_CORRECTED)
+ * take the slab and return its PARTIAL sum: the sum over the cells whose outermost index lies in [outer_begin, outer_end), every
+ * simplex with the whole grid's weight 1 / (d! npt^d).  The partial sums of the slabs of a partition of [0, npt) add up to the
+ * whole grid's value; N is exactly 0 below the bands on every slab.  Everything else keeps refusing slabs with
+ * ABZ_ERR_UNSUPPORTED, halo or not: ABZ_LTM_A_ELEMENTS, abz_rule_ltm_elements, _orbitals, _elements_export, _fermi, _unfold.
+ * ABZ_ERR_ARG: a whole periodic grid (nothing to attach), a rule without eigenvalues.  ABZ_ERR_UNSUPPORTED: a node list or
+ * symmetric rule, a rule of abz_rule_ltm_unfold.  A refusal or failure leaves r as it was.  Entry point added without a
+ * change of ABZ_VERSION. */
+int abz_rule_ltm_halo(abz_rule* r);
 
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.

@@ -486,6 +486,18 @@ function ltm_unfold!(u::HIPRule, r::HIPRule, syms, ::Val{d}) where {d}
     return u
 end
 
+"""
+    ltm_halo!(r)                              -> r
+
+Attach the halo plane to a slab rule with eigenvalues (`abz_rule_ltm_halo`): the one plane behind the slab, built by the
+slab's own builder and owned by `r`.  `ltm_weighted(r, Es; energy=true, ...)` and `abz_rule_ltm` then return the slab's
+partial sum, with the whole grid's weights; the slabs of a partition of the outermost variable add up to the grid's value.
+"""
+function ltm_halo!(r::HIPRule)
+    check(ccall((:abz_rule_ltm_halo, libabz), Cint, (Ptr{Cvoid},), r.h))
+    return r
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
