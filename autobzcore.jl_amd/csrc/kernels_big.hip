@@ -781,10 +781,12 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
         for (int q = 0; q < NQ; ++q) acc[q] = make_double2(0.0, 0.0);
         for (int64_t kb = k0; kb < k1; kb += kstep * SUBS) {
             const int64_t k = kb + sub * kstep;
-            const bool valid = k < k1;  // (the second half of a wave may be without a node: it inverts z I)
+            // (a part of a wave may be without a node: it inverts the identity, whatever z is, and adds nothing to acc)
+            const bool valid = k < k1;
             const int64_t kk = valid ? k : kb;
             const double sw = a.sweep_per_node ? a.sweep_per_node[a.node0 + kk] : (a.sweep ? a.sweep[s] : a.sweep0);
             const double2* __restrict__ h = a.Hbuf + kk * (int64_t)nn;
+            const double dr = valid ? sw : 1.0, di = valid ? a.eta : 0.0;  // without a node: the identity
             double2 W[NQ];
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
@@ -792,7 +794,7 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
                 W[q] = make_double2(0.0, 0.0);
                 if (rowon && j < n) {
                     const double2 hv = valid ? h[r + n * j] : make_double2(0.0, 0.0);
-                    W[q] = make_double2((r == j ? sw : 0.0) - hv.x, (r == j ? a.eta : 0.0) - hv.y);
+                    W[q] = make_double2((r == j ? dr : 0.0) - hv.x, (r == j ? di : 0.0) - hv.y);
                 }
             }
             // pivots c = 4 cq + cm: cq unrolled (the entry of column c in its wave's registers is W[cq], a static index), cm rolled
@@ -800,10 +802,12 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
             const double wk = (sum && valid) ? (a.w ? a.w[a.node0 + k] : 1.0) : (valid ? 1.0 : 0.0);
             if (a.kind == 0) {
                 if (sum) {
+                    if (valid) {  // (lanes without a node keep their sums: nothing is multiplied by a zero weight)
 #pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-                        acc[q].x = fma(wk, W[q].x, acc[q].x);
-                        acc[q].y = fma(wk, W[q].y, acc[q].y);
+                        for (int q = 0; q < NQ; ++q) {
+                            acc[q].x = fma(wk, W[q].x, acc[q].x);
+                            acc[q].y = fma(wk, W[q].y, acc[q].y);
+                        }
                     }
                 } else if (rowon && valid) {
                     double2* __restrict__ vo = a.values + ((a.node0 + k) * a.n_sweep + s) * (int64_t)nn;
@@ -836,7 +840,7 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
                         tr = -ti * 0.31830988618379067153776752674503;
                         ti = 0.0;
                     }
-                    if (sum) {
+                    if (sum && valid) {
                         acc[0].x = fma(wk, tr, acc[0].x);
                         acc[0].y = fma(wk, ti, acc[0].y);
                     } else if (valid) {

@@ -10,7 +10,13 @@
 //
 // A = (omega + i eta) I - H has a positive-definite anti-Hermitian part (eta > 0) whenever H is
 // Hermitian, so elimination without pivoting is backward stable up to a growth factor <= ||A||/eta;
-// that is what the Gauss-Jordan below relies on.
+// that is what the Gauss-Jordan below relies on.  At eta = 0 it holds for a dissipative
+// H = H_h - i Gamma with Gamma >= gamma I > 0 (a series that carries a self-energy): gamma takes the
+// place of eta.  For a Hermitian H at eta = 0 a gap around omega makes A invertible but not every
+// leading block of it: the elimination is safe where those blocks are definite, as for the
+// diagonally dominant diag(+D, -D) + hopping that is tested, and may meet a zero pivot otherwise
+// (H = [[0, 1], [1, 0]] at omega = 0).  Nothing is claimed for a general H that is not Hermitian
+// and not dissipative.  tests/test_gpu_resolvent_edges.py pins the two cases and the bound.
 #include <utility>
 
 #include "abz_internal.h"

@@ -192,7 +192,13 @@ int abz_rule_export(abz_rule* r, double* x, double* w, double* H, double* eig, d
  * for a built-in integrand, for n_sweep parameter values in one pass (batchsolve's omega sweep,
  * src/interfaces.jl:210-222, fused).  out_reim [n_sweep][ncomp][2] receives
  *   (sum_k w_k f(k, H(k); sweep_i)) / (npt^d * nsyms)        (nsyms = 1 on a full grid)
- * -- the caller applies |det B| and symmetrisation like do_solve_autobz (src/brillouin.jl:337-355). */
+ * -- the caller applies |det B| and symmetrisation like do_solve_autobz (src/brillouin.jl:337-355).
+ * DOS, TRGLOC and GLOC invert (omega + i eta) I - H(k) WITHOUT PIVOTING.  That is stable, with an error of a modest multiple
+ * of eps sum_k ||G_k||^2 (||H_k|| + |z|) (times ||z - H_k|| / eta at worst), for a Hermitian series with eta > 0 and for a
+ * dissipative series H = H_h - i Gamma, Gamma >= gamma I > 0, at eta >= 0; at eta = 0 a Hermitian series needs omega in a gap
+ * AND definite leading blocks of omega I - H(k) (a diagonally dominant diag(+D, -D) + hopping has them).  For a general series
+ * that is not Hermitian and not dissipative no bound is claimed: a pivoting inverse (LAPACK) may be accurate where this one is
+ * not, and nothing tests that case. */
 int abz_rule_reduce(abz_rule* r, int integrand, const double* params, int nparams,
                     const double* sweep, int n_sweep, int nsyms, double* out_reim);
 
@@ -242,6 +248,8 @@ int abz_series_drop_rules(abz_series* s);
  * more than 128 points, the tridiagonal form of every node above; GLOC above 4 bands, series that are not Hermitian and short
  * lines: the inverse of every node, chunk by chunk).  Other integrands: Hermitian series of n <= 4 bands with npt > 128;
  * ABZ_ERR_UNSUPPORTED otherwise (build a rule instead).
+ * The resolvents are inverted without pivoting, as in abz_rule_reduce: the same cases are covered and the same one -- a series
+ * that is neither Hermitian nor dissipative -- is not.
  * Replaces: FourierPTR ctor + rule(f, B) back to back (src/fourier.jl:166-207). */
 int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int integrand,
                 const double* params, int nparams, const double* sweep, int n_sweep, int nsyms,
