@@ -30,6 +30,8 @@ PROTOTYPES = {
     "abz_series_create": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_i32p, c_i32p, c_f64p, C.c_int, c_vpp]),
     "abz_series_destroy": (C.c_int, [C.c_void_p]),
     "abz_series_update": (C.c_int, [C.c_void_p, c_f64p]),
+    "abz_series_set_pivoting": (C.c_int, [C.c_void_p, C.c_int]),
+    "abz_series_get_pivoting": (C.c_int, [C.c_void_p, c_ip]),
     "abz_eval_nodes": (C.c_int, [C.c_void_p, c_f64p, C.c_int64, C.c_int, c_f64p, c_f64p]),
     "abz_ptr_rule_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_i32p, c_i64p, C.c_int, c_vpp]),
     "abz_ptr_rule_build_sym": (C.c_int, [C.c_void_p, C.c_int, c_i32p, C.c_int, C.c_int, c_vpp]),
@@ -83,6 +85,7 @@ K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
 LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
 LTM_MAX_COMP = 16
+PIVOT_NONE, PIVOT_PARTIAL = 0, 1  # abz_series_set_pivoting
 ERR_ARG, ERR_HIP, ERR_NOGPU, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 
 

@@ -241,6 +241,7 @@ struct abz_series {
     int first[ABZ_MAX_DIM] = {0, 0, 0};
     double period[ABZ_MAX_DIM] = {1, 1, 1};
     bool hermitian = false;   // c(-R) == c(R)^dagger exactly  =>  H(k) Hermitian: half the Fourier work
+    int pivoting = ABZ_PIVOT_NONE;  // abz_series_set_pivoting: read at every launch of a resolvent integrand (series_pivots below)
     size_t coef_cap = 0;
     abz::DevBuf coef_pk;       // Hermitian series, n <= 4: the coefficients with the innermost variable packed (packed_herm.h)
     bool coef_pk_valid = false;
@@ -277,6 +278,9 @@ struct abz_series {
 };
 
 namespace abz {
+inline bool integrand_resolvent(int integrand) { return integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC; }
+// ABZ_PIVOT_PARTIAL: every inverse of (w + i eta) I - H(k) this integrand takes for the series pivots by rows
+inline bool series_pivots(const abz_series* s, int integrand) { return s->pivoting == ABZ_PIVOT_PARTIAL && integrand_resolvent(integrand); }
 // at least `count` lane views of s (same device coefficients, own context / stream / pools); owned by s
 int series_lane_views(abz_series* s, int count);
 }  // namespace abz
@@ -424,6 +428,7 @@ struct ReduceSpec {
     const int32_t* idx;   // null: full grid (k -> grid indices implicitly)
     int64_t k_offset = 0; // full grid: flat index of node 0
     bool herm = false;    // the cached H(k) are exactly Hermitian (rule of a Hermitian series)
+    bool pivot = false;   // series_pivots: the row-pivoted inverse of every node (big_inverse_kernel), whatever the series
     double params[4];
     const double* sweep_dev;  // device [n_sweep]
     int n_sweep;
@@ -544,6 +549,7 @@ struct NodeEvalSpec {
     bool panels15 = false;  // every aligned run of 15 nodes is one GK(7,15) panel (same parent)
     bool packed = false;  // `src` holds PACKED Hermitian level-1 sets (packed_herm.h), n <= 4
     bool herm = false;    // the series is Hermitian (33...64 bands: resolvent traces come from the tridiagonal of Hermitian(h))
+    bool pivot = false;   // series_pivots, more than 4 bands: node values from the row-pivoted inverse (launch_big_nodes)
 };
 int launch_node_integrand(abz_ctx* ctx, const NodeEvalSpec& ns, double2* values_dev);
 
@@ -635,6 +641,7 @@ struct GenSpec {
     PlaneView Eplanes;
     PlaneView Uplanes;  // eigenvectors out (velocity builds)
     bool herm = false;  // the series is Hermitian: H(k) = H(k)^dagger to rounding
+    bool pivot = false;  // series_pivots: `values` from the row-pivoted inverse of every node (launch_big_nodes)
     double2* Haos;
     double* Eaos;
     int integrand;
@@ -660,6 +667,7 @@ struct SumSpec {
     double scale;
     bool herm = true;  // the series is Hermitian (a series that is not goes through the inverse of every node)
     bool force_inverse = false;  // n <= 4 without a closed-form store-free kernel for this case: the inverse of every node as well
+    bool pivot = false;  // series_pivots (with force_inverse): that inverse pivots by rows
     SumOut out;  // [n_sweep][ncomp] sums, scale * sum over the nlines * npt nodes
 };
 

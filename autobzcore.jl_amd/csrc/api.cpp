@@ -983,6 +983,23 @@ int abz_series_update(abz_series* s, const double* coef_reim) try {
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
+int abz_series_set_pivoting(abz_series* s, int mode) try {
+    ABZ_REQUIRE(s, "abz_series_set_pivoting: null series");
+    int rc = check_series(s);
+    if (rc) return rc;
+    ABZ_REQUIRE(mode == ABZ_PIVOT_NONE || mode == ABZ_PIVOT_PARTIAL, "abz_series_set_pivoting: mode %d is neither ABZ_PIVOT_NONE nor ABZ_PIVOT_PARTIAL", mode);
+    s->pivoting = mode;  // (read at launch time: rules built from the series hold H(k), which does not depend on it)
+    for (abz_series* v : s->lanes) v->pivoting = mode;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_series_get_pivoting(const abz_series* s, int* mode) try {
+    ABZ_REQUIRE(s && mode, "abz_series_get_pivoting: null argument");
+    ABZ_REQUIRE(!s->closed, "abz_series_get_pivoting: the series was destroyed");
+    *mode = s->pivoting;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
 }  // extern "C"
 
 namespace abz {
@@ -1001,6 +1018,7 @@ int series_lane_views(abz_series* s, int count) {
             v->period[j] = s->period[j];
         }
         v->hermitian = s->hermitian;
+        v->pivoting = s->pivoting;
         v->coef = s->coef;
         v->coef_borrowed = true;
         c->refs += 1;
@@ -1657,6 +1675,11 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     const bool use_eig = integrand == ABZ_F_DOS_EIG;
+    const bool pivot = series_pivots(r->s, integrand);
+    if (pivot && !r->H.base) {
+        set_error("ABZ_PIVOT_PARTIAL: the pivoted inverse reads the matrices H(k) of every node: build the rule with ABZ_WANT_H");
+        return ABZ_ERR_UNSUPPORTED;
+    }
     if (use_eig)
         ABZ_REQUIRE(r->E.base, "integrand needs cached eigenvalues: build the rule with ABZ_WANT_EIG");
     else if (integrand != ABZ_F_ONE)
@@ -1678,6 +1701,7 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
     rs.idx = r->idx;
     rs.k_offset = r->k_offset;
     rs.herm = r->herm;
+    rs.pivot = pivot;
     if (big_supported(rs.n) && r->herm && r->H.base && !r->H.compact && r->plan && (integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC)) {
         RulePlan* rp = static_cast<RulePlan*>(r->plan);
         const int64_t tnk = (r->nk + 63) / 64 * 64;
@@ -1730,9 +1754,16 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
     ABZ_REQUIRE(d >= 2 || (outer_begin == 0 && outer_end == npt), "a slab needs at least two variables");
     // n <= 4 without a closed-form store-free kernel for this case (a series that is not Hermitian, a short grid line): the
     // inverse of every node like the larger matrices (kernels_big.hip), for the integrands it serves
-    const bool inv_small = n <= 4 && !eval_sum_supported(n, s->dims[0], npt, integrand, s->hermitian) &&
-                           (integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC);
+    // ABZ_PIVOT_PARTIAL: that route for every series, 1...64 bands, with the row-pivoted kernel
+    const bool pivot = series_pivots(s, integrand);
+    const bool inv_small = pivot ? npt < 65536
+                                 : (n <= 4 && !eval_sum_supported(n, s->dims[0], npt, integrand, s->hermitian) &&
+                                    (integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC || integrand == ABZ_F_GLOC));
     const bool generic = n > 4 || inv_small;
+    if (pivot && !inv_small) {
+        set_error("ABZ_PIVOT_PARTIAL: store-free sums take grid lines of fewer than 65536 points (use a rule)");
+        return ABZ_ERR_UNSUPPORTED;
+    }
     if (!inv_small && !(generic ? gen_sum_supported(n, s->dims[0], npt, integrand, s->hermitian)
                                 : eval_sum_supported(n, s->dims[0], npt, integrand, s->hermitian))) {
         set_error("store-free sum not available for this series / grid / integrand (use a rule)");
@@ -1772,6 +1803,7 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
     ss.integrand = integrand;
     ss.herm = s->hermitian;
     ss.force_inverse = inv_small;
+    ss.pivot = pivot;
     ss.n_sweep = n_sweep;
     ss.sweep_host = sweep;
     ss.out.host = out_reim;
@@ -1867,7 +1899,8 @@ int abz_autoptr_solve_many(abz_series* s, const int32_t* syms, int nsyms, int in
     }
     // rules of a Hermitian series keep the upper triangle of H(k): every built-in integrand reads those planes only
     int want = integrand == ABZ_F_DOS_EIG ? ABZ_WANT_EIG : ABZ_WANT_H;
-    if ((want & ABZ_WANT_H) && s->hermitian) want |= ABZ_WANT_H_COMPACT;  // (ignored where no compact kernel exists)
+    // (ABZ_PIVOT_PARTIAL: the pivoted inverse takes whole matrices -- no reason to store half and expand it at every scan)
+    if ((want & ABZ_WANT_H) && s->hermitian && !series_pivots(s, integrand)) want |= ABZ_WANT_H_COMPACT;  // (ignored where no compact kernel exists)
     const size_t ncs = (size_t)ncomp;
     std::vector<double2> I1((size_t)n_sweep * ncs), I2((size_t)n_sweep * ncs), vals((size_t)n_sweep * ncs);
     std::vector<double> sw((size_t)n_sweep);

@@ -692,6 +692,7 @@ int IaiDriver::eval_nodes(int64_t nn) {
     ns.src = (d == 1) ? top_coef() : s->iai_pool[1].as<double2>();
     ns.packed = pk;
     ns.herm = s->hermitian;
+    ns.pivot = series_pivots(s, integrand);
     ns.parents = s->iai_io[0].as<int64_t>();
     ns.x = s->iai_io[1].as<double>();
     ns.tail = need_tail ? s->iai_io[2].as<double>() : nullptr;
@@ -1506,7 +1507,10 @@ static int iai_solve_lane(abz_series* s, int lims_kind, const double* lim_a, con
         // at every level
         const bool ok = s->n > 4 ? gen_inner_panel_supported(s->n, s->dims[0], integrand, s->hermitian)
                                  : inner_adaptive_supported(s->n, s->dims[0], integrand);
-        drv.device_inner = max_batch <= 0 && s->d >= 2 && ok && abz_switch(SW_IAI_DEVICE_INNER) != 0;
+        // ABZ_PIVOT_PARTIAL above 4 bands: the panel kernels eliminate without pivoting, so the innermost loops stay on the host
+        // and their node values come from the row-pivoted inverse (eval_nodes -> launch_big_nodes)
+        const bool host_pivot = series_pivots(s, integrand) && s->n > 4;
+        drv.device_inner = max_batch <= 0 && s->d >= 2 && ok && !host_pivot && abz_switch(SW_IAI_DEVICE_INNER) != 0;
     }
     {
         // ABZ_IAI_PACKED=0: the full coefficient rows (per call: tests compare both)

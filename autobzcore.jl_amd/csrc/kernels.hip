@@ -2087,6 +2087,10 @@ static constexpr int reduce_kt(int n) {
 }
 
 int launch_reduce(abz_ctx* ctx, const ReduceSpec& rs) {
+    // ABZ_PIVOT_PARTIAL: the row-pivoted inverse of every node (kernels_big.hip, 1...64 bands) instead of the tridiagonal, closed-
+    // form and row-kernel routes; up to 4 bands a series that is not Hermitian stays here (cinv pivots, n = 2, 3 traces: p'/p of
+    // the characteristic polynomial -- no elimination)
+    if (rs.pivot && (rs.n > 4 || rs.herm)) return launch_big_reduce(ctx, rs);
     if (rs.n > 4) return launch_gen_reduce(ctx, rs);
     const int ncomp = integrand_ncomp(rs.integrand, rs.n, rs.d);
     if (ncomp < 0) {
@@ -2306,6 +2310,7 @@ int launch_node_integrand(abz_ctx* ctx, const NodeEvalSpec& ns, double2* values_
         gs.deriv = false;
         gs.panels15 = ns.panels15;
         gs.herm = ns.herm;
+        gs.pivot = ns.pivot;
         gs.nnodes = ns.nnodes;
         gs.Hplanes = PlaneView();
         gs.Eplanes = PlaneView();

@@ -246,6 +246,24 @@ __global__ __launch_bounds__(256) void big_load_h_kernel(double2* __restrict__ H
         Hbuf[node * nn + e] = make_double2(hi[(int64_t)(2 * e) * H.pitch], hi[(int64_t)(2 * e + 1) * H.pitch]);
     }
 }
+// the same from upper-triangle planes (ABZ_WANT_H_COMPACT: entry (a, b), a <= b, at planes b b + 2 a + {0, 1}), expanded to the
+// full matrix: what the row-pivoted inverse of a Hermitian rule reads (ABZ_PIVOT_PARTIAL)
+__global__ __launch_bounds__(256) void big_load_h_compact_kernel(double2* __restrict__ Hbuf, int64_t node0, int64_t nnodes, int n, PlaneView H) {
+    const int nn = n * n;
+    const int64_t total = (nnodes + 63) / 64 * 64 * nn;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+        const int64_t grp = t / (64 * nn);
+        const int64_t rem = t - grp * (64 * nn);
+        const int e = (int)(rem / 64);
+        const int64_t node = grp * 64 + (rem & 63);
+        if (node >= nnodes) continue;
+        const double* hi = H.base + bview_off(H, node0 + node);
+        const int ea = e % n, eb = e / n, lo = min(ea, eb), up = max(ea, eb);
+        const double re = hi[(int64_t)(up * up + 2 * lo) * H.pitch];
+        const double im = ea == eb ? 0.0 : hi[(int64_t)(up * up + 2 * lo + 1) * H.pitch];
+        Hbuf[node * nn + e] = make_double2(re, ea > eb ? -im : im);
+    }
+}
 
 // Householder tridiagonalisation of Hermitian(h) (the upper triangle of each n x n block of Hbuf, like the reference's
 // Hermitian wrapper): d_j -> tri[j][t], |e_j|^2 -> tri[BIG_NP + j][t], t = t0 + node.  One wave per node; lane i owns row i of
@@ -698,7 +716,8 @@ __global__ __launch_bounds__(256) void big_accumulate_kernel(double2* __restrict
 
 // inv((w + i eta) I - H) of a node, ONE WORKGROUP OF FOUR WAVES PER NODE (two nodes up to 32 bands), the matrix in registers,
 // Gauss-Jordan in place without pivoting (what the <= 32-band kernels do: for Hermitian H the matrix is eta I plus a skew-
-// Hermitian part times i -- no small pivots; a general H gets no more here than there); big_inv_pivot4 below has the step.
+// Hermitian part times i -- no small pivots) or, for a series in mode ABZ_PIVOT_PARTIAL, with partial pivoting by rows (the
+// PIV instantiations: any H); big_inv_pivot4 below has the step.
 // Serves what the tridiagonal cannot: matrix-valued G (ABZ_F_GLOC) and the traces of series that are not Hermitian.  Node mode:
 // values[node][swept value][component]; sum mode: every workgroup adds the weighted values of its nodes (registers) and leaves
 // partial[block][swept value][component] for launch_final_reduce.
@@ -719,8 +738,16 @@ struct BigInvArgs {
 // f = A(r, c) of every row -- lives in wave c & 3 and reaches the other waves through LDS (two rooms in turn, one barrier per
 // pivot); row c -- A(c, j) of this wave's sixteen columns -- lives in lane c of THIS wave: v_readlane, scalar operands of the FMAs
 // (SUBS = 2, 4, 8: that many nodes of <= 32, 16, 8 bands side by side in every wave: lane c of the lane's own part, a shuffle).
-template <int NQ, int CQ, int SUBS>
-__device__ __forceinline__ void big_inv_pivot4(int n, int lane, int r, int jq, double2 (*colb)[64], double2 (&W)[NQ]) {
+// PIV (ABZ_PIVOT_PARTIAL): partial pivoting by rows, IMPLICIT -- the rows stay in their lanes.  Column c is in colb for every wave
+// anyway, so every wave finds the pivot row by itself: the row of the node not used yet with the largest |f|^2, a shuffle
+// reduction over the node's 64 / SUBS lanes of one 64-bit key (the magnitude's bits with the row in the low six, so that equal
+// magnitudes go to the lowest row and every wave finds the same one) -- no barrier more.  The pivot row is then read from lane
+// `pl` instead of lane c (SUBS = 1: still a v_readlane, the lane in a scalar register).  `step` is the pivot at which this lane's
+// row was used, pcol[q] the row used at pivot jq + 4 q: after the last pivot lane l holds row step(l) of the inverse and its entry
+// q the column pcol[q] (big_inverse_kernel undoes both where it stores or sums).  A NaN or Inf magnitude counts as the largest, a
+// used or padding row as none, so the rows used are a permutation of 0 ... n - 1 whatever the numbers are.
+template <int NQ, int CQ, int SUBS, bool PIV>
+__device__ __forceinline__ void big_inv_pivot4(int n, int lane, int r, int jq, double2 (*colb)[64], double2 (&W)[NQ], int (&pcol)[NQ], int& step) {
     constexpr int LW = 64 / SUBS;
 #pragma unroll 1
     for (int cm = 0; cm < 4; ++cm) {
@@ -729,11 +756,29 @@ __device__ __forceinline__ void big_inv_pivot4(int n, int lane, int r, int jq, d
         const int pb = c & 1;
         if (jq == cm) colb[pb][lane] = W[CQ];
         __syncthreads();
-        const int lc = (lane & ~(LW - 1)) + c;  // the lane that holds row c of this lane's node
-        const double2 p = colb[pb][lc], f = colb[pb][lane];
+        int lc = (lane & ~(LW - 1)) + c;  // the lane that holds row c of this lane's node
+        const double2 f = colb[pb][lane];
+        if constexpr (PIV) {
+            double m = f.x * f.x + f.y * f.y;
+            if (!(m <= 1.7976931348623157e308)) m = __longlong_as_double(0x7ff0000000000000ll);
+            unsigned long long key = (step < 0 && r < n) ? (((unsigned long long)__double_as_longlong(m) & ~127ull) | 64ull | (unsigned long long)(63 - r)) : 0ull;
+#pragma unroll
+            for (int off = LW / 2; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_xor(key, off, 64);
+                key = o > key ? o : key;
+            }
+            const int prw = 63 - (int)(key & 63ull);  // the pivot's row (c < n: at least one row is left, so the key is one of a row)
+            if constexpr (SUBS == 1)
+                lc = __builtin_amdgcn_readfirstlane(prw);
+            else
+                lc = (lane & ~(LW - 1)) + prw;
+            if (jq == cm) pcol[CQ] = prw;
+        }
+        const double2 p = colb[pb][lc];
         const double ipn = 1.0 / (p.x * p.x + p.y * p.y);
         const double ipr = p.x * ipn, ipi = -p.y * ipn;  // 1 / pivot
-        const bool prow = r == c;
+        const bool prow = PIV ? lane == lc : r == c;
+        if (PIV && prow) step = c;
         const double qr = f.x * ipr - f.y * ipi, qi = f.x * ipi + f.y * ipr;  // f / pivot
         // one straight line for every entry: A(r, j) - (f / p) A(c, j); in the pivot row itself 0 + (1 / p) A(c, j)
         const double fr = prow ? -ipr : qr, fi = prow ? -ipi : qi;
@@ -741,8 +786,8 @@ __device__ __forceinline__ void big_inv_pivot4(int n, int lane, int r, int jq, d
         for (int q = 0; q < NQ; ++q) {
             double gx, gy;  // A(c, jq + 4 q) before the step
             if constexpr (SUBS == 1) {
-                gx = brl(W[q].x, c);
-                gy = brl(W[q].y, c);
+                gx = brl(W[q].x, PIV ? lc : c);
+                gy = brl(W[q].y, PIV ? lc : c);
             } else {
                 gx = __shfl(W[q].x, lc, 64);
                 gy = __shfl(W[q].y, lc, 64);
@@ -753,20 +798,26 @@ __device__ __forceinline__ void big_inv_pivot4(int n, int lane, int r, int jq, d
         if (jq == cm) W[CQ] = prow ? make_double2(ipr, ipi) : make_double2(-qr, -qi);  // the pivot column: -f / p, the pivot 1 / p
     }
 }
-template <int NQ, int SUBS, int... CQ>
-__device__ __forceinline__ void big_inv_pivots(int n, int lane, int r, int jq, double2 (*colb)[64], double2 (&W)[NQ],
+template <int NQ, int SUBS, bool PIV, int... CQ>
+__device__ __forceinline__ void big_inv_pivots(int n, int lane, int r, int jq, double2 (*colb)[64], double2 (&W)[NQ], int (&pcol)[NQ], int& step,
                                                std::integer_sequence<int, CQ...>) {
-    ((void)((4 * CQ < n) ? (big_inv_pivot4<NQ, CQ, SUBS>(n, lane, r, jq, colb, W), 0) : 0), ...);
+    ((void)((4 * CQ < n) ? (big_inv_pivot4<NQ, CQ, SUBS, PIV>(n, lane, r, jq, colb, W, pcol, step), 0) : 0), ...);
 }
 
 // NQ: column groups of four the instance holds (n <= 4 NQ); SUBS: nodes side by side in a wave (2: n <= 32, rows in 32 lanes)
-template <int NQ, int SUBS>
+// PIV: the rows pivot (big_inv_pivot4), and lane l ends with row step(l) of the inverse, its entry q being column pcol[q].  The
+// traces pick their diagonal entries through that, node values of G are stored at their permuted addresses, and the sums of G --
+// over nodes whose permutations differ -- are kept in LDS instead of registers: gsum[sub][n n], one room per node of a wave, every
+// entry of a node added by exactly one thread, the nodes of a workgroup one after the other (the barriers of the next node's
+// pivots lie between two additions to an address): the same bits on every run.  n n SUBS complex numbers, 64 KB at 64 bands.
+template <int NQ, int SUBS, bool PIV>
 __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
     // The matrix lives in REGISTERS: lane r of wave jq holds the entries (r, jq + 4 q), q < NQ (big_inv_pivot4 above).
     static_assert(4 * NQ <= 64 / SUBS, "SUBS nodes per wave: 64 / SUBS lanes of rows each");
     constexpr int LW = 64 / SUBS;
     __shared__ double2 colb[2][64];
     __shared__ double2 trb[4][8];
+    extern __shared__ double2 lds_gsum[];  // PIV, sums of G: [SUBS][n n]
     const int n = a.n, nn = n * n, tid = threadIdx.x;
     const int lane = tid & 63, r = lane & (LW - 1), sub = lane / LW, jq = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool rowon = r < n;
@@ -775,6 +826,10 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
     const int64_t k0 = sum ? (int64_t)blockIdx.x * a.nodes_per_block : blockIdx.x;
     const int64_t k1 = sum ? min(a.nnodes, k0 + a.nodes_per_block) : a.nnodes;
     const int64_t kstep = sum ? 1 : gridDim.x;
+    if constexpr (PIV) {
+        if (sum && a.kind == 0)
+            for (int e = tid; e < SUBS * nn; e += 256) lds_gsum[e] = make_double2(0.0, 0.0);  // (a pivot's barrier comes before the first sum)
+    }
     for (int s = 0; s < a.n_sweep; ++s) {
         double2 acc[NQ];  // sum mode: the weighted sum of this thread's entries, or the trace in acc[0] of the node's first lane
 #pragma unroll
@@ -798,11 +853,25 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
                 }
             }
             // pivots c = 4 cq + cm: cq unrolled (the entry of column c in its wave's registers is W[cq], a static index), cm rolled
-            big_inv_pivots<NQ, SUBS>(n, lane, r, jq, colb, W, std::make_integer_sequence<int, NQ>());
+            int pcol[NQ], step = -1;  // PIV: the row used at pivot jq + 4 q; the pivot this lane's row was used at
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) pcol[q] = 0;
+            big_inv_pivots<NQ, SUBS, PIV>(n, lane, r, jq, colb, W, pcol, step, std::make_integer_sequence<int, NQ>());
             const double wk = (sum && valid) ? (a.w ? a.w[a.node0 + k] : 1.0) : (valid ? 1.0 : 0.0);
             if (a.kind == 0) {
                 if (sum) {
-                    if (valid) {  // (lanes without a node keep their sums: nothing is multiplied by a zero weight)
+                    if constexpr (PIV) {
+                        if (valid && rowon) {  // entry (step, pcol[q]) of this node's inverse: this thread alone adds to it
+                            double2* __restrict__ go = lds_gsum + sub * nn + step;
+#pragma unroll
+                            for (int q = 0; q < NQ; ++q) {
+                                if (jq + 4 * q < n) {
+                                    const double2 g = go[n * pcol[q]];
+                                    go[n * pcol[q]] = make_double2(fma(wk, W[q].x, g.x), fma(wk, W[q].y, g.y));
+                                }
+                            }
+                        }
+                    } else if (valid) {  // (lanes without a node keep their sums: nothing is multiplied by a zero weight)
 #pragma unroll
                         for (int q = 0; q < NQ; ++q) {
                             acc[q].x = fma(wk, W[q].x, acc[q].x);
@@ -814,15 +883,23 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) {
                         const int j = jq + 4 * q;
-                        if (j < n) vo[r + n * j] = W[q];
+                        if constexpr (PIV) {
+                            if (j < n) vo[step + n * pcol[q]] = W[q];
+                        } else {
+                            if (j < n) vo[r + n * j] = W[q];
+                        }
                     }
                 }
             } else {
                 // the diagonal entry (r, r) sits in wave r & 3 at q = r >> 2: partial traces per wave and node, met in LDS
+                // (PIV: lane l holds row step(l), its entry j column pcol(j) = the row used at pivot j: the diagonal entry is the one
+                // with pcol(j) = step(l), and pcol(j) = l' means step(l') = j, so j = step(step(l)))
+                int dcol = r;
+                if constexpr (PIV) dcol = __shfl(step, (lane & ~(LW - 1)) + max(step, 0), 64);
                 double tr = 0.0, ti = 0.0;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
-                    const bool d = rowon && (jq + 4 * q) == r;
+                    const bool d = rowon && (jq + 4 * q) == dcol;
                     tr += d ? W[q].x : 0.0;
                     ti += d ? W[q].y : 0.0;
                 }
@@ -863,12 +940,28 @@ __global__ __launch_bounds__(256) void big_inverse_kernel(BigInvArgs a) {
                 }
             }
             if (a.kind == 0) {
+                if constexpr (PIV) {
+                    __syncthreads();  // the last node's additions
+                    for (int e = tid; e < nn; e += 256) {
+                        double2 g = lds_gsum[e];
+                        lds_gsum[e] = make_double2(0.0, 0.0);  // (for the next swept value: a pivot's barrier comes before its first sum)
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const int j = jq + 4 * q;
-                    if (rowon && sub == 0 && j < n) {
-                        po[r + n * j].x += acc[q].x;
-                        po[r + n * j].y += acc[q].y;
+                        for (int u = 1; u < SUBS; ++u) {
+                            g.x += lds_gsum[u * nn + e].x;
+                            g.y += lds_gsum[u * nn + e].y;
+                            lds_gsum[u * nn + e] = make_double2(0.0, 0.0);
+                        }
+                        po[e].x += g.x;
+                        po[e].y += g.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const int j = jq + 4 * q;
+                        if (rowon && sub == 0 && j < n) {
+                            po[r + n * j].x += acc[q].x;
+                            po[r + n * j].y += acc[q].y;
+                        }
                     }
                 }
             } else if (tid == 0) {
@@ -927,37 +1020,36 @@ int big_tridiag(abz_ctx* ctx, const BigWork& w, int n, int64_t cn, double2* keep
     return ABZ_OK;
 }
 
-static int big_inverse(abz_ctx* ctx, BigInvArgs& ia, int64_t blocks) {
+template <int NQ, int SUBS>
+static int big_inverse_launch(abz_ctx* ctx, const BigInvArgs& ia, int64_t blocks, bool pivot) {
+    if (pivot) {
+        // sums of G: the workgroup's sums in LDS (big_inverse_kernel), <= 64 KB beside the 2.5 KB of the columns and traces
+        const size_t lds = (ia.partial && ia.kind == 0) ? sizeof(double2) * (size_t)SUBS * ia.n * ia.n : 0;
+        if (lds > 0) ABZ_HIP(hipFuncSetAttribute((const void*)big_inverse_kernel<NQ, SUBS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        launch(ctx, (big_inverse_kernel<NQ, SUBS, true>), dim3((unsigned)blocks), dim3(256), (unsigned)lds, ia);
+    } else {
+        launch(ctx, (big_inverse_kernel<NQ, SUBS, false>), dim3((unsigned)blocks), dim3(256), 0, ia);
+    }
+    ABZ_HIP(hipGetLastError());
+    return ABZ_OK;
+}
+static int big_inverse(abz_ctx* ctx, BigInvArgs& ia, int64_t blocks, bool pivot) {
     if (ia.n <= 32 && !ia.partial) {  // (several nodes per workgroup pass)
         const int subs = ia.n <= 8 ? 8 : (ia.n <= 16 ? 4 : 2);
         blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (ia.nnodes + subs - 1) / subs));
     }
-    if (ia.n <= 4)
-        launch(ctx, (big_inverse_kernel<1, 8>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 8)
-        launch(ctx, (big_inverse_kernel<2, 8>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 12)
-        launch(ctx, (big_inverse_kernel<3, 4>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 16)
-        launch(ctx, (big_inverse_kernel<4, 4>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 20)
-        launch(ctx, (big_inverse_kernel<5, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 24)
-        launch(ctx, (big_inverse_kernel<6, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 28)
-        launch(ctx, (big_inverse_kernel<7, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 32)
-        launch(ctx, (big_inverse_kernel<8, 2>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 40)
-        launch(ctx, (big_inverse_kernel<10, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 48)
-        launch(ctx, (big_inverse_kernel<12, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else if (ia.n <= 56)
-        launch(ctx, (big_inverse_kernel<14, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    else
-        launch(ctx, (big_inverse_kernel<16, 1>), dim3((unsigned)blocks), dim3(256), 0, ia);
-    ABZ_HIP(hipGetLastError());
-    return ABZ_OK;
+    if (ia.n <= 4) return big_inverse_launch<1, 8>(ctx, ia, blocks, pivot);
+    if (ia.n <= 8) return big_inverse_launch<2, 8>(ctx, ia, blocks, pivot);
+    if (ia.n <= 12) return big_inverse_launch<3, 4>(ctx, ia, blocks, pivot);
+    if (ia.n <= 16) return big_inverse_launch<4, 4>(ctx, ia, blocks, pivot);
+    if (ia.n <= 20) return big_inverse_launch<5, 2>(ctx, ia, blocks, pivot);
+    if (ia.n <= 24) return big_inverse_launch<6, 2>(ctx, ia, blocks, pivot);
+    if (ia.n <= 28) return big_inverse_launch<7, 2>(ctx, ia, blocks, pivot);
+    if (ia.n <= 32) return big_inverse_launch<8, 2>(ctx, ia, blocks, pivot);
+    if (ia.n <= 40) return big_inverse_launch<10, 1>(ctx, ia, blocks, pivot);
+    if (ia.n <= 48) return big_inverse_launch<12, 1>(ctx, ia, blocks, pivot);
+    if (ia.n <= 56) return big_inverse_launch<14, 1>(ctx, ia, blocks, pivot);
+    return big_inverse_launch<16, 1>(ctx, ia, blocks, pivot);
 }
 static int big_inv_kind(int integrand) { return integrand == ABZ_F_GLOC ? 0 : (integrand == ABZ_F_TRGLOC ? 1 : (integrand == ABZ_F_DOS ? 2 : -1)); }
 
@@ -1074,7 +1166,7 @@ int launch_big_nodes(abz_ctx* ctx, const GenSpec& gs) {
     }
     // values: the traces of a Hermitian series come from the tridiagonal; matrix-valued G and series that are not Hermitian
     // from the inverse (eigenvalues are those of Hermitian(h), the upper triangle, whatever the series)
-    const bool inv_values = gs.values && (gs.integrand == ABZ_F_GLOC || !gs.herm);
+    const bool inv_values = gs.values && (gs.integrand == ABZ_F_GLOC || !gs.herm || gs.pivot);
     BigWork w;
     int rc = big_reserve(ctx, gs.n, gs.grid ? gs.npt : 0, gs.nnodes, w);
     if (rc) return rc;
@@ -1116,7 +1208,7 @@ int launch_big_nodes(abz_ctx* ctx, const GenSpec& gs) {
             ia.values = gs.values;
             ia.partial = nullptr;
             ia.nodes_per_block = 0;
-            if ((rc = big_inverse(ctx, ia, std::min<int64_t>(cn, 256 * 8)))) return rc;
+            if ((rc = big_inverse(ctx, ia, std::min<int64_t>(cn, 256 * 8), gs.pivot))) return rc;
         }
         if (!(gs.Eplanes.base || gs.Eaos || (gs.values && !inv_values))) continue;
         if ((rc = big_tridiag(ctx, w, gs.n, cn))) return rc;
@@ -1214,10 +1306,15 @@ struct BigJob {
     const double* weights;  // device [nnodes], null: 1
     int prof_id;
     const SumOut* out;
+    bool pivot = false;  // ABZ_PIVOT_PARTIAL: the inverses pivot by rows
 };
 
 static int big_load_h(abz_ctx* ctx, const BigWork& w, int n, PlaneView H, int64_t c0, int64_t cn) {
-    launch(ctx, big_load_h_kernel, dim3((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * n * n, 256), 256 * 16)), dim3(256), 0, w.Hbuf, c0, cn, n, H);
+    const dim3 grid((unsigned)std::min<int64_t>(cdivb((cn + 63) / 64 * 64 * n * n, 256), 256 * 16));
+    if (H.compact)
+        launch(ctx, big_load_h_compact_kernel, grid, dim3(256), 0, w.Hbuf, c0, cn, n, H);
+    else
+        launch(ctx, big_load_h_kernel, grid, dim3(256), 0, w.Hbuf, c0, cn, n, H);
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
@@ -1267,7 +1364,7 @@ static int big_inverse_groups(abz_ctx* ctx, const BigWork& w, const BigJob& j, b
             ia.values = nullptr;
             ia.partial = partial;
             ia.nodes_per_block = (int)cdivb(cn, blocks);
-            if ((rc = big_inverse(ctx, ia, cdivb(cn, ia.nodes_per_block)))) return rc;
+            if ((rc = big_inverse(ctx, ia, cdivb(cn, ia.nodes_per_block), j.pivot))) return rc;
         }
         if ((rc = launch_final_reduce(ctx, partial, blocks, ncols, j.scale, outd))) return rc;
         one.reset();
@@ -1297,7 +1394,7 @@ static int big_tridiag_chunks(abz_ctx* ctx, const BigWork& w, const BigJob& j, F
 
 // store-free PTR sums (abz_ptr_sum)
 int launch_big_sum(abz_ctx* ctx, const SumSpec& ss) {
-    BigJob j{ss.n, ss.integrand, ss.n_sweep, ss.nlines * ss.npt, ss.params[0], ss.scale, nullptr, nullptr, ABZ_K_EVAL, &ss.out};
+    BigJob j{ss.n, ss.integrand, ss.n_sweep, ss.nlines * ss.npt, ss.params[0], ss.scale, nullptr, nullptr, ABZ_K_EVAL, &ss.out, ss.pivot};
     BigWork w;
     int rc = big_reserve(ctx, ss.n, ss.npt, j.nnodes, w);
     if (rc) return rc;
@@ -1325,16 +1422,16 @@ int launch_big_sum(abz_ctx* ctx, const SumSpec& ss) {
 // scans of a cached rule: DOS / tr G from the matrices (tridiagonalised chunk by chunk); the eigenvalue form goes through
 // gen_eig_dos_kernel (kernels_generic.hip), which is generic in n
 int launch_big_reduce(abz_ctx* ctx, const ReduceSpec& rs) {
-    if (big_inv_kind(rs.integrand) < 0 || !rs.H.base || rs.H.compact) {
+    if (big_inv_kind(rs.integrand) < 0 || !rs.H.base || (rs.H.compact && !rs.pivot)) {
         set_error("n = %d bands: scans of a cached rule offer G, tr G and DOS from the matrices (full layout) and DOS from eigenvalues", rs.n);
         return ABZ_ERR_UNSUPPORTED;
     }
-    const BigJob j{rs.n, rs.integrand, rs.n_sweep, rs.nk, rs.params[0], rs.scale, rs.sweep_dev, rs.w, ABZ_K_REDUCE, &rs.out};
+    const BigJob j{rs.n, rs.integrand, rs.n_sweep, rs.nk, rs.params[0], rs.scale, rs.sweep_dev, rs.w, ABZ_K_REDUCE, &rs.out, rs.pivot};
     BigWork w;
     int rc = big_reserve(ctx, rs.n, 0, rs.nk, w);
     if (rc) return rc;
     auto fill = [&](int64_t c0, int64_t cn) { return big_load_h(ctx, w, rs.n, rs.H, c0, cn); };
-    if (rs.integrand == ABZ_F_GLOC || !rs.herm) return big_inverse_groups(ctx, w, j, true, fill);
+    if (rs.integrand == ABZ_F_GLOC || !rs.herm || rs.pivot) return big_inverse_groups(ctx, w, j, true, fill);
     if (!(rs.tri_cache && rs.tri_state)) return big_tridiag_chunks(ctx, w, j, fill);
     // the rule keeps the tridiagonal forms of its nodes: tridiagonalise once per fill of the rule, then every scan is the p'/p pass
     double2* total = nullptr;

@@ -15,8 +15,13 @@
 // place of eta.  For a Hermitian H at eta = 0 a gap around omega makes A invertible but not every
 // leading block of it: the elimination is safe where those blocks are definite, as for the
 // diagonally dominant diag(+D, -D) + hopping that is tested, and may meet a zero pivot otherwise
-// (H = [[0, 1], [1, 0]] at omega = 0).  Nothing is claimed for a general H that is not Hermitian
-// and not dissipative.  tests/test_gpu_resolvent_edges.py pins the two cases and the bound.
+// (H = [[0, 1], [1, 0]] at omega = 0); nothing is claimed here for a general H that is not
+// Hermitian and not dissipative.  tests/test_gpu_resolvent_edges.py pins the two cases and the bound.
+// Those inputs are served by ABZ_PIVOT_PARTIAL (abz_series_set_pivoting): scans, sums and node
+// values of such a series never reach the kernels of this file -- launch_reduce, abz_ptr_sum and
+// launch_gen_nodes send them to the row-pivoted big_inverse_kernel (kernels_big.hip;
+// tests/test_gpu_pivot.py).  Not pivoted in any mode: the wave_inverse of gen_node_kernel (not
+// reached in that mode) and the IAI panel kernels (that mode keeps IAI's inner loops on the host).
 #include <utility>
 
 #include "abz_internal.h"
@@ -1912,6 +1917,7 @@ static int gen_waves_per_block(int n, int M) {
 int launch_gen_nodes(abz_ctx* ctx, const GenSpec& gs) {
     if (gs.nnodes == 0) return ABZ_OK;
     if (big_supported(gs.n)) return launch_big_nodes(ctx, gs);  // 33...64 bands: kernels_big.hip
+    if (gs.pivot && gs.values && gs.n > 4) return launch_big_nodes(ctx, gs);  // ABZ_PIVOT_PARTIAL: the row-pivoted inverse
     // arbitrary nodes (abz_eval_nodes) with eigenvalues, 9...32 bands: Householder + QR through the kernels of kernels_big.hip (generic in
     // n) instead of the wave-per-node Jacobi below (4 096 nodes of 32 bands: 18 ms of kernels; a rule build of 13 824 nodes 0.8 ms)
     if (!gs.grid && gs.x && !gs.values && (gs.Eplanes.base || gs.Eaos) && !gs.Uplanes.base && !gs.deriv && !gs.Hplanes.compact && gs.n > 4)

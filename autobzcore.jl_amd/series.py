@@ -61,12 +61,16 @@ class FourierSeries:
         for dev in self._dev.values():
             dev.update()
 
-    def device(self, ctx=None):
+    def device(self, ctx=None, pivoting=None):
+        """The series' copy on the device of `ctx`.  pivoting "none" / "partial": set that mode on it
+        (DeviceSeries.set_pivoting); None leaves the copy's mode alone."""
         ctx = ctx or L.Context.default()
         dev = self._dev.get(id(ctx))
         if dev is None:
             dev = DeviceSeries(self, ctx)
             self._dev[id(ctx)] = dev
+        if pivoting is not None:
+            dev.set_pivoting(pivoting)
         return dev
 
     def __call__(self, x):
@@ -80,6 +84,9 @@ def julia_coefficient_order(c, d):
     (block column-major, i_1 fastest ... i_d slowest)."""
     axes = tuple(range(d - 1, -1, -1)) + (d + 1, d)
     return np.ascontiguousarray(np.transpose(c, axes)).reshape(-1)
+
+
+PIVOTING_MODES = {"none": L.PIVOT_NONE, "partial": L.PIVOT_PARTIAL}
 
 
 class DeviceSeries:
@@ -157,6 +164,20 @@ class DeviceSeries:
         if any(r.want & L.WANT_H_COMPACT for r in self.rules.values()) and not self.hermitian():
             self.drop_rules()  # upper-triangle rules cannot hold the values of a series that stopped being Hermitian
 
+    # ---- how the resolvent integrands invert (abz_series_set_pivoting)
+    def set_pivoting(self, mode):
+        """"none": the default routes.  "partial": every inverse of (omega + i eta) I - H(k) taken for this copy of the
+        series -- rule scans, store-free sums, AutoPTR and IAI solves -- pivots by rows, as LAPACK's does.  Rules built
+        before the call follow it too; update() keeps it."""
+        if mode not in PIVOTING_MODES:
+            raise ValueError(f"pivoting must be one of {sorted(PIVOTING_MODES)}, not {mode!r}")
+        L.check(L.lib().abz_series_set_pivoting(self.h, PIVOTING_MODES[mode]))
+
+    def pivoting(self):
+        m = C.c_int(0)
+        L.check(L.lib().abz_series_get_pivoting(self.h, C.byref(m)))
+        return {v: k for k, v in PIVOTING_MODES.items()}[m.value]
+
     # ---- arbitrary nodes (BatchIntegrand body / fallback evaluator)
     def eval_nodes(self, k, want=L.WANT_H):
         k = np.ascontiguousarray(np.asarray(k, dtype=np.float64).reshape(-1, self.s.d))
@@ -227,6 +248,8 @@ class DeviceSeries:
 
     def ptr_sum_supported(self, npt, fid):
         s = self.s
+        if fid in (L.F_DOS, L.F_TRGLOC, L.F_GLOC) and self.pivoting() == "partial":
+            return npt < 65536  # the pivoted inverse of every node, 1...64 bands
         if s.n > 4:  # generic-n kernels: resolvent traces of Hermitian series from the tridiagonal form; G, and series that are not Hermitian, from the inverse of every node
             if fid in (L.F_DOS, L.F_TRGLOC) and self.hermitian():
                 return True

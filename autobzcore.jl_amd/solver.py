@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib as L
 from .bz import (Basis, CubicLimits, HyperCube, PolygonLimits, PolyhedralLimits, PuncturedInterval, SymmetricBZ,
                  TetrahedralLimits, nsyms)
-from .series import FourierSeries
+from .series import PIVOTING_MODES, FourierSeries
 
 
 # ---------------------------------------------------------------------------- parameters
@@ -225,6 +225,20 @@ class DeviceIntegrand:
         raise NotImplementedError
 
 
+def _check_pivoting(pivoting):
+    if pivoting is not None and pivoting not in PIVOTING_MODES:
+        raise ValueError(f"pivoting must be None or one of {sorted(PIVOTING_MODES)}, not {pivoting!r}")
+    return pivoting
+
+
+def _apply_pivoting(fi, dev):
+    """The integrand's `pivoting` keyword, if it was given, becomes the mode of the series' device copy (the mode is a
+    property of the series in the library, read when the solve launches)."""
+    mode = getattr(fi, "pivoting", None)
+    if mode is not None:
+        dev.set_pivoting(mode)
+
+
 class UnitIntegrand(DeviceIntegrand):
     """(x, p) -> 1.  ref: test/brillouin.jl:38."""
     fid = L.F_ONE
@@ -259,10 +273,12 @@ class DOSIntegrand(DeviceIntegrand):
     argnames = ("eta", "omega")
     swept = True
 
-    def __init__(self, form="inv"):
+    def __init__(self, form="inv", pivoting=None):
+        """pivoting="partial": the device inverts with partial pivoting by rows (DeviceSeries.set_pivoting; form "inv")."""
         if form not in ("inv", "eig"):
             raise ValueError("form must be 'inv' or 'eig'")
         self.form = form
+        self.pivoting = _check_pivoting(pivoting)
         self.fid = L.F_DOS if form == "inv" else L.F_DOS_EIG
 
     def host(self, v, eta, omega):
@@ -276,6 +292,10 @@ class TrGlocIntegrand(DeviceIntegrand):
     argnames = ("eta", "omega")
     swept = True
 
+    def __init__(self, pivoting=None):
+        """pivoting="partial": the device inverts with partial pivoting by rows (DeviceSeries.set_pivoting)."""
+        self.pivoting = _check_pivoting(pivoting)
+
     def host(self, v, eta, omega):
         h = np.atleast_2d(v.s)
         return np.trace(np.linalg.inv(complex(omega, eta) * np.eye(len(h)) - h))
@@ -287,6 +307,10 @@ class GlocIntegrand(DeviceIntegrand):
     argnames = ("eta", "omega")
     swept = True
     matrix = True
+
+    def __init__(self, pivoting=None):
+        """pivoting="partial": the device inverts with partial pivoting by rows (DeviceSeries.set_pivoting)."""
+        self.pivoting = _check_pivoting(pivoting)
 
     def host(self, v, eta, omega):
         h = np.atleast_2d(v.s)
@@ -821,6 +845,7 @@ def do_solve(f, dom, p, alg, cacheval=None, abstol=None, reltol=None, maxiters=2
     dev = cacheval if cacheval is not None else f.w.device()
     pm = _as_params(f, p)
     fi = f.f.f
+    _apply_pivoting(fi, dev)
     isdev = isinstance(fi, DeviceIntegrand)
 
     # ---- BZ algorithms: rescale like do_solve_autobz
@@ -1110,6 +1135,7 @@ def batchsolve(solver: IntegralSolver, ps, nthreads=1, callback=None):
         base = solver.p0 if isinstance(solver.p0, MixedParameters) else MixedParameters()
         plist = [f.f.p.merge(base.merge(_to_params(arr[i]))) for i in flat_idx]
         dev = f.w.device()
+        _apply_pivoting(f.f.f, dev)
         bz = solver.dom
         abstol, reltol = solver.kwargs.get("abstol"), solver.kwargs.get("reltol")
         maxiters = solver.kwargs.get("maxiters", 2**62)

@@ -139,6 +139,27 @@ int abz_series_destroy(abz_series* s);
 /* Replace the coefficients in place (same shape).  Replaces: mutating `h.c` / assigning cache.H
  * (test/dos.jl:122-129); rules built from the series become stale until abz_rule_rebuild. */
 int abz_series_update(abz_series* s, const double* coef_reim);
+/* How the device inverts (omega + i eta) I - H(k) for this series' resolvent integrands (ABZ_F_DOS, ABZ_F_TRGLOC, ABZ_F_GLOC).
+ * ABZ_PIVOT_NONE, the default: the fastest route for the series, band count and integrand (closed forms, p'/p of the
+ * tridiagonal form, Gauss-Jordan without pivoting); what that covers is written at abz_rule_reduce.
+ * ABZ_PIVOT_PARTIAL: every such value comes from a Gauss-Jordan inverse with partial pivoting by rows, the choice LAPACK's
+ * `inv` makes (at each step the row left with the largest |entry|^2 in the pivot column; entries below 1e-154 in magnitude
+ * count as zero for the choice): accurate wherever cond(z I - H(k)) is modest, Hermitian or not, at any eta.  A column that
+ * is exactly zero gives Inf / NaN where LAPACK would raise a singular-matrix error.  Hermitian series give up their
+ * tridiagonal and closed-form routes in this mode, and every series is inverted node by node: the cost is tabulated in
+ * DESIGN.md section 9.  Results are the same bits on every repeat of a call.
+ * The mode belongs to the series and is read when a scan, sum or solve is launched: it holds for abz_rule_reduce(_device),
+ * abz_ptr_sum, abz_autoptr_solve(_many) and abz_iai_solve(_many) / abz_eval_line_nodes, for rules built before or after the
+ * call (their H(k) do not depend on it), and survives abz_series_update.  A scan in this mode needs the matrices: a rule
+ * without ABZ_WANT_H answers ABZ_ERR_UNSUPPORTED; ABZ_WANT_H_COMPACT rules are expanded as they are read.  Up to 4 bands the
+ * scans of a series that is not Hermitian are the default's (they pivot already, or use p'/p of the characteristic polynomial
+ * for the traces of 2 and 3 bands).  abz_iai_solve* above 4 bands keeps the innermost adaptive loops on the host in this mode
+ * (the device panel kernels do not pivot) and is slower for it.  Other integrands, ABZ_F_DOS_EIG among them, are untouched.
+ * A mode that is neither, or a null pointer: ABZ_ERR_ARG.  Entry points added without a change of ABZ_VERSION. */
+#define ABZ_PIVOT_NONE 0     /* default: today's routes, bit for bit */
+#define ABZ_PIVOT_PARTIAL 1  /* every inverse of (w + i eta) I - H(k) taken for this series pivots by rows */
+int abz_series_set_pivoting(abz_series* s, int mode);
+int abz_series_get_pivoting(const abz_series* s, int* mode);
 
 /* ---------------------------------------------------------------- arbitrary nodes
  * Replaces: the fallback evaluator f.w(x) (src/fourier.jl:120-122) and the body of a
@@ -193,12 +214,13 @@ int abz_rule_export(abz_rule* r, double* x, double* w, double* H, double* eig, d
  * src/interfaces.jl:210-222, fused).  out_reim [n_sweep][ncomp][2] receives
  *   (sum_k w_k f(k, H(k); sweep_i)) / (npt^d * nsyms)        (nsyms = 1 on a full grid)
  * -- the caller applies |det B| and symmetrisation like do_solve_autobz (src/brillouin.jl:337-355).
- * DOS, TRGLOC and GLOC invert (omega + i eta) I - H(k) WITHOUT PIVOTING.  That is stable, with an error of a modest multiple
- * of eps sum_k ||G_k||^2 (||H_k|| + |z|) (times ||z - H_k|| / eta at worst), for a Hermitian series with eta > 0 and for a
- * dissipative series H = H_h - i Gamma, Gamma >= gamma I > 0, at eta >= 0; at eta = 0 a Hermitian series needs omega in a gap
- * AND definite leading blocks of omega I - H(k) (a diagonally dominant diag(+D, -D) + hopping has them).  For a general series
- * that is not Hermitian and not dissipative no bound is claimed: a pivoting inverse (LAPACK) may be accurate where this one is
- * not, and nothing tests that case. */
+ * By default (ABZ_PIVOT_NONE) DOS, TRGLOC and GLOC invert (omega + i eta) I - H(k) WITHOUT PIVOTING.  That is stable, with an
+ * error of a modest multiple of eps sum_k ||G_k||^2 (||H_k|| + |z|) (times ||z - H_k|| / eta at worst), for a Hermitian series
+ * with eta > 0 and for a dissipative series H = H_h - i Gamma, Gamma >= gamma I > 0, at eta >= 0; at eta = 0 a Hermitian
+ * series needs omega in a gap AND definite leading blocks of omega I - H(k) (a diagonally dominant diag(+D, -D) + hopping has
+ * them).  A series that is neither Hermitian nor dissipative, or a Hermitian one outside those conditions ([[0,1],[1,0]] at
+ * omega = eta = 0), can lose every digit that way: set ABZ_PIVOT_PARTIAL on the series (abz_series_set_pivoting) and every
+ * inverse pivots by rows like LAPACK's, tested against it within 64 eps sum_k ||G_k||^2 (||H_k|| + |z|) on such cases. */
 int abz_rule_reduce(abz_rule* r, int integrand, const double* params, int nparams,
                     const double* sweep, int n_sweep, int nsyms, double* out_reim);
 
@@ -248,8 +270,8 @@ int abz_series_drop_rules(abz_series* s);
  * more than 128 points, the tridiagonal form of every node above; GLOC above 4 bands, series that are not Hermitian and short
  * lines: the inverse of every node, chunk by chunk).  Other integrands: Hermitian series of n <= 4 bands with npt > 128;
  * ABZ_ERR_UNSUPPORTED otherwise (build a rule instead).
- * The resolvents are inverted without pivoting, as in abz_rule_reduce: the same cases are covered and the same one -- a series
- * that is neither Hermitian nor dissipative -- is not.
+ * By default the resolvents are inverted without pivoting, as in abz_rule_reduce, and the same cases are covered; with
+ * ABZ_PIVOT_PARTIAL on the series every node's inverse pivots by rows (1...64 bands, every series, lines of < 65536 points).
  * Replaces: FourierPTR ctor + rule(f, B) back to back (src/fourier.jl:166-207). */
 int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int integrand,
                 const double* params, int nparams, const double* sweep, int n_sweep, int nsyms,

@@ -612,6 +612,23 @@ function update!(hs::HIPSeries, s::FourierSeries)
     end
     return hs
 end
+const PIVOT_NONE = Cint(0)
+const PIVOT_PARTIAL = Cint(1)
+"""
+`:none` (the default routes) or `:partial`: every inverse of (omega + i eta) I - H(k) taken for this series -- rule scans,
+store-free sums, AutoPTR and IAI solves -- pivots by rows like LAPACK's `inv` (abz_series_set_pivoting).  Read at launch
+time: rules built before the call follow it, `update!` keeps it.
+"""
+function set_pivoting!(hs::HIPSeries, mode::Symbol)
+    mode in (:none, :partial) || throw(ArgumentError("pivoting must be :none or :partial, not $(repr(mode))"))
+    check(ccall((:abz_series_set_pivoting, libabz), Cint, (Ptr{Cvoid}, Cint), hs.h, mode === :partial ? PIVOT_PARTIAL : PIVOT_NONE))
+    return hs
+end
+function pivoting(hs::HIPSeries)
+    m = Ref{Cint}(0)
+    check(ccall((:abz_series_get_pivoting, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}), hs.h, m))
+    return m[] == PIVOT_PARTIAL ? :partial : :none
+end
 "Context on a stream the caller owns (e.g. AMDGPU.jl's task-local HIP stream): launches are ordered with the caller's work."
 function HIPContext(device::Integer, stream::Ptr{Cvoid})
     ref = Ref{Ptr{Cvoid}}(C_NULL)
