@@ -18,7 +18,8 @@
 //                1 - (e4-E)^3 / (e41 e42 e43) | 1
 //      d = 2, g: 2 (E-e1) / (e21 e31) | 2 (e3-E) / (e31 e32);   N: (E-e1)^2 / (e21 e31) | 1 - (e3-E)^2 / (e31 e32) | 1
 //      d = 1, g: 1 / e21;   N: (E-e1) / e21 | 1
-//  * Shape: that of ggr_window_kernel (kernels_ggr.hip).  The energies are ascending and live in LDS; blockIdx.y is the
+//  * Shape (ltm_window_kernel<D, STATES, SLAB, P>, ONE kernel for every scan; P is the payload, see below): that of
+//    ggr_window_kernel (kernels_ggr.hip).  The energies are ascending and live in LDS; blockIdx.y is the
 //    band, a block walks 256 cells at a time in two passes.  Pass 1, one cell per thread: load the 2^d corner
 //    eigenvalues (the i_1 neighbour is the same padded row shifted by one, the i_2 / i_3 neighbours are other lines),
 //    find the first energy of the cell's window [min, max) -- by arithmetic in an equispaced list, by binary search
@@ -36,7 +37,14 @@
 //    N(above all bands) = d! npt^d n * weight = n to one rounding, and N(below all bands) is exactly 0.
 //  * Locals are plain scalars and fully unrolled constant-index arrays: nothing goes to scratch (DESIGN section 4e has
 //    the compiler's resource report).
-//  * Matrix elements (wltm_window_kernel).  With a quantity A_b(k) per node and band, interpolated linearly inside a
+//  * Payloads.  What a corner carries besides its energy is a policy of the kernel: LtmPlain (nothing; the closed forms above
+//    with their fmin / fmax sorting network; a different instruction stream on purpose, 1933 instructions against 2553) or
+//    LtmElems<NC, CORR> (NC matrix elements, next item).  The policy gives the per-corner load, picks the simplex routine and
+//    says what a cell without an energy in its window adds to the step histogram; the cell walk, the corner geometry (whole
+//    grid or slab with its halo plane), the window, the queue and the write-out are the kernel's and exist once.  One final
+//    and one prefix kernel serve both (the plain scan is one component), one host function (ltm_scan) launches them, and the
+//    table LTM_WINDOWS lists the compiled instantiations: a scan that is not in it is refused.
+//  * Matrix elements (LtmElems<NC, false>).  With a quantity A_b(k) per node and band, interpolated linearly inside a
 //    simplex like the energy, the same scan gives g_A(E) = sum_b int A_b delta(E - e_b) and N_A(E) = sum_b int A_b
 //    theta(E - e_b).  The compare-exchange network that sorts the corner energies swaps the corners' A values along; per
 //    (simplex, energy) the d + 1 corner weights w_c are formed from the energies alone and every component adds
@@ -49,12 +57,12 @@
 //             densities 3 t13 (1 - t23) / e41 and 3 t23 (1 - t24) / e41, each giving a third to its vertices; a vertex
 //             P_ij hands (1 - t_ij, t_ij) of its share to the corners i, j
 //             e3 <= E < e4: the mirror image of the first region from corner 4, N: w = 1/4 - (that)
-//      d = 2, d = 1: the same with one and two corners fewer (wltm_simplex2, wltm_simplex1)
+//      d = 2, d = 1: the same with one and two corners fewer (the LtmVec overloads of ltm_simplex2, ltm_simplex1)
 //    A simplex wholly below E adds the mean of its corners' A to the step histogram, which is therefore no longer
 //    integer; its prefix sum keeps a fixed order.  The elements live in ncomp n planes tiled like the eigenvalue
 //    planes (plane c n + b: component c of band b); a launch carries 1, 2 or 4 components, so that the corners of a
 //    cell (8 energies + 8 NC elements) stay in registers, and a call walks the grid once per group of components.
-//  * Curvature correction (wltm_window_kernel<D, true, NC, true>, ABZ_LTM_STATES_CORRECTED).  Linear interpolation misplaces
+//  * Curvature correction (LtmElems<NC, true> with STATES, ABZ_LTM_STATES_CORRECTED).  Linear interpolation misplaces
 //    the weight inside a simplex by the band's curvature; to leading order (eq. 22 of the paper for d = 3)
 //      N_A^corr(E) = N_A(E) + w sum_T g_T(E) kappa_T,   kappa_T = f_d sum_i A_i (sum_l e_l - (d+1) e_i),   f_d = 1 / (2 (d+1)(d+2)),
 //    f_3 = 1/40, f_2 = 1/24, f_1 = 1/12; g_T is the simplex's own DOS, unit = one simplex: the g formulas above.  Window:
@@ -96,10 +104,10 @@ struct LtmArgs {
     double inv_step = 0.0;  // > 0: the energies are equispaced: Es[i] = Es[0] + i / inv_step to rounding
 };
 
-// A slab of the outermost variable (abz_rule_ltm_halo): E holds the slab's nz planes, `halo` the one plane behind them
+// A slab of the outermost variable (abz_rule_ltm_halo): E holds the slab's nz planes, `haloE` the one plane behind them
 // (plane outer_end mod npt of the grid, a rule of its own); ncell = nz npt^(d-1) and npt stays the grid's.
 struct LtmSlabArgs : LtmArgs {
-    PlaneView halo;
+    PlaneView haloE;
     int nz = 0;
 };
 
@@ -128,10 +136,14 @@ __device__ __forceinline__ void ltm_add(double* h, double f) {
     __hip_atomic_fetch_add(h, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// What a corner of the plain scan carries besides its energy.  The simplex routines of both payloads (LtmPlain, LtmElems
+// below) take the corners' payloads behind the energies, so that the scan's one call finds its routine by their type.
+struct LtmNone {};
+
 // One tetrahedron with corner energies (a, b, c, d) in any order; i0 = first energy >= the cell's minimum.
-template <bool STATES>
-__device__ __forceinline__ void ltm_simplex3(double a, double b, double c, double d, const double* Esl, int nE, int i0,
-                                             double* hist, double* step) {
+template <bool STATES, class P>
+__device__ __forceinline__ void ltm_simplex3(double a, double b, double c, double d, LtmNone, LtmNone, LtmNone, LtmNone, const double* Esl,
+                                             int nE, int i0, double* hist, double* step) {
     // 5-compare sorting network
     const double lo1 = fmin(a, b), hi1 = fmax(a, b), lo2 = fmin(c, d), hi2 = fmax(c, d);
     const double e1 = fmin(lo1, lo2), m1 = fmax(lo1, lo2), e4 = fmax(hi1, hi2), m2 = fmin(hi1, hi2);
@@ -165,9 +177,9 @@ __device__ __forceinline__ void ltm_simplex3(double a, double b, double c, doubl
     if (STATES && i < nE) ltm_add(step + i, 1.0);  // i: first energy >= e4
 }
 
-template <bool STATES>
-__device__ __forceinline__ void ltm_simplex2(double a, double b, double c, const double* Esl, int nE, int i0, double* hist,
-                                             double* step) {
+template <bool STATES, class P>
+__device__ __forceinline__ void ltm_simplex2(double a, double b, double c, LtmNone, LtmNone, LtmNone, const double* Esl, int nE, int i0,
+                                             double* hist, double* step) {
     const double lo = fmin(a, b), hi = fmax(a, b);
     const double e1 = fmin(lo, c), e3 = fmax(hi, c), e2 = fmax(lo, fmin(hi, c));
     int i = i0;
@@ -193,8 +205,9 @@ __device__ __forceinline__ void ltm_simplex2(double a, double b, double c, const
     if (STATES && i < nE) ltm_add(step + i, 1.0);
 }
 
-template <bool STATES>
-__device__ __forceinline__ void ltm_simplex1(double a, double b, const double* Esl, int nE, int i0, double* hist, double* step) {
+template <bool STATES, class P>
+__device__ __forceinline__ void ltm_simplex1(double a, double b, LtmNone, LtmNone, const double* Esl, int nE, int i0, double* hist,
+                                             double* step) {
     const double e1 = fmin(a, b), e2 = fmax(a, b);
     int i = i0;
     if (i < nE && Esl[i] < e2) {
@@ -209,187 +222,6 @@ __device__ __forceinline__ void ltm_simplex1(double a, double b, const double* E
         }
     }
     if (STATES && i < nE) ltm_add(step + i, 1.0);
-}
-
-// Passes with at most this many of their 256 cells queued redistribute the simplices over the block; measured on the
-// 150^3 grid of 3 bands: 32 energies (a fifth of the cells queued) 0.23 ms direct, 0.14 ms queued; 256 energies (most
-// cells queued) 0.28 ms direct, 0.46 ms queued.
-constexpr unsigned LTM_QUEUE_MAX = 128;
-
-// partial [STATES ? 2 nE : nE][nrows]: columns 0 .. nE-1 the formula sums, nE .. 2 nE-1 the step counts
-// SLAB (d >= 2): the cells of a slab of the outermost variable, whose index does not wrap: the step past the slab's last
-// plane reads the halo plane.  Everything else, and the whole-grid instantiations, are as without it.
-template <int D, bool STATES, bool SLAB = false>
-__global__ __launch_bounds__(256) void ltm_window_kernel(std::conditional_t<SLAB, LtmSlabArgs, LtmArgs> a, double* __restrict__ partial,
-                                                         int64_t nrows) {
-    static_assert(!SLAB || D >= 2, "a slab needs at least two variables");
-    // [nE] energies | [4 waves][nE] sums | STATES: [4 waves][nE] steps | [256] queue of a pass | [2][4] per-wave counts
-    extern __shared__ __attribute__((aligned(16))) double ldsl[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int nE = a.nE;
-    constexpr int NH = STATES ? 8 : 4;
-    constexpr int NS = D == 3 ? 6 : (D == 2 ? 2 : 1);  // simplices per cell
-    const double* const Esl = ldsl;
-    double* const hist = ldsl + (size_t)(1 + wave) * nE;
-    double* const step = ldsl + (size_t)(5 + wave) * nE;  // STATES only
-    uint32_t* const queue = reinterpret_cast<uint32_t*>(ldsl + (size_t)(1 + NH) * nE);
-    uint32_t* const wcount = queue + 256;
-    for (int i = threadIdx.x; i < nE; i += 256) ldsl[i] = a.Es[i];
-    for (int i = threadIdx.x; i < NH * nE; i += 256) ldsl[nE + i] = 0.0;
-    __syncthreads();
-    const int npt = a.npt;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const int64_t tile = a.E.tile;
-    [[maybe_unused]] const double* __restrict__ Hb = nullptr;  // SLAB: this band's plane of the halo, its line stride, the slab's planes
-    [[maybe_unused]] int64_t htile = 0;
-    [[maybe_unused]] int nz = 0;
-    if constexpr (SLAB) {
-        Hb = a.halo.base + (int64_t)blockIdx.y * a.halo.pitch;
-        htile = a.halo.tile;
-        nz = a.nz;
-    }
-    // eigenvalue at corner `bits` (bit j: +1 along variable j+1, wrapped) of cell k
-    auto corner = [&](int i1, int i2, int i3, int bits) -> double {
-        if ((bits & 1) && ++i1 == npt) i1 = 0;
-        if constexpr (SLAB) {
-            // the outermost index is local to the slab and does not wrap: behind plane nz - 1 lies the halo, line i_2 of it (d = 2: its only line)
-            if constexpr (D == 3) {
-                if ((bits & 2) && ++i2 == npt) i2 = 0;
-                if ((bits & 4) && ++i3 == nz) return Hb[(int64_t)i2 * htile + i1];
-            } else {
-                if ((bits & 2) && ++i2 == nz) return Hb[i1];
-            }
-        } else {
-            if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
-            if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
-        }
-        return Eb[((int64_t)i3 * npt + i2) * tile + i1];
-    };
-    // Two passes over 256 cells at a time (the trip count is the block's, so the barriers are uniform).  Pass 1, one cell
-    // per thread: the cell's window against the energy list; cells that hold an energy are queued, in thread order.  Pass 2,
-    // one (queued cell, simplex) per thread: in a coarse sweep a fifth of the cells holds an energy, and a wave that walked
-    // the 6 simplices of its own cells would do so for nearly every cell (some lane always has one) with most lanes idle.
-    unsigned pass = 0;
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
-        const int64_t k = base + threadIdx.x;
-        bool active = false;
-        int i0 = 0;
-        double c[1 << D];
-        if (k < a.ncell) {
-            // k < 2^32 on every grid that fits in HBM: 32-bit division
-            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
-            const int i1 = (int)(k - line * npt);
-            const int i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
-            const int i2 = (int)line - i3 * npt;
-#pragma unroll
-            for (int j = 0; j < (1 << D); ++j) c[j] = corner(i1, i2, i3, j);
-            double cmin = c[0], cmax = c[0];
-#pragma unroll
-            for (int j = 1; j < (1 << D); ++j) {
-                cmin = fmin(cmin, c[j]);
-                cmax = fmax(cmax, c[j]);
-            }
-            i0 = ltm_first(Esl, nE, a.inv_step, cmin);
-            if (i0 < nE) {  // else every energy lies below the cell
-                if (Esl[i0] < cmax) active = true;
-                else if (STATES) ltm_add(step + i0, (double)NS);  // no energy inside the window: all simplices step at the same index
-            }
-        }
-        const unsigned long long mask = __ballot(active);
-        // the counts alternate between two sets: a direct pass has this one barrier only, and a thread that is already
-        // in the next pass must not overwrite the counts a slower one is still reading
-        uint32_t* const wc = wcount + 4 * (pass & 1);
-        ++pass;
-        if (lane == 0) wc[wave] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        uint32_t off = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const uint32_t cw = wc[w];
-            off += w < wave ? cw : 0u;
-            total += cw;
-        }
-        if (total > LTM_QUEUE_MAX) {
-            // Most cells hold an energy (a fine sweep): every thread walks the simplices of its own cell from the corners
-            // it still holds; the queue would only add its reloads.  `total` is the block's: a uniform branch.
-            if (active) {
-                if constexpr (D == 3) {
-                    ltm_simplex3<STATES>(c[0], c[1], c[3], c[7], Esl, nE, i0, hist, step);
-                    ltm_simplex3<STATES>(c[0], c[1], c[5], c[7], Esl, nE, i0, hist, step);
-                    ltm_simplex3<STATES>(c[0], c[2], c[3], c[7], Esl, nE, i0, hist, step);
-                    ltm_simplex3<STATES>(c[0], c[2], c[6], c[7], Esl, nE, i0, hist, step);
-                    ltm_simplex3<STATES>(c[0], c[4], c[5], c[7], Esl, nE, i0, hist, step);
-                    ltm_simplex3<STATES>(c[0], c[4], c[6], c[7], Esl, nE, i0, hist, step);
-                } else if constexpr (D == 2) {
-                    ltm_simplex2<STATES>(c[0], c[1], c[3], Esl, nE, i0, hist, step);
-                    ltm_simplex2<STATES>(c[0], c[2], c[3], Esl, nE, i0, hist, step);
-                } else {
-                    ltm_simplex1<STATES>(c[0], c[1], Esl, nE, i0, hist, step);
-                }
-            }
-            continue;
-        }
-        if (active) queue[off + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((uint32_t)i0 << 8) | threadIdx.x;
-        __syncthreads();  // the next pass writes the queue after its own first barrier
-        for (uint32_t p = threadIdx.x; p < NS * total; p += 256) {
-            const uint32_t cell = p / NS, t = p - cell * NS;
-            const uint32_t q = queue[cell];
-            const int64_t kq = base + (q & 255u);
-            const int j0 = (int)(q >> 8);
-            const int64_t line = kq <= 0xffffffffll ? (int64_t)((uint32_t)kq / (uint32_t)npt) : kq / npt;
-            const int i1 = (int)(kq - line * npt);
-            const int i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
-            const int i2 = (int)line - i3 * npt;
-            const double c0 = corner(i1, i2, i3, 0), c1 = corner(i1, i2, i3, (1 << D) - 1);
-            if constexpr (D == 3) {
-                // the permutation (A, B, C) of the axes: corners 0, e_A, e_A + e_B, (1,1,1)
-                const int A = (int)(t >> 1), B = (A + 1 + (int)(t & 1)) % 3;
-                const double ca = corner(i1, i2, i3, 1 << A), cb = corner(i1, i2, i3, (1 << A) | (1 << B));
-                ltm_simplex3<STATES>(c0, ca, cb, c1, Esl, nE, j0, hist, step);
-            } else if constexpr (D == 2) {
-                ltm_simplex2<STATES>(c0, corner(i1, i2, i3, 1 << t), c1, Esl, nE, j0, hist, step);
-            } else {
-                ltm_simplex1<STATES>(c0, c1, Esl, nE, j0, hist, step);
-            }
-        }
-    }
-    __syncthreads();
-    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const double* h = ldsl + nE;
-    // transposed partials [column][row]: the final reduction reads the rows of one column contiguously
-    for (int t = threadIdx.x; t < nE; t += 256) {
-        partial[(int64_t)t * nrows + prow] = (h[t] + h[nE + t]) + (h[2 * nE + t] + h[3 * nE + t]);
-        if (STATES) partial[(int64_t)(nE + t) * nrows + prow] = (h[4 * nE + t] + h[5 * nE + t]) + (h[6 * nE + t] + h[7 * nE + t]);
-    }
-}
-
-// out[col] = scale * sum_rows partial[col][row], one block per column, fixed summation order (ggr_final_kernel's)
-__global__ __launch_bounds__(256) void ltm_final_kernel(const double* __restrict__ partial, int64_t nrows, double scale,
-                                                        double* __restrict__ out) {
-    __shared__ double red[256];
-    const double* __restrict__ p = partial + (int64_t)blockIdx.x * nrows;
-    double s = 0.0;
-    for (int64_t r = threadIdx.x; r < nrows; r += 256) s += p[r];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = scale * red[0];
-}
-
-// State count of a chunk: out[i] = weight * (sums[i] + steps[0] + ... + steps[i]); col = [nE sums | nE steps], nE <= 512.
-// The steps are integers, their prefix sums exact.
-__global__ __launch_bounds__(256) void ltm_prefix_kernel(const double* __restrict__ col, int nE, double weight, double* __restrict__ out) {
-    __shared__ double st[512];
-    for (int i = threadIdx.x; i < nE; i += 256) st[i] = col[nE + i];
-    __syncthreads();
-    for (int i = threadIdx.x; i < nE; i += 256) {
-        double run = 0.0;
-        for (int j = 0; j <= i; ++j) run += st[j];
-        out[i] = weight * (col[i] + run);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -431,11 +263,13 @@ __device__ __forceinline__ void ltm_cx(double& ea, double& eb, LtmVec<NC>& Aa, L
     }
 }
 
-// One tetrahedron, corners in any order.  hist / step: [NC][nE] of the wave.
+// One tetrahedron, corners in any order.  hist / step: [NC][nE] of the wave.  P: LtmElems<NC, CORR> below.
 // CORR (with STATES): the curvature correction, g_T(E) kappa_T added to the sum of the selected region.
-template <bool STATES, int NC, bool CORR = false>
-__device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, double e4, LtmVec<NC> A1, LtmVec<NC> A2, LtmVec<NC> A3,
-                                              LtmVec<NC> A4, const double* Esl, int nE, int i0, double* hist, double* step) {
+template <bool STATES, class P>
+__device__ __forceinline__ void ltm_simplex3(double e1, double e2, double e3, double e4, LtmVec<P::NC> A1, LtmVec<P::NC> A2, LtmVec<P::NC> A3,
+                                              LtmVec<P::NC> A4, const double* Esl, int nE, int i0, double* hist, double* step) {
+    constexpr int NC = P::NC;
+    constexpr bool CORR = P::CORR;
     ltm_cx(e1, e2, A1, A2);
     ltm_cx(e3, e4, A3, A4);
     ltm_cx(e1, e3, A1, A3);
@@ -519,9 +353,11 @@ __device__ __forceinline__ void wltm_simplex3(double e1, double e2, double e3, d
     }
 }
 
-template <bool STATES, int NC, bool CORR = false>
-__device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, LtmVec<NC> A1, LtmVec<NC> A2, LtmVec<NC> A3,
+template <bool STATES, class P>
+__device__ __forceinline__ void ltm_simplex2(double e1, double e2, double e3, LtmVec<P::NC> A1, LtmVec<P::NC> A2, LtmVec<P::NC> A3,
                                               const double* Esl, int nE, int i0, double* hist, double* step) {
+    constexpr int NC = P::NC;
+    constexpr bool CORR = P::CORR;
     ltm_cx(e1, e2, A1, A2);
     ltm_cx(e2, e3, A2, A3);
     ltm_cx(e1, e2, A1, A2);
@@ -573,9 +409,11 @@ __device__ __forceinline__ void wltm_simplex2(double e1, double e2, double e3, L
     }
 }
 
-template <bool STATES, int NC, bool CORR = false>
-__device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A1, LtmVec<NC> A2, const double* Esl, int nE, int i0,
+template <bool STATES, class P>
+__device__ __forceinline__ void ltm_simplex1(double e1, double e2, LtmVec<P::NC> A1, LtmVec<P::NC> A2, const double* Esl, int nE, int i0,
                                               double* hist, double* step) {
+    constexpr int NC = P::NC;
+    constexpr bool CORR = P::CORR;
     ltm_cx(e1, e2, A1, A2);
     int i = i0;
     if (i < nE && Esl[i] < e2) {
@@ -606,21 +444,92 @@ __device__ __forceinline__ void wltm_simplex1(double e1, double e2, LtmVec<NC> A
     }
 }
 
-// ltm_window_kernel with NC components of matrix elements.
+// ---------------------------------------------------------------------------------------------------------------------
+// The scan: one kernel, two payloads
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int ltm_nsimplex(int d) { return d == 3 ? 6 : (d == 2 ? 2 : 1); }  // simplices per cell
+
+// A payload says what a corner carries besides its energy (Vec; load, where it carries anything), which routine takes a simplex (the overload of
+// ltm_simplex1/2/3 for its Vec) and what a cell adds to the step histogram when no energy falls inside its window (below_add
+// per corner, below_put once).  Args<SLAB> is its kernel-argument struct, args() that struct from the host's description of a
+// launch (the superset, WLtmSlabArgs).  The hooks are inlined before anything else and call nothing of the kernel's: together
+// with the kernel's corner lambdas this keeps the instruction streams of the two kernels this one replaced.
+//
+// The plain payload: nothing but the energy, the closed forms; every simplex of a cell below E steps by 1.
+struct LtmPlain {
+    static constexpr int NC = 1;  // histograms per wave and kind
+    static constexpr bool ELEMS = false, CORR = false;
+    template <bool SLAB>
+    using Args = std::conditional_t<SLAB, LtmSlabArgs, LtmArgs>;
+    using Vec = LtmNone;
+    template <bool SLAB>
+    static Args<SLAB> args(const WLtmSlabArgs& s) {
+        return LtmSlabArgs{{s.E, s.Es, s.ncell, s.npt, s.nE, s.inv_step}, s.haloE, s.nz};  // (whole grid: its LtmArgs part)
+    }
+    template <int D>
+    static __device__ __forceinline__ void below_add(Vec&, int, const Vec&) {}
+    template <int D>
+    static __device__ __forceinline__ void below_put(double* step, int, int i0, const Vec&) {
+        ltm_add(step + i0, (double)ltm_nsimplex(D));  // every simplex of the cell steps by 1
+    }
+};
+
+// The element payload: NC components per corner, carried through the sort; CORR: the curvature correction.
+template <int NC_, bool CORR_>
+struct LtmElems {
+    static constexpr int NC = NC_;
+    static constexpr bool ELEMS = true, CORR = CORR_;
+    template <bool SLAB>
+    using Args = std::conditional_t<SLAB, WLtmSlabArgs, WLtmArgs>;
+    using Vec = LtmVec<NC>;
+    template <bool SLAB>
+    static Args<SLAB> args(const WLtmSlabArgs& s) {
+        return s;  // (whole grid: its WLtmArgs part)
+    }
+    // the NC components of the corner whose first one lies at p, `acomp` doubles apart
+    static __device__ __forceinline__ Vec load(const double* __restrict__ p, int64_t acomp) {
+        Vec r;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) r.v[c] = p[(int64_t)c * acomp];
+        return r;
+    }
+    // By the sum of the simplices' means in one add per component.  Corner 0 and corner (1..1) belong to all d! simplices, every
+    // other corner to d! / d of them... d = 3: (6 (A0 + A7) + 2 sum others) / 4, d = 2: (2 (A0 + A3) + A1 + A2) / 3
+    template <int D>
+    static __device__ __forceinline__ void below_add(Vec& m, int j, const Vec& Aj) {
+        const bool ends = j == 0 || j == (1 << D) - 1;
+        const double wj = D == 3 ? (ends ? 1.5 : 0.5) : (D == 2 ? (ends ? 2.0 / 3.0 : 1.0 / 3.0) : 0.5);
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) m.v[cc] += wj * Aj.v[cc];
+    }
+    template <int D>
+    static __device__ __forceinline__ void below_put(double* step, int nE, int i0, const Vec& m) {
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) ltm_add(step + (size_t)cc * nE + i0, m.v[cc]);
+    }
+};
+
+// Passes with at most this many of their 256 cells queued redistribute the simplices over the block; measured on the
+// 150^3 grid of 3 bands: 32 energies (a fifth of the cells queued) 0.23 ms direct, 0.14 ms queued; 256 energies (most
+// cells queued) 0.28 ms direct, 0.46 ms queued.
+constexpr unsigned LTM_QUEUE_MAX = 128;
+
 // partial [(STATES ? 2 : 1) NC nE][nrows]: columns c nE + i the formula sums of component c, NC nE + c nE + i its steps
-// CORR (with STATES only): N_A with the curvature correction; same histograms, same launches.
-// SLAB: as in ltm_window_kernel, for the energies and the elements alike.
-template <int D, bool STATES, int NC, bool CORR = false, bool SLAB = false>
-__global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLAB, WLtmSlabArgs, WLtmArgs> a, double* __restrict__ partial,
-                                                          int64_t nrows) {
+// SLAB (d >= 2): the cells of a slab of the outermost variable (the `corner` lambda); everything else is as on the whole grid.
+// P: LtmPlain or LtmElems<NC, CORR> (CORR with STATES only: N_A with the curvature correction; same histograms, same launches).
+template <int D, bool STATES, bool SLAB, class P>
+__global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Args<SLAB> a, double* __restrict__ partial, int64_t nrows) {
     static_assert(!SLAB || D >= 2, "a slab needs at least two variables");
+    static_assert(STATES || !P::CORR, "the curvature correction belongs to the state sum");
     // [nE] energies | [4 waves][NC][nE] sums | STATES: [4 waves][NC][nE] steps | [256] queue of a pass | [2][4] per-wave counts
     extern __shared__ __attribute__((aligned(16))) double ldsl[];
+    using Vec = typename P::Vec;
+    constexpr int NC = P::NC;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nE = a.nE;
     constexpr int NH = (STATES ? 8 : 4) * NC;
-    constexpr int NS = D == 3 ? 6 : (D == 2 ? 2 : 1);  // simplices per cell
-    constexpr int NV = 1 << D;                         // corners per cell
+    constexpr int NS = ltm_nsimplex(D);
+    constexpr int NV = 1 << D;  // corners per cell
     const double* const Esl = ldsl;
     double* const hist = ldsl + (size_t)(1 + wave * NC) * nE;
     double* const step = ldsl + (size_t)(1 + (4 + wave) * NC) * nE;  // STATES only
@@ -630,59 +539,70 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLA
     for (int i = threadIdx.x; i < NH * nE; i += 256) ldsl[nE + i] = 0.0;
     __syncthreads();
     const int npt = a.npt;
+    // this band's eigenvalue planes and their line stride; ELEMS: the planes of the launch's first component
     const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const double* __restrict__ const Ab = a.A.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.A.pitch;
-    const int64_t tileE = a.E.tile, tileA = a.A.tile, acomp = a.acomp;
-    // corner `bits` (bit j: +1 along variable j+1, wrapped) of cell (i1, i2, i3): its grid line and its place in the line
-    auto wrap = [&](int& i1, int& i2, int& i3, int bits) {
-        if ((bits & 1) && ++i1 == npt) i1 = 0;
-        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
-        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
-    };
+    [[maybe_unused]] const double* __restrict__ Ab = nullptr;
+    const int64_t tileE = a.E.tile;
+    [[maybe_unused]] int64_t tileA = 0, acomp = 0;
+    if constexpr (P::ELEMS) {
+        Ab = a.A.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.A.pitch;
+        tileA = a.A.tile;
+        acomp = a.acomp;
+    }
     [[maybe_unused]] const double* __restrict__ EHb = nullptr;  // SLAB: this band's planes of the halo, their line strides, the slab's planes
     [[maybe_unused]] const double* __restrict__ AHb = nullptr;
     [[maybe_unused]] int64_t htileE = 0, htileA = 0;
     [[maybe_unused]] int nz = 0;
     if constexpr (SLAB) {
         EHb = a.haloE.base + (int64_t)blockIdx.y * a.haloE.pitch;
-        AHb = a.haloA.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.haloA.pitch;
         htileE = a.haloE.tile;
-        htileA = a.haloA.tile;
+        if constexpr (P::ELEMS) {
+            AHb = a.haloA.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.haloA.pitch;
+            htileA = a.haloA.tile;
+        }
         nz = a.nz;
     }
-    // SLAB: the same step with a local outermost index that does not wrap; true: the corner lies in the halo plane, at
-    // (i1, line i2) of it for d = 3, (i1, line 0) for d = 2
-    [[maybe_unused]] auto wrap_slab = [&](int& i1, int& i2, int& i3, int bits) -> bool {
+    // THE geometry, for energies and elements alike: corner `bits` (bit j: +1 along variable j+1) of cell (i1, i2, i3), which
+    // become the corner's own indices.  Whole grid: every index wraps mod npt, the corner is column i1 of line i3 npt + i2 of the
+    // band's planes.  SLAB: the outermost index is local to the slab's nz planes and does not wrap; true: the corner lies behind
+    // plane nz - 1, in the halo plane, at column i1 of its line i2 (d = 2: of its only line, 0).
+    auto corner = [&](int& i1, int& i2, int& i3, int bits) -> bool {
         if ((bits & 1) && ++i1 == npt) i1 = 0;
-        if constexpr (D == 3) {
-            if ((bits & 2) && ++i2 == npt) i2 = 0;
-            return (bits & 4) && ++i3 == nz;
-        } else {
-            if ((bits & 2) && ++i2 == nz) {
-                i2 = 0;
-                return true;
+        if constexpr (SLAB) {
+            if constexpr (D == 3) {
+                if ((bits & 2) && ++i2 == npt) i2 = 0;
+                return (bits & 4) && ++i3 == nz;
+            } else {
+                if ((bits & 2) && ++i2 == nz) {
+                    i2 = 0;
+                    return true;
+                }
             }
-            return false;
+        } else {
+            if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
+            if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
         }
+        return false;
     };
     auto cornerE = [&](int i1, int i2, int i3, int bits) -> double {
+        [[maybe_unused]] const bool halo = corner(i1, i2, i3, bits);
         if constexpr (SLAB) {
-            if (wrap_slab(i1, i2, i3, bits)) return EHb[(int64_t)i2 * htileE + i1];
-        } else {
-            wrap(i1, i2, i3, bits);
+            if (halo) return EHb[(int64_t)i2 * htileE + i1];
         }
         return Eb[((int64_t)i3 * npt + i2) * tileE + i1];
     };
-    auto cornerA = [&](int i1, int i2, int i3, int bits) -> LtmVec<NC> {
-        bool halo = false;
-        if constexpr (SLAB) halo = wrap_slab(i1, i2, i3, bits);
-        else wrap(i1, i2, i3, bits);
-        const double* __restrict__ const p = SLAB && halo ? AHb + (int64_t)i2 * htileA + i1 : Ab + ((int64_t)i3 * npt + i2) * tileA + i1;
-        LtmVec<NC> r;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) r.v[c] = p[(int64_t)c * acomp];
-        return r;
+    auto cornerA = [&](int i1, int i2, int i3, int bits) -> Vec {
+        if constexpr (P::ELEMS) {
+            const bool halo = corner(i1, i2, i3, bits);
+            return P::load(SLAB && halo ? AHb + (int64_t)i2 * htileA + i1 : Ab + ((int64_t)i3 * npt + i2) * tileA + i1, acomp);
+        } else {
+            return {};  // the plain scan has no element planes
+        }
     };
+    // Two passes over 256 cells at a time (the trip count is the block's, so the barriers are uniform).  Pass 1, one cell
+    // per thread: the cell's window against the energy list; cells that hold an energy are queued, in thread order.  Pass 2,
+    // one (queued cell, simplex) per thread: in a coarse sweep a fifth of the cells holds an energy, and a wave that walked
+    // the 6 simplices of its own cells would do so for nearly every cell (some lane always has one) with most lanes idle.
     unsigned pass = 0;
     for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
         const int64_t k = base + threadIdx.x;
@@ -704,30 +624,20 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLA
             }
             i0 = ltm_first(Esl, nE, a.inv_step, cmin);
             if (i0 < nE) {  // else every energy lies below the cell
-                if (Esl[i0] < cmax) {
-                    active = true;
-                } else if (STATES) {
-                    // no energy inside the window: all simplices step at the same index, by the sum of their means in one
-                    // add per component.  Corner 0 and corner (1..1) belong to all d! simplices, every other corner to
-                    // d! / d of them... d = 3: (6 (A0 + A7) + 2 sum others) / 4, d = 2: (2 (A0 + A3) + A1 + A2) / 3
-                    LtmVec<NC> m;
+                if (Esl[i0] < cmax) active = true;
+                else if (STATES) {
+                    // no energy inside the window: all simplices step at the same index, in one add from the cell's corners
+                    Vec m{};
 #pragma unroll
-                    for (int cc = 0; cc < NC; ++cc) m.v[cc] = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) {
-                        const LtmVec<NC> Aj = cornerA(i1, i2, i3, j);
-                        const bool ends = j == 0 || j == NV - 1;
-                        const double wj = D == 3 ? (ends ? 1.5 : 0.5) : (D == 2 ? (ends ? 2.0 / 3.0 : 1.0 / 3.0) : 0.5);
-#pragma unroll
-                        for (int cc = 0; cc < NC; ++cc) m.v[cc] += wj * Aj.v[cc];
-                    }
-#pragma unroll
-                    for (int cc = 0; cc < NC; ++cc) ltm_add(step + (size_t)cc * nE + i0, m.v[cc]);
+                    for (int j = 0; j < NV; ++j) P::template below_add<D>(m, j, cornerA(i1, i2, i3, j));
+                    P::template below_put<D>(step, nE, i0, m);
                 }
             }
         }
         const unsigned long long mask = __ballot(active);
-        uint32_t* const wc = wcount + 4 * (pass & 1);  // two sets in turn, as in ltm_window_kernel
+        // the counts alternate between two sets: a direct pass has this one barrier only, and a thread that is already
+        // in the next pass must not overwrite the counts a slower one is still reading
+        uint32_t* const wc = wcount + 4 * (pass & 1);
         ++pass;
         if (lane == 0) wc[wave] = (uint32_t)__popcll(mask);
         __syncthreads();
@@ -739,23 +649,25 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLA
             total += cw;
         }
         if (total > LTM_QUEUE_MAX) {
-            // the direct walk: the energies of the corners are held, their elements are loaded now
+            // Most cells hold an energy (a fine sweep): every thread walks the simplices of its own cell from the corner
+            // energies it still holds (their elements are loaded now); the queue would only add its reloads.  `total` is
+            // the block's: a uniform branch.
             if (active) {
-                LtmVec<NC> Av[NV];
+                Vec Av[NV];
 #pragma unroll
                 for (int j = 0; j < NV; ++j) Av[j] = cornerA(i1, i2, i3, j);
                 if constexpr (D == 3) {
-                    wltm_simplex3<STATES, NC, CORR>(c[0], c[1], c[3], c[7], Av[0], Av[1], Av[3], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC, CORR>(c[0], c[1], c[5], c[7], Av[0], Av[1], Av[5], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC, CORR>(c[0], c[2], c[3], c[7], Av[0], Av[2], Av[3], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC, CORR>(c[0], c[2], c[6], c[7], Av[0], Av[2], Av[6], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC, CORR>(c[0], c[4], c[5], c[7], Av[0], Av[4], Av[5], Av[7], Esl, nE, i0, hist, step);
-                    wltm_simplex3<STATES, NC, CORR>(c[0], c[4], c[6], c[7], Av[0], Av[4], Av[6], Av[7], Esl, nE, i0, hist, step);
+                    ltm_simplex3<STATES, P>(c[0], c[1], c[3], c[7], Av[0], Av[1], Av[3], Av[7], Esl, nE, i0, hist, step);
+                    ltm_simplex3<STATES, P>(c[0], c[1], c[5], c[7], Av[0], Av[1], Av[5], Av[7], Esl, nE, i0, hist, step);
+                    ltm_simplex3<STATES, P>(c[0], c[2], c[3], c[7], Av[0], Av[2], Av[3], Av[7], Esl, nE, i0, hist, step);
+                    ltm_simplex3<STATES, P>(c[0], c[2], c[6], c[7], Av[0], Av[2], Av[6], Av[7], Esl, nE, i0, hist, step);
+                    ltm_simplex3<STATES, P>(c[0], c[4], c[5], c[7], Av[0], Av[4], Av[5], Av[7], Esl, nE, i0, hist, step);
+                    ltm_simplex3<STATES, P>(c[0], c[4], c[6], c[7], Av[0], Av[4], Av[6], Av[7], Esl, nE, i0, hist, step);
                 } else if constexpr (D == 2) {
-                    wltm_simplex2<STATES, NC, CORR>(c[0], c[1], c[3], Av[0], Av[1], Av[3], Esl, nE, i0, hist, step);
-                    wltm_simplex2<STATES, NC, CORR>(c[0], c[2], c[3], Av[0], Av[2], Av[3], Esl, nE, i0, hist, step);
+                    ltm_simplex2<STATES, P>(c[0], c[1], c[3], Av[0], Av[1], Av[3], Esl, nE, i0, hist, step);
+                    ltm_simplex2<STATES, P>(c[0], c[2], c[3], Av[0], Av[2], Av[3], Esl, nE, i0, hist, step);
                 } else {
-                    wltm_simplex1<STATES, NC, CORR>(c[0], c[1], Av[0], Av[1], Esl, nE, i0, hist, step);
+                    ltm_simplex1<STATES, P>(c[0], c[1], Av[0], Av[1], Esl, nE, i0, hist, step);
                 }
             }
             continue;
@@ -765,31 +677,32 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLA
         for (uint32_t p = threadIdx.x; p < NS * total; p += 256) {
             const uint32_t cell = p / NS, t = p - cell * NS;
             const uint32_t q = queue[cell];
-            const int64_t kq = base + (q & 255u);
             const int j0 = (int)(q >> 8);
+            const int64_t kq = base + (q & 255u);
             const int64_t line = kq <= 0xffffffffll ? (int64_t)((uint32_t)kq / (uint32_t)npt) : kq / npt;
             const int q1 = (int)(kq - line * npt);
             const int q3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
             const int q2 = (int)line - q3 * npt;
             const double c0 = cornerE(q1, q2, q3, 0), c1 = cornerE(q1, q2, q3, NV - 1);
-            const LtmVec<NC> A0 = cornerA(q1, q2, q3, 0), A1 = cornerA(q1, q2, q3, NV - 1);
+            const Vec A0 = cornerA(q1, q2, q3, 0), A1 = cornerA(q1, q2, q3, NV - 1);
             if constexpr (D == 3) {
-                // the permutation (A, B, C) of the axes: corners 0, e_A, e_A + e_B, (1,1,1)
+                // the permutation (X, Y, Z) of the axes: corners 0, e_X, e_X + e_Y, (1,1,1)
                 const int X = (int)(t >> 1), Y = (X + 1 + (int)(t & 1)) % 3;
                 const int ba = 1 << X, bb = (1 << X) | (1 << Y);
-                wltm_simplex3<STATES, NC, CORR>(c0, cornerE(q1, q2, q3, ba), cornerE(q1, q2, q3, bb), c1, A0, cornerA(q1, q2, q3, ba),
-                                          cornerA(q1, q2, q3, bb), A1, Esl, nE, j0, hist, step);
+                ltm_simplex3<STATES, P>(c0, cornerE(q1, q2, q3, ba), cornerE(q1, q2, q3, bb), c1, A0, cornerA(q1, q2, q3, ba),
+                                            cornerA(q1, q2, q3, bb), A1, Esl, nE, j0, hist, step);
             } else if constexpr (D == 2) {
-                wltm_simplex2<STATES, NC, CORR>(c0, cornerE(q1, q2, q3, 1 << t), c1, A0, cornerA(q1, q2, q3, 1 << t), A1, Esl, nE, j0, hist, step);
+                ltm_simplex2<STATES, P>(c0, cornerE(q1, q2, q3, 1 << t), c1, A0, cornerA(q1, q2, q3, 1 << t), A1, Esl, nE, j0, hist, step);
             } else {
-                wltm_simplex1<STATES, NC, CORR>(c0, c1, A0, A1, Esl, nE, j0, hist, step);
+                ltm_simplex1<STATES, P>(c0, c1, A0, A1, Esl, nE, j0, hist, step);
             }
         }
     }
     __syncthreads();
     const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const double* h = ldsl + nE;
-    // transposed partials [column][row]; column c nE + t sits at the same place in every wave's block
+    // transposed partials [column][row]: the final reduction reads the rows of one column contiguously; column c nE + t
+    // sits at the same place in every wave's block
     for (int t = threadIdx.x; t < NC * nE; t += 256) {
         const size_t w = (size_t)NC * nE;  // from one wave's histograms to the next
         partial[(int64_t)t * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
@@ -797,9 +710,10 @@ __global__ __launch_bounds__(256) void wltm_window_kernel(std::conditional_t<SLA
     }
 }
 
-// ltm_final_kernel for a group of components: block (c, i) -> out[c * ostride + i]
-__global__ __launch_bounds__(256) void wltm_final_kernel(const double* __restrict__ partial, int64_t nrows, double scale, int cnt,
-                                                         int64_t ostride, double* __restrict__ out) {
+// out[c * ostride + i] = scale * sum_rows partial[c * cnt + i][row], one block per column (c, i), fixed summation order
+// (ggr_final_kernel's)
+__global__ __launch_bounds__(256) void ltm_final_kernel(const double* __restrict__ partial, int64_t nrows, double scale, int cnt,
+                                                        int64_t ostride, double* __restrict__ out) {
     __shared__ double red[256];
     const double* __restrict__ p = partial + (int64_t)blockIdx.x * nrows;
     double s = 0.0;
@@ -814,10 +728,11 @@ __global__ __launch_bounds__(256) void wltm_final_kernel(const double* __restric
     if (threadIdx.x == 0) out[(int64_t)c * ostride + i] = scale * red[0];
 }
 
-// ltm_prefix_kernel, one block per component: col = [NC][nE] sums | [NC][nE] steps, nE <= 512.  The steps are means of
-// elements, not integers: the prefix sum runs in index order, the same at every call.
-__global__ __launch_bounds__(256) void wltm_prefix_kernel(const double* __restrict__ col, int nE, int nc, double weight, int64_t ostride,
-                                                          double* __restrict__ out) {
+// State count of a chunk, one block per component: out[c * ostride + i] = weight * (sums[c][i] + steps[c][0] + ... + steps[c][i]);
+// col = [nc][nE] sums | [nc][nE] steps, nE <= 512.  The prefix sum runs in index order, the same at every call (the plain
+// scan's steps are integers, their sums exact; means of elements are not).
+__global__ __launch_bounds__(256) void ltm_prefix_kernel(const double* __restrict__ col, int nE, int nc, double weight, int64_t ostride,
+                                                         double* __restrict__ out) {
     __shared__ double st[512];
     const int c = (int)blockIdx.x;
     for (int i = threadIdx.x; i < nE; i += 256) st[i] = col[(size_t)(nc + c) * nE + i];
@@ -927,146 +842,111 @@ __global__ __launch_bounds__(256) void ltm_unfold_kernel(PlaneView src, PlaneVie
     for (int b = 0; b < n; ++b) out[(int64_t)b * dst.pitch] = in[(int64_t)b * src.pitch];
 }
 
-}  // namespace
-
-#define ABZ_LTM_D(ST)                                                                                         \
-    switch (d) {                                                                                              \
-        case 1: launch(ctx, (ltm_window_kernel<1, ST>), grid, dim3(256), lds, ag, partial, nrows); break;      \
-        case 2: launch(ctx, (ltm_window_kernel<2, ST>), grid, dim3(256), lds, ag, partial, nrows); break;      \
-        default: launch(ctx, (ltm_window_kernel<3, ST>), grid, dim3(256), lds, ag, partial, nrows); break;     \
-    }
-
-// the slab kernels take the same grid, block and LDS
-#define ABZ_LTM_SLAB_D(ST)                                                                                          \
-    if (d == 2) launch(ctx, (ltm_window_kernel<2, ST, true>), grid, dim3(256), lds, a, partial, nrows);             \
-    else launch(ctx, (ltm_window_kernel<3, ST, true>), grid, dim3(256), lds, a, partial, nrows);
-
-int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host,
-               const LtmSlab* slab) {
-    LtmSlabArgs a;
-    const LtmArgs& ag = a;  // what the whole-grid kernels take
-    a.E = E;
-    a.npt = npt;
-    a.ncell = 1;
-    for (int j = 0; j < d; ++j) a.ncell *= npt;
-    // the weight of a simplex is the whole grid's: the partial sums of the slabs of a partition add up to the grid's value
-    const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);
-    if (slab) {
-        if (d < 2 || slab->nz < 1 || slab->nz > npt || !slab->E.base) {
-            set_error("launch_ltm: a slab of %d planes of a %d-d grid of %d points", slab->nz, d, npt);
-            return ABZ_ERR_INTERNAL;
-        }
-        a.halo = slab->E;
-        a.nz = slab->nz;
-        a.ncell = a.ncell / npt * slab->nz;
-    }
-    // energies per launch: (1 + 4) x 8 KB of LDS for g, (1 + 8) x 4 KB for N (+ 1 KB of queue).  Chunks are independent: the steps of all
-    // simplices below a chunk's first energy land on its index 0.
-    const int CH = states ? 512 : 1024;
-    const int ncol = states ? 2 : 1;
-    // one block row per band; enough blocks to fill the device several times over, few enough partial rows to sum
-    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
-    const int64_t nrows = nblocks * n;
-    const int chmax = std::min(nE, CH);
-    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)(nrows * chmax * ncol));
-    if (rc) return rc;
-    double* partial = ctx->scratch[1].as<double>();
-    EnergyList el;
-    if ((rc = energies_to_device(ctx, Es_host, nE, true, 2 * (size_t)CH, el))) return rc;
-    double* col = el.extra;  // states: column sums of a chunk [cnt sums | cnt steps]
-    a.inv_step = el.inv_step;
-    for (int s0 = 0; s0 < nE; s0 += CH) {
-        const int cnt = std::min(CH, nE - s0);
-        a.Es = el.dev + s0;
-        a.nE = cnt;
-        ProfScope ps(ctx, ABZ_K_LTM);
-        const size_t lds = sizeof(double) * (states ? 9 : 5) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
-        const dim3 grid((unsigned)nblocks, (unsigned)n);
-        if (states) {
-            if (slab) {
-                ABZ_LTM_SLAB_D(true);
-            } else {
-                ABZ_LTM_D(true);
-            }
-            ABZ_HIP(hipGetLastError());
-            launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
-            ABZ_HIP(hipGetLastError());
-            launch(ctx, ltm_prefix_kernel, dim3(1), dim3(256), 0, col, cnt, weight, el.out + s0);
-        } else {
-            if (slab) {
-                ABZ_LTM_SLAB_D(false);
-            } else {
-                ABZ_LTM_D(false);
-            }
-            ABZ_HIP(hipGetLastError());
-            launch(ctx, ltm_final_kernel, dim3((unsigned)cnt), dim3(256), 0, partial, nrows, weight, el.out + s0);
-        }
-        ABZ_HIP(hipGetLastError());
-    }
-    return energies_deliver(ctx, el, out_host);
-}
-#undef ABZ_LTM_D
-#undef ABZ_LTM_SLAB_D
-
-namespace {
-template <int D, bool ST, int NC, bool CORR>
-void wltm_launch(abz_ctx* ctx, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
-    launch(ctx, (wltm_window_kernel<D, ST, NC, CORR>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
-}
-template <bool ST, int NC, bool CORR>
-void wltm_launch_d(abz_ctx* ctx, int d, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
-    switch (d) {
-        case 1: wltm_launch<1, ST, NC, CORR>(ctx, grid, lds, a, partial, nrows); break;
-        case 2: wltm_launch<2, ST, NC, CORR>(ctx, grid, lds, a, partial, nrows); break;
-        default: wltm_launch<3, ST, NC, CORR>(ctx, grid, lds, a, partial, nrows); break;
-    }
-}
-template <bool ST, bool CORR = false>
-void wltm_launch_nc(abz_ctx* ctx, int d, int nc, dim3 grid, size_t lds, const WLtmArgs& a, double* partial, int64_t nrows) {
-    switch (nc) {
-        case 1: wltm_launch_d<ST, 1, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
-        case 2: wltm_launch_d<ST, 2, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
-        default: wltm_launch_d<ST, 4, CORR>(ctx, d, grid, lds, a, partial, nrows); break;
-    }
-}
-// a slab: the energy as the element (one component), with or without the correction
-template <bool ST, bool CORR = false>
-void wltm_launch_slab(abz_ctx* ctx, int d, dim3 grid, size_t lds, const WLtmSlabArgs& a, double* partial, int64_t nrows) {
-    if (d == 2) launch(ctx, (wltm_window_kernel<2, ST, 1, CORR, true>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
-    else launch(ctx, (wltm_window_kernel<3, ST, 1, CORR, true>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
-}
-// dynamic LDS of the shipped scans: 5 x 1024 (g) energies x 8 B + queue and counts; the weighted scans stay within it
+// dynamic LDS of the plain g scan at 1024 energies: 5 x 1024 x 8 B + queue and counts; every scan stays within it
 constexpr size_t LTM_LDS_MAX = sizeof(double) * 5 * 1024 + sizeof(uint32_t) * (256 + 8);
-}  // namespace
 
-int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
-                        int what, double* out_host, const LtmSlab* slab) {
+using LtmWindowFn = void (*)(abz_ctx*, dim3, size_t, const WLtmSlabArgs&, double*, int64_t);
+template <int D, bool STATES, bool SLAB, class P>
+void ltm_window(abz_ctx* ctx, dim3 grid, size_t lds, const WLtmSlabArgs& a, double* partial, int64_t nrows) {
+    launch(ctx, (ltm_window_kernel<D, STATES, SLAB, P>), grid, dim3(256), (unsigned)lds, P::template args<SLAB>(a), partial, nrows);
+}
+
+// The compiled window kernels, all of them: a scan that is not in this table is refused.
+struct LtmWindowRow {
+    int d;
+    bool states, slab, elems;
+    int nc;
+    bool corr;
+    LtmWindowFn fn;
+};
+template <int D, bool STATES, bool SLAB, class P>
+constexpr LtmWindowRow ltm_row() {
+    return {D, STATES, SLAB, P::ELEMS, P::NC, P::CORR, ltm_window<D, STATES, SLAB, P>};
+}
+// the element payloads of the table: without and with the curvature correction; the digit is NC
+using Elems1 = LtmElems<1, false>;
+using Elems2 = LtmElems<2, false>;
+using Elems4 = LtmElems<4, false>;
+using Corr1 = LtmElems<1, true>;
+using Corr2 = LtmElems<2, true>;
+using Corr4 = LtmElems<4, true>;
+constexpr LtmWindowRow LTM_WINDOWS[] = {
+    // plain, whole grid (6) and slab (4)
+    ltm_row<1, false, false, LtmPlain>(), ltm_row<2, false, false, LtmPlain>(), ltm_row<3, false, false, LtmPlain>(),
+    ltm_row<1, true, false, LtmPlain>(), ltm_row<2, true, false, LtmPlain>(), ltm_row<3, true, false, LtmPlain>(),
+    ltm_row<2, false, true, LtmPlain>(), ltm_row<3, false, true, LtmPlain>(),
+    ltm_row<2, true, true, LtmPlain>(), ltm_row<3, true, true, LtmPlain>(),
+    // elements, whole grid: g_A and N_A with 1, 2, 4 components (18)
+    ltm_row<1, false, false, Elems1>(), ltm_row<2, false, false, Elems1>(), ltm_row<3, false, false, Elems1>(),
+    ltm_row<1, false, false, Elems2>(), ltm_row<2, false, false, Elems2>(), ltm_row<3, false, false, Elems2>(),
+    ltm_row<1, false, false, Elems4>(), ltm_row<2, false, false, Elems4>(), ltm_row<3, false, false, Elems4>(),
+    ltm_row<1, true, false, Elems1>(), ltm_row<2, true, false, Elems1>(), ltm_row<3, true, false, Elems1>(),
+    ltm_row<1, true, false, Elems2>(), ltm_row<2, true, false, Elems2>(), ltm_row<3, true, false, Elems2>(),
+    ltm_row<1, true, false, Elems4>(), ltm_row<2, true, false, Elems4>(), ltm_row<3, true, false, Elems4>(),
+    // elements, whole grid: corrected N_A (9)
+    ltm_row<1, true, false, Corr1>(), ltm_row<2, true, false, Corr1>(), ltm_row<3, true, false, Corr1>(),
+    ltm_row<1, true, false, Corr2>(), ltm_row<2, true, false, Corr2>(), ltm_row<3, true, false, Corr2>(),
+    ltm_row<1, true, false, Corr4>(), ltm_row<2, true, false, Corr4>(), ltm_row<3, true, false, Corr4>(),
+    // elements, slab: one component (the energy as the element), g_A, N_A, corrected N_A (6)
+    ltm_row<2, false, true, Elems1>(), ltm_row<3, false, true, Elems1>(),
+    ltm_row<2, true, true, Elems1>(), ltm_row<3, true, true, Elems1>(),
+    ltm_row<2, true, true, Corr1>(), ltm_row<3, true, true, Corr1>(),
+};
+static_assert(sizeof(LTM_WINDOWS) / sizeof(LTM_WINDOWS[0]) == 43, "the shipped window kernels");
+
+LtmWindowFn ltm_window_fn(int d, bool states, bool slab, bool elems, int nc, bool corr) {
+    for (const LtmWindowRow& r : LTM_WINDOWS)
+        if (r.d == d && r.states == states && r.slab == slab && r.elems == elems && r.nc == nc && r.corr == corr) return r.fn;
+    return nullptr;
+}
+
+// The scan behind launch_ltm (A == nullptr: the plain payload, one "component") and launch_ltm_weighted.
+int ltm_scan(abz_ctx* ctx, const char* who, int n, int d, int npt, PlaneView E, const PlaneView* A, int ncomp, const double* Es_host, int nE,
+             int what, double* out_host, const LtmSlab* slab) {
     const bool states = what != ABZ_LTM_DOS, corrected = what == ABZ_LTM_STATES_CORRECTED;
-    WLtmSlabArgs a;  // (the whole-grid kernels take its WLtmArgs part)
+    WLtmSlabArgs a;  // the superset: every kernel takes its own part (args() of its payload)
     a.E = E;
-    a.A = A;
-    a.acomp = (int64_t)n * A.pitch;
     a.npt = npt;
     a.ncell = 1;
     for (int j = 0; j < d; ++j) a.ncell *= npt;
-    const double weight = 1.0 / ((d == 3 ? 6.0 : (d == 2 ? 2.0 : 1.0)) * (double)a.ncell);  // the whole grid's, as in launch_ltm
+    if (A) {
+        a.A = *A;
+        a.acomp = (int64_t)n * A->pitch;
+    }
+    // the weight of a simplex is the whole grid's: the partial sums of the slabs of a partition add up to the grid's value
+    const double weight = 1.0 / ((double)ltm_nsimplex(d) * (double)a.ncell);
     if (slab) {
-        if (d < 2 || slab->nz < 1 || slab->nz > npt || !slab->E.base || !slab->A.base || ncomp != 1) {
-            set_error("launch_ltm_weighted: a slab of %d planes of a %d-d grid of %d points with %d components", slab->nz, d, npt, ncomp);
+        if (d < 2 || slab->nz < 1 || slab->nz > npt || !slab->E.base || (A && (!slab->A.base || ncomp != 1))) {
+            if (A) set_error("%s: a slab of %d planes of a %d-d grid of %d points with %d components", who, slab->nz, d, npt, ncomp);
+            else set_error("%s: a slab of %d planes of a %d-d grid of %d points", who, slab->nz, d, npt);
             return ABZ_ERR_INTERNAL;
         }
         a.haloE = slab->E;
-        a.haloA = slab->A;
+        if (A) a.haloA = slab->A;
         a.nz = slab->nz;
         a.ncell = a.ncell / npt * slab->nz;
     }
+    // the window kernels of the component groups this call will form (4s, then a 2, then a 1): refused before anything is
+    // reserved or launched
+    LtmWindowFn window[5] = {};
+    for (int nc : {1, 2, 4}) {
+        if (!(nc == 4 ? ncomp >= 4 : (ncomp % 4 & nc) != 0)) continue;
+        window[nc] = ltm_window_fn(d, states, slab != nullptr, A != nullptr, nc, corrected);
+        if (!window[nc]) {
+            set_error("%s: no tetrahedron scan for d = %d, what = %d, %d components%s%s", who, d, what, nc, A ? " of elements" : "",
+                      slab ? ", on a slab" : "");
+            return ABZ_ERR_INTERNAL;
+        }
+    }
     const int ncol = states ? 2 : 1;
-    // Energies per launch of NC components: 8 (1 + 4 NC ncol) B of LDS each, within LTM_LDS_MAX, and at most 512 where the
-    // prefix kernel holds a chunk's steps: g 1024 / 568 / 301, N 512 / 301 / 155 for NC = 1 / 2 / 4.
+    // Energies per launch of NC components: 8 (1 + 4 NC ncol) B of LDS each (+ 1 KB of queue), within LTM_LDS_MAX, and at most
+    // 512 where the prefix kernel holds a chunk's steps: g 1024 / 568 / 301, N 512 / 301 / 155 for NC = 1 / 2 / 4.  Chunks are
+    // independent: the steps of all simplices below a chunk's first energy land on its index 0.
     auto chunk = [&](int nc) {
         const size_t fit = (LTM_LDS_MAX - sizeof(uint32_t) * (256 + 8)) / (sizeof(double) * (size_t)(1 + 4 * nc * ncol));
         return (int)std::min<size_t>(fit, states ? 512 : 1024);
     };
+    // one block row per band; enough blocks to fill the device several times over, few enough partial rows to sum
     const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
     const int64_t nrows = nblocks * n;
     size_t pmax = 0;
@@ -1076,8 +956,9 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
     if (rc) return rc;
     double* partial = ctx->scratch[1].as<double>();
     EnergyList el;
-    if ((rc = energies_to_device(ctx, Es_host, nE, true, 2 * 4 * (size_t)512, el, ncomp))) return rc;
-    double* col = el.extra;  // states: column sums of a launch [nc][cnt] sums | [nc][cnt] steps
+    // behind the energies: the column sums of a launch, [nc][cnt] sums | [nc][cnt] steps (states)
+    if ((rc = energies_to_device(ctx, Es_host, nE, true, A ? 2 * 4 * (size_t)512 : 2 * (size_t)chunk(1), el, ncomp))) return rc;
+    double* col = el.extra;
     a.inv_step = el.inv_step;
     const dim3 grid((unsigned)nblocks, (unsigned)n);
     // groups of 4 components, then 2, then 1; every group walks the grid once per chunk of energies
@@ -1092,26 +973,31 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
             ProfScope ps(ctx, ABZ_K_LTM);
             const size_t lds = sizeof(double) * (size_t)(1 + 4 * nc * ncol) * (size_t)cnt + sizeof(uint32_t) * (256 + 8);
             double* const o = el.out + (size_t)c0 * nE + s0;  // results [ncomp][nE] in sorted order
+            window[nc](ctx, grid, lds, a, partial, nrows);
+            ABZ_HIP(hipGetLastError());
             if (states) {
-                if (slab && corrected) wltm_launch_slab<true, true>(ctx, d, grid, lds, a, partial, nrows);
-                else if (slab) wltm_launch_slab<true>(ctx, d, grid, lds, a, partial, nrows);
-                else if (corrected) wltm_launch_nc<true, true>(ctx, d, nc, grid, lds, a, partial, nrows);
-                else wltm_launch_nc<true>(ctx, d, nc, grid, lds, a, partial, nrows);
+                launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, partial, nrows, 1.0, 2 * nc * cnt, (int64_t)0, col);
                 ABZ_HIP(hipGetLastError());
-                launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, partial, nrows, 1.0, col);
-                ABZ_HIP(hipGetLastError());
-                launch(ctx, wltm_prefix_kernel, dim3((unsigned)nc), dim3(256), 0, col, cnt, nc, weight, (int64_t)nE, o);
+                launch(ctx, ltm_prefix_kernel, dim3((unsigned)nc), dim3(256), 0, col, cnt, nc, weight, (int64_t)nE, o);
             } else {
-                if (slab) wltm_launch_slab<false>(ctx, d, grid, lds, a, partial, nrows);
-                else wltm_launch_nc<false>(ctx, d, nc, grid, lds, a, partial, nrows);
-                ABZ_HIP(hipGetLastError());
-                launch(ctx, wltm_final_kernel, dim3((unsigned)(nc * cnt)), dim3(256), 0, partial, nrows, weight, cnt, (int64_t)nE, o);
+                launch(ctx, ltm_final_kernel, dim3((unsigned)(nc * cnt)), dim3(256), 0, partial, nrows, weight, cnt, (int64_t)nE, o);
             }
             ABZ_HIP(hipGetLastError());
         }
         c0 += nc;
     }
     return energies_deliver(ctx, el, out_host);
+}
+}  // namespace
+
+int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host,
+               const LtmSlab* slab) {
+    return ltm_scan(ctx, "launch_ltm", n, d, npt, E, nullptr, 1, Es_host, nE, states ? ABZ_LTM_STATES : ABZ_LTM_DOS, out_host, slab);
+}
+
+int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
+                        int what, double* out_host, const LtmSlab* slab) {
+    return ltm_scan(ctx, "launch_ltm_weighted", n, d, npt, E, &A, ncomp, Es_host, nE, what, out_host, slab);
 }
 
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk) {

@@ -1,5 +1,5 @@
 """Bloechl's curvature correction of the weighted state sums on the device (ABZ_LTM_STATES_CORRECTED of
-abz_rule_ltm_weighted; wltm_window_kernel<D, true, NC, true> of kernels_ltm.hip) against the numpy restatements:
+abz_rule_ltm_weighted; ltm_window_kernel<D, true, SLAB, LtmElems<NC, true>> of kernels_ltm.hip) against the numpy restatements:
 N_A of tests/wltm_numpy.py plus the correction of tests/bloechl_numpy.py, both fed the rule's own exported eigenvalues
 and the very elements that are attached.
 

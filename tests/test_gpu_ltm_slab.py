@@ -1,4 +1,4 @@
-"""LTM on slabs of the grid (abz_rule_ltm_halo; the slab instantiations of ltm_window_kernel / wltm_window_kernel in
+"""LTM on slabs of the grid (abz_rule_ltm_halo; the slab instantiations of ltm_window_kernel, both payloads, in
 kernels_ltm.hip; DeviceRule.ltm_halo and dos.solve(..., LTM()) under dist.kshard) against the slab restatement of
 tests/slab_ltm_numpy.py and against the whole-grid scans.
 

@@ -1,5 +1,5 @@
 """Tetrahedron method with matrix elements and the Fermi level on the device (abz_rule_ltm_elements,
-abz_rule_ltm_weighted, abz_rule_ltm_fermi; wltm_window_kernel of kernels_ltm.hip) against the geometric restatement
+abz_rule_ltm_weighted, abz_rule_ltm_fermi; ltm_window_kernel with the LtmElems payload, kernels_ltm.hip) against the geometric restatement
 of tests/wltm_numpy.py and against the shipped unweighted scan.
 
 Parity bound: the restatement is fed the rule's own exported eigenvalues and the very elements that are attached, so
