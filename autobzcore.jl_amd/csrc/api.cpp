@@ -2222,6 +2222,22 @@ int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) tr
     return launch_ltm(ctx, r->s->n, r->s->d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out, ltm_slab_of(r, slab) ? &slab : nullptr);
 } ABZ_CATCH_ALL
 
+int abz_rule_ltm_green(abz_rule* r, const double* z, int nz, double* out) try {
+    int rc0 = check_rule(r);
+    if (rc0) return rc0;
+    ABZ_REQUIRE(z && out && nz >= 1, "abz_rule_ltm_green: bad arguments");
+    int rc = ltm_check_grid(r, "abz_rule_ltm_green");
+    if (rc) return rc;
+    for (int i = 0; i < nz; ++i) {
+        const double re = z[2 * (size_t)i], im = z[2 * (size_t)i + 1];
+        ABZ_REQUIRE(std::isfinite(re) && std::isfinite(im), "abz_rule_ltm_green: z[%d] = (%g, %g) is not finite", i, re, im);
+        ABZ_REQUIRE(im != 0.0, "abz_rule_ltm_green: z[%d] = %g is real; the trace is computed off the real axis (Im z != 0)", i, re);
+    }
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    return launch_ltm_green(ctx, r->s->n, r->s->d, r->npt, r->E, z, nz, out);
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
     int rc = check_rule(r);
     if (rc) return rc;

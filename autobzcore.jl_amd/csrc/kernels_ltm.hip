@@ -988,7 +988,304 @@ int ltm_scan(abz_ctx* ctx, const char* who, int n, int d, int npt, PlaneView E, 
     }
     return energies_deliver(ctx, el, out_host);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Trace of the Green's function at complex energies (abz_rule_ltm_green)
+// ---------------------------------------------------------------------------------------------------------------------
+// tr G(z) = w sum_{cells} sum_{d! simplices} sum_{bands} J[x_0 .. x_d](z), w = 1 / (d! npt^d), on the mesh of the scans above.
+// J[x_0 .. x_m](z) is the mean of 1 / (z - e) over a simplex in which e is linear with the sorted corner values x_0 <= .. <= x_m
+// (the mean over the normalised B-spline with those knots).  With u_i = z - x_i, which all share Im z > 0:
+//      m = 0:  J = 1 / u_0
+//      m = 1:  J = (log u_0 - log u_1) / (x_1 - x_0)     principal logs of one open half plane: no branch fix-up
+//      m >= 2: J[x_0..x_m] = m / (m-1) (u_0 J[x_0..x_{m-1}] - u_m J[x_1..x_m]) / (x_m - x_0)
+//  * Evaluation rule.  The recursion divides by a width and loses |u| / width per level; a symmetric grid is full of equal and
+//    nearly equal corners.  A sub-range x_i..x_j with x_j - x_i < rho |z - mean|, rho = 1/2, is summed by its Taylor series
+//      J = sum_k  m! k! / (m+k)!  h_k(delta) / ubar^(k+1),   delta_l = x_l - mean,  ubar = z - mean,
+//    h_k the complete homogeneous symmetric polynomial by H_l^(k) = H_(l-1)^(k) + delta_l H_l^(k-1), H_0^(k) = delta_0^k: one
+//    row of m + 1 registers carried from k - 1 to k, the coefficients from a table.  It stops when (max |delta| / |ubar|)^k < 2^-52:
+//    max |delta| <= m / (m+1) width, so the ratio stays below 3/8 and 37 terms are the most a sub-range takes.  Only wider
+//    sub-ranges recurse: nothing is divided by a width below rho |ubar|.  The series runs on delta / |ubar| and ubar / |ubar|, so
+//    neither power leaves the range of a double; at width 0 it is 1 / u.
+//  * Shape (ltm_green_kernel<D>).  Not a window scan: every simplex contributes at every z, there is no queue and no histogram.
+//    The cell walk and the whole-grid corner geometry are ltm_window_kernel's: blocks of 256 cells, one cell per thread,
+//    blockIdx.y the band, the 2^d corner energies in registers, the values of z in LDS.  Per (cell, z) the 2^d complex logs of
+//    z - e_corner are taken once and shared by the cell's d! simplices; the sorting network of a simplex carries each corner's
+//    log along with its energy, as LtmElems carries elements, and the pair formula reads them.  blockIdx.z splits the values of
+//    z of a launch where the cells alone do not fill the device.
+//  * Reduction.  Per z in a fixed order: a butterfly over the wave, lane 0 adds into the wave's LDS slot [nz][re, im] in
+//    program order, the four waves are summed as above into transposed partials and ltm_final_kernel finishes.  No atomics:
+//    two calls return the same bits.
+constexpr double GREEN_RHO2 = 0.25;      // rho^2
+constexpr double GREEN_EPS2 = 0x1p-104;  // (2^-52)^2
+constexpr int GREEN_KMAX = 40;           // terms beyond k = 37 are never asked for (see above)
+constexpr int LTM_GREEN_CHUNK = 512;     // values of z per launch: 8 (2 + 4 x 2) B of LDS each
+static_assert(sizeof(double) * 10 * LTM_GREEN_CHUNK <= LTM_LDS_MAX, "the z list and the four waves' sums fit the scans' LDS");
+
+// m! k! / (m+k)! for m = 1, 2, 3
+struct GreenCoef {
+    double c[3][GREEN_KMAX + 1];
+};
+constexpr GreenCoef green_coef() {
+    GreenCoef t{};
+    for (int m = 1; m <= 3; ++m) {
+        t.c[m - 1][0] = 1.0;
+        for (int k = 1; k <= GREEN_KMAX; ++k) t.c[m - 1][k] = t.c[m - 1][k - 1] * (double)k / (double)(m + k);
+    }
+    return t;
+}
+__constant__ const GreenCoef GREEN_COEF = green_coef();
+
+struct GreenArgs {
+    PlaneView E;
+    const double* z;  // device [nz][2]: re, im > 0
+    int64_t ncell;    // npt^d
+    int npt, nz;
+    int zper;         // values of z per blockIdx.z
+};
+
+struct Cx {
+    double re, im;
+};
+__device__ __forceinline__ Cx cx_mul(Cx a, Cx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+
+// what the sort of a simplex carries per corner: the energy and log(z - energy)
+struct GreenCorner {
+    double x, lr, li;
+};
+__device__ __forceinline__ GreenCorner green_sel(bool first, const GreenCorner& a, const GreenCorner& b) {
+    return {first ? a.x : b.x, first ? a.lr : b.lr, first ? a.li : b.li};
+}
+__device__ __forceinline__ void green_cx(GreenCorner& a, GreenCorner& b) {
+    const bool sw = b.x < a.x;
+    const GreenCorner lo = green_sel(sw, b, a), hi = green_sel(sw, a, b);
+    a = lo;
+    b = hi;
+}
+
+// The Taylor series of J[x_0 .. x_M] about the mean; u[l] = Re z - x_l, ur their mean, (ur, ui) = ubar, n2 = |ubar|^2.  The mean
+// and delta_l = ur - u[l] come from the differences Re z - x_l, which are exact and small close to a corner: ubar then carries a
+// relative error of eps, where the rounding of mean(x), eps |x|, would move 1 / ubar by eps |x| / |ubar|^2.
+template <int M>
+__device__ __forceinline__ Cx green_series(const double (&u)[M + 1], double ur, double ui, double n2) {
+    const double s = 1.0 / sqrt(n2);
+    double dl[M + 1], H[M + 1];
+    double r2 = 0.0;
+#pragma unroll
+    for (int l = 0; l <= M; ++l) {
+        dl[l] = (ur - u[l]) * s;
+        H[l] = 1.0;
+        r2 = fmax(r2, dl[l] * dl[l]);
+    }
+    const Cx q = {ur * s, -ui * s};  // 1 / (ubar / |ubar|)
+    Cx acc = q, p = q;
+    double rk2 = r2;
+    for (int k = 1; rk2 >= GREEN_EPS2 && k <= GREEN_KMAX; ++k) {
+        H[0] *= dl[0];
+#pragma unroll
+        for (int l = 1; l <= M; ++l) H[l] = H[l - 1] + dl[l] * H[l];
+        p = cx_mul(p, q);
+        const double t = GREEN_COEF.c[M - 1][k] * H[M];
+        acc.re += t * p.re;
+        acc.im += t * p.im;
+        rk2 *= r2;
+    }
+    return {acc.re * s, acc.im * s};
+}
+
+// J of two sorted corners
+__device__ __forceinline__ Cx green_pair(const GreenCorner& a, const GreenCorner& b, double zr, double zi) {
+    const double u[2] = {zr - a.x, zr - b.x};
+    const double w = b.x - a.x, ur = 0.5 * (u[0] + u[1]), n2 = ur * ur + zi * zi;
+    if (w * w < GREEN_RHO2 * n2) return green_series<1>(u, ur, zi, n2);
+    const double iw = 1.0 / w;
+    return {(a.lr - b.lr) * iw, (a.li - b.li) * iw};
+}
+
+// J of three sorted corners from the J of its two pairs, which only a wide triple reads
+__device__ __forceinline__ Cx green_triple(const GreenCorner& a, const GreenCorner& b, const GreenCorner& c, Cx pab, Cx pbc, double zr,
+                                           double zi) {
+    const double u[3] = {zr - a.x, zr - b.x, zr - c.x};
+    const double w = c.x - a.x, ur = (u[0] + u[1] + u[2]) * (1.0 / 3.0), n2 = ur * ur + zi * zi;
+    if (w * w < GREEN_RHO2 * n2) return green_series<2>(u, ur, zi, n2);
+    const Cx t0 = cx_mul({u[0], zi}, pab), t1 = cx_mul({u[2], zi}, pbc);
+    const double f = 2.0 / w;
+    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
+}
+
+// J of a simplex with corners in any order
+__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, double zr, double zi) {
+    green_cx(a, b);
+    return green_pair(a, b, zr, zi);
+}
+__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenCorner c, double zr, double zi) {
+    green_cx(a, b);
+    green_cx(b, c);
+    green_cx(a, b);
+    return green_triple(a, b, c, green_pair(a, b, zr, zi), green_pair(b, c, zr, zi), zr, zi);
+}
+__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenCorner c, GreenCorner d, double zr, double zi) {
+    green_cx(a, b);
+    green_cx(c, d);
+    green_cx(a, c);
+    green_cx(b, d);
+    green_cx(b, c);
+    const double u[4] = {zr - a.x, zr - b.x, zr - c.x, zr - d.x};
+    const double w = d.x - a.x, ur = 0.25 * ((u[0] + u[1]) + (u[2] + u[3])), n2 = ur * ur + zi * zi;
+    if (w * w < GREEN_RHO2 * n2) return green_series<3>(u, ur, zi, n2);
+    // the two triples share the middle pair
+    const Cx p01 = green_pair(a, b, zr, zi), p12 = green_pair(b, c, zr, zi), p23 = green_pair(c, d, zr, zi);
+    const Cx j0 = green_triple(a, b, c, p01, p12, zr, zi), j1 = green_triple(b, c, d, p12, p23, zr, zi);
+    const Cx t0 = cx_mul({u[0], zi}, j0), t1 = cx_mul({u[3], zi}, j1);
+    const double f = 1.5 / w;
+    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
+}
+
+// partial [2 nz][nrows]: column 2 i + {0, 1} the real and imaginary part of the sum at z_i
+template <int D>
+__global__ __launch_bounds__(256) void ltm_green_kernel(GreenArgs a, double* __restrict__ partial, int64_t nrows) {
+    // [zn][2] this block's values of z | [4 waves][zn][2] sums
+    extern __shared__ __attribute__((aligned(16))) double ldsg[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr int NV = 1 << D;  // corners per cell
+    const int z0 = (int)blockIdx.z * a.zper;
+    const int zn = min(a.zper, a.nz - z0);
+    const double* const zl = ldsg;
+    double* const acc = ldsg + (size_t)2 * zn * (1 + wave);
+    for (int i = threadIdx.x; i < 2 * zn; i += 256) ldsg[i] = a.z[2 * z0 + i];
+    for (int i = threadIdx.x; i < 8 * zn; i += 256) ldsg[2 * zn + i] = 0.0;
+    __syncthreads();
+    const int npt = a.npt;
+    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
+    const int64_t tileE = a.E.tile;
+    // the whole-grid geometry of ltm_window_kernel: corner `bits` of cell (i1, i2, i3), every index wrapped mod npt
+    auto cornerE = [&](int i1, int i2, int i3, int bits) -> double {
+        if ((bits & 1) && ++i1 == npt) i1 = 0;
+        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
+        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
+        return Eb[((int64_t)i3 * npt + i2) * tileE + i1];
+    };
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
+        const int64_t k = base + threadIdx.x;
+        const bool active = k < a.ncell;
+        double c[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) c[j] = 0.0;
+        if (active) {
+            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
+            const int i1 = (int)(k - line * npt);
+            const int i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
+            const int i2 = (int)line - i3 * npt;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) c[j] = cornerE(i1, i2, i3, j);
+        }
+        for (int iz = 0; iz < zn; ++iz) {
+            const double zr = zl[2 * iz], zi = zl[2 * iz + 1];
+            double sr = 0.0, si = 0.0;
+            if (active) {
+                GreenCorner g[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const double ur = zr - c[j];
+                    g[j] = {c[j], 0.5 * log(ur * ur + zi * zi), atan2(zi, ur)};
+                }
+                if constexpr (D == 3) {
+                    // the permutation (X, Y, Z) of the axes: corners 0, e_X, e_X + e_Y, (1,1,1); a loop, the corners by selects
+#pragma unroll 1
+                    for (int t = 0; t < 6; ++t) {
+                        const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3;
+                        const int bb = (1 << X) | (1 << Y);
+                        const GreenCorner ga = green_sel(X == 0, g[1], green_sel(X == 1, g[2], g[4]));
+                        const GreenCorner gb = green_sel(bb == 3, g[3], green_sel(bb == 5, g[5], g[6]));
+                        const Cx J = green_simplex(g[0], ga, gb, g[7], zr, zi);
+                        sr += J.re;
+                        si += J.im;
+                    }
+                } else if constexpr (D == 2) {
+#pragma unroll 1
+                    for (int t = 0; t < 2; ++t) {
+                        const Cx J = green_simplex(g[0], green_sel(t == 0, g[1], g[2]), g[3], zr, zi);
+                        sr += J.re;
+                        si += J.im;
+                    }
+                } else {
+                    const Cx J = green_simplex(g[0], g[1], zr, zi);
+                    sr = J.re;
+                    si = J.im;
+                }
+            }
+            // every lane ends with the same bits: a + b == b + a at every level of the butterfly
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                sr += __shfl_xor(sr, off);
+                si += __shfl_xor(si, off);
+            }
+            if (lane == 0) {
+                acc[2 * iz] += sr;
+                acc[2 * iz + 1] += si;
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const double* h = ldsg + 2 * zn;
+    const size_t w = (size_t)2 * zn;  // from one wave's sums to the next
+    for (int t = threadIdx.x; t < 2 * zn; t += 256)
+        partial[(int64_t)(2 * z0 + t) * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
+}
+
+using LtmGreenFn = void (*)(GreenArgs, double*, int64_t);
+constexpr LtmGreenFn LTM_GREEN[3] = {ltm_green_kernel<1>, ltm_green_kernel<2>, ltm_green_kernel<3>};
 }  // namespace
+
+// z_host [nz][2] with Im z != 0, out_host [nz][2].  Im z < 0: the conjugate of the value at conj(z), to the bit.
+int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* z_host, int nz, double* out_host) {
+    GreenArgs a;
+    a.E = E;
+    a.npt = npt;
+    a.ncell = 1;
+    for (int j = 0; j < d; ++j) a.ncell *= npt;
+    const double weight = 1.0 / ((double)ltm_nsimplex(d) * (double)a.ncell);
+    std::vector<double> zup(2 * (size_t)nz);
+    for (size_t i = 0; i < (size_t)nz; ++i) {
+        zup[2 * i] = z_host[2 * i];
+        zup[2 * i + 1] = std::fabs(z_host[2 * i + 1]);
+    }
+    // the scans' grid: one block row per band, enough blocks to fill the device several times over, few enough partial rows
+    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
+    const int64_t nrows = nblocks * n;
+    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * 2 * (size_t)std::min(nz, LTM_GREEN_CHUNK));
+    if (rc) return rc;
+    double* partial = ctx->scratch[1].as<double>();
+    const double* zdev = nullptr;
+    if ((rc = sweep_to_device(ctx, zup.data(), 2 * nz, &zdev))) return rc;
+    SumOut so;
+    so.host = out_host;
+    if (mbox_reserve(ctx) == ABZ_OK && sizeof(double2) * (size_t)nz <= ctx->mbox_cap / 2) {  // the mailbox's result half
+        so.map_dev = reinterpret_cast<double2*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
+        so.map_host = reinterpret_cast<const double2*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
+    }
+    double2* where = nullptr;
+    if ((rc = sum_target(ctx, so, 0, nz, &where))) return rc;
+    for (int s0 = 0; s0 < nz; s0 += LTM_GREEN_CHUNK) {
+        const int cnt = std::min(LTM_GREEN_CHUNK, nz - s0);
+        // where the cells give fewer than ~2048 blocks the values of z are dealt to blockIdx.z, at least 4 per block
+        const int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(2048, nrows), cdiv64(cnt, 4)));
+        a.z = zdev + 2 * (size_t)s0;
+        a.nz = cnt;
+        a.zper = (int)cdiv64(cnt, nsplit);
+        const dim3 grid((unsigned)nblocks, (unsigned)n, (unsigned)cdiv64(cnt, a.zper));
+        ProfScope ps(ctx, ABZ_K_LTM);
+        launch(ctx, LTM_GREEN[d - 1], grid, dim3(256), (unsigned)(sizeof(double) * 10 * (size_t)a.zper), a, partial, nrows);
+        ABZ_HIP(hipGetLastError());
+        launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * cnt)), dim3(256), 0, (const double*)partial, nrows, weight, 2 * cnt, (int64_t)0,
+               reinterpret_cast<double*>(where + s0));
+        ABZ_HIP(hipGetLastError());
+    }
+    if ((rc = sum_deliver(ctx, so, where, 0, nz))) return rc;
+    for (size_t i = 0; i < (size_t)nz; ++i)
+        if (z_host[2 * i + 1] < 0.0) out_host[2 * i + 1] = -out_host[2 * i + 1];
+    return ABZ_OK;
+}
 
 int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* Es_host, int nE, bool states, double* out_host,
                const LtmSlab* slab) {

@@ -54,11 +54,25 @@ class LTM(DOSAlgorithm):
     On a k-sharded series (dist.kshard) every rank builds its slab of the grid and the one halo plane behind it
     (DeviceRule.ltm_halo), scans the cells of its slab, and the partial sums are summed over the ranks: `elements` None or
     "energy", with or without `cumulative` and `correction`.  "orbitals", a callable, `symmetric=True` on a symmetric zone,
-    `fermi_level` and `band_energy` raise NotImplementedError there."""
+    `fermi_level` and `band_energy` raise NotImplementedError there.
+
+    `eta > 0` returns the DOS broadened by a Lorentzian of half width eta instead, -Im tr G(E + i eta) / pi at the domain's
+    real energies, from the closed-form mean of 1 / (z - e) over every simplex (DeviceRule.ltm_green, `green_trace`).  Its
+    error is the interpolation error O(1/npt^2) whatever eta is -- a grid sum of the resolvent needs npt >~ bandwidth / eta --
+    and it tends to the plain g(E) linearly in eta.  It goes with `symmetric` only: `cumulative`, `elements` and
+    `correction` raise ValueError, a k-sharded series NotImplementedError.  Without `eta` nothing changes."""
 
     def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None,
-                 correction=False):
+                 correction=False, eta=None):
         self.npt = int(npt)
+        if eta is not None:
+            eta = float(eta)
+            if not (np.isfinite(eta) and eta > 0.0):
+                raise ValueError(f"LTM: eta = {eta!r} is not a positive finite broadening")
+            if cumulative or elements is not None or correction:
+                raise ValueError("LTM: eta gives the broadened DOS -Im tr G(E + i eta) / pi: it does not go with cumulative, elements "
+                                 "or correction")
+        self.eta = eta
         self.cumulative = bool(cumulative)
         self.symmetric = bool(symmetric)
         if not (elements is None or callable(elements) or elements in ("energy", "orbitals")):
@@ -133,6 +147,9 @@ def _init_cacheval(h, domain, p, alg):
         raise ValueError('LTM: elements = "orbitals" needs symmetric=False (orbital weights are not invariant under the zone\'s '
                          "symmetries, and an unfolded rule stores no H(k))")
     h.invalidate()  # coefficients may have been mutated in place (test/dos.jl:123): re-upload, rules refill lazily
+    if isinstance(alg, LTM) and alg.eta is not None and _ksharded(h.device()):
+        raise NotImplementedError("LTM(eta=...) on a k-sharded series is not implemented: the trace of the Green's function is "
+                                  "computed on whole grids")
     if isinstance(alg, LTM) and _ksharded(h.device()):
         # slabs of the full grid, each with its halo plane; what needs more than a sum of partial scans is refused here
         if alg.elements is not None and alg.elements != "energy":
@@ -194,6 +211,8 @@ def _ltm_elements(rule, alg):
 
 def _ltm_solve(c, Es):
     rule, el = c.cacheval, c.elements
+    if c.alg.eta is not None:
+        return -rule.ltm_green(Es + 1j * c.alg.eta).imag / np.pi
     if el is None or isinstance(el, str):
         return rule.ltm(Es, states=c.alg.cumulative, elements=el, correction=c.alg.correction)
     rule.h  # a stale rule refills here and loses its elements
@@ -245,6 +264,23 @@ def fermi_level(prob_or_cache, nstates, tol=1e-10):
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     return c.cacheval.ltm_fermi(nstates, tol)
+
+
+def green_trace(prob_or_cache, zs):
+    """tr G(z) = sum_b int dk / (z - e_b(k)) at the complex energies `zs` (Im z != 0), per unit cell, complex128 [nz], from the
+    eigenvalues of an LTM cache or of a DOSProblem (solved with LTM()): DeviceRule.ltm_green on the cache's grid."""
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+        raise NotImplementedError("green_trace on a k-sharded series is not implemented: the trace of the Green's function is "
+                                  "computed on whole grids")
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    if not isinstance(c.alg, LTM):
+        raise ValueError("green_trace needs an LTM cache")
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    return c.cacheval.ltm_green(zs)
 
 
 def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):

@@ -688,6 +688,21 @@ class DeviceRule:
                                                   Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
         return self._sum_over_ranks(out)
 
+    def ltm_green(self, zs):
+        """Trace of the Green's function tr G(z) = sum_b int dk / (z - e_b(k)) at the complex energies `zs`, per unit cell and
+        summed over bands, as complex128 [nz] (abz_rule_ltm_green): the closed-form mean of 1 / (z - e) over every simplex of
+        the mesh `ltm` scans, e linear inside a simplex.  -Im tr G(E + i eta) / pi is the DOS broadened by eta and tends to
+        `ltm(E)` as eta -> 0; the error is the interpolation error O(1/npt^2) whatever eta is, where a grid sum of the
+        resolvent needs npt >~ bandwidth / eta.  Every z needs Im z != 0 (Im z < 0 gives the conjugate of the value at conj z,
+        to the bit); two calls return the same bits.  The rule must be a whole periodic grid (an unfolded rule is one); a
+        k-sharded rule raises NotImplementedError, with or without its halo plane."""
+        self._ltm_refuse_shard("ltm_green")
+        zs = np.ascontiguousarray(np.asarray(zs, dtype=np.complex128).reshape(-1))
+        out = np.zeros(len(zs), dtype=np.complex128)
+        h = self.h  # (a stale rule is refilled here)
+        L.check(L.lib().abz_rule_ltm_green(h, zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs), out.view(np.float64).ctypes.data_as(L.c_f64p)))
+        return out
+
     def ltm_fermi(self, nstates, tol=1e-10):
         """(E_F, N(E_F)): the Fermi level of `nstates` states per unit cell, 0 < nstates < n, to within `tol`
         (abz_rule_ltm_fermi: a few N(E) scans of 512 energies each, no host bisection)."""

@@ -363,6 +363,23 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
  * symmetric rule, a rule of abz_rule_ltm_unfold.  A refusal or failure leaves r as it was.  Entry point added without a
  * change of ABZ_VERSION. */
 int abz_rule_ltm_halo(abz_rule* r);
+/* Trace of the Green's function at complex energies by the tetrahedron method: out[i] = tr G(z_i),
+ *      tr G(z) = w sum_{cells} sum_{d! simplices} sum_{bands} J[x_0 .. x_d](z),   w = 1 / (d! npt^d),
+ * per unit cell and summed over bands, on the mesh, weights and band convention of abz_rule_ltm, so that
+ * -Im tr G(E + i0) / pi -> g(E) of abz_rule_ltm and z tr G(z) -> n as |z| -> inf.  J[x_0 .. x_m](z) is the mean of 1 / (z - e)
+ * over a simplex in which e is linear with the sorted corner values x_0 <= .. <= x_m; with u_i = z - x_i:
+ *      m = 0: 1 / u_0;   m = 1: (log u_0 - log u_1) / (x_1 - x_0), principal logs;
+ *      m >= 2: J[x_0..x_m] = m / (m-1) (u_0 J[x_0..x_{m-1}] - u_m J[x_1..x_m]) / (x_m - x_0).
+ * Evaluation rule: a sub-range x_i..x_j with x_j - x_i < rho |z - mean|, rho = 1/2, is summed by its Taylor series about the
+ * mean, sum_k m! k! / (m+k)! h_k(x - mean) / (z - mean)^(k+1) (h_k: complete homogeneous symmetric polynomial), truncated where
+ * (max |x_l - mean| / |z - mean|)^k < 2^-52, at most 37 terms; only wider sub-ranges recurse, so nothing is divided by a width
+ * below rho |z - mean|, and equal corners give 1 / u.  The error is the interpolation error O(1 / npt^2) whatever Im z is.
+ * Im z < 0 is computed as the conjugate of the value at conj(z): tr G(conj z) == conj(tr G(z)) to the bit.  No floating-point
+ * atomics: two calls return the same bits.
+ * Takes the whole periodic grids abz_rule_ltm takes (full-grid rules and rules of abz_rule_ltm_unfold, 1...64 bands, d = 1...3).
+ * ABZ_ERR_UNSUPPORTED: slabs, with or without a halo; lists of irreducible nodes; symmetric rules.  ABZ_ERR_ARG: a rule without
+ * eigenvalues, nz < 1, a NULL pointer, any Im z == 0 or non-finite z.  Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_green(abz_rule* r, const double* z /* [nz][2]: re, im */, int nz, double* out /* [nz][2] */);
 
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.

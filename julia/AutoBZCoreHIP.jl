@@ -498,6 +498,19 @@ function ltm_halo!(r::HIPRule)
     return r
 end
 
+"""
+    ltm_green(r, zs)                          -> Vector{ComplexF64}
+
+Trace of the Green's function `tr G(z) = sum_b int dk / (z - e_b(k))` at the complex energies `zs` (`Im z != 0`), per unit
+cell, by the tetrahedron method on the eigenvalues of a whole-grid rule (`abz_rule_ltm_green`): `-imag(tr G(E + im*eta)) / pi`
+is the DOS broadened by `eta`, with the interpolation error `O(1/npt^2)` whatever `eta` is.
+"""
+function ltm_green(r::HIPRule, zs::Vector{ComplexF64})
+    out = Vector{ComplexF64}(undef, length(zs))
+    check(ccall((:abz_rule_ltm_green, libabz), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}), r.h, zs, length(zs), out))
+    return out
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
