@@ -6,13 +6,16 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/abzhip.h"
+#include "dev_buf.h"
 
 namespace abz {
 struct ProfScope;
+struct RulePlan;
 
 void set_error(const char* fmt, ...);
 int catch_status() noexcept;  // status + abz_last_error message of the exception in flight
@@ -134,20 +137,6 @@ struct SymTables;
 int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, SymTables& out);
 void preload_symptr_code();  // kernels_symptr.hip: force the lazy code-object load
 
-// caching device allocator (api.cpp): blocks freed with dev_free are reused by later dev_alloc calls
-int dev_alloc(void** out, size_t bytes, size_t* cap_out);
-void dev_free(void* p, size_t cap);
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool view = false;  // p points into a block owned elsewhere (release only forgets it)
-    int reserve(size_t bytes);
-    void release();
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
 // Tiled planar addressing of rule values: nodes are grouped in tiles of `line_len` consecutive nodes
 // (a grid line, or 64 nodes of an irregular list); a tile stores all its planes back to back, each
 // plane row `pitch` doubles long (pitch >= line_len, multiple of 16 = 128 B).  Element (node k,
@@ -181,7 +170,6 @@ struct SymTables {
     int64_t* parent[ABZ_MAX_DIM + 1] = {nullptr, nullptr, nullptr, nullptr};  // [0] level-1 item of a node, [L] level-(L+1) item of a level-L item
     int64_t* runs = nullptr;         // [nitems[1] + 1]: first node of every level-1 item (d >= 2)
     std::vector<int32_t> syms;       // the key, with npt and d
-    void release();
 };
 
 struct ProfSlot {
@@ -211,7 +199,7 @@ struct abz_ctx {
     size_t pin_cap = 0;
     // small pinned, device-visible mailbox: swept values go in through it without a synchronising pageable copy, and the
     // last kernel of a reduction writes its few sums straight into it (zero copy) -- one stream synchronisation per call
-    std::vector<abz::SymTables*> sym_cache;  // most recently used last
+    std::vector<std::unique_ptr<abz::SymTables>> sym_cache;  // most recently used last
     // phase tables e^{2 pi i j / npt} already on the device, by npt (they depend on nothing else): a rule build copies
     // its table device to device instead of 2 npt long-double sincos + a synchronising upload (0.03-0.07 ms per build)
     std::vector<std::pair<int, abz::DevBuf>> phase_cache;
@@ -242,11 +230,9 @@ struct abz_series {
     double period[ABZ_MAX_DIM] = {1, 1, 1};
     bool hermitian = false;   // c(-R) == c(R)^dagger exactly  =>  H(k) Hermitian: half the Fourier work
     int pivoting = ABZ_PIVOT_NONE;  // abz_series_set_pivoting: read at every launch of a resolvent integrand (series_pivots below)
-    size_t coef_cap = 0;
     abz::DevBuf coef_pk;       // Hermitian series, n <= 4: the coefficients with the innermost variable packed (packed_herm.h)
     bool coef_pk_valid = false;
-    double2* coef = nullptr;  // level d: [M_d]...[M_1][n*n] complex, i_1 fastest (Julia order)
-    bool coef_borrowed = false;       // a lane view: `coef` is its parent's block
+    abz::DevBuf coef;  // level d: [M_d]...[M_1][n*n] complex (double2), i_1 fastest (Julia order); a lane view: a view of its parent's block
     std::vector<abz_series*> lanes;   // views of this series on contexts (streams) of their own: the sweep lanes of abz_iai_solve_many
     // pools of contracted coefficient sets: level j (1 <= j < d) holds (j)-dim series of
     // elems(j) = M_1*...*M_j*n*n complex numbers per slot.
@@ -293,27 +279,25 @@ struct abz_rule {
     bool full = true;     // full grid (implicit nodes/weights) or explicit irregular list
     bool herm = false;    // values come from a Hermitian series (set by every fill): H(k) = H(k)^dagger
     int64_t k_offset = 0;  // full grids: flat grid index of node 0 (non-zero for a slab of the outermost variable)
-    double* vals = nullptr;  // [ntiles][planes][pitch]: H planes 2*(a + n*b) + {re, im}, then E (n), then V (d*n)
-    size_t vals_cap = 0, w_cap = 0, idx_cap = 0;  // block sizes as handed out by dev_alloc
+    abz::DevBuf vals;  // double [ntiles][planes][pitch]: H planes 2*(a + n*b) + {re, im}, then E (n), then V (d*n)
     int planes = 0;
     abz::PlaneView H, E, V;  // views into vals (base == nullptr when absent)
-    double* ltm_elems = nullptr;  // matrix elements of abz_rule_ltm_elements: [ntiles][ltm_ncomp * n planes][row]
-    size_t ltm_elems_cap = 0;
+    abz::DevBuf ltm_elems;  // matrix elements of abz_rule_ltm_elements: double [ntiles][ltm_ncomp * n planes][row]
     int ltm_ncomp = 0;
     abz::PlaneView A;        // view of ltm_elems
-    double* w = nullptr;   // [nk] weights (symmetric rules)
-    int32_t* idx = nullptr;  // [d][nk] grid indices (symmetric rules)
-    void* plan = nullptr;    // abz::RulePlan (api.cpp): contraction plan + phase table, device resident
-    bool tables_view = false;  // w and idx point into the plan's copy of the symmetric-rule tables
+    // symmetric rules: double [nk] weights and int32 [d][nk] grid indices; of a device-built rule, views into the plan's arena
+    abz::DevBuf w, idx;
+    std::unique_ptr<abz::RulePlan> plan;  // (api.cpp): contraction plan + phase table, device resident
     // a full-grid rule whose eigenvalue planes abz_rule_ltm_unfold gathers from the irreducible nodes of another rule:
-    int32_t* node_of = nullptr;  // [npt^d] the source node in the orbit of every grid point (the orbit map)
-    size_t node_of_cap = 0;
+    abz::DevBuf node_of;         // int32 [npt^d] the source node in the orbit of every grid point (the orbit map)
     int64_t unfold_nk = 0;       // nodes of the source rule the map was made for
     std::vector<int32_t> unfold_syms;  // the symmetries the map was made under [nsyms][d][d]
     // a slab rule made scannable by abz_rule_ltm_halo: the eigenvalue-only rule of the one plane behind the slab,
     // plane (outer_end mod npt) of the grid.  Owned by this rule (freed with it, refilled with it); holds no reference of
     // its own on the series.
-    abz_rule* ltm_halo = nullptr;
+    std::unique_ptr<abz_rule> ltm_halo;
+    abz_rule();
+    ~abz_rule();  // (api.cpp, where RulePlan is complete) on the owner's device, like every path that lets device blocks go
 };
 
 namespace abz {

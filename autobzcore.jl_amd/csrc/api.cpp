@@ -384,26 +384,6 @@ int energies_deliver(abz_ctx* ctx, EnergyList& el, double* out_host) {
     return ABZ_OK;
 }
 
-int DevBuf::reserve(size_t bytes) {
-    if (!view && bytes <= cap) return ABZ_OK;
-    release();
-    const size_t want = bytes + (bytes >> 2) + 256;  // grow geometrically
-    int rc = dev_alloc(&p, want, &cap);
-    if (rc) rc = dev_alloc(&p, bytes, &cap);
-    if (rc) {
-        p = nullptr;
-        cap = 0;
-    }
-    return rc;
-}
-
-void DevBuf::release() {
-    if (!view) dev_free(p, cap);
-    p = nullptr;
-    cap = 0;
-    view = false;
-}
-
 ProfScope::ProfScope(abz_ctx* c, int kernel_id) : ctx(c), id(kernel_id) {
     if (!(ctx->prof & (1u << id))) return;
     auto get = [&]() {
@@ -556,16 +536,6 @@ struct PlanDev {
     DevBuf phg[ABZ_MAX_DIM + 1];  // full grids: phase table [npt][M_{L+1}] of the contraction at level L
     DevBuf runs;                  // irregular lists: run_start
     DevBuf arena;                 // symmetric rules: the copy of the cached tables that gi / parent / runs (and the rule's w, idx) point into
-    void release() {
-        runs.release();
-        arena.release();
-        for (int i = 0; i <= ABZ_MAX_DIM; ++i) {
-            gi[i].release();
-            xs[i].release();
-            parent[i].release();
-            phg[i].release();
-        }
-    }
 };
 
 static int plan_upload(abz_ctx* ctx, const Plan& p, PlanDev& pd) {
@@ -622,7 +592,7 @@ int series_ensure_packed(abz_series* s) {
     const int64_t nrows = s->elems(s->d) / row_full;
     int rc = s->coef_pk.reserve(sizeof(double2) * (size_t)(nrows * row_len));
     if (rc) return rc;
-    if ((rc = launch_pack_rows(s->ctx, s->n, s->dims[0], s->coef, nrows, s->coef_pk.as<double2>()))) return rc;
+    if ((rc = launch_pack_rows(s->ctx, s->n, s->dims[0], s->coef.as<double2>(), nrows, s->coef_pk.as<double2>()))) return rc;
     s->coef_pk_valid = true;
     return ABZ_OK;
 }
@@ -638,7 +608,7 @@ static int build_chain(abz_series* s, const Plan& p, const PlanDev& pd, const do
         int rc = series_ensure_packed(s);
         if (rc) return rc;
     }
-    const double2* src = packed ? s->coef_pk.as<double2>() : s->coef;
+    const double2* src = (packed ? s->coef_pk : s->coef).as<double2>();
     int64_t src_elems = elems_of(d);
     // 3-D full grids down to level 1 without a derivative factor in the contractions: variables 3 and 2 in one
     // launch (contract_chain_kernel), the very sums of the two scalar-phase launches of the loop below
@@ -729,24 +699,17 @@ static void ctx_release(abz_ctx* ctx) {
     if (--ctx->refs > 0) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto& b : ctx->scratch) b.release();
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->mbox) (void)hipHostFree(ctx->mbox);
-    for (SymTables* c : ctx->sym_cache) {
-        c->release();
-        delete c;
-    }
-    ctx->sym_cache.clear();
-    for (auto& e : ctx->phase_cache) e.second.release();
-    ctx->phase_cache.clear();
     for (auto& sl : ctx->prof_slots)
         for (auto& pr : sl.pending) {
             (void)hipEventDestroy(pr.first);
             (void)hipEventDestroy(pr.second);
         }
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-    if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t own = ctx->owns_stream ? ctx->stream : nullptr;
+    delete ctx;  // with its device blocks: the device is selected, the stream idle and still there
+    if (own) (void)hipStreamDestroy(own);
 }
 
 static void series_release(abz_series* s) {
@@ -754,9 +717,6 @@ static void series_release(abz_series* s) {
     abz_ctx* ctx = s->ctx;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto& b : s->pool) b.release();
-    for (auto& b : s->iai_pool) b.release();
-    for (auto& b : s->iai_io) b.release();
     for (auto& q : s->iai_pin)
         if (q) (void)hipHostFree(q);
     for (abz_series* v : s->lanes) {  // the views go with their series, and each one's context with it
@@ -766,11 +726,8 @@ static void series_release(abz_series* s) {
         (void)abz_ctx_destroy(vc);
         (void)hipSetDevice(ctx->device);
     }
-    if (!s->coef_borrowed) dev_free(s->coef, s->coef_cap);
-    s->coef_pk.release();
-    s->auto_io.release();
     if (s->auto_pin) (void)hipHostFree(s->auto_pin);
-    delete s;
+    delete s;  // with its device blocks (the device is selected, the stream idle)
     ctx_release(ctx);
 }
 
@@ -902,35 +859,26 @@ int abz_series_create(abz_ctx* ctx, const double* coef_reim, int d, const int32_
     ABZ_REQUIRE(n >= 1 && n <= ABZ_MAX_BANDS, "n = %d bands not in 1..%d", n, ABZ_MAX_BANDS);
     *out = nullptr;
     ABZ_HIP(hipSetDevice(ctx->device));
-    abz_series* s = new abz_series();
+    std::unique_ptr<abz_series> s(new abz_series());
     s->ctx = ctx;
     s->d = d;
     s->n = n;
     for (int j = 0; j < d; ++j) {
-        if (dims[j] < 1 || !(period[j] > 0)) {
-            delete s;
-            set_error("dims[%d] = %d / period = %g invalid", j, dims[j], period[j]);
-            return ABZ_ERR_ARG;
-        }
+        ABZ_REQUIRE(dims[j] >= 1 && period[j] > 0, "dims[%d] = %d / period = %g invalid", j, dims[j], period[j]);
         s->dims[j] = dims[j];
         s->first[j] = first[j];
         s->period[j] = period[j];
     }
     const size_t bytes = sizeof(double2) * (size_t)s->elems(d);
-    if (dev_alloc((void**)&s->coef, bytes, &s->coef_cap)) {  // through the library's allocator: abz_mem_info sees it
-        delete s;
-        return ABZ_ERR_NOMEM;
-    }
-    hipError_t e = hipMemcpy(s->coef, coef_reim, bytes, hipMemcpyHostToDevice);
+    if (s->coef.alloc(bytes)) return ABZ_ERR_NOMEM;  // through the library's allocator: abz_mem_info sees it
+    hipError_t e = hipMemcpy(s->coef.p, coef_reim, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        dev_free(s->coef, s->coef_cap);
-        delete s;
         set_error("coefficient upload failed: %s", hipGetErrorString(e));
         return ABZ_ERR_HIP;
     }
-    s->hermitian = detect_hermitian(s, coef_reim);
+    s->hermitian = detect_hermitian(s.get(), coef_reim);
     ctx->refs += 1;
-    *out = s;
+    *out = s.release();  // (the handle: not a device block)
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
@@ -968,7 +916,7 @@ int abz_series_update(abz_series* s, const double* coef_reim) try {
     if (rc) return rc;
     ABZ_REQUIRE(coef_reim, "null coefficients");
     ABZ_HIP(hipSetDevice(s->ctx->device));
-    ABZ_HIP(hipMemcpyAsync(s->coef, coef_reim, sizeof(double2) * (size_t)s->elems(s->d), hipMemcpyHostToDevice,
+    ABZ_HIP(hipMemcpyAsync(s->coef.p, coef_reim, sizeof(double2) * (size_t)s->elems(s->d), hipMemcpyHostToDevice,
                            s->ctx->stream));
     ABZ_HIP(hipStreamSynchronize(s->ctx->stream));
     s->hermitian = detect_hermitian(s, coef_reim);
@@ -1019,8 +967,7 @@ int series_lane_views(abz_series* s, int count) {
         }
         v->hermitian = s->hermitian;
         v->pivoting = s->pivoting;
-        v->coef = s->coef;
-        v->coef_borrowed = true;
+        v->coef = DevBuf::view_of(s->coef.p);
         c->refs += 1;
         s->lanes.push_back(v);
     }
@@ -1030,12 +977,11 @@ int series_lane_views(abz_series* s, int count) {
 
 extern "C" {
 
-static void rule_free(abz_rule* r);
 static void series_drop_kept_rules(abz_series* s) {
     if (s->kept_rules.empty()) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    for (auto& k : s->kept_rules) rule_free(k.r);  // they hold no reference on the series
+    for (auto& k : s->kept_rules) delete k.r;  // they hold no reference on the series
     s->kept_rules.clear();
     s->summed_once.clear();
 }
@@ -1070,37 +1016,13 @@ struct RulePlan {
 };
 }  // namespace abz
 
+abz_rule::abz_rule() = default;
+abz_rule::~abz_rule() = default;  // the halo plane of abz_rule_ltm_halo goes with its slab (it holds no reference on the series)
+
 static void rule_drop_ltm_elements(abz_rule* r) {
-    dev_free(r->ltm_elems, r->ltm_elems_cap);
-    r->ltm_elems = nullptr;
-    r->ltm_elems_cap = 0;
+    r->ltm_elems = DevBuf();
     r->ltm_ncomp = 0;
     r->A = PlaneView();
-}
-
-static void rule_free(abz_rule* r) {
-    if (!r) return;
-    rule_free(r->ltm_halo);  // the halo plane of abz_rule_ltm_halo goes with its slab (it holds no reference on the series)
-    r->ltm_halo = nullptr;
-    rule_drop_ltm_elements(r);
-    dev_free(r->vals, r->vals_cap);
-    dev_free(r->node_of, r->node_of_cap);
-    if (!r->tables_view) {
-        dev_free(r->w, r->w_cap);
-        dev_free(r->idx, r->idx_cap);
-    }
-    if (r->plan) {
-        RulePlan* rp = static_cast<RulePlan*>(r->plan);
-        rp->pd.release();
-        rp->tab.release();
-        rp->tmpU.release();
-        rp->tmpD.release();
-        rp->fam[0].release();
-        rp->fam[1].release();
-        rp->tri.release();
-        delete rp;
-    }
-    delete r;
 }
 
 int abz_rule_destroy(abz_rule* r) try {
@@ -1108,7 +1030,7 @@ int abz_rule_destroy(abz_rule* r) try {
     abz_series* s = r->s;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    rule_free(r);
+    delete r;
     series_release(s);
     return ABZ_OK;
 } ABZ_CATCH_ALL
@@ -1117,7 +1039,7 @@ int abz_rule_destroy(abz_rule* r) try {
 // level-1 set: the fused build in the row layout (kernels_ggr_rows.hip).  ABZ_GGR_FUSED=0: the unfused build (tests compare)
 static bool rule_ggr_rows(const abz_rule* r) {
     const abz_series* s = r->s;
-    const RulePlan* rp = static_cast<const RulePlan*>(r->plan);
+    const RulePlan* rp = r->plan.get();
     if (!(r->want & ABZ_WANT_VEL) || !rp) return false;
     if (big_supported(s->n)) {  // 33...64 bands: the only velocity build there is; H, when wanted as well, by the plain build after it
         if (!r->full && rp->plan.coords) return false;  // (lists of grid nodes; explicit coordinates have no velocity build)
@@ -1140,7 +1062,7 @@ static bool rule_ggr_fused(const abz_rule* r) {
 static int rule_fill(abz_rule* r) {
     abz_series* s = r->s;
     abz_ctx* ctx = s->ctx;
-    RulePlan* rp = static_cast<RulePlan*>(r->plan);
+    RulePlan* rp = r->plan.get();
     const Plan& plan = rp->plan;
     const int d = s->d, n = s->n;
     const double2* tab = rp->tab.as<double2>();
@@ -1280,24 +1202,6 @@ static int rule_fill(abz_rule* r) {
     return ABZ_OK;
 }
 
-#define RULE_TRY(expr)        \
-    do {                      \
-        int rc_ = (expr);     \
-        if (rc_) {            \
-            rule_free(r);     \
-            return rc_;       \
-        }                     \
-    } while (0)
-#define RULE_HIP(call)                                                                   \
-    do {                                                                                 \
-        hipError_t e_ = (call);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_));                    \
-            rule_free(r);                                                                \
-            return e_ == hipErrorOutOfMemory ? ABZ_ERR_NOMEM : ABZ_ERR_HIP;              \
-        }                                                                                \
-    } while (0)
-
 static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_idx, const int64_t* wsym, int want,
                       int outer0, int outer_n, abz_rule** out, const SymTables* st = nullptr, bool wait = true) {
     int rc = check_series(s);
@@ -1313,9 +1217,10 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
     abz_ctx* ctx = s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     const int d = s->d, n = s->n;
-    abz_rule* r = new abz_rule();
-    RulePlan* rp = new RulePlan();
-    r->plan = rp;
+    std::unique_ptr<abz_rule> owner(new abz_rule());  // (after hipSetDevice: a return from here on frees what was built)
+    abz_rule* const r = owner.get();
+    r->plan.reset(new RulePlan());
+    RulePlan* const rp = r->plan.get();
     r->s = s;
     r->npt = npt;
     r->want = want;
@@ -1349,7 +1254,6 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
         for (int64_t k = 0; k < nirr * d; ++k) {
             if (irr_idx[k] < 0 || irr_idx[k] >= npt) {
                 set_error("irr_idx[%lld] = %d outside the grid", (long long)k, irr_idx[k]);
-                rule_free(r);
                 return ABZ_ERR_ARG;
             }
         }
@@ -1376,31 +1280,27 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
     const int64_t tile = (int64_t)r->planes * pitch;
     const int pstride = pitch;  // plane to plane
     if (st) {  // ONE device-to-device copy of the cached tables (a single block): the rule owns its plan like any other
-        RULE_TRY(rp->pd.arena.reserve(st->arena_bytes));
-        RULE_HIP(hipMemcpyAsync(rp->pd.arena.p, st->arena.p, st->arena_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        auto at = [&](const void* q) -> void* { return static_cast<char*>(rp->pd.arena.p) + (static_cast<const char*>(q) - static_cast<const char*>(st->arena.p)); };
-        auto view = [&](DevBuf& b, const void* q) {
-            b.release();
-            b.p = at(q);
-            b.view = true;
+        if ((rc = rp->pd.arena.reserve(st->arena_bytes))) return rc;
+        ABZ_HIP(hipMemcpyAsync(rp->pd.arena.p, st->arena.p, st->arena_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        auto view = [&](const void* q) {  // of the table that the cached arena holds at q
+            return DevBuf::view_of(static_cast<char*>(rp->pd.arena.p) + (static_cast<const char*>(q) - static_cast<const char*>(st->arena.p)));
         };
         for (int L = 0; L < d; ++L) {
-            view(rp->pd.gi[L], st->gi[L]);
-            view(rp->pd.parent[L], st->parent[L]);
+            rp->pd.gi[L] = view(st->gi[L]);
+            rp->pd.parent[L] = view(st->parent[L]);
         }
-        if (d >= 2) view(rp->pd.runs, st->runs);
-        r->w = static_cast<double*>(at(st->w));
-        r->idx = static_cast<int32_t*>(at(st->idx));
-        r->tables_view = true;
-    } else {
-        RULE_TRY(plan_upload(ctx, plan, rp->pd));
+        if (d >= 2) rp->pd.runs = view(st->runs);
+        r->w = view(st->w);
+        r->idx = view(st->idx);
+    } else if ((rc = plan_upload(ctx, plan, rp->pd))) {
+        return rc;
     }
     lap("plan_upload");
-    RULE_TRY(make_phase_table(ctx, npt, rp->tab));
+    if ((rc = make_phase_table(ctx, npt, rp->tab))) return rc;
     lap("phase_table");
-    if (r->full) RULE_TRY(level_phase_tables(s, npt, rp->tab.as<double2>(), rp->pd));
+    if (r->full && (rc = level_phase_tables(s, npt, rp->tab.as<double2>(), rp->pd))) return rc;
     const size_t bytes = sizeof(double) * (size_t)(r->ntiles * (int64_t)r->planes * pitch);
-    RULE_TRY(dev_alloc((void**)&r->vals, bytes, &r->vals_cap));
+    if ((rc = r->vals.alloc(bytes))) return rc;
     // on the context's stream: it is non-blocking, a null-stream memset would not be ordered before the
     // fill kernels below (and could land on top of their results)
     // Irregular node lists: the last tile is partly empty and kernels that walk whole tiles multiply its slots by a zero
@@ -1410,11 +1310,11 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
     // 5...32 bands, velocity planes) leave the padding alone: the block comes from a recycling pool, and a client of
     // abz_rule_values_ptr sees the whole block, so it is zeroed once here (abzhip.h: padding is zero or filler, finite).
     const bool filler_written = r->full && n <= 4 && !(want & ABZ_WANT_VEL);
-    if (!(r->full && (pitch == line_len || filler_written))) RULE_HIP(hipMemsetAsync(r->vals, 0, bytes, ctx->stream));
+    if (!(r->full && (pitch == line_len || filler_written))) ABZ_HIP(hipMemsetAsync(r->vals.p, 0, bytes, ctx->stream));
     auto mkview = [&](int plane0, bool present) {
         PlaneView v;
         if (present) {
-            v.base = r->vals + (int64_t)plane0 * pstride;
+            v.base = r->vals.as<double>() + (int64_t)plane0 * pstride;
             v.tile = tile;
             v.pitch = pstride;
             v.line_len = line_len;
@@ -1431,35 +1331,32 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
     } else if (!r->full) {
         std::vector<double> wd(std::max<int64_t>(nirr, 1));
         for (int64_t k = 0; k < nirr; ++k) wd[k] = (double)wsym[k];
-        RULE_TRY(dev_alloc((void**)&r->w, sizeof(double) * wd.size(), &r->w_cap));
-        RULE_TRY(stage_h2d(ctx, r->w, wd.data(), sizeof(double) * (size_t)nirr));
+        if ((rc = r->w.alloc(sizeof(double) * wd.size()))) return rc;
+        if ((rc = stage_h2d(ctx, r->w.p, wd.data(), sizeof(double) * (size_t)nirr))) return rc;
         std::vector<int32_t> it((size_t)std::max<int64_t>(nirr * d, 1));
         for (int64_t k = 0; k < nirr; ++k)
             for (int j = 0; j < d; ++j) it[(size_t)j * nirr + k] = irr_idx[k * d + j];
-        RULE_TRY(dev_alloc((void**)&r->idx, sizeof(int32_t) * it.size(), &r->idx_cap));
-        RULE_TRY(stage_h2d(ctx, r->idx, it.data(), sizeof(int32_t) * (size_t)(nirr * d)));
+        if ((rc = r->idx.alloc(sizeof(int32_t) * it.size()))) return rc;
+        if ((rc = stage_h2d(ctx, r->idx.p, it.data(), sizeof(int32_t) * (size_t)(nirr * d)))) return rc;
     }
     if ((want & ABZ_WANT_VEL) && !rule_ggr_fused(r)) {
         const size_t tb = sizeof(double) * (size_t)(r->ntiles * 2 * n * n * pitch);  // tiled temporaries
-        RULE_TRY(rp->tmpU.reserve(tb));
-        RULE_TRY(rp->tmpD.reserve(tb));
+        if ((rc = rp->tmpU.reserve(tb)) || (rc = rp->tmpD.reserve(tb))) return rc;
     }
     lap("alloc+w/idx");
-    RULE_TRY(rule_fill(r));
+    if ((rc = rule_fill(r))) return rc;
     // the C-ABI hands out a finished rule (a client may read its values from another stream); the library's own solve
     // loops (series_rule) keep going: the scan of the rule is ordered behind its fill on the context's stream
-    if (wait || dbg) RULE_HIP(hipStreamSynchronize(ctx->stream));
+    if (wait || dbg) ABZ_HIP(hipStreamSynchronize(ctx->stream));
     lap("fill");
-    if (want & ABZ_WANT_VEL) {  // keep the big temporaries only while a rebuild needs them
+    if (want & ABZ_WANT_VEL) {  // early: the big temporaries are kept only while a (re)build needs them
         rp->tmpU.release();
         rp->tmpD.release();
     }
     s->refs += 1;
-    *out = r;
+    *out = owner.release();  // (the handle: not a device block)
     return ABZ_OK;
 }
-#undef RULE_TRY
-#undef RULE_HIP
 
 int abz_ptr_rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_idx, const int64_t* wsym, int want,
                        abz_rule** out) try {
@@ -1479,35 +1376,28 @@ static int rule_build_sym(abz_series* s, int npt, const int32_t* syms, int nsyms
     ABZ_HIP(hipSetDevice(ctx->device));
     const int d = s->d;
     const size_t nsy = (size_t)nsyms * d * d;
-    SymTables* st = nullptr;
+    std::unique_ptr<SymTables> found;
     for (size_t i = 0; i < ctx->sym_cache.size(); ++i) {
-        SymTables* c = ctx->sym_cache[i];
+        const SymTables* c = ctx->sym_cache[i].get();
         if (c->npt == npt && c->d == d && c->syms.size() == nsy && std::equal(c->syms.begin(), c->syms.end(), syms)) {
-            st = c;
+            found = std::move(ctx->sym_cache[i]);
             ctx->sym_cache.erase(ctx->sym_cache.begin() + (long)i);
             break;
         }
     }
-    if (!st) {
-        st = new SymTables();
-        rc = sym_tables_device(ctx, npt, d, syms, nsyms, *st);
-        if (rc) {
-            st->release();
-            delete st;
-            return rc;
-        }
+    if (!found) {
+        found.reset(new SymTables());
+        if ((rc = sym_tables_device(ctx, npt, d, syms, nsyms, *found))) return rc;
     }
-    ctx->sym_cache.push_back(st);
+    ctx->sym_cache.push_back(std::move(found));
+    const SymTables* st = ctx->sym_cache.back().get();
     // a few grids stay cached (AutoPTR walks npt = 50, 100, 150, ...): 32 B per irreducible node
     size_t bytes = 0;
-    for (const SymTables* c : ctx->sym_cache) bytes += (size_t)c->nk * 40;
+    for (const auto& c : ctx->sym_cache) bytes += (size_t)c->nk * 40;
     while (ctx->sym_cache.size() > 8 || (bytes > ((size_t)2 << 30) && ctx->sym_cache.size() > 1)) {
-        SymTables* old = ctx->sym_cache.front();
-        ctx->sym_cache.erase(ctx->sym_cache.begin());
-        bytes -= (size_t)old->nk * 40;
+        bytes -= (size_t)ctx->sym_cache.front()->nk * 40;
         (void)hipStreamSynchronize(ctx->stream);
-        old->release();
-        delete old;
+        ctx->sym_cache.erase(ctx->sym_cache.begin());
     }
     ABZ_REQUIRE(st->nk > 0, "the symmetry set leaves no node");
     return rule_build(s, npt, 0, nullptr, nullptr, want, 0, npt, out, st, wait);
@@ -1525,15 +1415,15 @@ int abz_ptr_rule_build_slab(abz_series* s, int npt, int outer_begin, int outer_e
 int abz_rule_rebuild(abz_rule* r) try {
     int rc0 = check_rule(r);
     if (rc0) return rc0;
-    if (r->node_of) {
+    if (r->node_of.p) {
         set_error("abz_rule_rebuild: the rule holds eigenvalues unfolded from another rule and no plan of its own; rebuild the source "
                   "and call abz_rule_ltm_unfold(src, syms, nsyms, &rule) again");
         return ABZ_ERR_UNSUPPORTED;
     }
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    RulePlan* rp = static_cast<RulePlan*>(r->plan);
-    if (r->ltm_elems) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
+    RulePlan* rp = r->plan.get();
+    if (r->ltm_elems.p) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
         ABZ_HIP(hipStreamSynchronize(ctx->stream));
         rule_drop_ltm_elements(r);
     }
@@ -1545,7 +1435,7 @@ int abz_rule_rebuild(abz_rule* r) try {
     }
     int rc = rule_fill(r);
     // the halo plane of abz_rule_ltm_halo belongs to the same values: behind the slab on the same stream, launches only
-    if (!rc && r->ltm_halo) rc = rule_fill(r->ltm_halo);
+    if (!rc && r->ltm_halo) rc = rule_fill(r->ltm_halo.get());
     return rc;
 } ABZ_CATCH_ALL
 
@@ -1560,19 +1450,19 @@ int abz_rule_ltm_halo(abz_rule* r) try {
                   "its simplices lack the mesh, not a plane");
         return ABZ_ERR_UNSUPPORTED;
     }
-    if (r->node_of) {
+    if (r->node_of.p) {
         set_error("abz_rule_ltm_halo: the rule was unfolded from irreducible nodes (abz_rule_ltm_unfold): it is a whole grid and has no "
                   "plan to build a plane from; unfolding into a slab is not implemented");
         return ABZ_ERR_UNSUPPORTED;
     }
     abz_series* s = r->s;
-    const Plan& plan = static_cast<RulePlan*>(r->plan)->plan;
+    const Plan& plan = r->plan->plan;
     ABZ_REQUIRE(!(plan.outer0 == 0 && plan.outer_n == r->npt), "abz_rule_ltm_halo: the rule is a whole periodic grid: nothing to attach");
     ABZ_REQUIRE(r->E.base, "abz_rule_ltm_halo: the rule holds no eigenvalues (build the slab with ABZ_WANT_EIG)");
     abz_ctx* ctx = s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     if (r->ltm_halo) {  // a second call: the same plane from the series' current coefficients
-        if ((rc = rule_fill(r->ltm_halo))) return rc;
+        if ((rc = rule_fill(r->ltm_halo.get()))) return rc;
         ABZ_HIP(hipStreamSynchronize(ctx->stream));
         return ABZ_OK;
     }
@@ -1580,7 +1470,7 @@ int abz_rule_ltm_halo(abz_rule* r) try {
     const int z = (plan.outer0 + plan.outer_n) % r->npt;
     if ((rc = rule_build(s, r->npt, 0, nullptr, nullptr, ABZ_WANT_EIG, z, 1, &halo))) return rc;  // (waits for the fill)
     s->refs -= 1;  // the slab's reference covers its halo
-    r->ltm_halo = halo;
+    r->ltm_halo.reset(halo);
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
@@ -1606,8 +1496,8 @@ int abz_rule_export(abz_rule* r, double* x, double* w, double* H, double* eig, d
         if (!r->full) {
             it.resize((size_t)(r->nk * d));
             wd.resize((size_t)r->nk);
-            ABZ_HIP(hipMemcpy(it.data(), r->idx, sizeof(int32_t) * it.size(), hipMemcpyDeviceToHost));
-            ABZ_HIP(hipMemcpy(wd.data(), r->w, sizeof(double) * wd.size(), hipMemcpyDeviceToHost));
+            ABZ_HIP(hipMemcpy(it.data(), r->idx.p, sizeof(int32_t) * it.size(), hipMemcpyDeviceToHost));
+            ABZ_HIP(hipMemcpy(wd.data(), r->w.p, sizeof(double) * wd.size(), hipMemcpyDeviceToHost));
         }
         for (int64_t k = 0; k < r->nk; ++k) {
             int64_t rem = k + r->k_offset;
@@ -1644,6 +1534,8 @@ int abz_rule_export(abz_rule* r, double* x, double* w, double* H, double* eig, d
 
 static int rule_reduce(abz_rule* r, int integrand, const double* params, int nparams, const double* sweep, int n_sweep,
                        int nsyms, double* out_reim, bool device_io, double2* map_dev = nullptr);
+// bytes of the rule's value block as asked for (vals.cap may be more: the allocator hands out blocks of up to twice the request)
+static size_t rule_vals_bytes(const abz_rule* r) { return sizeof(double) * (size_t)(r->ntiles * r->planes * (r->H.base ? r->H.row : r->E.row)); }
 
 int abz_rule_reduce(abz_rule* r, int integrand, const double* params, int nparams, const double* sweep, int n_sweep,
                     int nsyms, double* out_reim) try {
@@ -1658,8 +1550,8 @@ int abz_rule_reduce_device(abz_rule* r, int integrand, const double* params, int
 int abz_rule_values_ptr(const abz_rule* r, void** base, int64_t* nbytes) try {
     int rc0 = check_rule(r);
     if (rc0) return rc0;
-    if (base) *base = r->vals;
-    if (nbytes) *nbytes = (int64_t)sizeof(double) * r->ntiles * r->planes * (r->H.base ? r->H.row : r->E.row);
+    if (base) *base = r->vals.p;
+    if (nbytes) *nbytes = (int64_t)rule_vals_bytes(r);
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
@@ -1697,13 +1589,13 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
     rs.H = r->H.base ? r->H : r->E;  // ABZ_F_ONE never dereferences it
     rs.E = r->E;
     rs.nk = r->nk;
-    rs.w = r->w;
-    rs.idx = r->idx;
+    rs.w = r->w.as<double>();
+    rs.idx = r->idx.as<int32_t>();
     rs.k_offset = r->k_offset;
     rs.herm = r->herm;
     rs.pivot = pivot;
     if (big_supported(rs.n) && r->herm && r->H.base && !r->H.compact && r->plan && (integrand == ABZ_F_DOS || integrand == ABZ_F_TRGLOC)) {
-        RulePlan* rp = static_cast<RulePlan*>(r->plan);
+        RulePlan* rp = r->plan.get();
         const int64_t tnk = (r->nk + 63) / 64 * 64;
         if (rp->tri.reserve(sizeof(double) * 2 * 64 * (size_t)tnk) == ABZ_OK) {  // (no room: the scan tridiagonalises on the fly)
             rs.tri_cache = rp->tri.as<double>();
@@ -1779,16 +1671,11 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
     plan_full(plan, d, npt, d >= 2 ? outer_begin : 0, d >= 2 ? outer_end - outer_begin : npt);
     PlanDev pd;
     DevBuf tab;
-    auto done = [&](int code) {
-        pd.release();
-        tab.release();
-        return code;
-    };
-    if ((rc = make_phase_table(ctx, npt, tab))) return done(rc);
-    if ((rc = level_phase_tables(s, npt, tab.as<double2>(), pd))) return done(rc);
+    if ((rc = make_phase_table(ctx, npt, tab))) return rc;
+    if ((rc = level_phase_tables(s, npt, tab.as<double2>(), pd))) return rc;
     const double2* level1 = nullptr;
     // n <= 4: the store-free kernel takes packed Hermitian sets (eval_sum_supported requires a Hermitian series)
-    if ((rc = build_chain(s, plan, pd, tab.as<double2>(), 0, &level1, 1, nullptr, !generic))) return done(rc);
+    if ((rc = build_chain(s, plan, pd, tab.as<double2>(), 0, &level1, 1, nullptr, !generic))) return rc;
     SumSpec ss;
     ss.n = n;
     ss.d = d;
@@ -1813,12 +1700,12 @@ int abz_ptr_sum(abz_series* s, int npt, int outer_begin, int outer_end, int inte
     ss.scale = 1.0 / (vol * (double)nsyms);
     rc = inv_small ? launch_big_sum(ctx, ss) : (generic ? launch_gen_sum(ctx, ss) : launch_eval_sum(ctx, ss));
     (void)hipStreamSynchronize(ctx->stream);
-    return done(rc);
+    return rc;
 } ABZ_CATCH_ALL
 
 // ---------------------------------------------------------------- whole AutoPTR solves
 // The rule of grid `npt` kept by the series (built on first use, refilled after abz_series_update).  `keep` = false: a
-// rule for one use; the caller frees it with rule_free.
+// rule for one use; the caller deletes it.
 static int series_rule(abz_series* s, int npt, const int32_t* syms, int nsyms, int want, bool keep, abz_rule** out, bool* owned) {
     const size_t nsy = syms ? (size_t)nsyms * s->d * s->d : 0;
     *owned = false;
@@ -1827,7 +1714,7 @@ static int series_rule(abz_series* s, int npt, const int32_t* syms, int nsyms, i
         if (k.npt != npt || (k.want & want) != want || k.syms.size() != nsy || !std::equal(k.syms.begin(), k.syms.end(), syms)) continue;
         if (k.generation != s->generation) {
             if (k.r->H.compact && !s->hermitian) {  // the series stopped being Hermitian: an upper-triangle rule cannot hold it
-                rule_free(k.r);
+                delete k.r;
                 s->kept_rules.erase(s->kept_rules.begin() + (long)i);
                 break;
             }
@@ -1839,23 +1726,23 @@ static int series_rule(abz_series* s, int npt, const int32_t* syms, int nsyms, i
         *out = k.r;
         return ABZ_OK;
     }
-    abz_rule* r = nullptr;
-    int rc = syms ? rule_build_sym(s, npt, syms, nsyms, want, &r, false) : rule_build(s, npt, 0, nullptr, nullptr, want, 0, npt, &r, nullptr, false);
+    abz_rule* built = nullptr;
+    int rc = syms ? rule_build_sym(s, npt, syms, nsyms, want, &built, false) : rule_build(s, npt, 0, nullptr, nullptr, want, 0, npt, &built, nullptr, false);
     if (rc) return rc;
+    std::unique_ptr<abz_rule> r(built);
     s->refs -= 1;  // owned by the series or by the caller of this function: no reference cycle
     if (keep) {
         SeriesRule k;
         k.npt = npt;
         k.want = r->want;
         if (syms) k.syms.assign(syms, syms + nsy);
-        k.r = r;
+        k.r = r.get();
         k.generation = s->generation;
         k.stamp = ++s->kept_stamp;
         s->kept_rules.push_back(std::move(k));
-    } else {
-        *owned = true;
     }
-    *out = r;
+    *owned = !keep;
+    *out = r.release();  // (the handle: to the series' list or to the caller)
     return ABZ_OK;
 }
 
@@ -1970,7 +1857,7 @@ int abz_autoptr_solve_many(abz_series* s, const int32_t* syms, int nsyms, int in
         bool keep = fits && gindex < keepmost;
         if (!have && fits && !keep) {
             size_t kept = 0;
-            for (const SeriesRule& k : s->kept_rules) kept += (size_t)(sizeof(double) * k.r->ntiles * k.r->planes * (k.r->H.base ? k.r->H.row : k.r->E.row));
+            for (const SeriesRule& k : s->kept_rules) kept += rule_vals_bytes(k.r);
             const size_t budget = total_b / 4;
             while (kept + rbytes > budget && !s->kept_rules.empty()) {
                 size_t victim = s->kept_rules.size();
@@ -1978,9 +1865,9 @@ int abz_autoptr_solve_many(abz_series* s, const int32_t* syms, int nsyms, int in
                     if (s->kept_rules[i].stamp < call_stamp && (victim == s->kept_rules.size() || s->kept_rules[i].stamp < s->kept_rules[victim].stamp)) victim = i;
                 if (victim == s->kept_rules.size()) break;  // everything left serves this very call
                 abz_rule* vr = s->kept_rules[victim].r;
-                kept -= (size_t)(sizeof(double) * vr->ntiles * vr->planes * (vr->H.base ? vr->H.row : vr->E.row));
+                kept -= rule_vals_bytes(vr);
                 (void)hipStreamSynchronize(ctx->stream);
-                rule_free(vr);
+                delete vr;
                 s->kept_rules.erase(s->kept_rules.begin() + (long)victim);
             }
             keep = kept + rbytes <= budget;
@@ -2007,6 +1894,7 @@ int abz_autoptr_solve_many(abz_series* s, const int32_t* syms, int nsyms, int in
         bool owned = false;
         int rc2 = series_rule(s, npt, syms, nsyms, want, keep, &r, &owned);
         if (rc2) return rc2;
+        const std::unique_ptr<abz_rule> once(owned ? r : nullptr);  // a rule for this grid only
         *nk_out = r->nk;
         if (swept && !sweeps_current) {
             for (int i = 0; i < na; ++i) sw_h[i] = sweeps[act[(size_t)i]];
@@ -2022,10 +1910,7 @@ int abz_autoptr_solve_many(abz_series* s, const int32_t* syms, int nsyms, int in
         double* const out_d = reinterpret_cast<double*>(io + sw_bytes + (size_t)slot * out_bytes);
         double2* const map = mapped ? reinterpret_cast<double2*>(out_map + (size_t)slot * out_bytes) : nullptr;
         if (!rc2) rc2 = rule_reduce(r, integrand, params, nparams, sw_d, swept ? na : 1, ns_eff, out_d, true, map);
-        if (owned) {  // a rule for this grid only: its blocks go back to the allocator once the stream has drained
-            (void)hipStreamSynchronize(ctx->stream);
-            rule_free(r);
-        }
+        if (once) (void)hipStreamSynchronize(ctx->stream);  // its blocks go back to the allocator once the stream has drained
         if (rc2) return rc2;
         pend->pending = true;
         return ABZ_OK;
@@ -2172,7 +2057,7 @@ int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out) try {
     ABZ_REQUIRE(r->V.base && r->E.base, "GGR needs a rule built with ABZ_WANT_VEL");
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    return launch_ggr(ctx, r->s->n, r->s->d, r->npt, r->E, r->V, r->w, r->nk, E, nE, out);
+    return launch_ggr(ctx, r->s->n, r->s->d, r->npt, r->E, r->V, r->w.as<double>(), r->nk, E, nE, out);
 } ABZ_CATCH_ALL
 
 // The rule is a whole periodic grid with eigenvalues -- or, where the caller scans slabs (`slab_ok`: abz_rule_ltm and the
@@ -2205,7 +2090,7 @@ static int ltm_check_grid(const abz_rule* r, const char* who, bool slab_ok = fal
 static bool ltm_slab_of(const abz_rule* r, LtmSlab& slab) {
     if (!r->ltm_halo) return false;
     slab.E = slab.A = r->ltm_halo->E;  // (the energy is the only element of a slab scan)
-    slab.nz = static_cast<const RulePlan*>(r->plan)->plan.outer_n;
+    slab.nz = r->plan->plan.outer_n;
     return true;
 }
 
@@ -2252,17 +2137,17 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
     const int n = r->s->n;
     const int planes = ncomp * n;
     const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
-    if ((rc = dev_alloc((void**)&r->ltm_elems, bytes, &r->ltm_elems_cap))) return rc;
+    if ((rc = r->ltm_elems.alloc(bytes))) return rc;
     r->ltm_ncomp = ncomp;
     r->A = r->E;  // the tiling of the eigenvalue planes: same rows, same lines, ncomp n planes per tile
-    r->A.base = r->ltm_elems;
+    r->A.base = r->ltm_elems.as<double>();
     r->A.tile = (int64_t)planes * r->E.row;
     r->A.pitch = r->E.row;
     r->A.compact = 0;
     DevBuf stage;  // one component at a time in the host's order
     const size_t cbytes = sizeof(double) * (size_t)r->nk * (size_t)n;
     rc = stage.reserve(cbytes);
-    if (!rc && hipMemsetAsync(r->ltm_elems, 0, bytes, ctx->stream) != hipSuccess) {  // the padding columns hold finite numbers
+    if (!rc && hipMemsetAsync(r->ltm_elems.p, 0, bytes, ctx->stream) != hipSuccess) {  // the padding columns hold finite numbers
         set_error("abz_rule_ltm_elements: hipMemsetAsync failed");
         rc = ABZ_ERR_HIP;
     }
@@ -2274,7 +2159,6 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
         set_error("abz_rule_ltm_elements: the upload failed");
         rc = ABZ_ERR_HIP;
     }
-    stage.release();
     if (rc) rule_drop_ltm_elements(r);
     return rc;
 } ABZ_CATCH_ALL
@@ -2286,7 +2170,7 @@ int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
     int rc = check_rule(r);
     if (rc) return rc;
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_orbitals"))) return rc;
-    if (r->node_of) {
+    if (r->node_of.p) {
         set_error("abz_rule_ltm_orbitals: the rule's eigenvalues were unfolded from irreducible nodes; eigenvectors at every grid "
                   "point are what such a rule avoids (build a full-grid rule with abz_ptr_rule_build)");
         return ABZ_ERR_UNSUPPORTED;
@@ -2310,17 +2194,18 @@ int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
     const int ncomp = orb ? norb : n;
     abz_ctx* ctx = s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    abz_rule* tmp = nullptr;  // H(k) of a rule that keeps eigenvalues only (one band: the weight is 1, no H needed)
+    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: the weight is 1, no H needed)
     if (!r->H.base && n > 1) {
-        if ((rc = rule_build(r->s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &tmp, nullptr, false))) return rc;
+        abz_rule* built = nullptr;
+        if ((rc = rule_build(r->s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
+        tmp.reset(built);
     }
     const int planes = ncomp * n;
     const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
-    double* block = nullptr;
-    size_t cap = 0;
-    rc = dev_alloc((void**)&block, bytes, &cap);
+    DevBuf block;
+    rc = block.alloc(bytes);
     PlaneView A = r->E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements)
-    A.base = block;
+    A.base = block.as<double>();
     A.tile = (int64_t)planes * r->E.row;
     A.pitch = r->E.row;
     A.compact = 0;
@@ -2331,16 +2216,11 @@ int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
         rc = ABZ_ERR_HIP;
     }
     if (tmp) {
-        rule_free(tmp);
+        tmp.reset();
         series_release(r->s);
     }
-    if (rc) {
-        dev_free(block, cap);
-        return rc;
-    }
-    rule_drop_ltm_elements(r);
-    r->ltm_elems = block;
-    r->ltm_elems_cap = cap;
+    if (rc) return rc;
+    r->ltm_elems = std::move(block);  // (what was attached goes here)
     r->ltm_ncomp = ncomp;
     r->A = A;
     return ABZ_OK;
@@ -2352,8 +2232,8 @@ int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {
     ABZ_REQUIRE(ncomp, "abz_rule_ltm_elements_export: null ncomp");
     // a slab made scannable by abz_rule_ltm_halo names its limit here too (any other rule without elements answers 0 components)
     if (r->ltm_halo && (rc = ltm_check_grid(r, "abz_rule_ltm_elements_export"))) return rc;
-    *ncomp = r->ltm_elems ? r->ltm_ncomp : 0;
-    if (!A || !r->ltm_elems) return ABZ_OK;
+    *ncomp = r->ltm_elems.p ? r->ltm_ncomp : 0;
+    if (!A || !r->ltm_elems.p) return ABZ_OK;
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     const int n = r->s->n;
@@ -2374,7 +2254,7 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
     ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
                 "abz_rule_ltm_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_weighted", source == ABZ_LTM_A_ENERGY))) return rc;
-    ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems,
+    ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems.p,
                 "abz_rule_ltm_weighted: no matrix elements are attached (abz_rule_ltm_elements; abz_rule_rebuild drops them)");
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
@@ -2406,7 +2286,7 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
     ABZ_REQUIRE(src->E.base, "abz_rule_ltm_unfold: the source rule holds no eigenvalues (build it with ABZ_WANT_EIG)");
     if (src->full) {
         set_error("abz_rule_ltm_unfold: the source rule is %s, not a list of irreducible nodes: there is nothing to unfold",
-                  src->node_of ? "an unfolded grid" : "a full grid or a slab of one");
+                  src->node_of.p ? "an unfolded grid" : "a full grid or a slab of one");
         return ABZ_ERR_UNSUPPORTED;
     }
     abz_series* s = src->s;
@@ -2419,26 +2299,25 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
         return ABZ_ERR_UNSUPPORTED;
     }
     ABZ_HIP(hipSetDevice(ctx->device));
-    abz_rule* r = *out;
-    if (r) {  // gather again through the map the rule has
+    if (abz_rule* const r = *out) {  // gather again through the map the rule has
         if ((rc = check_rule(r))) return rc;
-        ABZ_REQUIRE(r->node_of && r != src, "abz_rule_ltm_unfold: *out is not a rule made by abz_rule_ltm_unfold (pass NULL to create one)");
+        ABZ_REQUIRE(r->node_of.p && r != src, "abz_rule_ltm_unfold: *out is not a rule made by abz_rule_ltm_unfold (pass NULL to create one)");
         ABZ_REQUIRE(r->s == s && r->npt == npt && r->unfold_nk == src->nk,
                     "abz_rule_ltm_unfold: *out was unfolded from another geometry (series, npt = %d, %lld nodes; the source has npt = %d, %lld nodes)",
                     r->npt, (long long)r->unfold_nk, npt, (long long)src->nk);
         ABZ_REQUIRE(r->unfold_syms.size() == (size_t)nsyms * d * d && std::equal(r->unfold_syms.begin(), r->unfold_syms.end(), syms),
                     "abz_rule_ltm_unfold: *out was unfolded under another symmetry set (its orbit map does not fit these %d matrices)", nsyms);
-        if (r->ltm_elems) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
+        if (r->ltm_elems.p) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
             ABZ_HIP(hipStreamSynchronize(ctx->stream));
             rule_drop_ltm_elements(r);
         }
         r->herm = src->herm;
-        if ((rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of, n, npt, r->ntiles))) return rc;
+        if ((rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of.as<int32_t>(), n, npt, r->ntiles))) return rc;
         ABZ_HIP(hipStreamSynchronize(ctx->stream));
         return ABZ_OK;
     }
-    r = new abz_rule();
-    r->plan = new RulePlan();  // empty: an unfolded rule has no contraction plan (abz_rule_rebuild refuses it)
+    std::unique_ptr<abz_rule> r(new abz_rule());
+    r->plan.reset(new RulePlan());  // empty: an unfolded rule has no contraction plan (abz_rule_rebuild refuses it)
     r->s = s;
     r->npt = npt;
     r->want = ABZ_WANT_EIG;
@@ -2454,37 +2333,30 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
     r->E.pitch = row;
     r->E.line_len = npt;
     r->E.row = row;
-    int32_t* rank = nullptr;  // scratch: [N] node of a point, then the counter of points without one
-    size_t rank_cap = 0;
+    DevBuf rank;  // scratch: int32 [N] node of a point, then the counter of points without one
     int missing = 0;
-    rc = dev_alloc((void**)&r->vals, sizeof(double) * (size_t)r->ntiles * (size_t)n * (size_t)row, &r->vals_cap);
-    if (!rc) rc = dev_alloc((void**)&r->node_of, sizeof(int32_t) * (size_t)N, &r->node_of_cap);
-    if (!rc) rc = dev_alloc((void**)&rank, sizeof(int32_t) * ((size_t)N + 1), &rank_cap);
-    if (!rc) {
-        r->E.base = r->vals;
-        int* const missing_dev = reinterpret_cast<int*>(rank + N);
-        rc = launch_ltm_orbit_map(ctx, npt, d, syms, nsyms, src->idx, src->nk, rank, r->node_of, missing_dev);
-        if (!rc) rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of, n, npt, r->ntiles);
-        // the call's one synchronisation: the counter, the map and the planes have arrived
-        hipError_t e = hipMemcpyAsync(&missing, missing_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess && !rc) {
-            set_error("abz_rule_ltm_unfold: %s", hipGetErrorString(e));
-            rc = ABZ_ERR_HIP;
-        }
+    if ((rc = r->vals.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)n * (size_t)row))) return rc;
+    if ((rc = r->node_of.alloc(sizeof(int32_t) * (size_t)N))) return rc;
+    if ((rc = rank.alloc(sizeof(int32_t) * ((size_t)N + 1)))) return rc;
+    r->E.base = r->vals.as<double>();
+    int* const missing_dev = reinterpret_cast<int*>(rank.as<int32_t>() + N);
+    rc = launch_ltm_orbit_map(ctx, npt, d, syms, nsyms, src->idx.as<int32_t>(), src->nk, rank.as<int32_t>(), r->node_of.as<int32_t>(), missing_dev);
+    if (!rc) rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of.as<int32_t>(), n, npt, r->ntiles);
+    // the call's one synchronisation: the counter, the map and the planes have arrived
+    hipError_t e = hipMemcpyAsync(&missing, missing_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_unfold: %s", hipGetErrorString(e));
+        rc = ABZ_ERR_HIP;
     }
-    dev_free(rank, rank_cap);
-    if (!rc && missing != 0) {
+    if (rc) return rc;
+    if (missing != 0) {
         set_error("abz_rule_ltm_unfold: %d of the %lld grid points have no image under the %d symmetries among the %lld nodes of the source rule "
                   "(the node list does not cover every orbit)", missing, (long long)N, nsyms, (long long)src->nk);
-        rc = ABZ_ERR_ARG;
-    }
-    if (rc) {
-        rule_free(r);
-        return rc;
+        return ABZ_ERR_ARG;
     }
     s->refs += 1;
-    *out = r;
+    *out = r.release();  // (the handle: not a device block)
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
@@ -2506,18 +2378,17 @@ int abz_eval_nodes(abz_series* s, const double* k, int64_t nk, int want, double*
     int64_t chunk = std::max<int64_t>(256, std::min<int64_t>(nk, ((int64_t)1 << 30) / std::max<int64_t>(per, 1)));
     DevBuf Hd, Ed;
     PlanDev pd;
-    int status = ABZ_OK;
-    for (int64_t k0 = 0; k0 < nk && status == ABZ_OK; k0 += chunk) {
+    for (int64_t k0 = 0; k0 < nk; k0 += chunk) {
         const int64_t m = std::min(chunk, nk - k0);
         const int64_t ntl = (m + 63) / 64;
         PlaneView Hv, Ev;
         Plan plan;
         plan_runs<double>(plan, d, 0, k + k0 * d, m, true);
-        if ((status = plan_upload(ctx, plan, pd))) break;
+        if ((rc = plan_upload(ctx, plan, pd))) return rc;
         const double2* level1 = nullptr;
-        if ((status = build_chain(s, plan, pd, nullptr, 0, &level1))) break;
+        if ((rc = build_chain(s, plan, pd, nullptr, 0, &level1))) return rc;
         if (want & ABZ_WANT_H) {
-            if ((status = Hd.reserve(sizeof(double) * (size_t)ntl * 64 * 2 * n * n))) break;
+            if ((rc = Hd.reserve(sizeof(double) * (size_t)ntl * 64 * 2 * n * n))) return rc;
             Hv.base = Hd.as<double>();
             Hv.pitch = 64;
             Hv.row = 64;
@@ -2525,7 +2396,7 @@ int abz_eval_nodes(abz_series* s, const double* k, int64_t nk, int want, double*
             Hv.tile = (int64_t)2 * n * n * 64;
         }
         if (want & ABZ_WANT_EIG) {
-            if ((status = Ed.reserve(sizeof(double) * (size_t)ntl * 64 * n))) break;
+            if ((rc = Ed.reserve(sizeof(double) * (size_t)ntl * 64 * n))) return rc;
             Ev.base = Ed.as<double>();
             Ev.pitch = 64;
             Ev.row = 64;
@@ -2551,16 +2422,13 @@ int abz_eval_nodes(abz_series* s, const double* k, int64_t nk, int want, double*
         es.H = Hv;
         es.E = Ev;
         es.U = PlaneView();
-        if ((status = launch_eval(ctx, es))) break;
+        if ((rc = launch_eval(ctx, es))) return rc;
         if (want & ABZ_WANT_H)
-            if ((status = export_planes(ctx, Hv, 2 * n * n, m, H_out + k0 * 2 * n * n, (want & ABZ_WANT_H_ROW_MAJOR) ? n : 0))) break;
+            if ((rc = export_planes(ctx, Hv, 2 * n * n, m, H_out + k0 * 2 * n * n, (want & ABZ_WANT_H_ROW_MAJOR) ? n : 0))) return rc;
         if (want & ABZ_WANT_EIG)
-            if ((status = export_planes(ctx, Ev, n, m, eig_out + k0 * n))) break;
+            if ((rc = export_planes(ctx, Ev, n, m, eig_out + k0 * n))) return rc;
     }
-    Hd.release();
-    Ed.release();
-    pd.release();
-    return status;
+    return ABZ_OK;
 } ABZ_CATCH_ALL
 
 }  // extern "C"

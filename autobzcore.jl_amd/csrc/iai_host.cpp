@@ -397,7 +397,7 @@ struct IaiDriver {
         const int64_t row_full = (int64_t)s->dims[0] * s->n * s->n;
         return pk ? s->elems(level) / row_full * (int64_t)packed_row_elems(s->n, s->dims[0]) : s->elems(level);
     }
-    const double2* top_coef() const { return pk ? s->coef_pk.as<double2>() : s->coef; }
+    const double2* top_coef() const { return (pk ? s->coef_pk : s->coef).as<double2>(); }
     int contract_nodes(int L, int64_t nn, int64_t base_slot, int64_t off = 0, const int64_t* par = nullptr, const double* x = nullptr,
                        const int64_t* par_dev = nullptr, const double* x_dev = nullptr);
     int panels_enqueue(int L, int64_t c0p, int64_t cnp, int buf, const Lims& lims);
@@ -1584,7 +1584,7 @@ int abz_iai_solve_many(abz_series* s, int lims_kind, const double* lim_a, const 
                        int64_t maxevals, int64_t max_batch, double* out_reim, double* err, int64_t* numevals,
                        double* panels, int64_t max_panels, int64_t* npanels) try {
     int lanes = 1, ncomp = 0;
-    if (s && s->ctx && !s->closed && !s->ctx->closed && sweeps && out_reim && lim_a && !panels && !s->ex_fn && !s->coef_borrowed &&
+    if (s && s->ctx && !s->closed && !s->ctx->closed && sweeps && out_reim && lim_a && !panels && !s->ex_fn && !s->coef.view &&
         (ncomp = integrand_ncomp(integrand, s->n, s->d)) > 0)
         lanes = std::max(1, std::min(abz_switch(SW_IAI_LANES), n_sweep / std::max(1, abz_switch(SW_IAI_LANE_MIN))));
     if (lanes > 1 && series_lane_views(s, lanes - 1) != ABZ_OK) lanes = 1;
@@ -1701,8 +1701,7 @@ int abz_contract_nodes(abz_series* s, int src_level, const int64_t* parents, con
         ABZ_HIP(hipMemcpyAsync(bigger.p, pool.p, sizeof(double2) * (size_t)(base * Lrow), hipMemcpyDeviceToDevice,
                                s->ctx->stream));
         ABZ_HIP(hipStreamSynchronize(s->ctx->stream));
-        pool.release();
-        pool = bigger;
+        pool = std::move(bigger);  // (the old pool is freed here)
     }
     int rc = drv.contract_nodes(src_level, nnodes, base);
     if (rc) return rc;

@@ -89,20 +89,12 @@ int symptr_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, 
     if ((rc = flag.reserve(sizeof(int) * (size_t)a.N))) return rc;
     if ((rc = counts.reserve(sizeof(int) * (size_t)nb))) return rc;
     if ((rc = offs.reserve(sizeof(int64_t) * (size_t)nb))) return rc;
-    auto cleanup = [&]() {
-        flag.release();
-        counts.release();
-        offs.release();
-        didx.release();
-        dw.release();
-    };
     hipLaunchKernelGGL(symptr_flag_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, flag.as<int>());
     hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, flag.as<int>(), a.N, counts.as<int>());
     std::vector<int> hc((size_t)nb);
     hipError_t e = hipMemcpyAsync(hc.data(), counts.p, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
-        cleanup();
         set_error("symptr_device: %s", hipGetErrorString(e));
         return ABZ_ERR_HIP;
     }
@@ -115,26 +107,19 @@ int symptr_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, 
     idx.resize((size_t)(tot * d));
     w.resize((size_t)tot);
     if (tot > 0) {
-        if ((rc = didx.reserve(sizeof(int32_t) * (size_t)(tot * d))) || (rc = dw.reserve(sizeof(int64_t) * (size_t)tot))) {
-            cleanup();
-            return rc;
-        }
+        if ((rc = didx.reserve(sizeof(int32_t) * (size_t)(tot * d))) || (rc = dw.reserve(sizeof(int64_t) * (size_t)tot))) return rc;
         e = hipMemcpyAsync(offs.p, ho.data(), sizeof(int64_t) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream);
         hipLaunchKernelGGL(compact_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, flag.as<int>(), a.N,
                            offs.as<int64_t>(), npt, d, didx.as<int32_t>(), dw.as<int64_t>());
         if (e != hipSuccess) {
-            cleanup();
             set_error("symptr_device: %s", hipGetErrorString(e));
             return ABZ_ERR_HIP;
         }
         // MB-sized results: through the pinned staging buffer
         if ((rc = stage_d2h(ctx, idx.data(), didx.p, sizeof(int32_t) * idx.size())) ||
-            (rc = stage_d2h(ctx, w.data(), dw.p, sizeof(int64_t) * w.size()))) {
-            cleanup();
+            (rc = stage_d2h(ctx, w.data(), dw.p, sizeof(int64_t) * w.size())))
             return rc;
-        }
     }
-    cleanup();
     return ABZ_OK;
 }
 
@@ -305,8 +290,6 @@ __global__ __launch_bounds__(SYMW_THREADS) void sym_weight_kernel(SymArgs a, con
     w[k] = (double)cnt;
 }
 
-void SymTables::release() { arena.release(); }
-
 // load this file's code object now (abz_ctx_create) instead of inside the first symmetric solve: 0.6 ms of a cold 2.1 ms
 void preload_symptr_code() {
     hipFuncAttributes fa;
@@ -374,12 +357,8 @@ int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsy
                  o_r2 = o_cnt2 + up(sizeof(int) * (size_t)std::max<int64_t>(nplanes, 1)),
                  o_end = o_r2 + up(sizeof(int64_t) * (size_t)std::max<int64_t>(nplanes, 1));
     DevBuf tmp;
-    auto cleanup = [&]() { tmp.release(); };
     int rc;
-    if ((rc = tmp.reserve(o_end)) || (rc = mbox_reserve(ctx))) {
-        cleanup();
-        return rc;
-    }
+    if ((rc = tmp.reserve(o_end)) || (rc = mbox_reserve(ctx))) return rc;
     char* const tb = static_cast<char*>(tmp.p);
     uint8_t* const rep = reinterpret_cast<uint8_t*>(tb + o_rep);
     int* const cnt1 = reinterpret_cast<int*>(tb + o_cnt1);
@@ -415,12 +394,11 @@ int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsy
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st_);
     if (e != hipSuccess) {
-        cleanup();
         set_error("symmetric rule tables: %s", hipGetErrorString(e));
         return ABZ_ERR_HIP;
     }
     lap("counts+scans");
-    st.release();
+    st.arena.release();  // early: tables that `st` already held go before the new ones are sized
     st.npt = npt;
     st.d = d;
     st.nk = tot_host[0];
@@ -435,11 +413,7 @@ int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsy
                      p_p1 = p_g1 + up(sizeof(int32_t) * (size_t)n1), p_ru = p_p1 + up(sizeof(int64_t) * (size_t)n1),
                      p_g2 = p_ru + up(sizeof(int64_t) * (size_t)(n1 + 1)), p_p2 = p_g2 + up(sizeof(int32_t) * (size_t)n2),
                      p_end = p_p2 + up(sizeof(int64_t) * (size_t)n2);
-        if ((rc = st.arena.reserve(p_end))) {
-            cleanup();
-            st.release();
-            return rc;
-        }
+        if ((rc = st.arena.reserve(p_end))) return rc;
         st.arena_bytes = p_end;
         char* const ab = static_cast<char*>(st.arena.p);
         st.idx = reinterpret_cast<int32_t*>(ab + p_idx);
@@ -479,15 +453,13 @@ int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsy
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(st_);  // the temporaries below go back to the allocator
         if (e != hipSuccess) {
-            cleanup();
-            st.release();
             set_error("symmetric rule tables: %s", hipGetErrorString(e));
             return ABZ_ERR_HIP;
         }
     }
     lap("weights");
     st.syms.assign(syms, syms + (size_t)nsyms * d * d);
-    cleanup();
+    tmp.release();  // early: under the timing lap below
     lap("free tmp");
     return ABZ_OK;
 }
