@@ -59,6 +59,7 @@ PROTOTYPES = {
     "abz_rule_ltm_unfold": (C.c_int, [C.c_void_p, c_i32p, C.c_int, c_vpp]),
     "abz_rule_ltm_halo": (C.c_int, [C.c_void_p]),
     "abz_rule_ltm_green": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
+    "abz_rule_ltm_green_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, c_f64p]),
     "abz_mem_info": (C.c_int, [C.c_void_p, c_i64p]),
     "abz_symptr_rule": (C.c_int, [C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
     "abz_symptr_rule_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),

@@ -501,6 +501,10 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 // tr G(z) by the tetrahedron method on a whole grid (abz_rule_ltm_green): z_host [nz][2] with Im z != 0, out_host [nz][2]
 int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* z_host, int nz, double* out_host);
+// G_A(z) of `ncomp` components of elements A (A = E, ncomp = 1: the energy) on a whole grid (abz_rule_ltm_green_weighted):
+// out_host [nz][ncomp][2]
+int launch_ltm_green_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* z_host, int nz,
+                              double* out_host);
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
 // Orbital weights as matrix elements (kernels_ltm_orb.hip): plane c n + b of A (ncomp n planes tiled like the eigenvalue planes,
 // padding columns included) <- |U_{orb[c], b}|^2 from the H planes of the same whole grid (full or compact); orb == nullptr:

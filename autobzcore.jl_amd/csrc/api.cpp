@@ -2264,6 +2264,27 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
                                what, out, ltm_slab_of(r, slab) ? &slab : nullptr);
 } ABZ_CATCH_ALL
 
+int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z, int nz, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(z && out && nz >= 1, "abz_rule_ltm_green_weighted: bad arguments");
+    ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
+                "abz_rule_ltm_green_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_weighted"))) return rc;
+    ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems.p,
+                "abz_rule_ltm_green_weighted: no matrix elements are attached (abz_rule_ltm_elements, abz_rule_ltm_orbitals; "
+                "abz_rule_rebuild drops them)");
+    for (int i = 0; i < nz; ++i) {
+        const double re = z[2 * (size_t)i], im = z[2 * (size_t)i + 1];
+        ABZ_REQUIRE(std::isfinite(re) && std::isfinite(im), "abz_rule_ltm_green_weighted: z[%d] = (%g, %g) is not finite", i, re, im);
+        ABZ_REQUIRE(im != 0.0, "abz_rule_ltm_green_weighted: z[%d] = %g is real; G_A is computed off the real axis (Im z != 0)", i, re);
+    }
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const bool energy = source == ABZ_LTM_A_ENERGY;
+    return launch_ltm_green_weighted(ctx, r->s->n, r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, z, nz, out);
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {
     int rc = check_rule(r);
     if (rc) return rc;

@@ -1017,17 +1017,17 @@ int ltm_scan(abz_ctx* ctx, const char* who, int n, int d, int npt, PlaneView E, 
 //    two calls return the same bits.
 constexpr double GREEN_RHO2 = 0.25;      // rho^2
 constexpr double GREEN_EPS2 = 0x1p-104;  // (2^-52)^2
-constexpr int GREEN_KMAX = 40;           // terms beyond k = 37 are never asked for (see above)
+constexpr int GREEN_KMAX = 40;           // terms beyond k = 37 (the five knots of a corner weight: 39) are never asked for
 constexpr int LTM_GREEN_CHUNK = 512;     // values of z per launch: 8 (2 + 4 x 2) B of LDS each
 static_assert(sizeof(double) * 10 * LTM_GREEN_CHUNK <= LTM_LDS_MAX, "the z list and the four waves' sums fit the scans' LDS");
 
-// m! k! / (m+k)! for m = 1, 2, 3
+// m! k! / (m+k)! for m = 1, 2, 3 and, for the five knots of a corner weight in 3-D, 4
 struct GreenCoef {
-    double c[3][GREEN_KMAX + 1];
+    double c[4][GREEN_KMAX + 1];
 };
 constexpr GreenCoef green_coef() {
     GreenCoef t{};
-    for (int m = 1; m <= 3; ++m) {
+    for (int m = 1; m <= 4; ++m) {
         t.c[m - 1][0] = 1.0;
         for (int k = 1; k <= GREEN_KMAX; ++k) t.c[m - 1][k] = t.c[m - 1][k - 1] * (double)k / (double)(m + k);
     }
@@ -1284,6 +1284,385 @@ int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const dou
     if ((rc = sum_deliver(ctx, so, where, 0, nz))) return rc;
     for (size_t i = 0; i < (size_t)nz; ++i)
         if (z_host[2 * i + 1] < 0.0) out_host[2 * i + 1] = -out_host[2 * i + 1];
+    return ABZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Green's function with matrix elements at complex energies (abz_rule_ltm_green_weighted)
+// ---------------------------------------------------------------------------------------------------------------------
+// G_A,c(z) = w sum_{cells} sum_{d! simplices} sum_{bands} sum_{i=0..m} A_{c,i} W_i(z), m = d: the element of component c is linear
+// inside a simplex like the energy, and W_i is the mean of lambda_i / (z - e) over it.  The uniform density times lambda_i,
+// normalised, is Dirichlet(1, .., 2, .., 1), whose image under e is the B-spline with the knot x_i doubled:
+//      W_i = J[x_0 .. x_m, x_i](z) / (m + 1)
+//  * The J of m + 2 knots with one repeat obeys the recursion above with J[x, x] = 1 / u, and the evaluation rule carries over:
+//    a sub-range (a contiguous run of the sorted multiset) narrower than rho |z - mean| is summed by the same Taylor series,
+//    now of up to five knots (M = 4): max |delta| <= 4/5 width, the ratio stays below 2/5, (2/5)^k >= 2^-52 up to k = 39, within
+//    GREEN_KMAX; the coefficient table has the row m = 4.  Only wider sub-ranges are divided by their width.
+//  * Sharing.  The sub-ranges of the m + 1 multisets that hold at most one copy of the doubled knot are the plain ones, P[a][b] =
+//    J[x_a .. x_b]: computed once per (simplex, z), d = 3: 3 pairs (from the corner logs), 2 triples, 1 quadruple.  Those that
+//    hold both copies, D_i[a][b] = J[x_a .. x_i, x_i .. x_b] with a <= i <= b, start from D_i[i][i] = 1 / u_i and grow by
+//      D_i[a][b] = M / (M-1) (u_a lo - u_b hi) / (x_b - x_a),   M = b - a + 1,
+//      lo = b > i ? D_i[a][b-1] : P[a][b],   hi = a < i ? D_i[a+1][b] : P[a][b]
+//    (dropping the last or the first knot): 16 of them in 3-D, 6 in 2-D, 2 in 1-D.  Every sub-range is evaluated whether or not a
+//    wider one turns out narrow and ignores it: each is accurate by itself.  One shortcut comes first: where all m + 1 whole
+//    multisets are narrow the weights are m + 1 series and nothing else is formed (150^3 SVO grid, 256 z, one component:
+//    2790 ms without it, 1222 ms with it).
+//  * Shape (ltm_green_w_kernel<D, NC>).  The cell walk, the corner geometry, the z list in LDS, blockIdx.z and the reduction are
+//    ltm_green_kernel's; the 2^d corner energies and the NC 2^d corner elements of a group of NC components stay in registers
+//    (LtmElems::load through PlaneView / acomp), the sort of a simplex carries each corner's log and its NC elements, the m + 1
+//    weights of a (simplex, z) are formed once and every component contracts with them.  Groups as in ltm_scan: 4s, a 2, a 1.
+//    LDS: [zn][2] z | [4 waves][zn][NC][2] sums, so a launch takes green_w_chunk(NC) = 512 / 291 / 154 values of z.
+//    1 / (m + 1) goes into the scale of ltm_final_kernel.
+namespace {
+constexpr int green_w_chunk(int nc) {
+    const size_t fit = LTM_LDS_MAX / (sizeof(double) * (size_t)(2 + 8 * nc));
+    return fit < (size_t)LTM_GREEN_CHUNK ? (int)fit : LTM_GREEN_CHUNK;
+}
+static_assert(sizeof(double) * (2 + 8 * 1) * green_w_chunk(1) <= LTM_LDS_MAX && sizeof(double) * (2 + 8 * 2) * green_w_chunk(2) <= LTM_LDS_MAX &&
+                  sizeof(double) * (2 + 8 * 4) * green_w_chunk(4) <= LTM_LDS_MAX,
+              "the z list and the four waves' sums of every component group fit the scans' LDS");
+static_assert(green_w_chunk(4) >= 4 && green_w_chunk(4) <= green_w_chunk(2) && green_w_chunk(2) <= green_w_chunk(1), "chunks shrink with NC");
+
+struct GreenWArgs {
+    GreenArgs g;
+    PlaneView A;
+    int64_t acomp;  // doubles from a band's plane of one component to its plane of the next: n * A.pitch
+    int aplane0;    // first element plane of this launch: (its first component) * n
+};
+
+// what the sort of a simplex carries per corner: the energy, log(z - energy) and the NC elements
+template <int NC>
+struct GreenWCorner {
+    GreenCorner g;
+    LtmVec<NC> a;
+};
+template <int NC>
+__device__ __forceinline__ GreenWCorner<NC> green_wsel(bool first, const GreenWCorner<NC>& p, const GreenWCorner<NC>& q) {
+    GreenWCorner<NC> r;
+    r.g = green_sel(first, p.g, q.g);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) r.a.v[c] = first ? p.a.v[c] : q.a.v[c];
+    return r;
+}
+template <int NC>
+__device__ __forceinline__ void green_wcx(GreenWCorner<NC>& p, GreenWCorner<NC>& q) {
+    const bool sw = q.g.x < p.g.x;
+    const GreenWCorner<NC> lo = green_wsel(sw, q, p), hi = green_wsel(sw, p, q);
+    p = lo;
+    q = hi;
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loops whose index is a template argument
+template <int N, class F>
+__device__ __forceinline__ void green_for(F&& f) {
+    if constexpr (N > 0) {
+        green_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// J of the M + 1 >= 3 sorted knots with u[l] = Re z - knot l and width w, from `lo` (the J without the last knot) and `hi`
+// (without the first), which only a wide range reads
+template <int M>
+__device__ __forceinline__ double green_mean(const double (&u)[M + 1]) {
+    double ur = u[0];
+#pragma unroll
+    for (int l = 1; l <= M; ++l) ur += u[l];
+    return ur * (1.0 / (double)(M + 1));
+}
+template <int M>
+__device__ __forceinline__ Cx green_node(const double (&u)[M + 1], double w, Cx lo, Cx hi, double zi) {
+    const double ur = green_mean<M>(u), n2 = ur * ur + zi * zi;
+    if (w * w < GREEN_RHO2 * n2) return green_series<M>(u, ur, zi, n2);
+    const Cx t0 = cx_mul({u[0], zi}, lo), t1 = cx_mul({u[M], zi}, hi);
+    const double f = ((double)M / (double)(M - 1)) / w;
+    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
+}
+
+// (m + 1) W_i = J[x_0 .. x_m, x_i] of the NK = m + 1 sorted corners g
+template <int NK>
+__device__ __forceinline__ void green_weights(const GreenCorner (&g)[NK], double zr, double zi, Cx (&W)[NK]) {
+    double u[NK];
+#pragma unroll
+    for (int l = 0; l < NK; ++l) u[l] = zr - g[l].x;
+    // The m + 1 whole multisets first.  Where all of them are narrow -- a fine grid away from the corners' energies: most simplices
+    // -- each is its series and no sub-range is read; the value is the one the general path below gives (green_node makes the
+    // same decision from the same numbers).
+    {
+        const double w = g[NK - 1].x - g[0].x;
+        double uu[NK][NK + 1], ur[NK], n2[NK];
+        bool narrow = true;
+#pragma unroll
+        for (int i = 0; i < NK; ++i) {
+#pragma unroll
+            for (int l = 0; l <= NK; ++l) uu[i][l] = u[l - (l > i ? 1 : 0)];
+            ur[i] = green_mean<NK>(uu[i]);
+            n2[i] = ur[i] * ur[i] + zi * zi;
+            narrow = narrow && w * w < GREEN_RHO2 * n2[i];
+        }
+        if (narrow) {
+#pragma unroll
+            for (int i = 0; i < NK; ++i) W[i] = green_series<NK>(uu[i], ur[i], zi, n2[i]);
+            return;
+        }
+    }
+    Cx P[NK][NK];  // a <= b: J[x_a .. x_b]; P[a][a] = 1 / u_a
+#pragma unroll
+    for (int l = 0; l < NK; ++l) {
+        const double s = 1.0 / (u[l] * u[l] + zi * zi);
+        P[l][l] = {u[l] * s, -zi * s};
+    }
+    green_for<NK - 1>([&](auto L_) {
+        constexpr int L = decltype(L_)::value + 1;
+        green_for<NK - L>([&](auto a_) {
+            constexpr int a = decltype(a_)::value, b = a + L;
+            if constexpr (L == 1) {
+                P[a][b] = green_pair(g[a], g[b], zr, zi);
+            } else {
+                double uu[L + 1];
+#pragma unroll
+                for (int l = 0; l <= L; ++l) uu[l] = u[a + l];
+                P[a][b] = green_node<L>(uu, g[b].x - g[a].x, P[a][b - 1], P[a + 1][b], zi);
+            }
+        });
+    });
+    green_for<NK>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        Cx Dd[NK][NK];  // a <= i <= b: J[x_a .. x_i, x_i .. x_b]
+        Dd[i][i] = P[i][i];
+        green_for<NK - 1>([&](auto L_) {
+            constexpr int L = decltype(L_)::value + 1;
+            green_for<NK - L>([&](auto a_) {
+                constexpr int a = decltype(a_)::value, b = a + L;
+                if constexpr (a <= i && i <= b) {
+                    constexpr int M = L + 1;
+                    double uu[M + 1];
+#pragma unroll
+                    for (int l = 0; l <= M; ++l) uu[l] = u[a + l - (a + l > i ? 1 : 0)];
+                    const Cx lo = b > i ? Dd[a][b - 1] : P[a][b];
+                    const Cx hi = a < i ? Dd[a + 1][b] : P[a][b];
+                    Dd[a][b] = green_node<M>(uu, g[b].x - g[a].x, lo, hi, zi);
+                }
+            });
+        });
+        W[i] = Dd[0][NK - 1];
+    });
+}
+
+// sum_i A_{c,i} (m + 1) W_i of a simplex with corners in any order, added to (sr, si)[c]
+template <int NK, int NC>
+__device__ __forceinline__ void green_wsimplex(GreenWCorner<NC> (&q)[NK], double zr, double zi, double (&sr)[NC], double (&si)[NC]) {
+    if constexpr (NK == 2) {
+        green_wcx(q[0], q[1]);
+    } else if constexpr (NK == 3) {
+        green_wcx(q[0], q[1]);
+        green_wcx(q[1], q[2]);
+        green_wcx(q[0], q[1]);
+    } else {
+        green_wcx(q[0], q[1]);
+        green_wcx(q[2], q[3]);
+        green_wcx(q[0], q[2]);
+        green_wcx(q[1], q[3]);
+        green_wcx(q[1], q[2]);
+    }
+    GreenCorner g[NK];
+#pragma unroll
+    for (int l = 0; l < NK; ++l) g[l] = q[l].g;
+    Cx W[NK];
+    green_weights<NK>(g, zr, zi, W);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+        for (int l = 0; l < NK; ++l) {
+            sr[c] += q[l].a.v[c] * W[l].re;
+            si[c] += q[l].a.v[c] * W[l].im;
+        }
+    }
+}
+
+// partial [2 NC nz][nrows]: column (i NC + c) 2 + {0, 1} the real and imaginary part of component c's sum at z_i
+template <int D, int NC>
+__global__ __launch_bounds__(256) void ltm_green_w_kernel(GreenWArgs wa, double* __restrict__ partial, int64_t nrows) {
+    // [zn][2] this block's values of z | [4 waves][zn][NC][2] sums
+    extern __shared__ __attribute__((aligned(16))) double ldsw[];
+    const GreenArgs& a = wa.g;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr int NV = 1 << D;  // corners per cell
+    using Load = LtmElems<NC, false>;
+    using Corner = GreenWCorner<NC>;
+    const int z0 = (int)blockIdx.z * a.zper;
+    const int zn = min(a.zper, a.nz - z0);
+    const double* const zl = ldsw;
+    double* const acc = ldsw + (size_t)2 * zn * (1 + NC * wave);
+    for (int i = threadIdx.x; i < 2 * zn; i += 256) ldsw[i] = a.z[2 * z0 + i];
+    for (int i = threadIdx.x; i < 8 * NC * zn; i += 256) ldsw[2 * zn + i] = 0.0;
+    __syncthreads();
+    const int npt = a.npt;
+    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
+    const double* __restrict__ const Ab = wa.A.base + (int64_t)(wa.aplane0 + (int)blockIdx.y) * wa.A.pitch;
+    const int64_t tileE = a.E.tile, tileA = wa.A.tile, acomp = wa.acomp;
+    // the whole-grid geometry of ltm_window_kernel: corner `bits` of cell (i1, i2, i3), every index wrapped mod npt
+    auto wrap = [&](int& i1, int& i2, int& i3, int bits) {
+        if ((bits & 1) && ++i1 == npt) i1 = 0;
+        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
+        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
+    };
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
+        const int64_t k = base + threadIdx.x;
+        const bool active = k < a.ncell;
+        double c[NV];
+        LtmVec<NC> ca[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            c[j] = 0.0;
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc) ca[j].v[cc] = 0.0;
+        }
+        if (active) {
+            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
+            const int i1 = (int)(k - line * npt);
+            const int i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
+            const int i2 = (int)line - i3 * npt;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                int j1 = i1, j2 = i2, j3 = i3;
+                wrap(j1, j2, j3, j);
+                c[j] = Eb[((int64_t)j3 * npt + j2) * tileE + j1];
+                ca[j] = Load::load(Ab + ((int64_t)j3 * npt + j2) * tileA + j1, acomp);
+            }
+        }
+        for (int iz = 0; iz < zn; ++iz) {
+            const double zr = zl[2 * iz], zi = zl[2 * iz + 1];
+            double sr[NC], si[NC];
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc) sr[cc] = si[cc] = 0.0;
+            if (active) {
+                Corner g[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const double ur = zr - c[j];
+                    g[j].g = {c[j], 0.5 * log(ur * ur + zi * zi), atan2(zi, ur)};
+                    g[j].a = ca[j];
+                }
+                if constexpr (D == 3) {
+                    // the permutation (X, Y, Z) of the axes: corners 0, e_X, e_X + e_Y, (1,1,1); a loop, the corners by selects
+#pragma unroll 1
+                    for (int t = 0; t < 6; ++t) {
+                        const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3;
+                        const int bb = (1 << X) | (1 << Y);
+                        Corner q[4] = {g[0], green_wsel(X == 0, g[1], green_wsel(X == 1, g[2], g[4])),
+                                       green_wsel(bb == 3, g[3], green_wsel(bb == 5, g[5], g[6])), g[7]};
+                        green_wsimplex<4, NC>(q, zr, zi, sr, si);
+                    }
+                } else if constexpr (D == 2) {
+#pragma unroll 1
+                    for (int t = 0; t < 2; ++t) {
+                        Corner q[3] = {g[0], green_wsel(t == 0, g[1], g[2]), g[3]};
+                        green_wsimplex<3, NC>(q, zr, zi, sr, si);
+                    }
+                } else {
+                    Corner q[2] = {g[0], g[1]};
+                    green_wsimplex<2, NC>(q, zr, zi, sr, si);
+                }
+            }
+            // every lane ends with the same bits: a + b == b + a at every level of the butterfly
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    sr[cc] += __shfl_xor(sr[cc], off);
+                    si[cc] += __shfl_xor(si[cc], off);
+                }
+                if (lane == 0) {
+                    acc[2 * (iz * NC + cc)] += sr[cc];
+                    acc[2 * (iz * NC + cc) + 1] += si[cc];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const double* h = ldsw + 2 * zn;
+    const size_t w = (size_t)2 * NC * zn;  // from one wave's sums to the next
+    for (int t = threadIdx.x; t < 2 * NC * zn; t += 256)
+        partial[((int64_t)2 * NC * z0 + t) * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
+}
+
+using LtmGreenWFn = void (*)(GreenWArgs, double*, int64_t);
+// [d - 1][NC = 1, 2, 4]
+constexpr LtmGreenWFn LTM_GREEN_W[3][3] = {
+    {ltm_green_w_kernel<1, 1>, ltm_green_w_kernel<1, 2>, ltm_green_w_kernel<1, 4>},
+    {ltm_green_w_kernel<2, 1>, ltm_green_w_kernel<2, 2>, ltm_green_w_kernel<2, 4>},
+    {ltm_green_w_kernel<3, 1>, ltm_green_w_kernel<3, 2>, ltm_green_w_kernel<3, 4>},
+};
+}  // namespace
+
+// z_host [nz][2] with Im z != 0, A the element planes of `ncomp` components (A = E, ncomp = 1: the energy), out_host
+// [nz][ncomp][2].  Im z < 0: the conjugate of the value at conj(z), to the bit (the elements are real).
+int launch_ltm_green_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* z_host, int nz,
+                              double* out_host) {
+    GreenWArgs a;
+    a.g.E = E;
+    a.g.npt = npt;
+    a.g.ncell = 1;
+    for (int j = 0; j < d; ++j) a.g.ncell *= npt;
+    a.A = A;
+    a.acomp = (int64_t)n * A.pitch;
+    // of a simplex and, of its d + 1 corner weights, the 1 / (m + 1)
+    const double weight = 1.0 / ((double)ltm_nsimplex(d) * (double)a.g.ncell * (double)(d + 1));
+    std::vector<double> zup(2 * (size_t)nz);
+    for (size_t i = 0; i < (size_t)nz; ++i) {
+        zup[2 * i] = z_host[2 * i];
+        zup[2 * i + 1] = std::fabs(z_host[2 * i + 1]);
+    }
+    // the scans' grid: one block row per band, enough blocks to fill the device several times over, few enough partial rows
+    const int64_t nblocks = std::min<int64_t>(cdiv64(a.g.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
+    const int64_t nrows = nblocks * n;
+    size_t pmax = 0;
+    for (int nc : {1, 2, 4})
+        if (nc <= ncomp) pmax = std::max(pmax, (size_t)std::min(nz, green_w_chunk(nc)) * (size_t)(2 * nc));
+    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax);
+    if (rc) return rc;
+    double* partial = ctx->scratch[1].as<double>();
+    const double* zdev = nullptr;
+    if ((rc = sweep_to_device(ctx, zup.data(), 2 * nz, &zdev))) return rc;
+    const size_t ncols = (size_t)nz * (size_t)ncomp;
+    SumOut so;
+    so.host = out_host;
+    if (mbox_reserve(ctx) == ABZ_OK && sizeof(double2) * ncols <= ctx->mbox_cap / 2) {  // the mailbox's result half
+        so.map_dev = reinterpret_cast<double2*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
+        so.map_host = reinterpret_cast<const double2*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
+    }
+    double2* where = nullptr;
+    if ((rc = sum_target(ctx, so, 0, (int64_t)ncols, &where))) return rc;
+    // groups of 4 components, then 2, then 1; every group walks the grid once per chunk of z
+    for (int c0 = 0; c0 < ncomp;) {
+        const int nc = ncomp - c0 >= 4 ? 4 : (ncomp - c0 >= 2 ? 2 : 1);
+        const int CH = green_w_chunk(nc);
+        a.aplane0 = c0 * n;
+        for (int s0 = 0; s0 < nz; s0 += CH) {
+            const int cnt = std::min(CH, nz - s0);
+            // where the cells give fewer than ~2048 blocks the values of z are dealt to blockIdx.z, at least 4 per block
+            const int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(2048, nrows), cdiv64(cnt, 4)));
+            a.g.z = zdev + 2 * (size_t)s0;
+            a.g.nz = cnt;
+            a.g.zper = (int)cdiv64(cnt, nsplit);
+            const dim3 grid((unsigned)nblocks, (unsigned)n, (unsigned)cdiv64(cnt, a.g.zper));
+            ProfScope ps(ctx, ABZ_K_LTM);
+            launch(ctx, LTM_GREEN_W[d - 1][nc >> 1], grid, dim3(256), (unsigned)(sizeof(double) * (size_t)(2 + 8 * nc) * (size_t)a.g.zper), a,
+                   partial, nrows);
+            ABZ_HIP(hipGetLastError());
+            // column (i nc + c) 2 + t of the launch -> out[s0 + i][c0 + c][t]
+            launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, (const double*)partial, nrows, weight, 2 * nc,
+                   (int64_t)2 * ncomp, reinterpret_cast<double*>(where + ((size_t)s0 * (size_t)ncomp + (size_t)c0)));
+            ABZ_HIP(hipGetLastError());
+        }
+        c0 += nc;
+    }
+    if ((rc = sum_deliver(ctx, so, where, 0, (int64_t)ncols))) return rc;
+    for (size_t i = 0; i < (size_t)nz; ++i)
+        if (z_host[2 * i + 1] < 0.0)
+            for (size_t c = 0; c < (size_t)ncomp; ++c) out_host[2 * (i * (size_t)ncomp + c) + 1] = -out_host[2 * (i * (size_t)ncomp + c) + 1];
     return ABZ_OK;
 }
 

@@ -59,8 +59,12 @@ class LTM(DOSAlgorithm):
     `eta > 0` returns the DOS broadened by a Lorentzian of half width eta instead, -Im tr G(E + i eta) / pi at the domain's
     real energies, from the closed-form mean of 1 / (z - e) over every simplex (DeviceRule.ltm_green, `green_trace`).  Its
     error is the interpolation error O(1/npt^2) whatever eta is -- a grid sum of the resolvent needs npt >~ bandwidth / eta --
-    and it tends to the plain g(E) linearly in eta.  It goes with `symmetric` only: `cumulative`, `elements` and
-    `correction` raise ValueError, a k-sharded series NotImplementedError.  Without `eta` nothing changes."""
+    and it tends to the plain g(E) linearly in eta.  With `elements` ("energy", "orbitals" or a callable; `eigenvectors`,
+    `orbitals` and `symmetric` combine as without `eta`) the solution is the projected DOS broadened by eta,
+    -Im G_A(E + i eta) / pi as [nE, ncomp] ([ncomp] for a scalar domain), from the corner weights of every simplex
+    (DeviceRule.ltm_green with `elements`, `green_weighted`): with "orbitals" the diagonal G_aa of the local Green's function.
+    `cumulative` and `correction` raise ValueError with `eta`, a k-sharded series NotImplementedError.  Without `eta`
+    nothing changes."""
 
     def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None,
                  correction=False, eta=None):
@@ -69,9 +73,8 @@ class LTM(DOSAlgorithm):
             eta = float(eta)
             if not (np.isfinite(eta) and eta > 0.0):
                 raise ValueError(f"LTM: eta = {eta!r} is not a positive finite broadening")
-            if cumulative or elements is not None or correction:
-                raise ValueError("LTM: eta gives the broadened DOS -Im tr G(E + i eta) / pi: it does not go with cumulative, elements "
-                                 "or correction")
+            if cumulative or correction:
+                raise ValueError("LTM: eta gives the broadened DOS -Im G(E + i eta) / pi: it does not go with cumulative or correction")
         self.eta = eta
         self.cumulative = bool(cumulative)
         self.symmetric = bool(symmetric)
@@ -209,12 +212,8 @@ def _ltm_elements(rule, alg):
     return np.ascontiguousarray(A)
 
 
-def _ltm_solve(c, Es):
-    rule, el = c.cacheval, c.elements
-    if c.alg.eta is not None:
-        return -rule.ltm_green(Es + 1j * c.alg.eta).imag / np.pi
-    if el is None or isinstance(el, str):
-        return rule.ltm(Es, states=c.alg.cumulative, elements=el, correction=c.alg.correction)
+def _ltm_attach(rule, el):
+    """The cache's elements `el` (an array or a _DeviceOrbitals) attached to its rule, unless they still are."""
     rule.h  # a stale rule refills here and loses its elements
     if rule._ltm_ncomp == 0 or getattr(rule, "_ltm_owner", None) is not el:  # (another cache on the same rule attached its own)
         if isinstance(el, _DeviceOrbitals):
@@ -222,6 +221,20 @@ def _ltm_solve(c, Es):
         else:
             rule.ltm_elements(el)
         rule._ltm_owner = el
+
+
+def _ltm_solve(c, Es):
+    rule, el = c.cacheval, c.elements
+    if c.alg.eta is not None:
+        zs = Es + 1j * c.alg.eta
+        if el is None:
+            return -rule.ltm_green(zs).imag / np.pi
+        if not isinstance(el, str):
+            _ltm_attach(rule, el)
+        return -rule.ltm_green(zs, elements=el if isinstance(el, str) else "attached").imag / np.pi
+    if el is None or isinstance(el, str):
+        return rule.ltm(Es, states=c.alg.cumulative, elements=el, correction=c.alg.correction)
+    _ltm_attach(rule, el)
     return rule.ltm(Es, states=c.alg.cumulative, elements="attached", correction=c.alg.correction)
 
 
@@ -281,6 +294,30 @@ def green_trace(prob_or_cache, zs):
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     return c.cacheval.ltm_green(zs)
+
+
+def green_weighted(prob_or_cache, zs):
+    """G_A(z) = sum_b int dk A_b(k) / (z - e_b(k)) at the complex energies `zs` (Im z != 0), per unit cell, complex128
+    [nz, ncomp], with the elements of an LTM cache (`elements` = "energy", "orbitals" or a callable) or of a DOSProblem
+    (solved with LTM(elements="energy")): DeviceRule.ltm_green with the cache's elements on the cache's grid.  With orbital
+    weights it is the diagonal G_aa(z) of the local Green's function."""
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+        raise NotImplementedError("green_weighted on a k-sharded series is not implemented: the Green's function is computed on "
+                                  "whole grids")
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM(elements="energy"))
+    if not isinstance(c.alg, LTM):
+        raise ValueError("green_weighted needs an LTM cache")
+    if c.alg.elements is None:
+        raise ValueError("green_weighted needs an LTM cache with elements (green_trace gives the trace)")
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    el = c.elements
+    if not isinstance(el, str):
+        _ltm_attach(c.cacheval, el)
+    return c.cacheval.ltm_green(zs, elements=el if isinstance(el, str) else "attached")
 
 
 def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):

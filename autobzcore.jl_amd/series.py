@@ -688,19 +688,41 @@ class DeviceRule:
                                                   Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
         return self._sum_over_ranks(out)
 
-    def ltm_green(self, zs):
+    def ltm_green(self, zs, elements=None):
         """Trace of the Green's function tr G(z) = sum_b int dk / (z - e_b(k)) at the complex energies `zs`, per unit cell and
         summed over bands, as complex128 [nz] (abz_rule_ltm_green): the closed-form mean of 1 / (z - e) over every simplex of
         the mesh `ltm` scans, e linear inside a simplex.  -Im tr G(E + i eta) / pi is the DOS broadened by eta and tends to
         `ltm(E)` as eta -> 0; the error is the interpolation error O(1/npt^2) whatever eta is, where a grid sum of the
         resolvent needs npt >~ bandwidth / eta.  Every z needs Im z != 0 (Im z < 0 gives the conjugate of the value at conj z,
         to the bit); two calls return the same bits.  The rule must be a whole periodic grid (an unfolded rule is one); a
-        k-sharded rule raises NotImplementedError, with or without its halo plane."""
+        k-sharded rule raises NotImplementedError, with or without its halo plane.
+
+        `elements`: matrix elements A_b(k), linear inside a simplex like the energy; the result is then
+        G_A(z) = sum_b int dk A_b(k) / (z - e_b(k)) as complex128 [nz, ncomp] (abz_rule_ltm_green_weighted), from the mean of
+        lambda_i / (z - e) at every corner i of every simplex.  "energy": A = e itself (one component, z tr G(z) - n);
+        "attached": what ltm_elements or ltm_orbitals attached (orbital weights give the diagonal G_aa(z) of the local
+        Green's function); an array [ncomp, nk, n]: attached first."""
         self._ltm_refuse_shard("ltm_green")
         zs = np.ascontiguousarray(np.asarray(zs, dtype=np.complex128).reshape(-1))
-        out = np.zeros(len(zs), dtype=np.complex128)
-        h = self.h  # (a stale rule is refilled here)
-        L.check(L.lib().abz_rule_ltm_green(h, zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs), out.view(np.float64).ctypes.data_as(L.c_f64p)))
+        if elements is None:
+            out = np.zeros(len(zs), dtype=np.complex128)
+            h = self.h  # (a stale rule is refilled here)
+            L.check(L.lib().abz_rule_ltm_green(h, zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs), out.view(np.float64).ctypes.data_as(L.c_f64p)))
+            return out
+        if isinstance(elements, str):
+            if elements not in ("energy", "attached"):
+                raise ValueError(f"ltm_green: elements = {elements!r} is neither 'energy' nor 'attached'")
+        else:
+            self.ltm_elements(elements)
+            elements = "attached"
+        h = self.h  # (a stale rule is refilled here, which drops the attached elements)
+        ncomp = 1 if elements == "energy" else self._ltm_ncomp
+        if ncomp < 1:
+            raise ValueError("ltm_green: no matrix elements are attached (ltm_elements, ltm_orbitals; a rebuild of the rule drops them)")
+        out = np.zeros((len(zs), ncomp), dtype=np.complex128)
+        L.check(L.lib().abz_rule_ltm_green_weighted(h, L.LTM_A_ENERGY if elements == "energy" else L.LTM_A_ELEMENTS,
+                                                    zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs),
+                                                    out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out
 
     def ltm_fermi(self, nstates, tol=1e-10):

@@ -381,6 +381,22 @@ int abz_rule_ltm_halo(abz_rule* r);
  * eigenvalues, nz < 1, a NULL pointer, any Im z == 0 or non-finite z.  Entry point added without a change of ABZ_VERSION. */
 int abz_rule_ltm_green(abz_rule* r, const double* z /* [nz][2]: re, im */, int nz, double* out /* [nz][2] */);
 
+/* The same with matrix elements: G_A,c(z) = sum_b int dk A_{c,b}(k) / (z - e_b(k)) of every component c, per unit cell, e and A
+ * linear inside each simplex; with the orbital weights |U_ab|^2 of abz_rule_ltm_orbitals attached, the diagonal G_aa(z) of the
+ * local Green's function.  `source` as in abz_rule_ltm_weighted: ABZ_LTM_A_ENERGY (one component, A = e) or ABZ_LTM_A_ELEMENTS
+ * (what abz_rule_ltm_elements / abz_rule_ltm_orbitals attached, at most ABZ_LTM_MAX_COMP components).  out [nz][ncomp][2].
+ *      G_A,c(z) = w sum_{cells} sum_{d! simplices} sum_{bands} sum_{i=0..d} A_{c,i} W_i(z),   W_i = J[x_0 .. x_d, x_i](z) / (d + 1):
+ * the mean of lambda_i / (z - e) over a simplex is the J above with the knot x_i doubled (the recursion holds for repeated knots,
+ * J[x, x] = 1 / u).  The same evaluation rule, rho = 1/2, now on up to five knots: at most 39 terms of the series.  The d + 1
+ * weights of a (simplex, z) are formed once per group of components (4s, then a 2, then a 1) and every component contracts with
+ * them.  sum_i W_i = J and sum_i x_i W_i = z J - 1: elements == 1 give the trace, ABZ_LTM_A_ENERGY gives z tr G(z) - n.
+ * Im z < 0: the conjugate of the value at conj(z), to the bit.  No floating-point atomics: two calls return the same bits.
+ * Takes the rules abz_rule_ltm_green takes.  ABZ_ERR_UNSUPPORTED: slabs, with or without a halo; lists of irreducible nodes;
+ * symmetric rules.  ABZ_ERR_ARG: a `source` that is neither, ABZ_LTM_A_ELEMENTS with nothing attached, a rule without
+ * eigenvalues, nz < 1, a NULL pointer, any Im z == 0 or non-finite z; nothing is reserved, launched or written then.
+ * Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z /* [nz][2] */, int nz, double* out /* [nz][ncomp][2] */);
+
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.
  * First call with irr_idx = NULL to get *nirr; then with buffers irr_idx [nirr][d], wsym [nirr]. */

@@ -511,6 +511,21 @@ function ltm_green(r::HIPRule, zs::Vector{ComplexF64})
     return out
 end
 
+"""
+    ltm_green_weighted(r, zs; ncomp, energy=false)   -> Matrix{ComplexF64} [ncomp, nz]
+
+The Green's function with matrix elements, `G_A,c(z) = sum_b int dk A_cb(k) / (z - e_b(k))`, of the attached elements, `ncomp`
+of them, or with `energy` of `A = e` itself (`abz_rule_ltm_green_weighted`).  With the orbital weights of `ltm_orbitals!`
+attached it is the diagonal `G_aa(z)` of the local Green's function; `-imag(G_aa(E + im*eta)) / pi` is the projected DOS
+broadened by `eta`.
+"""
+function ltm_green_weighted(r::HIPRule, zs::Vector{ComplexF64}; ncomp::Integer=1, energy::Bool=false)
+    out = Matrix{ComplexF64}(undef, energy ? 1 : ncomp, length(zs))
+    check(ccall((:abz_rule_ltm_green_weighted, libabz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Float64}), r.h,
+        energy ? 1 : 0, zs, length(zs), out))
+    return out
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
