@@ -53,6 +53,7 @@ PROTOTYPES = {
     "abz_rule_ltm": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_rule_ltm_elements": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
     "abz_rule_ltm_orbitals": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
+    "abz_rule_ltm_projectors": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "abz_rule_ltm_elements_export": (C.c_int, [C.c_void_p, c_ip, c_f64p]),
     "abz_rule_ltm_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_rule_ltm_fermi": (C.c_int, [C.c_void_p, C.c_double, C.c_double, c_f64p, c_f64p]),

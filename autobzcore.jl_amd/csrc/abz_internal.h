@@ -511,6 +511,9 @@ int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plan
 // orbital c.  1...32 bands.  Launches only, under ABZ_K_EIG.
 bool ltm_orbitals_supported(int n);
 int launch_ltm_orbitals(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, PlaneView A, const int32_t* orb, int ncomp);
+// band projectors P^b_pq = U_pb conj(U_qb) into the same block: one component for p == q, Re and Im for p != q
+int ltm_projector_components(const int32_t* pairs, int npairs);
+int launch_ltm_projectors(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, PlaneView A, const int32_t* pairs, int npairs);
 // Orbit map of an unfolded rule: node_of[x] = the node k of the list idx [d][nk] that is x or its first image under syms that
 // is a node; rank [npt^d] is scratch; *missing_dev counts the points without one (their node_of is -1).  Launches only.
 int launch_ltm_orbit_map(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, const int32_t* idx, int64_t nk, int32_t* rank,

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <numeric>
@@ -2163,38 +2164,34 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
     return rc;
 } ABZ_CATCH_ALL
 
-// The same block filled on the device with |U_ab(k)|^2 (kernels_ltm_orb.hip).  H(k) comes from the rule's own planes or, for a
-// rule of eigenvalues only, from a transient H-only rule of the same grid that lives for this call.  Whatever was attached
-// stays in place until the new block is complete: a refusal or a failure leaves it untouched.
-int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
-    int rc = check_rule(r);
+// The same block filled on the device from the eigenvectors U(k) (kernels_ltm_orb.hip): |U_ab|^2 (abz_rule_ltm_orbitals) or the
+// band projectors U_pb conj(U_qb) (abz_rule_ltm_projectors).  H(k) comes from the rule's own planes or, for a rule of
+// eigenvalues only, from a transient H-only rule of the same grid that lives for this call.  Whatever was attached stays in
+// place until the new block is complete: a refusal or a failure leaves it untouched.
+
+// what both entry points ask of the rule, before they look at their selection
+static int ltm_eigvec_check_rule(abz_rule* r, const char* who, const char* what) {
+    int rc = ltm_check_grid(r, who);
     if (rc) return rc;
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_orbitals"))) return rc;
     if (r->node_of.p) {
-        set_error("abz_rule_ltm_orbitals: the rule's eigenvalues were unfolded from irreducible nodes; eigenvectors at every grid "
-                  "point are what such a rule avoids (build a full-grid rule with abz_ptr_rule_build)");
+        set_error("%s: the rule's eigenvalues were unfolded from irreducible nodes; eigenvectors at every grid "
+                  "point are what such a rule avoids (build a full-grid rule with abz_ptr_rule_build)", who);
         return ABZ_ERR_UNSUPPORTED;
     }
-    const abz_series* s = r->s;
-    const int n = s->n;
-    if (!ltm_orbitals_supported(n)) {
-        set_error("abz_rule_ltm_orbitals: %d bands; orbital weights are computed for 1...32", n);
+    if (!ltm_orbitals_supported(r->s->n)) {
+        set_error("%s: %d bands; %s are computed for 1...32", who, r->s->n, what);
         return ABZ_ERR_UNSUPPORTED;
     }
-    if (orb) {
-        ABZ_REQUIRE(norb >= 1 && norb <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: norb = %d outside 1..%d", norb, ABZ_LTM_MAX_COMP);
-        for (int c = 0; c < norb; ++c)
-            ABZ_REQUIRE(orb[c] >= 0 && orb[c] < n, "abz_rule_ltm_orbitals: orb[%d] = %d outside 0..%d", c, orb[c], n - 1);
-    } else {
-        ABZ_REQUIRE(n <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: all %d orbitals are more than %d components; select some (orb, norb)", n,
-                    ABZ_LTM_MAX_COMP);
-    }
-    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
-                "abz_rule_ltm_orbitals: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
-    const int ncomp = orb ? norb : n;
-    abz_ctx* ctx = s->ctx;
+    return ABZ_OK;
+}
+
+// allocate the block of ncomp components, fill it (`fill(H, A)` launches the kernel), wait once, attach
+static int ltm_eigvec_attach(abz_rule* r, const char* who, int ncomp, const std::function<int(PlaneView, PlaneView)>& fill) {
+    const int n = r->s->n;
+    abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: the weight is 1, no H needed)
+    int rc = ABZ_OK;
+    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: U = 1, no H needed)
     if (!r->H.base && n > 1) {
         abz_rule* built = nullptr;
         if ((rc = rule_build(r->s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
@@ -2209,10 +2206,10 @@ int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
     A.tile = (int64_t)planes * r->E.row;
     A.pitch = r->E.row;
     A.compact = 0;
-    if (!rc) rc = launch_ltm_orbitals(ctx, n, r->npt, r->ntiles, tmp ? tmp->H : r->H, A, orb, ncomp);
+    if (!rc) rc = fill(tmp ? tmp->H : r->H, A);
     // the one synchronisation of the call: the block is complete, nothing reads the old one or the transient rule any more
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_orbitals: the weight kernel failed");
+        set_error("%s: the kernel failed", who);
         rc = ABZ_ERR_HIP;
     }
     if (tmp) {
@@ -2224,6 +2221,50 @@ int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
     r->ltm_ncomp = ncomp;
     r->A = A;
     return ABZ_OK;
+}
+
+int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_orbitals", "orbital weights"))) return rc;
+    const abz_series* s = r->s;
+    const int n = s->n;
+    if (orb) {
+        ABZ_REQUIRE(norb >= 1 && norb <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: norb = %d outside 1..%d", norb, ABZ_LTM_MAX_COMP);
+        for (int c = 0; c < norb; ++c)
+            ABZ_REQUIRE(orb[c] >= 0 && orb[c] < n, "abz_rule_ltm_orbitals: orb[%d] = %d outside 0..%d", c, orb[c], n - 1);
+    } else {
+        ABZ_REQUIRE(n <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: all %d orbitals are more than %d components; select some (orb, norb)", n,
+                    ABZ_LTM_MAX_COMP);
+    }
+    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
+                "abz_rule_ltm_orbitals: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
+    const int ncomp = orb ? norb : n;
+    return ltm_eigvec_attach(r, "abz_rule_ltm_orbitals", ncomp, [&](PlaneView H, PlaneView A) {
+        return launch_ltm_orbitals(s->ctx, n, r->npt, r->ntiles, H, A, orb, ncomp);
+    });
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_projectors(abz_rule* r, const int32_t* pairs, int npairs) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_projectors", "band projectors"))) return rc;
+    const abz_series* s = r->s;
+    const int n = s->n;
+    ABZ_REQUIRE(pairs, "abz_rule_ltm_projectors: null pairs");
+    ABZ_REQUIRE(npairs >= 1 && npairs <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_projectors: npairs = %d outside 1..%d", npairs, ABZ_LTM_MAX_COMP);
+    for (int i = 0; i < npairs; ++i)
+        ABZ_REQUIRE(pairs[2 * i] >= 0 && pairs[2 * i] < n && pairs[2 * i + 1] >= 0 && pairs[2 * i + 1] < n,
+                    "abz_rule_ltm_projectors: pairs[%d] = (%d, %d) outside 0..%d", i, pairs[2 * i], pairs[2 * i + 1], n - 1);
+    const int ncomp = ltm_projector_components(pairs, npairs);
+    ABZ_REQUIRE(ncomp <= ABZ_LTM_MAX_COMP,
+                "abz_rule_ltm_projectors: %d pairs are %d components (one for p == q, two for p != q), more than %d; attach them in groups",
+                npairs, ncomp, ABZ_LTM_MAX_COMP);
+    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
+                "abz_rule_ltm_projectors: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
+    return ltm_eigvec_attach(r, "abz_rule_ltm_projectors", ncomp, [&](PlaneView H, PlaneView A) {
+        return launch_ltm_projectors(s->ctx, n, r->npt, r->ntiles, H, A, pairs, npairs);
+    });
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {

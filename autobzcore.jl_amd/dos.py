@@ -320,6 +320,29 @@ def green_weighted(prob_or_cache, zs):
     return c.cacheval.ltm_green(zs, elements=el if isinstance(el, str) else "attached")
 
 
+def green_local(prob_or_cache, zs, orbitals=None):
+    """The local Green's function G_pq(z) = [int dk inv(z - H(k))]_pq on the orbitals `orbitals` (None: all n) at the complex
+    energies `zs` (Im z != 0), per unit cell, complex128 [nz, m, m], on the grid of an LTM cache or of a DOSProblem (solved
+    with LTM()): DeviceRule.ltm_green_matrix, the band projectors U_pb conj(U_qb) as elements of the tetrahedron method.  Its
+    diagonal is `green_weighted` with orbital weights, its trace `green_trace`.  The cache's own elements are attached again by
+    its next solve."""
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+        raise NotImplementedError("green_local on a k-sharded series is not implemented: the Green's function is computed on "
+                                  "whole grids")
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    if not isinstance(c.alg, LTM):
+        raise ValueError("green_local needs an LTM cache")
+    if c.alg.symmetric and c.p.syms is not None and len(c.p.syms) > 1:
+        raise ValueError("green_local needs symmetric=False (band projectors are not invariant under the zone's symmetries, and "
+                         "an unfolded rule stores no H(k))")
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    return c.cacheval.ltm_green_matrix(zs, orbitals)
+
+
 def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):
     """(E_band, E_F): the band energy sum_b int e_b theta(E_F - e_b) of `nstates` states per unit cell.  E_F is
     `fermi_level`'s on the same grid; one single-energy scan with the energy as the element follows, with Bloechl's

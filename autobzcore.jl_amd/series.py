@@ -625,6 +625,66 @@ class DeviceRule:
         L.check(L.lib().abz_rule_ltm_orbitals(h, orb.ctypes.data_as(L.c_i32p), len(orb)))
         self._ltm_ncomp = len(orb)
 
+    def ltm_projectors(self, pairs):
+        """Attach the band projectors P^b_pq(k) = U_pb(k) conj(U_qb(k)) of the orbital pairs `pairs` [npairs, 2] as matrix
+        elements, computed on the device like the orbital weights (abz_rule_ltm_projectors).  A pair (p, p) is one component,
+        |U_pb|^2; a pair p != q is two, Re P then Im P; at most 16 components in all, in the order of the pairs.  No phase of
+        an eigenvector changes them; at a degenerate level they belong to some orthonormal basis of the eigenspace and only
+        their sum over the level is defined.  `ltm_green(zs, elements="attached")` then gives G_{Re P} and G_{Im P}, and
+        G_pq = G_{Re P} + i G_{Im P}, G_qp = G_{Re P} - i G_{Im P} (`ltm_green_matrix` does that)."""
+        self._ltm_refuse_shard("ltm_projectors")
+        h = self.h  # (a stale rule is refilled here)
+        pr = np.asarray(pairs)
+        if pr.size and not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError(f"ltm_projectors: pairs = {pairs!r} are not integer indices")
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError(f"ltm_projectors: pairs of shape {pr.shape}, expected [npairs, 2]")
+        pr = np.ascontiguousarray(pr.astype(np.int32))
+        L.check(L.lib().abz_rule_ltm_projectors(h, pr.ctypes.data_as(L.c_i32p), len(pr)))
+        self._ltm_ncomp = int(np.where(pr[:, 0] == pr[:, 1], 1, 2).sum())
+
+    def ltm_green_matrix(self, zs, orbitals=None):
+        """The local Green's function G_pq(z) = sum_b int dk U_pb conj(U_qb) / (z - e_b(k)) on the orbitals `orbitals` (None:
+        all n) at the complex energies `zs` (Im z != 0), per unit cell, complex128 [nz, m, m]: the tetrahedron counterpart of a
+        grid mean of inv(z - H(k)), with the interpolation error O(1/npt^2) whatever Im z is.  The m diagonal pairs and the
+        m (m - 1) / 2 pairs p < q are dealt, in that order, into groups of at most 16 components (one for a diagonal pair, two
+        for the others; m <= 4 is one group); every group is attached with `ltm_projectors` and scanned with
+        `ltm_green(zs, elements="attached")`.  Each group repeats the eigen-solve of the whole grid: the eigenvectors are
+        never stored.  The last group stays attached, and a DOS cache on the same rule attaches its own elements again."""
+        self._ltm_refuse_shard("ltm_green_matrix")
+        zs = np.ascontiguousarray(np.asarray(zs, dtype=np.complex128).reshape(-1))
+        n = self.dev.s.n
+        orb = np.arange(n) if orbitals is None else np.asarray(orbitals).reshape(-1)
+        if orb.size < 1 or not np.issubdtype(orb.dtype, np.integer):
+            raise ValueError(f"ltm_green_matrix: orbitals = {orbitals!r} is not a sequence of orbital indices")
+        if len(set(orb.tolist())) != len(orb):
+            raise ValueError(f"ltm_green_matrix: orbitals = {orbitals!r} names an orbital twice")
+        m = len(orb)
+        todo = [(a, a) for a in range(m)] + [(a, b) for a in range(m) for b in range(a + 1, m)]  # positions in `orb`
+        groups, ncomp = [[]], 0
+        for a, b in todo:
+            need = 1 if a == b else 2
+            if ncomp + need > L.LTM_MAX_COMP:
+                groups.append([])
+                ncomp = 0
+            groups[-1].append((a, b))
+            ncomp += need
+        G = np.zeros((len(zs), m, m), dtype=np.complex128)
+        for group in groups:
+            self.ltm_projectors([(orb[a], orb[b]) for a, b in group])
+            self._ltm_owner = None  # (whatever a DOS cache had attached is gone)
+            g = self.ltm_green(zs, elements="attached")
+            c = 0
+            for a, b in group:
+                if a == b:
+                    G[:, a, a] = g[:, c]
+                    c += 1
+                else:
+                    G[:, a, b] = g[:, c] + 1j * g[:, c + 1]
+                    G[:, b, a] = g[:, c] - 1j * g[:, c + 1]
+                    c += 2
+        return G
+
     def ltm_elements_export(self):
         """The attached matrix elements [ncomp, nk, n] back on the host (abz_rule_ltm_elements_export), in the order
         ltm_elements takes them; None when nothing is attached."""

@@ -314,6 +314,17 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp);
  * eigenvalues, norb outside 1..ABZ_LTM_MAX_COMP, an index outside 0..n-1 (duplicates are fine), orb == NULL with
  * n > ABZ_LTM_MAX_COMP, a series that is not Hermitian.  A refusal or failure leaves attached elements as they were. */
 int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb);
+/* Band projectors as LTM matrix elements, computed on the device like the orbital weights and attached like them:
+ * P^b_pq(k) = U_pb(k) conj(U_qb(k)), which no phase of an eigenvector changes.  Pair i = (pairs[2i], pairs[2i+1]) = (p, q) takes
+ * one component for p == q, |U_pb|^2 (the planes of abz_rule_ltm_orbitals, bit for bit), and two consecutive ones for p != q,
+ * Re P^b_pq = ur_p ur_q + ui_p ui_q, then Im P^b_pq = ui_p ur_q - ur_p ui_q; components follow the order of the pairs.  With
+ * them abz_rule_ltm_green_weighted returns G_{Re P}(z) and G_{Im P}(z), and the local Green's function is
+ *      G_pq(z) = sum_b int dk P^b_pq(k) / (z - e_b(k)) = G_{Re P}(z) + i G_{Im P}(z),   G_qp(z) = G_{Re P}(z) - i G_{Im P}(z).
+ * At a degenerate level single projectors are those of some orthonormal basis of the eigenspace; their sum over the level,
+ * sum_b P^b_pq = delta_pq and sum_b e_b P^b_pq = H_pq(k) are defined.  Rules, H(k), refusals and what a refusal leaves in place:
+ * as abz_rule_ltm_orbitals.  ABZ_ERR_ARG also for pairs == NULL, npairs < 1, an index outside 0..n-1, more than
+ * ABZ_LTM_MAX_COMP components in all (attach them in groups).  Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_projectors(abz_rule* r, const int32_t* pairs /* [npairs][2] */, int npairs);
 /* Attached elements back to the host: *ncomp (0 if none), and, if A != NULL, A [ncomp][nk][n] in the order
  * abz_rule_ltm_elements takes them. */
 int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A);
@@ -358,7 +369,8 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
  * take the slab and return its PARTIAL sum: the sum over the cells whose outermost index lies in [outer_begin, outer_end), every
  * simplex with the whole grid's weight 1 / (d! npt^d).  The partial sums of the slabs of a partition of [0, npt) add up to the
  * whole grid's value; N is exactly 0 below the bands on every slab.  Everything else keeps refusing slabs with
- * ABZ_ERR_UNSUPPORTED, halo or not: ABZ_LTM_A_ELEMENTS, abz_rule_ltm_elements, _orbitals, _elements_export, _fermi, _unfold.
+ * ABZ_ERR_UNSUPPORTED, halo or not: ABZ_LTM_A_ELEMENTS, abz_rule_ltm_elements, _orbitals, _projectors, _elements_export, _fermi,
+ * _unfold.
  * ABZ_ERR_ARG: a whole periodic grid (nothing to attach), a rule without eigenvalues.  ABZ_ERR_UNSUPPORTED: a node list or
  * symmetric rule, a rule of abz_rule_ltm_unfold.  A refusal or failure leaves r as it was.  Entry point added without a
  * change of ABZ_VERSION. */

@@ -526,6 +526,61 @@ function ltm_green_weighted(r::HIPRule, zs::Vector{ComplexF64}; ncomp::Integer=1
     return out
 end
 
+"""
+    ltm_projectors!(r, pairs)                 -> number of components
+
+Attach the band projectors `P^b[p, q](k) = U[p, b] * conj(U[q, b])` of the orbital pairs `pairs` (1-based tuples `(p, q)`) as
+matrix elements, computed on the device from `H(k)` (`abz_rule_ltm_projectors`): one component `|U[p, b]|^2` for `p == q`,
+two (`real`, then `imag`) for `p != q`, at most 16 in all, in the order of the pairs.
+"""
+function ltm_projectors!(r::HIPRule, pairs::AbstractVector{<:Tuple{Integer,Integer}})
+    pq = Cint[x - 1 for pr in pairs for x in pr]
+    check(ccall((:abz_rule_ltm_projectors, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint), r.h, pq, length(pairs)))
+    return sum(p == q ? 1 : 2 for (p, q) in pairs)
+end
+
+"""
+    ltm_green_matrix(r, zs, n; orbitals=1:n)   -> Array{ComplexF64,3} [m, m, nz]
+
+The local Green's function `G[p, q](z) = sum_b int dk U[p, b] conj(U[q, b]) / (z - e_b(k))` on the listed orbitals of an
+`n`-band rule: the diagonal pairs and the pairs `p < q` are dealt into groups of at most 16 components, each attached with
+`ltm_projectors!` and scanned with `ltm_green_weighted`; `G[p, q] = G_ReP + im * G_ImP`, `G[q, p] = G_ReP - im * G_ImP`.
+Each group repeats the eigen-solve of the grid; the last group stays attached.
+"""
+function ltm_green_matrix(r::HIPRule, zs::Vector{ComplexF64}, n::Integer; orbitals::AbstractVector{<:Integer}=1:n)
+    allunique(orbitals) || throw(ArgumentError("ltm_green_matrix: orbitals names an orbital twice"))
+    m = length(orbitals)
+    todo = vcat([(a, a) for a in 1:m], [(a, b) for a in 1:m for b in a+1:m])
+    groups = [Tuple{Int,Int}[]]
+    ncomp = 0
+    for (a, b) in todo
+        need = a == b ? 1 : 2
+        if ncomp + need > 16
+            push!(groups, Tuple{Int,Int}[])
+            ncomp = 0
+        end
+        push!(groups[end], (a, b))
+        ncomp += need
+    end
+    G = zeros(ComplexF64, m, m, length(zs))
+    for group in groups
+        nc = ltm_projectors!(r, [(orbitals[a], orbitals[b]) for (a, b) in group])
+        g = ltm_green_weighted(r, zs; ncomp=nc)
+        c = 1
+        for (a, b) in group
+            if a == b
+                G[a, a, :] = g[c, :]
+                c += 1
+            else
+                G[a, b, :] = g[c, :] .+ im .* g[c+1, :]
+                G[b, a, :] = g[c, :] .- im .* g[c+1, :]
+                c += 2
+            end
+        end
+    end
+    return G
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
