@@ -85,6 +85,7 @@ WANT_H_ROW_MAJOR = 16  # abz_eval_nodes: matrices row-major in H_out (numpy's or
 F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = range(7)
 LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = 0, 1, 2, 3
 K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
+K_EVAL_FUSED = 7  # launches only: the K_EVAL launches of the fused grid kernel
 LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
 LTM_MAX_COMP = 16

@@ -77,6 +77,7 @@ enum Switch {
     SW_IAI_LANES,        // ABZ_IAI_LANES       lanes (host thread + stream each) an IAI sweep is split over
     SW_IAI_LANE_MIN,     // ABZ_IAI_LANE_MIN    solves a lane needs before a sweep is split further
     SW_CHAIN_FUSED,      // ABZ_CHAIN_FUSED     3-D full grids: variables 3 and 2 contracted in one launch (0: one launch per level)
+    SW_EVAL_FUSED,       // ABZ_EVAL_FUSED      3-D full grids, n <= 4: the grid kernel contracts variable 2 itself (0: level-1 sets in memory)
     SW_COUNT
 };
 int abz_switch(Switch s);  // the switch's integer value from the environment, or its default
@@ -386,6 +387,12 @@ struct EvalSpec {
     bool deriv;
     bool herm;  // series is Hermitian-symmetric and deriv is false: evaluate the upper triangle only
     bool packed = false;  // grid mode: `src` holds PACKED Hermitian level-1 sets (packed_herm.h), Pk<n>::size((M - 1) / 2) numbers per line
+    // grid mode, 3-D full grids: the grid kernel contracts variable 2 itself (eval_fused_supported).  src2: level-2 sets
+    // [nlines / npt][M2][numbers per line] (packed like `src` would be); phs2: phase table [npt][M2], readable for
+    // ABZ_CONTRACT_GRID_MAXM entries from the start of every row (level_phase_tables pads it); `src` is not read
+    const double2* src2 = nullptr;
+    const double2* phs2 = nullptr;
+    int M2 = 0;
     // outputs (tiled planar views), base == nullptr when not wanted
     PlaneView H;
     PlaneView E;
@@ -393,6 +400,7 @@ struct EvalSpec {
 };
 int launch_eval(abz_ctx* ctx, const EvalSpec& es);
 bool eval_packed_supported(int n, int M, int npt);
+bool eval_fused_supported(int n, int64_t mnn, int M2, int npt);  // mnn: numbers per line (packed_row_elems or M n n)
 // rows [nrows][M n n] of full coefficients (innermost variable fastest) -> packed rows [nrows][P] (packed_herm.h)
 int launch_pack_rows(abz_ctx* ctx, int n, int M, const double2* src, int64_t nrows, double2* out);
 size_t packed_row_elems(int n, int M);

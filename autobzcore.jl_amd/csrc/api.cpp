@@ -90,6 +90,7 @@ const SwitchDef g_switches[SW_COUNT] = {
     {"ABZ_IAI_LANES", 4, "lanes (host thread + stream each) a sweep of independent IAI solves is split over; 1: off"},
     {"ABZ_IAI_LANE_MIN", 16, "solves per lane below which a sweep is not split further"},
     {"ABZ_CHAIN_FUSED", 1, "0: 3-D full-grid chains contract variables 3 and 2 in two launches instead of contract_chain_kernel"},
+    {"ABZ_EVAL_FUSED", 1, "0: 3-D full-grid rules (n <= 4) build level-1 sets with contract_chain_kernel instead of contracting variable 2 inside the grid kernel"},
 };
 }  // namespace
 
@@ -562,7 +563,8 @@ static int plan_upload(abz_ctx* ctx, const Plan& p, PlanDev& pd) {
 static int level_phase_tables(abz_series* s, int npt, const double2* tab, PlanDev& pd) {
     for (int L = 1; L < s->d; ++L) {
         const int M = s->dims[L];
-        int rc = pd.phg[L].reserve(sizeof(double2) * (size_t)npt * M);
+        // (padded: the fused grid kernel fetches ABZ_CONTRACT_GRID_MAXM entries from the start of a row, EvalSpec::phs2)
+        int rc = pd.phg[L].reserve(sizeof(double2) * ((size_t)npt * M + ABZ_CONTRACT_GRID_MAXM));
         if (rc) return rc;
         PhaseSpec ps;
         ps.B = npt;
@@ -1157,13 +1159,20 @@ static int rule_fill(abz_rule* r) {
     }
     // full grids of a Hermitian series (n <= 4, values / eigenvalues only): the chain and the grid kernel work on packed sets
     const bool packed_chain = r->full && s->hermitian && !(r->want & ABZ_WANT_VEL) && eval_packed_supported(n, s->dims[0], r->npt);
-    auto run_eval = [&](const double2* level1, bool deriv, PlaneView Hout, PlaneView Eout, PlaneView Uout) -> int {
+    // level2: the grid kernel contracts variable 2 itself from these level-2 sets (EvalSpec::src2); level1 is not read then
+    auto run_eval = [&](const double2* level1, bool deriv, PlaneView Hout, PlaneView Eout, PlaneView Uout,
+                        const double2* level2 = nullptr) -> int {
         EvalSpec es;
         es.n = n;
         es.M = s->dims[0];
         es.first = s->first[0];
         es.period = s->period[0];
         es.src = level1;
+        if (level2) {
+            es.src2 = level2;
+            es.phs2 = rp->pd.phg[1].as<double2>();
+            es.M2 = s->dims[1];
+        }
         es.grid = r->full;
         es.npt = r->npt;
         es.nlines = r->full ? (d == 1 ? 1 : plan.nitems[1]) : 0;
@@ -1186,6 +1195,26 @@ static int rule_fill(abz_rule* r) {
     };
     const double2* level1 = nullptr;
     int rc;
+    // 3-D full grids, values / eigenvalues only: the chain stops at the level-2 sets and the grid kernel contracts
+    // variable 2 itself, line by line from LDS -- wherever the chain kernel would run and the grid kernel has the LDS for
+    // it (contract_chain_fits also bounds the outermost indices by the 65535 rows of the kernel's launch grid).  The sums are
+    // those of contract_chain_kernel bit for bit.  ABZ_CHAIN_FUSED=0 keeps the whole per-level route.
+    const int64_t line_elems = packed_chain ? (int64_t)packed_row_elems(n, s->dims[0]) : (int64_t)s->dims[0] * n * n;
+    // Size rule (tools/time_eval_fused.py): rules of a Hermitian series that keep full matrices (the
+    // reference layout) are bound by their stores; they measured 2-8 % slower at 150 ... 250 points (3 bands) in one session or
+    // both and 3.5 % slower at 100 points with 4 bands in all three, so they keep the chain kernel beyond 64 points.  Every
+    // other supported shape measured faster or within 1 % in at least two of three sessions.
+    const bool ref_layout_large = s->hermitian && r->H.base && !r->H.compact && r->npt > 64;
+    const bool eval_fused = r->full && d == 3 && n <= 4 && !(r->want & ABZ_WANT_VEL) && !Uv.base && rp->pd.phg[2].p && rp->pd.phg[1].p &&
+                            !ref_layout_large &&
+                            abz_switch(SW_CHAIN_FUSED) && abz_switch(SW_EVAL_FUSED) &&
+                            contract_chain_fits(line_elems, s->dims[2], s->dims[1], r->npt, plan.outer_n) &&
+                            eval_fused_supported(n, line_elems, s->dims[1], r->npt);
+    if (eval_fused) {
+        const double2* level2 = nullptr;
+        if ((rc = build_chain(s, plan, rp->pd, tab, 0, &level2, 2, nullptr, packed_chain))) return rc;
+        return run_eval(nullptr, false, r->H, r->E, PlaneView(), level2);
+    }
     if ((rc = build_chain(s, plan, rp->pd, tab, 0, &level1, 1, nullptr, packed_chain))) return rc;
     if ((rc = run_eval(level1, false, r->H, vel_done ? PlaneView() : r->E, Uv))) return rc;
     if ((r->want & ABZ_WANT_VEL) && !vel_done) {

@@ -261,9 +261,12 @@ int launch_contract_grid(abz_ctx* ctx, const double2* src, int64_t src_slot_elem
     if (nparents == 0 || L == 0 || gcnt == 0) return ABZ_OK;
     ProfScope ps(ctx, ABZ_K_CONTRACT);
     const int64_t gx = cdiv(L, 128);
-    // enough blocks to fill the chip, at least ~4 grid indices per thread to amortise the loads
+    // enough blocks to fill the chip, at least ~4 grid indices per thread to amortise the loads.  The one-parent
+    // scalar-phase launch ahead of the fused eval (150^3 SVO: 561 columns, 150 indices) would be 190 workgroups whose
+    // threads wait for four scalar phase round trips in series: one index per thread there (750 workgroups)
     const int target_blocks = 4096;
-    int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(cdiv(gcnt, 4), cdiv(target_blocks, gx * nparents)));
+    const int per_thread = (nparents == 1 && phs_table && !deriv) ? 1 : 4;
+    int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(cdiv(gcnt, per_thread), cdiv(target_blocks, gx * nparents)));
     const int chunk = (int)cdiv(gcnt, nsplit);
     nsplit = cdiv(gcnt, chunk);
     if (nparents > 65535 || nsplit > 65535) {
@@ -550,6 +553,11 @@ struct EvalArgs {
     int nt;  // non-temporal stores (rule values larger than the Infinity Cache)
     int pk;    // the level-1 sets are PACKED Hermitian sets (packed_herm.h): Pk<N>::size((M - 1) / 2) numbers per line
     double inv_period;
+    // fused last contraction (eval_grid_kernel<..., FUSE>): level-2 sets [nlines / npt][M2][numbers per line], the
+    // phase table [npt][M2] of variable 2, blocks per outermost index
+    const double2* src2 = nullptr;
+    const double2* phs2 = nullptr;
+    int M2 = 0, bpk = 0;
 };
 
 // planes of one node at column i1 of tile `line`; with a wave-uniform line every plane row is a scalar
@@ -844,9 +852,54 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false>
+// Fused last contraction (eval_grid_kernel<..., FUSE>): one line's level-1 set from the level-2 set s2[M2][MNN] of its
+// outermost index (LDS) and the phases of its k2 (wave-uniform address: scalar loads), lane = column, with the very fma
+// sequence of contract_grid_s_kernel / contract_chain_kernel for m ascending -- the sums are theirs bit for bit.
+// The phases are fetched as a fixed group of ABZ_CONTRACT_GRID_MAXM, whatever M2 is (straight-line scalar loads that can
+// be issued ahead of the block's barrier): the table is readable that far past the start of any row (EvalSpec::phs2).
+struct LinePhases {
+    double x[ABZ_CONTRACT_GRID_MAXM], y[ABZ_CONTRACT_GRID_MAXM];
+};
+__device__ __forceinline__ void load_line_phases(cptr_t p, LinePhases& ph) {
+#pragma unroll
+    for (int m = 0; m < ABZ_CONTRACT_GRID_MAXM; ++m) {
+        ph.x[m] = p[m].x;
+        ph.y[m] = p[m].y;
+    }
+}
+
+template <int M2>
+__device__ __forceinline__ void contract_line(const double2* s2, const LinePhases& ph, double2* dst, int MNN, int lane) {
+    for (int l = lane; l < MNN; l += 64) {
+        double ar = 0.0, ai = 0.0;
+#pragma unroll
+        for (int m = 0; m < M2; ++m) {
+            const double2 c = s2[m * MNN + l];
+            ar = fma(c.x, ph.x[m], ar);
+            ar = fma(-c.y, ph.y[m], ar);
+            ai = fma(c.x, ph.y[m], ai);
+            ai = fma(c.y, ph.x[m], ai);
+        }
+        dst[l] = make_double2(ar, ai);
+    }
+}
+
+__device__ __forceinline__ void contract_line_m(int M2, const double2* s2, const LinePhases& ph, double2* dst, int MNN, int lane) {
+#define CL(MM) case MM: contract_line<MM>(s2, ph, dst, MNN, lane); break;
+    switch (M2) {  // exact coefficient count: straight-line code
+        CL(1) CL(2) CL(3) CL(4) CL(5) CL(6) CL(7) CL(8) CL(9) CL(10) CL(11) CL(12) CL(13) CL(14) CL(15) CL(16)
+        default: break;  // launch_eval admits 1 ... ABZ_CONTRACT_GRID_MAXM only
+    }
+#undef CL
+}
+
+// FUSE: the level-1 sets never exist in memory.  A block owns one outermost index k3 and the lines k2 = 4 seg + wave,
+// stepping by 4 bpk, of that index; it stages the level-2 set of k3 next to the phase table (one round trip) and
+// every wave contracts its next line into its other LDS buffer where the plain kernel hands over prefetched
+// registers: the work loop holds no vector load at all.
+template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false>
 __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
-    extern __shared__ double2 lds_c[];  // [4 waves][2 buffers][MNN]
+    extern __shared__ double2 lds_c[];  // [4 waves][2 buffers][MNN], phase table [npt], FUSE: level-2 set [M2][MNN]
     // the wave index is made an SGPR value: every per-line quantity (tile base, coefficient row) is
     // then scalar arithmetic
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -867,6 +920,67 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
     // come from an LDS copy of the table.  A unit of work is one pass (64 KPL nodes) of one line.
     const int npass = (a.npt + 64 * KPL - 1) / (64 * KPL);
     double2* const tab_l = lds_c + (size_t)4 * 2 * MNN;  // LDS copy of the phase table, shared by the block
+    if constexpr (FUSE) {
+        static_assert(!VEC, "the fused instance stores values and eigenvalues only");
+        const int k3 = blockIdx.y, seg = blockIdx.x;  // grid (bpk, outermost indices): both scalars
+        const int L2 = a.M2 * MNN;
+        const double2* __restrict__ src2 = a.src2 + (int64_t)k3 * L2;
+        double2* const s2 = tab_l + a.npt;
+        // the phases of the wave's first line: in flight across the copy and the barrier (a wave beyond the last line
+        // reads row 0)
+        const int kstride = 4 * a.bpk;
+        int k2 = 4 * seg + wave;
+        LinePhases ph;
+        load_line_phases(as_const(a.phs2 + (int64_t)(k2 < a.npt ? k2 : 0) * a.M2), ph);
+        // phase table and level-2 set in one round trip: the loads are unconditional, from clamped 32-bit indices off
+        // scalar bases, and the asm keeps the stores' bounds checks from being hoisted above them
+        {
+            const int it = threadIdx.x;
+            double2 vt = a.tab[min(it, a.npt - 1)];
+            double2 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = src2[min(it + 256 * j, L2 - 1)];
+            asm volatile("" : "+v"(vt.x), "+v"(vt.y));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(v[j].x), "+v"(v[j].y));
+            if (it < a.npt) tab_l[it] = vt;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (it + 256 * j < L2) s2[it + 256 * j] = v[j];
+            for (int i = it + 256; i < a.npt; i += 256) tab_l[i] = a.tab[i];       // (more than 256 points)
+            for (int i = it + 4 * 256; i < L2; i += 256) s2[i] = src2[i];          // (more than 1024 numbers)
+        }
+        __syncthreads();
+        if (k2 >= a.npt) return;
+        contract_line_m(a.M2, s2, ph, mybuf, MNN, lane);
+        int iz0[KPL], iw0[KPL];
+#pragma unroll
+        for (int j = 0; j < KPL; ++j) {
+            const int i1 = lane + 64 * j;
+            iz0[j] = i1 < a.npt ? i1 : 0;
+            iw0[j] = (int)(((unsigned)fm * (unsigned)iz0[j]) % (unsigned)a.npt);
+        }
+        int cur = 0, pass = 0;
+        while (k2 < a.npt) {
+            // the next unit is the same line again (its set stays where it is) or the wave's next line
+            const bool last_pass = pass + 1 >= npass;
+            const int nk2 = last_pass ? k2 + kstride : k2;
+            const bool contract_next = last_pass && nk2 < a.npt;
+            wave_lds_sync();
+            auto mid_fn = [&]() {
+                if (contract_next) {
+                    load_line_phases(as_const(a.phs2 + (int64_t)nk2 * a.M2), ph);
+                    contract_line_m(a.M2, s2, ph, mybuf + (size_t)(cur ^ 1) * MNN, MNN, lane);
+                }
+            };
+            eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK>(a, mybuf + (size_t)cur * MNN, tab_l, fm, iz0, iw0, npass, pass * (64 * KPL), lane,
+                                                                (int64_t)k3 * a.npt + k2, mid_fn);
+            if (last_pass) cur ^= 1;
+            pass = last_pass ? 0 : pass + 1;
+            k2 = nk2;
+        }
+        return;
+    }
     for (int i = threadIdx.x; i < a.npt; i += 256) tab_l[i] = a.tab[i];
     __syncthreads();
     const int64_t lstride = (int64_t)gridDim.x * 4;
@@ -998,6 +1112,13 @@ bool eval_packed_supported(int n, int M, int npt) {
     return P <= (size_t)EVAL_MAX_MNN && npt < 65536 && sizeof(double2) * (4 * 2 * P + (size_t)npt) <= 64 * 1024;
 }
 
+// Can the grid kernel contract variable 2 itself (EvalSpec::src2)?  Its LDS-staged path with the level-2 set of one
+// outermost index next to the four waves' double buffers and the phase table; `mnn` numbers per line.
+bool eval_fused_supported(int n, int64_t mnn, int M2, int npt) {
+    return n >= 1 && n <= 4 && mnn >= 1 && mnn <= EVAL_MAX_MNN && M2 >= 1 && M2 <= ABZ_CONTRACT_GRID_MAXM && npt >= 1 &&
+           npt < 65536 && sizeof(double2) * ((size_t)M2 * mnn + 4 * 2 * (size_t)mnn + (size_t)npt) <= 64 * 1024;
+}
+
 int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
     if (es.n > 4) {
         GenSpec gs;
@@ -1083,7 +1204,44 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
         }
         // + an LDS copy of the phase table (fm * i1 < npt^2 must fit 32 bits)
         const size_t lds = sizeof(double2) * (4 * 2 * (size_t)mnn + (size_t)a.npt);
-        if (mnn <= EVAL_MAX_MNN && lds <= 64 * 1024 && a.npt < 65536) {
+        if (es.src2) {
+            // fused last contraction: whole blocks per outermost index, about the block count chosen above (150^3: one
+            // line per wave, 38 blocks for each of the 150 indices)
+            if (es.deriv || es.U.base || !eval_fused_supported(es.n, mnn, es.M2, es.npt) || es.nlines % es.npt != 0 ||
+                es.nlines / es.npt > 65535) {
+                set_error("eval: fused contraction unsupported (n = %d, %d numbers per line, M2 = %d, npt = %d)", es.n, mnn, es.M2, es.npt);
+                return ABZ_ERR_UNSUPPORTED;
+            }
+            const int64_t gcnt = es.nlines / es.npt;
+            a.src2 = es.src2;
+            a.phs2 = es.phs2;
+            a.M2 = es.M2;
+            if (ctx->prof & (1u << ABZ_K_EVAL_FUSED)) ctx->prof_slots[ABZ_K_EVAL_FUSED].launches += 1;
+            // ... then the fewest blocks with the same number of lines per wave: every wave of an index gets its share
+            // (100 points: 21 blocks would give 16 of 84 waves a second line; 13 give 48 of 52 two)
+            a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(es.npt, 4), cdiv(blocks, gcnt)));
+            a.bpk = (int)cdiv(es.npt, 4 * cdiv(es.npt, 4 * a.bpk));
+            const size_t flds = lds + sizeof(double2) * (size_t)es.M2 * mnn;
+#define LK(NN, KK)                                                                                                                         \
+    {                                                                                                                                      \
+        constexpr int OO = NN == 3 ? 3 : 2;                                                                                                \
+        if (a.pk)                                                                                                                          \
+            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, true, true>, dim3((unsigned)a.bpk, (unsigned)gcnt), dim3(256), flds, a);  \
+        else if (a.herm)                                                                                                                   \
+            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, false, true>, dim3((unsigned)a.bpk, (unsigned)gcnt), dim3(256), flds, a); \
+        else                                                                                                                               \
+            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2, false, true>, dim3((unsigned)a.bpk, (unsigned)gcnt), dim3(256), flds, a); \
+    }
+#define FN(NN)                    \
+    switch (kpl) {                \
+        case 1: LK(NN, 1) break;  \
+        case 2: LK(NN, 2) break;  \
+        default: LK(NN, 3) break; \
+    }
+            ABZ_DISPATCH_N(es.n, FN)
+#undef FN
+#undef LK
+        } else if (mnn <= EVAL_MAX_MNN && lds <= 64 * 1024 && a.npt < 65536) {
             // waves per SIMD the register allocator is asked for: 3 on the Hermitian 3-band paths (2 and 4 measured
             // slower there), 2 elsewhere
 #define LK(NN, KK)                                                                                                             \
