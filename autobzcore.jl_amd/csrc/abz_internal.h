@@ -286,6 +286,11 @@ struct abz_rule {
     abz::DevBuf ltm_elems;  // matrix elements of abz_rule_ltm_elements: double [ntiles][ltm_ncomp * n planes][row]
     int ltm_ncomp = 0;
     abz::PlaneView A;        // view of ltm_elems
+    // integration weights of abz_rule_ltm_node_weights: double [ntiles][ltm_nodew_nE * n planes][row], tiled like ltm_elems; they go
+    // where attached elements go (rebuild, a new gather of an unfolded rule, destroy), not with the elements themselves
+    abz::DevBuf ltm_nodew;
+    int ltm_nodew_nE = 0;
+    abz::PlaneView NW;       // view of ltm_nodew
     // symmetric rules: double [nk] weights and int32 [d][nk] grid indices; of a device-built rule, views into the plan's arena
     abz::DevBuf w, idx;
     std::unique_ptr<abz::RulePlan> plan;  // (api.cpp): contraction plan + phase table, device resident
@@ -293,6 +298,8 @@ struct abz_rule {
     abz::DevBuf node_of;         // int32 [npt^d] the source node in the orbit of every grid point (the orbit map)
     int64_t unfold_nk = 0;       // nodes of the source rule the map was made for
     std::vector<int32_t> unfold_syms;  // the symmetries the map was made under [nsyms][d][d]
+    abz::DevBuf unfold_inv;      // the map's inverse, made by the first abz_rule_ltm_node_weights_fold: int64 [unfold_nk + 1] first member of
+                                 // every node's orbit, then int32 [npt^d] the grid points orbit by orbit, ascending inside an orbit
     // a slab rule made scannable by abz_rule_ltm_halo: the eigenvalue-only rule of the one plane behind the slab,
     // plane (outer_end mod npt) of the grid.  Owned by this rule (freed with it, refilled with it); holds no reference of
     // its own on the series.
@@ -528,6 +535,16 @@ int launch_ltm_orbit_map(abz_ctx* ctx, int npt, int d, const int32_t* syms, int 
                          int32_t* node_of, int* missing_dev);
 // dst (the n eigenvalue planes of the whole grid, padding included) <- src at node_of; a point without a node gets zeros
 int launch_ltm_unfold(abz_ctx* ctx, PlaneView src, PlaneView dst, const int32_t* node_of, int n, int npt, int64_t nlines);
+// Integration weights per node and band (kernels_ltm_nodew.hip).  W: nE n planes tiled like the eigenvalue planes with pitch = row,
+// plane i n + b = w_b(k; Es_host[i]), padding columns zero; 1 <= nE <= ABZ_LTM_NODEW_MAX_E.  Launches only.
+int launch_ltm_node_weights(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView W, const double* Es_host, int nE, int what);
+// out_host [nE][ncomp] = sum_k sum_b w_b(k; E_i) A_{c,b}(k), A an element block of ncomp components; one synchronisation
+int launch_ltm_node_weights_dot(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView W, int nE, PlaneView A, int ncomp, double* out_host);
+// host: the inverse of an orbit map node_of [N] with entries inside 0 .. nirr-1: start [nirr + 1], member [N] (ascending per orbit)
+void ltm_orbit_inverse(const int32_t* node_of, int64_t N, int64_t nirr, std::vector<int64_t>& start, std::vector<int32_t>& member);
+// out_dev [nE][nirr][n] = the weights summed over the orbit of every node.  Launches only.
+int launch_ltm_node_weights_fold(abz_ctx* ctx, int n, PlaneView W, int nE, const int64_t* start, const int32_t* member, int64_t nirr,
+                                 double* out_dev);
 // Fermi level by repeated N(E) scans of 512 energies between the smallest and largest eigenvalue (abz_rule_ltm_fermi)
 int ltm_fermi(abz_ctx* ctx, int n, int d, int npt, PlaneView E, int64_t nk, double nstates, double tol, double* E_F, double* N_F);
 

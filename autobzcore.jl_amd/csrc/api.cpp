@@ -1028,6 +1028,12 @@ static void rule_drop_ltm_elements(abz_rule* r) {
     r->A = PlaneView();
 }
 
+static void rule_drop_ltm_node_weights(abz_rule* r) {
+    r->ltm_nodew = DevBuf();
+    r->ltm_nodew_nE = 0;
+    r->NW = PlaneView();
+}
+
 int abz_rule_destroy(abz_rule* r) try {
     if (!r) return ABZ_OK;
     abz_series* s = r->s;
@@ -1453,9 +1459,10 @@ int abz_rule_rebuild(abz_rule* r) try {
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     RulePlan* rp = r->plan.get();
-    if (r->ltm_elems.p) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
+    if (r->ltm_elems.p || r->ltm_nodew.p) {  // matrix elements and integration weights described the old eigenstates
         ABZ_HIP(hipStreamSynchronize(ctx->stream));
         rule_drop_ltm_elements(r);
+        rule_drop_ltm_node_weights(r);
     }
     if ((r->want & ABZ_WANT_VEL) && !rule_ggr_fused(r)) {
         const size_t tb = sizeof(double) * (size_t)(r->ntiles * 2 * r->s->n * r->s->n * r->E.row);
@@ -2367,6 +2374,109 @@ int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, dou
     return ltm_fermi(ctx, r->s->n, r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
 } ABZ_CATCH_ALL
 
+// Integration weights w_b(k; E) per node and band (kernels_ltm_nodew.hip).  The new block is complete before it replaces the
+// resident one: a refusal or a failure leaves that one as it was, and the half-made block goes with its DevBuf.
+int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(E, "abz_rule_ltm_node_weights: null energies");
+    ABZ_REQUIRE(nE >= 1 && nE <= ABZ_LTM_NODEW_MAX_E, "abz_rule_ltm_node_weights: nE = %d outside 1..%d", nE, ABZ_LTM_NODEW_MAX_E);
+    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES || what == ABZ_LTM_STATES_CORRECTED,
+                "abz_rule_ltm_node_weights: what = %d is neither ABZ_LTM_DOS, ABZ_LTM_STATES nor ABZ_LTM_STATES_CORRECTED", what);
+    for (int i = 0; i < nE; ++i) ABZ_REQUIRE(std::isfinite(E[i]), "abz_rule_ltm_node_weights: E[%d] = %g is not finite", i, E[i]);
+    // (no slab_ok: a node needs the plane BEFORE it as well, which a halo does not give)
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights"))) return rc;
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = r->s->n;
+    const int planes = nE * n;
+    DevBuf block;
+    if ((rc = block.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row))) return rc;
+    PlaneView W = r->E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements): same rows, same lines, nE n planes per tile
+    W.base = block.as<double>();
+    W.tile = (int64_t)planes * r->E.row;
+    W.pitch = r->E.row;
+    W.compact = 0;
+    rc = launch_ltm_node_weights(ctx, n, r->s->d, r->npt, r->E, W, E, nE, what);
+    for (int i = 0; i < nE && !rc && out; ++i) {  // one energy [nk][n] at a time, in the node and band order of abz_rule_export's eig
+        PlaneView v = W;
+        v.base += (int64_t)i * n * v.pitch;
+        rc = export_planes(ctx, v, n, r->nk, out + (size_t)i * (size_t)r->nk * (size_t)n);
+    }
+    // the block is complete, and nothing reads the old one any more
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_node_weights: the kernel failed");
+        rc = ABZ_ERR_HIP;
+    }
+    if (rc) return rc;
+    r->ltm_nodew = std::move(block);  // (the previous weights go here)
+    r->ltm_nodew_nE = nE;
+    r->NW = W;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nE) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    const bool have = r->ltm_nodew.p != nullptr;
+    if (base) *base = r->ltm_nodew.p;
+    if (nbytes) *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * (size_t)r->ltm_nodew_nE * (size_t)r->s->n * (size_t)r->NW.row) : 0;
+    if (nE) *nE = have ? r->ltm_nodew_nE : 0;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_node_weights_dot: null out");
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights_dot"))) return rc;
+    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_node_weights_dot: the rule holds no integration weights (abz_rule_ltm_node_weights; "
+                                "abz_rule_rebuild drops them)");
+    ABZ_REQUIRE(r->ltm_elems.p, "abz_rule_ltm_node_weights_dot: no matrix elements are attached (abz_rule_ltm_elements, abz_rule_ltm_orbitals, "
+                                "abz_rule_ltm_projectors)");
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    return launch_ltm_node_weights_dot(ctx, r->s->n, r->npt, r->ntiles, r->NW, r->ltm_nodew_nE, r->A, r->ltm_ncomp, out);
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_node_weights_fold: null out");
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights_fold"))) return rc;
+    ABZ_REQUIRE(r->node_of.p, "abz_rule_ltm_node_weights_fold: the rule was not made by abz_rule_ltm_unfold: it has no orbits to fold over");
+    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_node_weights_fold: the rule holds no integration weights (abz_rule_ltm_node_weights; a new "
+                                "gather drops them)");
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = r->s->n, nE = r->ltm_nodew_nE;
+    const int64_t N = r->nk, nirr = r->unfold_nk;
+    const size_t start_bytes = sizeof(int64_t) * ((size_t)nirr + 1);
+    if (!r->unfold_inv.p) {  // once per rule: the map does not change with the values
+        std::vector<int32_t> node_of((size_t)N), member;
+        std::vector<int64_t> start;
+        if ((rc = stage_d2h(ctx, node_of.data(), r->node_of.p, sizeof(int32_t) * (size_t)N))) return rc;
+        for (int64_t x = 0; x < N; ++x)
+            if (node_of[(size_t)x] < 0 || node_of[(size_t)x] >= nirr) {
+                set_error("abz_rule_ltm_node_weights_fold: the orbit map names node %d at grid point %lld (the source has %lld nodes)",
+                          node_of[(size_t)x], (long long)x, (long long)nirr);
+                return ABZ_ERR_INTERNAL;
+            }
+        ltm_orbit_inverse(node_of.data(), N, nirr, start, member);
+        DevBuf inv;
+        if ((rc = inv.alloc(start_bytes + sizeof(int32_t) * (size_t)N))) return rc;
+        if ((rc = stage_h2d(ctx, inv.p, start.data(), start_bytes))) return rc;
+        if ((rc = stage_h2d(ctx, static_cast<char*>(inv.p) + start_bytes, member.data(), sizeof(int32_t) * (size_t)N))) return rc;
+        r->unfold_inv = std::move(inv);
+    }
+    const size_t obytes = sizeof(double) * (size_t)nE * (size_t)nirr * (size_t)n;
+    if ((rc = ctx->scratch[3].reserve(obytes))) return rc;
+    const int64_t* start_dev = r->unfold_inv.as<int64_t>();
+    const int32_t* member_dev = reinterpret_cast<const int32_t*>(static_cast<const char*>(r->unfold_inv.p) + start_bytes);
+    if ((rc = launch_ltm_node_weights_fold(ctx, n, r->NW, nE, start_dev, member_dev, nirr, ctx->scratch[3].as<double>()))) return rc;
+    return stage_d2h(ctx, out, ctx->scratch[3].p, obytes);
+} ABZ_CATCH_ALL
+
 // One eigenvalue per band is a scalar that the zone's symmetries leave alone, e_b(S k) = e_b(k): the planes of the whole grid
 // are a gather from the irreducible nodes.  The orbit map depends on (npt, d, syms, node list) only and stays with the rule.
 int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule** out) try {
@@ -2398,9 +2508,10 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
                     r->npt, (long long)r->unfold_nk, npt, (long long)src->nk);
         ABZ_REQUIRE(r->unfold_syms.size() == (size_t)nsyms * d * d && std::equal(r->unfold_syms.begin(), r->unfold_syms.end(), syms),
                     "abz_rule_ltm_unfold: *out was unfolded under another symmetry set (its orbit map does not fit these %d matrices)", nsyms);
-        if (r->ltm_elems.p) {  // matrix elements of abz_rule_ltm_elements described the old eigenstates
+        if (r->ltm_elems.p || r->ltm_nodew.p) {  // matrix elements and integration weights described the old eigenstates
             ABZ_HIP(hipStreamSynchronize(ctx->stream));
             rule_drop_ltm_elements(r);
+            rule_drop_ltm_node_weights(r);
         }
         r->herm = src->herm;
         if ((rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of.as<int32_t>(), n, npt, r->ntiles))) return rc;

@@ -354,5 +354,42 @@ def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):
     return float(u[0, 0]), E_F
 
 
+def integration_weights(prob_or_cache, E=None, nstates=None, kind="states", correction=False, fold=False):
+    """(W, E): Bloechl's integration weights w_b(k; E) of the grid of an LTM cache, or of a DOSProblem (solved with LTM()), and
+    the energies they belong to.  Exactly one of `E` (at most 16 energies; W is [nE, nk, n], [nk, n] for a scalar) and `nstates`
+    (W [nk, n] at `fermi_level`'s energy on the same rule: the occupations of that filling) is given.  `kind`: "states"
+    (sum_k sum_b W A = N_A) or "dos" (= g_A); `correction=True` (with "states") adds Bloechl's curvature correction, made for
+    sums at the grid's own Fermi level.  Nodes and bands are ordered like the eigenvalues of the cache's rule
+    (`cache.cacheval.export(eig=True)`).  With `LTM(symmetric=True)` on a symmetric zone and `fold=True` the weights come back
+    summed over orbits on the irreducible nodes that were solved, [.., nirr, n] in the order of
+    `cache.cacheval.source.export(eig=True)`; anywhere else `fold=True` raises ValueError."""
+    if (E is None) == (nstates is None):
+        raise ValueError("integration_weights: give exactly one of E and nstates")
+    if kind not in ("states", "dos"):
+        raise ValueError(f"integration_weights: kind = {kind!r} is neither 'states' nor 'dos'")
+    if correction and kind != "states":
+        raise ValueError("integration_weights: correction=True corrects the state sum: it needs kind='states' (the DOS has no correction)")
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+        raise NotImplementedError("integration_weights on a k-sharded series is not implemented: a node's weight needs its whole "
+                                  "neighbourhood, which a slab with its halo plane does not hold")
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    if not isinstance(c.alg, LTM):
+        raise ValueError("integration_weights needs an LTM cache")
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    rule = c.cacheval
+    if fold and not hasattr(rule, "ltm_node_weights_fold"):
+        raise ValueError("integration_weights: fold=True needs an LTM(symmetric=True) cache on a symmetric zone (nothing was unfolded)")
+    scalar = nstates is not None or np.ndim(E) == 0
+    Es = np.array([fermi_level(c, nstates)[0]]) if nstates is not None else np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
+    W = rule.ltm_node_weights(Es, states=kind == "states", correction=bool(correction), export=not fold)
+    if fold:
+        W = rule.ltm_node_weights_fold()
+    return (W[0], float(Es[0])) if scalar else (W, Es)
+
+
 def solve(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):
     return solve_(init(prob, alg, **kwargs))

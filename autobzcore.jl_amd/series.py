@@ -785,6 +785,57 @@ class DeviceRule:
                                                     out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out
 
+    def ltm_node_weights(self, Es, states=True, correction=False, export=True):
+        """Bloechl's integration weights w_b(k; E) per grid point and band (abz_rule_ltm_node_weights), [nE, nk, n] in the node
+        and band order of export()'s eig: the numbers with N_A(E) = sum_k sum_b w_b(k; E) A_b(k) for ANY A (`states`, the
+        default), g_A(E) likewise (`states=False`), or N_A with Bloechl's curvature correction (`correction=True`, validated
+        as in `ltm`; the block then still sums to N(E)).  At most 16 energies per call, in any order.  The weights also stay
+        on the device, tiled like attached elements, until the next call, a rebuild of the rule or `close`:
+        `ltm_node_weights_dot` contracts them with attached elements without another walk over the simplices, and
+        `export=False` (returns None) skips the copy to the host.  The rule must be a whole periodic grid (an unfolded rule
+        is one); a k-sharded rule raises NotImplementedError, with or without its halo plane."""
+        self._ltm_refuse_shard("ltm_node_weights")
+        if correction and not states:
+            raise ValueError("ltm_node_weights: correction=True corrects the state sum N_A: it needs states=True (the DOS has no correction)")
+        Es = np.ascontiguousarray(np.asarray(Es, dtype=np.float64).reshape(-1))
+        if not 1 <= len(Es) <= L.LTM_NODEW_MAX_E:
+            raise ValueError(f"ltm_node_weights: {len(Es)} energies, a call takes 1..{L.LTM_NODEW_MAX_E}")
+        what = L.LTM_STATES_CORRECTED if correction else (L.LTM_STATES if states else L.LTM_DOS)
+        h = self.h  # (a stale rule is refilled here, which drops the weights it held)
+        out = np.empty((len(Es), self.nk, self.dev.s.n)) if export else None
+        L.check(L.lib().abz_rule_ltm_node_weights(h, Es.ctypes.data_as(L.c_f64p), len(Es), what,
+                                                  out.ctypes.data_as(L.c_f64p) if export else None))
+        return out
+
+    def ltm_node_weights_ptr(self):
+        """(device address, bytes, nE) of the resident weight block of `ltm_node_weights`; (0, 0, 0) when there is none."""
+        self._ltm_refuse_shard("ltm_node_weights_ptr")
+        base, nb, ne = C.c_void_p(), C.c_int64(0), C.c_int(0)
+        L.check(L.lib().abz_rule_ltm_node_weights_ptr(self.h, C.byref(base), C.byref(nb), C.byref(ne)))
+        return int(base.value or 0), int(nb.value), int(ne.value)
+
+    def ltm_node_weights_dot(self, elements="attached"):
+        """sum_k sum_b w_b(k; E_i) A_{c,b}(k) of the resident weights of `ltm_node_weights` as [nE, ncomp]
+        (abz_rule_ltm_node_weights_dot): one pass over the two blocks, no walk over the simplices.  `elements`: "attached"
+        (what ltm_elements, ltm_orbitals or ltm_projectors attached) or an array [ncomp, nk, n], attached first; attaching
+        elements leaves the weights in place."""
+        self._ltm_refuse_shard("ltm_node_weights_dot")
+        if isinstance(elements, str):
+            if elements != "attached":
+                raise ValueError(f"ltm_node_weights_dot: elements = {elements!r} is neither 'attached' nor an array")
+        else:
+            self.h  # (a stale rule is refilled first: it loses its weights, and the call below says so)
+            self.ltm_elements(elements)
+        h = self.h
+        _, _, nE = self.ltm_node_weights_ptr()
+        if nE < 1:
+            raise ValueError("ltm_node_weights_dot: the rule holds no weights (ltm_node_weights; a rebuild of the rule drops them)")
+        if self._ltm_ncomp < 1:
+            raise ValueError("ltm_node_weights_dot: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
+        out = np.zeros((nE, self._ltm_ncomp))
+        L.check(L.lib().abz_rule_ltm_node_weights_dot(h, out.ctypes.data_as(L.c_f64p)))
+        return out
+
     def ltm_fermi(self, nstates, tol=1e-10):
         """(E_F, N(E_F)): the Fermi level of `nstates` states per unit cell, 0 < nstates < n, to within `tol`
         (abz_rule_ltm_fermi: a few N(E) scans of 512 energies each, no host bisection)."""
@@ -863,3 +914,16 @@ class UnfoldedRule(DeviceRule):
 
     def unfold(self):
         raise ValueError("unfold: the rule is a full grid already (no symmetries to unfold)")
+
+    def ltm_node_weights_fold(self):
+        """The resident weights of `ltm_node_weights` summed over each orbit onto the irreducible nodes of the source rule,
+        [nE, nirr, n] in the source's node order (abz_rule_ltm_node_weights_fold): sum_j sum_b fold_b(j) A_b(j) is then the
+        full-grid N_A of any A that the zone's symmetries leave alone, from values at the irreducible nodes only.  The Kuhn
+        mesh is invariant under 12 of the 48 cubic operations, so this is a sum over the orbit, not multiplicity x weight."""
+        h = self.h
+        _, _, nE = self.ltm_node_weights_ptr()
+        if nE < 1:
+            raise ValueError("ltm_node_weights_fold: the rule holds no weights (ltm_node_weights; a new gather drops them)")
+        out = np.zeros((nE, len(self.source), self.dev.s.n))
+        L.check(L.lib().abz_rule_ltm_node_weights_fold(h, out.ctypes.data_as(L.c_f64p)))
+        return out

@@ -410,6 +410,45 @@ int abz_rule_ltm_green(abz_rule* r, const double* z /* [nz][2]: re, im */, int n
  * Entry point added without a change of ABZ_VERSION. */
 int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z /* [nz][2] */, int nz, double* out /* [nz][ncomp][2] */);
 
+/* Bloechl's integration weights themselves, per grid point and band: the numbers w_b(k; E) with
+ *      N_A(E) = sum_k sum_b w_b(k; E) A_b(k)     (ABZ_LTM_STATES; likewise g_A with ABZ_LTM_DOS and the corrected N_A with
+ *                                                 ABZ_LTM_STATES_CORRECTED)
+ * for ANY A on the mesh, band convention, half-open regions and simplex weight 1 / (d! npt^d) of abz_rule_ltm: what
+ * abz_rule_ltm_weighted forms inside its scan and contracts at once.  The weight of node k is the sum, over the (d+1)! Kuhn
+ * simplices that contain k (2, 6 or 24: their corners are the 3^d neighbours k + {-1,0,1}^d, indices wrapped mod npt), of what
+ * the simplex gives that corner.  ABZ_LTM_STATES: a simplex wholly below E gives 1 / (d+1) to each corner, so a node whose whole
+ * neighbourhood lies below E weighs 1 / npt^d and one whose neighbourhood lies above E exactly 0.0; ABZ_LTM_DOS: a flat simplex
+ * gives nothing; ABZ_LTM_STATES_CORRECTED: plus g_T(E) f_d (sum_l e_l - (d+1) e_k) per simplex inside its window, kappa_T of
+ * abz_rule_ltm_weighted split by corner (the block then sums to N(E): the correction of A = 1 is zero).
+ * E [nE], 1 <= nE <= ABZ_LTM_NODEW_MAX_E, in any order, duplicates allowed.  out [nE][nk][n] (or NULL: nothing is copied) is in
+ * the node and band order of abz_rule_export's eig, as abz_rule_ltm_elements takes elements.  A gather without atomics: two calls
+ * write the same bits.
+ * The weights stay resident in HBM, nE n planes tiled like an element block of abz_rule_ltm_elements (plane i n + b of a grid
+ * line's tile: band b at E[i]; padding columns zero), until the next call replaces them, abz_rule_rebuild or a new gather of
+ * abz_rule_ltm_unfold (they described the old eigenvalues), or abz_rule_destroy; attaching or dropping ELEMENTS leaves them
+ * alone: attach, dot, attach, dot costs one pass over memory each.  They are counted by abz_mem_info.
+ * Takes full-grid rules and rules of abz_rule_ltm_unfold, d = 1...3, 1...64 bands.  ABZ_ERR_UNSUPPORTED: slabs, with or without
+ * a halo (a node needs the plane BEFORE it as well), lists of irreducible nodes, symmetric rules.  ABZ_ERR_ARG: a rule without
+ * eigenvalues, E == NULL, nE outside 1..ABZ_LTM_NODEW_MAX_E, a non-finite energy, a `what` that is none of the three.  A refusal
+ * or failure leaves the resident weights as they were.  Entry points added without a change of ABZ_VERSION. */
+#define ABZ_LTM_NODEW_MAX_E 16
+int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, double* out /* [nE][nk][n] or NULL */);
+/* The resident weights: device address, bytes and energies of the block; NULL, 0, 0 when the rule holds none (any of the three
+ * pointers may be NULL). */
+int abz_rule_ltm_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nE);
+/* out [nE][ncomp] = sum_k sum_b w_b(k; E_i) A_{c,b}(k): the resident weights against the attached elements
+ * (abz_rule_ltm_elements, _orbitals, _projectors), i.e. abz_rule_ltm_weighted(r, ABZ_LTM_A_ELEMENTS, E, nE, what, out) of the
+ * call that made the weights, without another walk over the simplices.  Fixed-order reduction: two calls return the same bits.
+ * ABZ_ERR_ARG: no resident weights, nothing attached, out == NULL; ABZ_ERR_UNSUPPORTED as above. */
+int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out /* [nE][ncomp] */);
+/* For a rule of abz_rule_ltm_unfold: the resident weights summed over each orbit onto the nirr nodes of the source rule, in the
+ * source's node order; with them sum_j sum_b fold_b(j) A_b(j) is the full-grid N_A for every A that is invariant under the zone's
+ * symmetries, from values at the irreducible nodes alone.  The Kuhn mesh is invariant under 12 of the 48 cubic operations only,
+ * so w(S k) != w(k) in general: the fold is the plain sum over the orbit, not multiplicity x w.  The inverse of the rule's orbit
+ * map is made at the first call and kept (8 B per node, 4 B per grid point, counted by abz_mem_info).  No floating-point atomics:
+ * two calls return the same bits.  ABZ_ERR_ARG: a rule that was not unfolded, no resident weights, out == NULL. */
+int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out /* [nE][nirr][n] */);
+
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.
  * First call with irr_idx = NULL to get *nirr; then with buffers irr_idx [nirr][d], wsym [nirr]. */
