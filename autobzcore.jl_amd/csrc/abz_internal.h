@@ -210,6 +210,22 @@ struct abz_ctx {
 };
 
 namespace abz {
+// the halves of the mailbox: inputs of a call in the first, its results in the second
+inline bool mbox_half_fits(abz_ctx* ctx, size_t bytes) { return mbox_reserve(ctx) == ABZ_OK && bytes <= ctx->mbox_cap / 2; }
+template <class T>
+inline T* mbox_results(abz_ctx* ctx, bool device_view) {
+    return reinterpret_cast<T*>(static_cast<char*>(device_view ? ctx->mbox_dev : ctx->mbox) + ctx->mbox_cap / 2);
+}
+// `ncols` complex sums to `host`: through the mailbox (reserved here) where they fit its result half, else by a copy
+inline SumOut sum_out_mailbox(abz_ctx* ctx, double* host, size_t ncols) {
+    SumOut so;
+    so.host = host;
+    if (mbox_half_fits(ctx, sizeof(double2) * ncols)) {
+        so.map_dev = mbox_results<double2>(ctx, true);
+        so.map_host = mbox_results<const double2>(ctx, false);
+    }
+    return so;
+}
 // a rule kept by its series for the whole-solve entry points (abz_autoptr_solve*): owned by the series (it holds no
 // reference on it), refreshed when the coefficients change
 struct SeriesRule {
@@ -521,6 +537,9 @@ int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const dou
 int launch_ltm_green_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* z_host, int nz,
                               double* out_host);
 int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plane0, int n, int64_t nk);
+// The last step of every tetrahedron sum: out[c * ostride + i] = scale * sum_rows partial[c * cnt + i][row] for the `ncols` columns
+// (c, i) of transposed partials [ncols][nrows], in a fixed order
+int launch_ltm_final(abz_ctx* ctx, const double* partial, int64_t nrows, double scale, int ncols, int cnt, int64_t ostride, double* out);
 // Orbital weights as matrix elements (kernels_ltm_orb.hip): plane c n + b of A (ncomp n planes tiled like the eigenvalue planes,
 // padding columns included) <- |U_{orb[c], b}|^2 from the H planes of the same whole grid (full or compact); orb == nullptr:
 // orbital c.  1...32 bands.  Launches only, under ABZ_K_EIG.

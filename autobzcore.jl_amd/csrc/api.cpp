@@ -293,13 +293,6 @@ int stage_d2h(abz_ctx* ctx, void* dst, const void* src, size_t bytes) {
     return ABZ_OK;
 }
 
-// the halves of the mailbox: inputs of a call in the first, its results in the second
-static bool mbox_half_fits(abz_ctx* ctx, size_t bytes) { return mbox_reserve(ctx) == ABZ_OK && bytes <= ctx->mbox_cap / 2; }
-template <class T>
-static T* mbox_results(abz_ctx* ctx, bool device_view) {
-    return reinterpret_cast<T*>(static_cast<char*>(device_view ? ctx->mbox_dev : ctx->mbox) + ctx->mbox_cap / 2);
-}
-
 int sweep_to_device(abz_ctx* ctx, const double* host, int n, const double** dev) {
     const size_t bytes = sizeof(double) * (size_t)n;
     int rc = ctx->scratch[5].reserve(std::max(bytes, sizeof(double)));
@@ -1660,12 +1653,9 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
         rs.out.dev = out_reim;
     else
         rs.out.host = out_reim;
-    if (!device_io && rs.n <= 4 && ctx->mbox) {  // sums land in the second half of the mailbox (zero copy)
+    if (!device_io && rs.n <= 4 && ctx->mbox) {  // sums land in the second half of the mailbox (zero copy); it exists: nothing is reserved
         const int nc = integrand_ncomp(integrand, rs.n, rs.d);
-        if (nc > 0 && sizeof(double2) * (size_t)ns * (size_t)nc <= ctx->mbox_cap / 2) {
-            rs.out.map_dev = mbox_results<double2>(ctx, true);
-            rs.out.map_host = mbox_results<const double2>(ctx, false);
-        }
+        if (nc > 0) rs.out = sum_out_mailbox(ctx, out_reim, (size_t)ns * (size_t)nc);
     }
     return launch_reduce(ctx, rs);
 }

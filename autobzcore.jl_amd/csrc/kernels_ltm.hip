@@ -39,7 +39,7 @@
 //    the compiler's resource report).
 //  * Payloads.  What a corner carries besides its energy is a policy of the kernel: LtmPlain (nothing; the closed forms above
 //    with their fmin / fmax sorting network; a different instruction stream on purpose, 1933 instructions against 2553) or
-//    LtmElems<NC, CORR> (NC matrix elements, next item).  The policy gives the per-corner load, picks the simplex routine and
+//    LtmElems<NC, CORR> (NC matrix elements, next item).  The policy says what a corner carries (elements: ltm_load of ltm_device.h), picks the simplex routine and
 //    says what a cell without an energy in its window adds to the step histogram; the cell walk, the corner geometry (whole
 //    grid or slab with its halo plane), the window, the queue and the write-out are the kernel's and exist once.  One final
 //    and one prefix kernel serve both (the plain scan is one component), one host function (ltm_scan) launches them, and the
@@ -87,14 +87,13 @@
 #include <vector>
 
 #include "abz_internal.h"
+#include "ltm_device.h"
 #include "rows_device.h"
 #include "sym_image.h"
 
 namespace abz {
 
 namespace {
-
-inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 struct LtmArgs {
     PlaneView E;
@@ -241,11 +240,6 @@ struct WLtmArgs {
 struct WLtmSlabArgs : WLtmArgs {
     PlaneView haloE, haloA;
     int nz = 0;
-};
-
-template <int NC>
-struct LtmVec {
-    double v[NC];
 };
 
 // compare-exchange of two corners: the energies, and the elements with them
@@ -447,9 +441,7 @@ __device__ __forceinline__ void ltm_simplex1(double e1, double e2, LtmVec<P::NC>
 // ---------------------------------------------------------------------------------------------------------------------
 // The scan: one kernel, two payloads
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int ltm_nsimplex(int d) { return d == 3 ? 6 : (d == 2 ? 2 : 1); }  // simplices per cell
-
-// A payload says what a corner carries besides its energy (Vec; load, where it carries anything), which routine takes a simplex (the overload of
+// A payload says what a corner carries besides its energy (Vec), which routine takes a simplex (the overload of
 // ltm_simplex1/2/3 for its Vec) and what a cell adds to the step histogram when no energy falls inside its window (below_add
 // per corner, below_put once).  Args<SLAB> is its kernel-argument struct, args() that struct from the host's description of a
 // launch (the superset, WLtmSlabArgs).  The hooks are inlined before anything else and call nothing of the kernel's: together
@@ -485,13 +477,6 @@ struct LtmElems {
     template <bool SLAB>
     static Args<SLAB> args(const WLtmSlabArgs& s) {
         return s;  // (whole grid: its WLtmArgs part)
-    }
-    // the NC components of the corner whose first one lies at p, `acomp` doubles apart
-    static __device__ __forceinline__ Vec load(const double* __restrict__ p, int64_t acomp) {
-        Vec r;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) r.v[c] = p[(int64_t)c * acomp];
-        return r;
     }
     // By the sum of the simplices' means in one add per component.  Corner 0 and corner (1..1) belong to all d! simplices, every
     // other corner to d! / d of them... d = 3: (6 (A0 + A7) + 2 sum others) / 4, d = 2: (2 (A0 + A3) + A1 + A2) / 3
@@ -562,13 +547,12 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Ar
         }
         nz = a.nz;
     }
-    // THE geometry, for energies and elements alike: corner `bits` (bit j: +1 along variable j+1) of cell (i1, i2, i3), which
-    // become the corner's own indices.  Whole grid: every index wraps mod npt, the corner is column i1 of line i3 npt + i2 of the
-    // band's planes.  SLAB: the outermost index is local to the slab's nz planes and does not wrap; true: the corner lies behind
-    // plane nz - 1, in the halo plane, at column i1 of its line i2 (d = 2: of its only line, 0).
+    // The geometry, for energies and elements alike: corner `bits` of cell (i1, i2, i3), which become the corner's own indices.
+    // Whole grid: ltm_wrap.  SLAB: the outermost index is local to the slab's nz planes and does not wrap; true: the corner lies
+    // behind plane nz - 1, in the halo plane, at column i1 of its line i2 (d = 2: of its only line, 0).
     auto corner = [&](int& i1, int& i2, int& i3, int bits) -> bool {
-        if ((bits & 1) && ++i1 == npt) i1 = 0;
         if constexpr (SLAB) {
+            if ((bits & 1) && ++i1 == npt) i1 = 0;
             if constexpr (D == 3) {
                 if ((bits & 2) && ++i2 == npt) i2 = 0;
                 return (bits & 4) && ++i3 == nz;
@@ -579,8 +563,7 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Ar
                 }
             }
         } else {
-            if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
-            if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
+            ltm_wrap<D>(i1, i2, i3, bits, npt);
         }
         return false;
     };
@@ -594,7 +577,7 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Ar
     auto cornerA = [&](int i1, int i2, int i3, int bits) -> Vec {
         if constexpr (P::ELEMS) {
             const bool halo = corner(i1, i2, i3, bits);
-            return P::load(SLAB && halo ? AHb + (int64_t)i2 * htileA + i1 : Ab + ((int64_t)i3 * npt + i2) * tileA + i1, acomp);
+            return ltm_load<P::NC>(SLAB && halo ? AHb + (int64_t)i2 * htileA + i1 : Ab + ((int64_t)i3 * npt + i2) * tileA + i1, acomp);
         } else {
             return {};  // the plain scan has no element planes
         }
@@ -610,10 +593,10 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Ar
         int i0 = 0, i1 = 0, i2 = 0, i3 = 0;
         double c[NV];
         if (k < a.ncell) {
-            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
-            i1 = (int)(k - line * npt);
-            i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
-            i2 = (int)line - i3 * npt;
+            const LtmCell cell = ltm_cell<D>(k, npt);
+            i1 = cell.i1;
+            i2 = cell.i2;
+            i3 = cell.i3;
 #pragma unroll
             for (int j = 0; j < NV; ++j) c[j] = cornerE(i1, i2, i3, j);
             double cmin = c[0], cmax = c[0];
@@ -678,11 +661,8 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Ar
             const uint32_t cell = p / NS, t = p - cell * NS;
             const uint32_t q = queue[cell];
             const int j0 = (int)(q >> 8);
-            const int64_t kq = base + (q & 255u);
-            const int64_t line = kq <= 0xffffffffll ? (int64_t)((uint32_t)kq / (uint32_t)npt) : kq / npt;
-            const int q1 = (int)(kq - line * npt);
-            const int q3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
-            const int q2 = (int)line - q3 * npt;
+            const LtmCell cq = ltm_cell<D>(base + (q & 255u), npt);
+            const int q1 = cq.i1, q2 = cq.i2, q3 = cq.i3;
             const double c0 = cornerE(q1, q2, q3, 0), c1 = cornerE(q1, q2, q3, NV - 1);
             const Vec A0 = cornerA(q1, q2, q3, 0), A1 = cornerA(q1, q2, q3, NV - 1);
             if constexpr (D == 3) {
@@ -711,7 +691,7 @@ __global__ __launch_bounds__(256) void ltm_window_kernel(typename P::template Ar
 }
 
 // out[c * ostride + i] = scale * sum_rows partial[c * cnt + i][row], one block per column (c, i), fixed summation order
-// (ggr_final_kernel's)
+// (ggr_final_kernel's); launch_ltm_final below launches it for every tetrahedron file
 __global__ __launch_bounds__(256) void ltm_final_kernel(const double* __restrict__ partial, int64_t nrows, double scale, int cnt,
                                                         int64_t ostride, double* __restrict__ out) {
     __shared__ double red[256];
@@ -841,9 +821,6 @@ __global__ __launch_bounds__(256) void ltm_unfold_kernel(PlaneView src, PlaneVie
 #pragma unroll 4
     for (int b = 0; b < n; ++b) out[(int64_t)b * dst.pitch] = in[(int64_t)b * src.pitch];
 }
-
-// dynamic LDS of the plain g scan at 1024 energies: 5 x 1024 x 8 B + queue and counts; every scan stays within it
-constexpr size_t LTM_LDS_MAX = sizeof(double) * 5 * 1024 + sizeof(uint32_t) * (256 + 8);
 
 using LtmWindowFn = void (*)(abz_ctx*, dim3, size_t, const WLtmSlabArgs&, double*, int64_t);
 template <int D, bool STATES, bool SLAB, class P>
@@ -976,693 +953,22 @@ int ltm_scan(abz_ctx* ctx, const char* who, int n, int d, int npt, PlaneView E, 
             window[nc](ctx, grid, lds, a, partial, nrows);
             ABZ_HIP(hipGetLastError());
             if (states) {
-                launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, partial, nrows, 1.0, 2 * nc * cnt, (int64_t)0, col);
-                ABZ_HIP(hipGetLastError());
+                if ((rc = launch_ltm_final(ctx, partial, nrows, 1.0, 2 * nc * cnt, 2 * nc * cnt, 0, col))) return rc;
                 launch(ctx, ltm_prefix_kernel, dim3((unsigned)nc), dim3(256), 0, col, cnt, nc, weight, (int64_t)nE, o);
-            } else {
-                launch(ctx, ltm_final_kernel, dim3((unsigned)(nc * cnt)), dim3(256), 0, partial, nrows, weight, cnt, (int64_t)nE, o);
+                ABZ_HIP(hipGetLastError());
+            } else if ((rc = launch_ltm_final(ctx, partial, nrows, weight, nc * cnt, cnt, nE, o))) {
+                return rc;
             }
-            ABZ_HIP(hipGetLastError());
         }
         c0 += nc;
     }
     return energies_deliver(ctx, el, out_host);
 }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Trace of the Green's function at complex energies (abz_rule_ltm_green)
-// ---------------------------------------------------------------------------------------------------------------------
-// tr G(z) = w sum_{cells} sum_{d! simplices} sum_{bands} J[x_0 .. x_d](z), w = 1 / (d! npt^d), on the mesh of the scans above.
-// J[x_0 .. x_m](z) is the mean of 1 / (z - e) over a simplex in which e is linear with the sorted corner values x_0 <= .. <= x_m
-// (the mean over the normalised B-spline with those knots).  With u_i = z - x_i, which all share Im z > 0:
-//      m = 0:  J = 1 / u_0
-//      m = 1:  J = (log u_0 - log u_1) / (x_1 - x_0)     principal logs of one open half plane: no branch fix-up
-//      m >= 2: J[x_0..x_m] = m / (m-1) (u_0 J[x_0..x_{m-1}] - u_m J[x_1..x_m]) / (x_m - x_0)
-//  * Evaluation rule.  The recursion divides by a width and loses |u| / width per level; a symmetric grid is full of equal and
-//    nearly equal corners.  A sub-range x_i..x_j with x_j - x_i < rho |z - mean|, rho = 1/2, is summed by its Taylor series
-//      J = sum_k  m! k! / (m+k)!  h_k(delta) / ubar^(k+1),   delta_l = x_l - mean,  ubar = z - mean,
-//    h_k the complete homogeneous symmetric polynomial by H_l^(k) = H_(l-1)^(k) + delta_l H_l^(k-1), H_0^(k) = delta_0^k: one
-//    row of m + 1 registers carried from k - 1 to k, the coefficients from a table.  It stops when (max |delta| / |ubar|)^k < 2^-52:
-//    max |delta| <= m / (m+1) width, so the ratio stays below 3/8 and 37 terms are the most a sub-range takes.  Only wider
-//    sub-ranges recurse: nothing is divided by a width below rho |ubar|.  The series runs on delta / |ubar| and ubar / |ubar|, so
-//    neither power leaves the range of a double; at width 0 it is 1 / u.
-//  * Shape (ltm_green_kernel<D>).  Not a window scan: every simplex contributes at every z, there is no queue and no histogram.
-//    The cell walk and the whole-grid corner geometry are ltm_window_kernel's: blocks of 256 cells, one cell per thread,
-//    blockIdx.y the band, the 2^d corner energies in registers, the values of z in LDS.  Per (cell, z) the 2^d complex logs of
-//    z - e_corner are taken once and shared by the cell's d! simplices; the sorting network of a simplex carries each corner's
-//    log along with its energy, as LtmElems carries elements, and the pair formula reads them.  blockIdx.z splits the values of
-//    z of a launch where the cells alone do not fill the device.
-//  * Reduction.  Per z in a fixed order: a butterfly over the wave, lane 0 adds into the wave's LDS slot [nz][re, im] in
-//    program order, the four waves are summed as above into transposed partials and ltm_final_kernel finishes.  No atomics:
-//    two calls return the same bits.
-constexpr double GREEN_RHO2 = 0.25;      // rho^2
-constexpr double GREEN_EPS2 = 0x1p-104;  // (2^-52)^2
-constexpr int GREEN_KMAX = 40;           // terms beyond k = 37 (the five knots of a corner weight: 39) are never asked for
-constexpr int LTM_GREEN_CHUNK = 512;     // values of z per launch: 8 (2 + 4 x 2) B of LDS each
-static_assert(sizeof(double) * 10 * LTM_GREEN_CHUNK <= LTM_LDS_MAX, "the z list and the four waves' sums fit the scans' LDS");
-
-// m! k! / (m+k)! for m = 1, 2, 3 and, for the five knots of a corner weight in 3-D, 4
-struct GreenCoef {
-    double c[4][GREEN_KMAX + 1];
-};
-constexpr GreenCoef green_coef() {
-    GreenCoef t{};
-    for (int m = 1; m <= 4; ++m) {
-        t.c[m - 1][0] = 1.0;
-        for (int k = 1; k <= GREEN_KMAX; ++k) t.c[m - 1][k] = t.c[m - 1][k - 1] * (double)k / (double)(m + k);
-    }
-    return t;
-}
-__constant__ const GreenCoef GREEN_COEF = green_coef();
-
-struct GreenArgs {
-    PlaneView E;
-    const double* z;  // device [nz][2]: re, im > 0
-    int64_t ncell;    // npt^d
-    int npt, nz;
-    int zper;         // values of z per blockIdx.z
-};
-
-struct Cx {
-    double re, im;
-};
-__device__ __forceinline__ Cx cx_mul(Cx a, Cx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-
-// what the sort of a simplex carries per corner: the energy and log(z - energy)
-struct GreenCorner {
-    double x, lr, li;
-};
-__device__ __forceinline__ GreenCorner green_sel(bool first, const GreenCorner& a, const GreenCorner& b) {
-    return {first ? a.x : b.x, first ? a.lr : b.lr, first ? a.li : b.li};
-}
-__device__ __forceinline__ void green_cx(GreenCorner& a, GreenCorner& b) {
-    const bool sw = b.x < a.x;
-    const GreenCorner lo = green_sel(sw, b, a), hi = green_sel(sw, a, b);
-    a = lo;
-    b = hi;
-}
-
-// The Taylor series of J[x_0 .. x_M] about the mean; u[l] = Re z - x_l, ur their mean, (ur, ui) = ubar, n2 = |ubar|^2.  The mean
-// and delta_l = ur - u[l] come from the differences Re z - x_l, which are exact and small close to a corner: ubar then carries a
-// relative error of eps, where the rounding of mean(x), eps |x|, would move 1 / ubar by eps |x| / |ubar|^2.
-template <int M>
-__device__ __forceinline__ Cx green_series(const double (&u)[M + 1], double ur, double ui, double n2) {
-    const double s = 1.0 / sqrt(n2);
-    double dl[M + 1], H[M + 1];
-    double r2 = 0.0;
-#pragma unroll
-    for (int l = 0; l <= M; ++l) {
-        dl[l] = (ur - u[l]) * s;
-        H[l] = 1.0;
-        r2 = fmax(r2, dl[l] * dl[l]);
-    }
-    const Cx q = {ur * s, -ui * s};  // 1 / (ubar / |ubar|)
-    Cx acc = q, p = q;
-    double rk2 = r2;
-    for (int k = 1; rk2 >= GREEN_EPS2 && k <= GREEN_KMAX; ++k) {
-        H[0] *= dl[0];
-#pragma unroll
-        for (int l = 1; l <= M; ++l) H[l] = H[l - 1] + dl[l] * H[l];
-        p = cx_mul(p, q);
-        const double t = GREEN_COEF.c[M - 1][k] * H[M];
-        acc.re += t * p.re;
-        acc.im += t * p.im;
-        rk2 *= r2;
-    }
-    return {acc.re * s, acc.im * s};
-}
-
-// J of two sorted corners
-__device__ __forceinline__ Cx green_pair(const GreenCorner& a, const GreenCorner& b, double zr, double zi) {
-    const double u[2] = {zr - a.x, zr - b.x};
-    const double w = b.x - a.x, ur = 0.5 * (u[0] + u[1]), n2 = ur * ur + zi * zi;
-    if (w * w < GREEN_RHO2 * n2) return green_series<1>(u, ur, zi, n2);
-    const double iw = 1.0 / w;
-    return {(a.lr - b.lr) * iw, (a.li - b.li) * iw};
-}
-
-// J of three sorted corners from the J of its two pairs, which only a wide triple reads
-__device__ __forceinline__ Cx green_triple(const GreenCorner& a, const GreenCorner& b, const GreenCorner& c, Cx pab, Cx pbc, double zr,
-                                           double zi) {
-    const double u[3] = {zr - a.x, zr - b.x, zr - c.x};
-    const double w = c.x - a.x, ur = (u[0] + u[1] + u[2]) * (1.0 / 3.0), n2 = ur * ur + zi * zi;
-    if (w * w < GREEN_RHO2 * n2) return green_series<2>(u, ur, zi, n2);
-    const Cx t0 = cx_mul({u[0], zi}, pab), t1 = cx_mul({u[2], zi}, pbc);
-    const double f = 2.0 / w;
-    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
-}
-
-// J of a simplex with corners in any order
-__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, double zr, double zi) {
-    green_cx(a, b);
-    return green_pair(a, b, zr, zi);
-}
-__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenCorner c, double zr, double zi) {
-    green_cx(a, b);
-    green_cx(b, c);
-    green_cx(a, b);
-    return green_triple(a, b, c, green_pair(a, b, zr, zi), green_pair(b, c, zr, zi), zr, zi);
-}
-__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenCorner c, GreenCorner d, double zr, double zi) {
-    green_cx(a, b);
-    green_cx(c, d);
-    green_cx(a, c);
-    green_cx(b, d);
-    green_cx(b, c);
-    const double u[4] = {zr - a.x, zr - b.x, zr - c.x, zr - d.x};
-    const double w = d.x - a.x, ur = 0.25 * ((u[0] + u[1]) + (u[2] + u[3])), n2 = ur * ur + zi * zi;
-    if (w * w < GREEN_RHO2 * n2) return green_series<3>(u, ur, zi, n2);
-    // the two triples share the middle pair
-    const Cx p01 = green_pair(a, b, zr, zi), p12 = green_pair(b, c, zr, zi), p23 = green_pair(c, d, zr, zi);
-    const Cx j0 = green_triple(a, b, c, p01, p12, zr, zi), j1 = green_triple(b, c, d, p12, p23, zr, zi);
-    const Cx t0 = cx_mul({u[0], zi}, j0), t1 = cx_mul({u[3], zi}, j1);
-    const double f = 1.5 / w;
-    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
-}
-
-// partial [2 nz][nrows]: column 2 i + {0, 1} the real and imaginary part of the sum at z_i
-template <int D>
-__global__ __launch_bounds__(256) void ltm_green_kernel(GreenArgs a, double* __restrict__ partial, int64_t nrows) {
-    // [zn][2] this block's values of z | [4 waves][zn][2] sums
-    extern __shared__ __attribute__((aligned(16))) double ldsg[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int NV = 1 << D;  // corners per cell
-    const int z0 = (int)blockIdx.z * a.zper;
-    const int zn = min(a.zper, a.nz - z0);
-    const double* const zl = ldsg;
-    double* const acc = ldsg + (size_t)2 * zn * (1 + wave);
-    for (int i = threadIdx.x; i < 2 * zn; i += 256) ldsg[i] = a.z[2 * z0 + i];
-    for (int i = threadIdx.x; i < 8 * zn; i += 256) ldsg[2 * zn + i] = 0.0;
-    __syncthreads();
-    const int npt = a.npt;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const int64_t tileE = a.E.tile;
-    // the whole-grid geometry of ltm_window_kernel: corner `bits` of cell (i1, i2, i3), every index wrapped mod npt
-    auto cornerE = [&](int i1, int i2, int i3, int bits) -> double {
-        if ((bits & 1) && ++i1 == npt) i1 = 0;
-        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
-        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
-        return Eb[((int64_t)i3 * npt + i2) * tileE + i1];
-    };
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
-        const int64_t k = base + threadIdx.x;
-        const bool active = k < a.ncell;
-        double c[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) c[j] = 0.0;
-        if (active) {
-            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
-            const int i1 = (int)(k - line * npt);
-            const int i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
-            const int i2 = (int)line - i3 * npt;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) c[j] = cornerE(i1, i2, i3, j);
-        }
-        for (int iz = 0; iz < zn; ++iz) {
-            const double zr = zl[2 * iz], zi = zl[2 * iz + 1];
-            double sr = 0.0, si = 0.0;
-            if (active) {
-                GreenCorner g[NV];
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const double ur = zr - c[j];
-                    g[j] = {c[j], 0.5 * log(ur * ur + zi * zi), atan2(zi, ur)};
-                }
-                if constexpr (D == 3) {
-                    // the permutation (X, Y, Z) of the axes: corners 0, e_X, e_X + e_Y, (1,1,1); a loop, the corners by selects
-#pragma unroll 1
-                    for (int t = 0; t < 6; ++t) {
-                        const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3;
-                        const int bb = (1 << X) | (1 << Y);
-                        const GreenCorner ga = green_sel(X == 0, g[1], green_sel(X == 1, g[2], g[4]));
-                        const GreenCorner gb = green_sel(bb == 3, g[3], green_sel(bb == 5, g[5], g[6]));
-                        const Cx J = green_simplex(g[0], ga, gb, g[7], zr, zi);
-                        sr += J.re;
-                        si += J.im;
-                    }
-                } else if constexpr (D == 2) {
-#pragma unroll 1
-                    for (int t = 0; t < 2; ++t) {
-                        const Cx J = green_simplex(g[0], green_sel(t == 0, g[1], g[2]), g[3], zr, zi);
-                        sr += J.re;
-                        si += J.im;
-                    }
-                } else {
-                    const Cx J = green_simplex(g[0], g[1], zr, zi);
-                    sr = J.re;
-                    si = J.im;
-                }
-            }
-            // every lane ends with the same bits: a + b == b + a at every level of the butterfly
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                sr += __shfl_xor(sr, off);
-                si += __shfl_xor(si, off);
-            }
-            if (lane == 0) {
-                acc[2 * iz] += sr;
-                acc[2 * iz + 1] += si;
-            }
-        }
-    }
-    __syncthreads();
-    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const double* h = ldsg + 2 * zn;
-    const size_t w = (size_t)2 * zn;  // from one wave's sums to the next
-    for (int t = threadIdx.x; t < 2 * zn; t += 256)
-        partial[(int64_t)(2 * z0 + t) * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
-}
-
-using LtmGreenFn = void (*)(GreenArgs, double*, int64_t);
-constexpr LtmGreenFn LTM_GREEN[3] = {ltm_green_kernel<1>, ltm_green_kernel<2>, ltm_green_kernel<3>};
 }  // namespace
 
-// z_host [nz][2] with Im z != 0, out_host [nz][2].  Im z < 0: the conjugate of the value at conj(z), to the bit.
-int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* z_host, int nz, double* out_host) {
-    GreenArgs a;
-    a.E = E;
-    a.npt = npt;
-    a.ncell = 1;
-    for (int j = 0; j < d; ++j) a.ncell *= npt;
-    const double weight = 1.0 / ((double)ltm_nsimplex(d) * (double)a.ncell);
-    std::vector<double> zup(2 * (size_t)nz);
-    for (size_t i = 0; i < (size_t)nz; ++i) {
-        zup[2 * i] = z_host[2 * i];
-        zup[2 * i + 1] = std::fabs(z_host[2 * i + 1]);
-    }
-    // the scans' grid: one block row per band, enough blocks to fill the device several times over, few enough partial rows
-    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
-    const int64_t nrows = nblocks * n;
-    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * 2 * (size_t)std::min(nz, LTM_GREEN_CHUNK));
-    if (rc) return rc;
-    double* partial = ctx->scratch[1].as<double>();
-    const double* zdev = nullptr;
-    if ((rc = sweep_to_device(ctx, zup.data(), 2 * nz, &zdev))) return rc;
-    SumOut so;
-    so.host = out_host;
-    if (mbox_reserve(ctx) == ABZ_OK && sizeof(double2) * (size_t)nz <= ctx->mbox_cap / 2) {  // the mailbox's result half
-        so.map_dev = reinterpret_cast<double2*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
-        so.map_host = reinterpret_cast<const double2*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
-    }
-    double2* where = nullptr;
-    if ((rc = sum_target(ctx, so, 0, nz, &where))) return rc;
-    for (int s0 = 0; s0 < nz; s0 += LTM_GREEN_CHUNK) {
-        const int cnt = std::min(LTM_GREEN_CHUNK, nz - s0);
-        // where the cells give fewer than ~2048 blocks the values of z are dealt to blockIdx.z, at least 4 per block
-        const int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(2048, nrows), cdiv64(cnt, 4)));
-        a.z = zdev + 2 * (size_t)s0;
-        a.nz = cnt;
-        a.zper = (int)cdiv64(cnt, nsplit);
-        const dim3 grid((unsigned)nblocks, (unsigned)n, (unsigned)cdiv64(cnt, a.zper));
-        ProfScope ps(ctx, ABZ_K_LTM);
-        launch(ctx, LTM_GREEN[d - 1], grid, dim3(256), (unsigned)(sizeof(double) * 10 * (size_t)a.zper), a, partial, nrows);
-        ABZ_HIP(hipGetLastError());
-        launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * cnt)), dim3(256), 0, (const double*)partial, nrows, weight, 2 * cnt, (int64_t)0,
-               reinterpret_cast<double*>(where + s0));
-        ABZ_HIP(hipGetLastError());
-    }
-    if ((rc = sum_deliver(ctx, so, where, 0, nz))) return rc;
-    for (size_t i = 0; i < (size_t)nz; ++i)
-        if (z_host[2 * i + 1] < 0.0) out_host[2 * i + 1] = -out_host[2 * i + 1];
-    return ABZ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Green's function with matrix elements at complex energies (abz_rule_ltm_green_weighted)
-// ---------------------------------------------------------------------------------------------------------------------
-// G_A,c(z) = w sum_{cells} sum_{d! simplices} sum_{bands} sum_{i=0..m} A_{c,i} W_i(z), m = d: the element of component c is linear
-// inside a simplex like the energy, and W_i is the mean of lambda_i / (z - e) over it.  The uniform density times lambda_i,
-// normalised, is Dirichlet(1, .., 2, .., 1), whose image under e is the B-spline with the knot x_i doubled:
-//      W_i = J[x_0 .. x_m, x_i](z) / (m + 1)
-//  * The J of m + 2 knots with one repeat obeys the recursion above with J[x, x] = 1 / u, and the evaluation rule carries over:
-//    a sub-range (a contiguous run of the sorted multiset) narrower than rho |z - mean| is summed by the same Taylor series,
-//    now of up to five knots (M = 4): max |delta| <= 4/5 width, the ratio stays below 2/5, (2/5)^k >= 2^-52 up to k = 39, within
-//    GREEN_KMAX; the coefficient table has the row m = 4.  Only wider sub-ranges are divided by their width.
-//  * Sharing.  The sub-ranges of the m + 1 multisets that hold at most one copy of the doubled knot are the plain ones, P[a][b] =
-//    J[x_a .. x_b]: computed once per (simplex, z), d = 3: 3 pairs (from the corner logs), 2 triples, 1 quadruple.  Those that
-//    hold both copies, D_i[a][b] = J[x_a .. x_i, x_i .. x_b] with a <= i <= b, start from D_i[i][i] = 1 / u_i and grow by
-//      D_i[a][b] = M / (M-1) (u_a lo - u_b hi) / (x_b - x_a),   M = b - a + 1,
-//      lo = b > i ? D_i[a][b-1] : P[a][b],   hi = a < i ? D_i[a+1][b] : P[a][b]
-//    (dropping the last or the first knot): 16 of them in 3-D, 6 in 2-D, 2 in 1-D.  Every sub-range is evaluated whether or not a
-//    wider one turns out narrow and ignores it: each is accurate by itself.  One shortcut comes first: where all m + 1 whole
-//    multisets are narrow the weights are m + 1 series and nothing else is formed (150^3 SVO grid, 256 z, one component:
-//    2790 ms without it, 1222 ms with it).
-//  * Shape (ltm_green_w_kernel<D, NC>).  The cell walk, the corner geometry, the z list in LDS, blockIdx.z and the reduction are
-//    ltm_green_kernel's; the 2^d corner energies and the NC 2^d corner elements of a group of NC components stay in registers
-//    (LtmElems::load through PlaneView / acomp), the sort of a simplex carries each corner's log and its NC elements, the m + 1
-//    weights of a (simplex, z) are formed once and every component contracts with them.  Groups as in ltm_scan: 4s, a 2, a 1.
-//    LDS: [zn][2] z | [4 waves][zn][NC][2] sums, so a launch takes green_w_chunk(NC) = 512 / 291 / 154 values of z.
-//    1 / (m + 1) goes into the scale of ltm_final_kernel.
-namespace {
-constexpr int green_w_chunk(int nc) {
-    const size_t fit = LTM_LDS_MAX / (sizeof(double) * (size_t)(2 + 8 * nc));
-    return fit < (size_t)LTM_GREEN_CHUNK ? (int)fit : LTM_GREEN_CHUNK;
-}
-static_assert(sizeof(double) * (2 + 8 * 1) * green_w_chunk(1) <= LTM_LDS_MAX && sizeof(double) * (2 + 8 * 2) * green_w_chunk(2) <= LTM_LDS_MAX &&
-                  sizeof(double) * (2 + 8 * 4) * green_w_chunk(4) <= LTM_LDS_MAX,
-              "the z list and the four waves' sums of every component group fit the scans' LDS");
-static_assert(green_w_chunk(4) >= 4 && green_w_chunk(4) <= green_w_chunk(2) && green_w_chunk(2) <= green_w_chunk(1), "chunks shrink with NC");
-
-struct GreenWArgs {
-    GreenArgs g;
-    PlaneView A;
-    int64_t acomp;  // doubles from a band's plane of one component to its plane of the next: n * A.pitch
-    int aplane0;    // first element plane of this launch: (its first component) * n
-};
-
-// what the sort of a simplex carries per corner: the energy, log(z - energy) and the NC elements
-template <int NC>
-struct GreenWCorner {
-    GreenCorner g;
-    LtmVec<NC> a;
-};
-template <int NC>
-__device__ __forceinline__ GreenWCorner<NC> green_wsel(bool first, const GreenWCorner<NC>& p, const GreenWCorner<NC>& q) {
-    GreenWCorner<NC> r;
-    r.g = green_sel(first, p.g, q.g);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) r.a.v[c] = first ? p.a.v[c] : q.a.v[c];
-    return r;
-}
-template <int NC>
-__device__ __forceinline__ void green_wcx(GreenWCorner<NC>& p, GreenWCorner<NC>& q) {
-    const bool sw = q.g.x < p.g.x;
-    const GreenWCorner<NC> lo = green_wsel(sw, q, p), hi = green_wsel(sw, p, q);
-    p = lo;
-    q = hi;
-}
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loops whose index is a template argument
-template <int N, class F>
-__device__ __forceinline__ void green_for(F&& f) {
-    if constexpr (N > 0) {
-        green_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
-// J of the M + 1 >= 3 sorted knots with u[l] = Re z - knot l and width w, from `lo` (the J without the last knot) and `hi`
-// (without the first), which only a wide range reads
-template <int M>
-__device__ __forceinline__ double green_mean(const double (&u)[M + 1]) {
-    double ur = u[0];
-#pragma unroll
-    for (int l = 1; l <= M; ++l) ur += u[l];
-    return ur * (1.0 / (double)(M + 1));
-}
-template <int M>
-__device__ __forceinline__ Cx green_node(const double (&u)[M + 1], double w, Cx lo, Cx hi, double zi) {
-    const double ur = green_mean<M>(u), n2 = ur * ur + zi * zi;
-    if (w * w < GREEN_RHO2 * n2) return green_series<M>(u, ur, zi, n2);
-    const Cx t0 = cx_mul({u[0], zi}, lo), t1 = cx_mul({u[M], zi}, hi);
-    const double f = ((double)M / (double)(M - 1)) / w;
-    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
-}
-
-// (m + 1) W_i = J[x_0 .. x_m, x_i] of the NK = m + 1 sorted corners g
-template <int NK>
-__device__ __forceinline__ void green_weights(const GreenCorner (&g)[NK], double zr, double zi, Cx (&W)[NK]) {
-    double u[NK];
-#pragma unroll
-    for (int l = 0; l < NK; ++l) u[l] = zr - g[l].x;
-    // The m + 1 whole multisets first.  Where all of them are narrow -- a fine grid away from the corners' energies: most simplices
-    // -- each is its series and no sub-range is read; the value is the one the general path below gives (green_node makes the
-    // same decision from the same numbers).
-    {
-        const double w = g[NK - 1].x - g[0].x;
-        double uu[NK][NK + 1], ur[NK], n2[NK];
-        bool narrow = true;
-#pragma unroll
-        for (int i = 0; i < NK; ++i) {
-#pragma unroll
-            for (int l = 0; l <= NK; ++l) uu[i][l] = u[l - (l > i ? 1 : 0)];
-            ur[i] = green_mean<NK>(uu[i]);
-            n2[i] = ur[i] * ur[i] + zi * zi;
-            narrow = narrow && w * w < GREEN_RHO2 * n2[i];
-        }
-        if (narrow) {
-#pragma unroll
-            for (int i = 0; i < NK; ++i) W[i] = green_series<NK>(uu[i], ur[i], zi, n2[i]);
-            return;
-        }
-    }
-    Cx P[NK][NK];  // a <= b: J[x_a .. x_b]; P[a][a] = 1 / u_a
-#pragma unroll
-    for (int l = 0; l < NK; ++l) {
-        const double s = 1.0 / (u[l] * u[l] + zi * zi);
-        P[l][l] = {u[l] * s, -zi * s};
-    }
-    green_for<NK - 1>([&](auto L_) {
-        constexpr int L = decltype(L_)::value + 1;
-        green_for<NK - L>([&](auto a_) {
-            constexpr int a = decltype(a_)::value, b = a + L;
-            if constexpr (L == 1) {
-                P[a][b] = green_pair(g[a], g[b], zr, zi);
-            } else {
-                double uu[L + 1];
-#pragma unroll
-                for (int l = 0; l <= L; ++l) uu[l] = u[a + l];
-                P[a][b] = green_node<L>(uu, g[b].x - g[a].x, P[a][b - 1], P[a + 1][b], zi);
-            }
-        });
-    });
-    green_for<NK>([&](auto i_) {
-        constexpr int i = decltype(i_)::value;
-        Cx Dd[NK][NK];  // a <= i <= b: J[x_a .. x_i, x_i .. x_b]
-        Dd[i][i] = P[i][i];
-        green_for<NK - 1>([&](auto L_) {
-            constexpr int L = decltype(L_)::value + 1;
-            green_for<NK - L>([&](auto a_) {
-                constexpr int a = decltype(a_)::value, b = a + L;
-                if constexpr (a <= i && i <= b) {
-                    constexpr int M = L + 1;
-                    double uu[M + 1];
-#pragma unroll
-                    for (int l = 0; l <= M; ++l) uu[l] = u[a + l - (a + l > i ? 1 : 0)];
-                    const Cx lo = b > i ? Dd[a][b - 1] : P[a][b];
-                    const Cx hi = a < i ? Dd[a + 1][b] : P[a][b];
-                    Dd[a][b] = green_node<M>(uu, g[b].x - g[a].x, lo, hi, zi);
-                }
-            });
-        });
-        W[i] = Dd[0][NK - 1];
-    });
-}
-
-// sum_i A_{c,i} (m + 1) W_i of a simplex with corners in any order, added to (sr, si)[c]
-template <int NK, int NC>
-__device__ __forceinline__ void green_wsimplex(GreenWCorner<NC> (&q)[NK], double zr, double zi, double (&sr)[NC], double (&si)[NC]) {
-    if constexpr (NK == 2) {
-        green_wcx(q[0], q[1]);
-    } else if constexpr (NK == 3) {
-        green_wcx(q[0], q[1]);
-        green_wcx(q[1], q[2]);
-        green_wcx(q[0], q[1]);
-    } else {
-        green_wcx(q[0], q[1]);
-        green_wcx(q[2], q[3]);
-        green_wcx(q[0], q[2]);
-        green_wcx(q[1], q[3]);
-        green_wcx(q[1], q[2]);
-    }
-    GreenCorner g[NK];
-#pragma unroll
-    for (int l = 0; l < NK; ++l) g[l] = q[l].g;
-    Cx W[NK];
-    green_weights<NK>(g, zr, zi, W);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-        for (int l = 0; l < NK; ++l) {
-            sr[c] += q[l].a.v[c] * W[l].re;
-            si[c] += q[l].a.v[c] * W[l].im;
-        }
-    }
-}
-
-// partial [2 NC nz][nrows]: column (i NC + c) 2 + {0, 1} the real and imaginary part of component c's sum at z_i
-template <int D, int NC>
-__global__ __launch_bounds__(256) void ltm_green_w_kernel(GreenWArgs wa, double* __restrict__ partial, int64_t nrows) {
-    // [zn][2] this block's values of z | [4 waves][zn][NC][2] sums
-    extern __shared__ __attribute__((aligned(16))) double ldsw[];
-    const GreenArgs& a = wa.g;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int NV = 1 << D;  // corners per cell
-    using Load = LtmElems<NC, false>;
-    using Corner = GreenWCorner<NC>;
-    const int z0 = (int)blockIdx.z * a.zper;
-    const int zn = min(a.zper, a.nz - z0);
-    const double* const zl = ldsw;
-    double* const acc = ldsw + (size_t)2 * zn * (1 + NC * wave);
-    for (int i = threadIdx.x; i < 2 * zn; i += 256) ldsw[i] = a.z[2 * z0 + i];
-    for (int i = threadIdx.x; i < 8 * NC * zn; i += 256) ldsw[2 * zn + i] = 0.0;
-    __syncthreads();
-    const int npt = a.npt;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const double* __restrict__ const Ab = wa.A.base + (int64_t)(wa.aplane0 + (int)blockIdx.y) * wa.A.pitch;
-    const int64_t tileE = a.E.tile, tileA = wa.A.tile, acomp = wa.acomp;
-    // the whole-grid geometry of ltm_window_kernel: corner `bits` of cell (i1, i2, i3), every index wrapped mod npt
-    auto wrap = [&](int& i1, int& i2, int& i3, int bits) {
-        if ((bits & 1) && ++i1 == npt) i1 = 0;
-        if (D >= 2 && (bits & 2) && ++i2 == npt) i2 = 0;
-        if (D == 3 && (bits & 4) && ++i3 == npt) i3 = 0;
-    };
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
-        const int64_t k = base + threadIdx.x;
-        const bool active = k < a.ncell;
-        double c[NV];
-        LtmVec<NC> ca[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            c[j] = 0.0;
-#pragma unroll
-            for (int cc = 0; cc < NC; ++cc) ca[j].v[cc] = 0.0;
-        }
-        if (active) {
-            const int64_t line = k <= 0xffffffffll ? (int64_t)((uint32_t)k / (uint32_t)npt) : k / npt;
-            const int i1 = (int)(k - line * npt);
-            const int i3 = D == 3 ? (int)((uint32_t)line / (uint32_t)npt) : 0;
-            const int i2 = (int)line - i3 * npt;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                int j1 = i1, j2 = i2, j3 = i3;
-                wrap(j1, j2, j3, j);
-                c[j] = Eb[((int64_t)j3 * npt + j2) * tileE + j1];
-                ca[j] = Load::load(Ab + ((int64_t)j3 * npt + j2) * tileA + j1, acomp);
-            }
-        }
-        for (int iz = 0; iz < zn; ++iz) {
-            const double zr = zl[2 * iz], zi = zl[2 * iz + 1];
-            double sr[NC], si[NC];
-#pragma unroll
-            for (int cc = 0; cc < NC; ++cc) sr[cc] = si[cc] = 0.0;
-            if (active) {
-                Corner g[NV];
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const double ur = zr - c[j];
-                    g[j].g = {c[j], 0.5 * log(ur * ur + zi * zi), atan2(zi, ur)};
-                    g[j].a = ca[j];
-                }
-                if constexpr (D == 3) {
-                    // the permutation (X, Y, Z) of the axes: corners 0, e_X, e_X + e_Y, (1,1,1); a loop, the corners by selects
-#pragma unroll 1
-                    for (int t = 0; t < 6; ++t) {
-                        const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3;
-                        const int bb = (1 << X) | (1 << Y);
-                        Corner q[4] = {g[0], green_wsel(X == 0, g[1], green_wsel(X == 1, g[2], g[4])),
-                                       green_wsel(bb == 3, g[3], green_wsel(bb == 5, g[5], g[6])), g[7]};
-                        green_wsimplex<4, NC>(q, zr, zi, sr, si);
-                    }
-                } else if constexpr (D == 2) {
-#pragma unroll 1
-                    for (int t = 0; t < 2; ++t) {
-                        Corner q[3] = {g[0], green_wsel(t == 0, g[1], g[2]), g[3]};
-                        green_wsimplex<3, NC>(q, zr, zi, sr, si);
-                    }
-                } else {
-                    Corner q[2] = {g[0], g[1]};
-                    green_wsimplex<2, NC>(q, zr, zi, sr, si);
-                }
-            }
-            // every lane ends with the same bits: a + b == b + a at every level of the butterfly
-#pragma unroll
-            for (int cc = 0; cc < NC; ++cc) {
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    sr[cc] += __shfl_xor(sr[cc], off);
-                    si[cc] += __shfl_xor(si[cc], off);
-                }
-                if (lane == 0) {
-                    acc[2 * (iz * NC + cc)] += sr[cc];
-                    acc[2 * (iz * NC + cc) + 1] += si[cc];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const double* h = ldsw + 2 * zn;
-    const size_t w = (size_t)2 * NC * zn;  // from one wave's sums to the next
-    for (int t = threadIdx.x; t < 2 * NC * zn; t += 256)
-        partial[((int64_t)2 * NC * z0 + t) * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
-}
-
-using LtmGreenWFn = void (*)(GreenWArgs, double*, int64_t);
-// [d - 1][NC = 1, 2, 4]
-constexpr LtmGreenWFn LTM_GREEN_W[3][3] = {
-    {ltm_green_w_kernel<1, 1>, ltm_green_w_kernel<1, 2>, ltm_green_w_kernel<1, 4>},
-    {ltm_green_w_kernel<2, 1>, ltm_green_w_kernel<2, 2>, ltm_green_w_kernel<2, 4>},
-    {ltm_green_w_kernel<3, 1>, ltm_green_w_kernel<3, 2>, ltm_green_w_kernel<3, 4>},
-};
-}  // namespace
-
-// z_host [nz][2] with Im z != 0, A the element planes of `ncomp` components (A = E, ncomp = 1: the energy), out_host
-// [nz][ncomp][2].  Im z < 0: the conjugate of the value at conj(z), to the bit (the elements are real).
-int launch_ltm_green_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* z_host, int nz,
-                              double* out_host) {
-    GreenWArgs a;
-    a.g.E = E;
-    a.g.npt = npt;
-    a.g.ncell = 1;
-    for (int j = 0; j < d; ++j) a.g.ncell *= npt;
-    a.A = A;
-    a.acomp = (int64_t)n * A.pitch;
-    // of a simplex and, of its d + 1 corner weights, the 1 / (m + 1)
-    const double weight = 1.0 / ((double)ltm_nsimplex(d) * (double)a.g.ncell * (double)(d + 1));
-    std::vector<double> zup(2 * (size_t)nz);
-    for (size_t i = 0; i < (size_t)nz; ++i) {
-        zup[2 * i] = z_host[2 * i];
-        zup[2 * i + 1] = std::fabs(z_host[2 * i + 1]);
-    }
-    // the scans' grid: one block row per band, enough blocks to fill the device several times over, few enough partial rows
-    const int64_t nblocks = std::min<int64_t>(cdiv64(a.g.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
-    const int64_t nrows = nblocks * n;
-    size_t pmax = 0;
-    for (int nc : {1, 2, 4})
-        if (nc <= ncomp) pmax = std::max(pmax, (size_t)std::min(nz, green_w_chunk(nc)) * (size_t)(2 * nc));
-    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax);
-    if (rc) return rc;
-    double* partial = ctx->scratch[1].as<double>();
-    const double* zdev = nullptr;
-    if ((rc = sweep_to_device(ctx, zup.data(), 2 * nz, &zdev))) return rc;
-    const size_t ncols = (size_t)nz * (size_t)ncomp;
-    SumOut so;
-    so.host = out_host;
-    if (mbox_reserve(ctx) == ABZ_OK && sizeof(double2) * ncols <= ctx->mbox_cap / 2) {  // the mailbox's result half
-        so.map_dev = reinterpret_cast<double2*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
-        so.map_host = reinterpret_cast<const double2*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
-    }
-    double2* where = nullptr;
-    if ((rc = sum_target(ctx, so, 0, (int64_t)ncols, &where))) return rc;
-    // groups of 4 components, then 2, then 1; every group walks the grid once per chunk of z
-    for (int c0 = 0; c0 < ncomp;) {
-        const int nc = ncomp - c0 >= 4 ? 4 : (ncomp - c0 >= 2 ? 2 : 1);
-        const int CH = green_w_chunk(nc);
-        a.aplane0 = c0 * n;
-        for (int s0 = 0; s0 < nz; s0 += CH) {
-            const int cnt = std::min(CH, nz - s0);
-            // where the cells give fewer than ~2048 blocks the values of z are dealt to blockIdx.z, at least 4 per block
-            const int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(2048, nrows), cdiv64(cnt, 4)));
-            a.g.z = zdev + 2 * (size_t)s0;
-            a.g.nz = cnt;
-            a.g.zper = (int)cdiv64(cnt, nsplit);
-            const dim3 grid((unsigned)nblocks, (unsigned)n, (unsigned)cdiv64(cnt, a.g.zper));
-            ProfScope ps(ctx, ABZ_K_LTM);
-            launch(ctx, LTM_GREEN_W[d - 1][nc >> 1], grid, dim3(256), (unsigned)(sizeof(double) * (size_t)(2 + 8 * nc) * (size_t)a.g.zper), a,
-                   partial, nrows);
-            ABZ_HIP(hipGetLastError());
-            // column (i nc + c) 2 + t of the launch -> out[s0 + i][c0 + c][t]
-            launch(ctx, ltm_final_kernel, dim3((unsigned)(2 * nc * cnt)), dim3(256), 0, (const double*)partial, nrows, weight, 2 * nc,
-                   (int64_t)2 * ncomp, reinterpret_cast<double*>(where + ((size_t)s0 * (size_t)ncomp + (size_t)c0)));
-            ABZ_HIP(hipGetLastError());
-        }
-        c0 += nc;
-    }
-    if ((rc = sum_deliver(ctx, so, where, 0, (int64_t)ncols))) return rc;
-    for (size_t i = 0; i < (size_t)nz; ++i)
-        if (z_host[2 * i + 1] < 0.0)
-            for (size_t c = 0; c < (size_t)ncomp; ++c) out_host[2 * (i * (size_t)ncomp + c) + 1] = -out_host[2 * (i * (size_t)ncomp + c) + 1];
+int launch_ltm_final(abz_ctx* ctx, const double* partial, int64_t nrows, double scale, int ncols, int cnt, int64_t ostride, double* out) {
+    launch(ctx, ltm_final_kernel, dim3((unsigned)ncols), dim3(256), 0, partial, nrows, scale, cnt, ostride, out);
+    ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }
 

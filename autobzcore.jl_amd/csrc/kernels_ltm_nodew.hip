@@ -40,7 +40,7 @@
 //  * No atomics anywhere: a thread sums its simplices in program order and two calls write the same bits.
 //  * ltm_nodew_dot_kernel: sum_k sum_b w_b(k; E_i) A_{c,b}(k) against the attached element block, [nE][ncomp]; one pass over the
 //    weights (blockIdx.y = energy, every component of a node contracted from one load of the weight), fixed-order two-stage
-//    reduction (a butterfly over the wave, the four waves in order, then one block per column as in ltm_final_kernel), results
+//    reduction (a butterfly over the wave, the four waves in order, then one block per column: launch_ltm_final), results
 //    through the pinned mailbox with one synchronisation.
 //  * ltm_nodew_fold_kernel: for a rule of abz_rule_ltm_unfold, the weights summed over each orbit onto the source rule's nodes.
 //    The Kuhn mesh is invariant under 12 of the 48 cubic operations only, so w(S k) != w(k) in general and the fold is a plain sum
@@ -55,12 +55,11 @@
 #include <vector>
 
 #include "abz_internal.h"
+#include "ltm_device.h"
 
 namespace abz {
 
 namespace {
-
-inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 struct NodeWArgs {
     PlaneView E, W;   // eigenvalue planes; the weight block (nE n planes per tile, pitch = row)
@@ -395,21 +394,6 @@ __global__ __launch_bounds__(256) void ltm_nodew_dot_kernel(PlaneView W, PlaneVi
     }
 }
 
-// out[column] = sum_rows partial[column][row], one block per column, fixed summation order (ltm_final_kernel's)
-__global__ __launch_bounds__(256) void ltm_nodew_final_kernel(const double* __restrict__ partial, int64_t nrows, double* __restrict__ out) {
-    __shared__ double red[256];
-    const double* __restrict__ p = partial + (int64_t)blockIdx.x * nrows;
-    double s = 0.0;
-    for (int64_t r = threadIdx.x; r < nrows; r += 256) s += p[r];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Fold: the weights of an unfolded rule summed over each orbit onto the source rule's nodes
 // ---------------------------------------------------------------------------------------------------------------------
@@ -469,20 +453,15 @@ int launch_ltm_node_weights_dot(abz_ctx* ctx, int n, int npt, int64_t nlines, Pl
     // the columns travel as pairs of doubles: the mailbox and its fallback speak double2
     const int64_t npair = (ncol + 1) / 2;
     std::vector<double> pairs(2 * (size_t)npair);
-    SumOut so;
-    so.host = pairs.data();
-    if (mbox_reserve(ctx) == ABZ_OK && sizeof(double2) * (size_t)npair <= ctx->mbox_cap / 2) {  // the mailbox's result half
-        so.map_dev = reinterpret_cast<double2*>(static_cast<char*>(ctx->mbox_dev) + ctx->mbox_cap / 2);
-        so.map_host = reinterpret_cast<const double2*>(static_cast<const char*>(ctx->mbox) + ctx->mbox_cap / 2);
-    }
+    const SumOut so = sum_out_mailbox(ctx, pairs.data(), (size_t)npair);
     double2* where = nullptr;
     if ((rc = sum_target(ctx, so, 0, npair, &where))) return rc;
     {
         ProfScope ps(ctx, ABZ_K_LTM);
         launch(ctx, ltm_nodew_dot_kernel, dim3((unsigned)nblocks, (unsigned)nE), dim3(256), 0, W, A, n, npt, ncomp, nlines, partial, nblocks);
         ABZ_HIP(hipGetLastError());
-        launch(ctx, ltm_nodew_final_kernel, dim3((unsigned)ncol), dim3(256), 0, (const double*)partial, nblocks, reinterpret_cast<double*>(where));
-        ABZ_HIP(hipGetLastError());
+        // column by column as they are (scale 1: x to the bit)
+        if ((rc = launch_ltm_final(ctx, partial, nblocks, 1.0, ncol, ncol, 0, reinterpret_cast<double*>(where)))) return rc;
     }
     if ((rc = sum_deliver(ctx, so, where, 0, npair))) return rc;
     std::memcpy(out_host, pairs.data(), sizeof(double) * (size_t)ncol);

@@ -1,5 +1,5 @@
-"""Tetrahedron trace of the Green's function on the device (abz_rule_ltm_green, ltm_green_kernel in kernels_ltm.hip) against
-the numpy restatement of tests/gltm_numpy.py and the reference's exact DOS formula.
+"""Tetrahedron trace of the Green's function on the device (abz_rule_ltm_green, ltm_green_kernel<D, GreenTrace> in
+kernels_ltm_green.hip) against the numpy restatement of tests/gltm_numpy.py and the reference's exact DOS formula.
 
 Parity bound: the restatement is fed the rule's own exported eigenvalues, so only summation order, FMA contraction and the
 device's log / atan2 remain; the bound is the LTM scans', |u - ref| <= 1e-9 max(1, max|ref|) (test_gpu_ltm.py), applied to the

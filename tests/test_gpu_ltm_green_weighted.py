@@ -1,5 +1,5 @@
-"""Tetrahedron Green's function with matrix elements on the device (abz_rule_ltm_green_weighted, ltm_green_w_kernel in
-kernels_ltm.hip) against the numpy restatement of tests/gwltm_numpy.py, its own identities and the trace abz_rule_ltm_green.
+"""Tetrahedron Green's function with matrix elements on the device (abz_rule_ltm_green_weighted, ltm_green_kernel<D, GreenElems<NC>> in
+kernels_ltm_green.hip) against the numpy restatement of tests/gwltm_numpy.py, its own identities and the trace abz_rule_ltm_green.
 
 Parity bound: the restatement is fed the rule's own exported eigenvalues and elements, so only summation order, FMA contraction
 and the device's log / atan2 remain; the bound is the LTM scans', |u - ref| <= 1e-9 max(1, max|ref|) (test_gpu_ltm.py), applied to
