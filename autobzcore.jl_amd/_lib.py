@@ -65,6 +65,7 @@ PROTOTYPES = {
     "abz_rule_ltm_node_weights_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p, c_ip]),
     "abz_rule_ltm_node_weights_dot": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_rule_ltm_node_weights_fold": (C.c_int, [C.c_void_p, c_f64p]),
+    "abz_rule_ltm_density_matrix": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_mem_info": (C.c_int, [C.c_void_p, c_i64p]),
     "abz_symptr_rule": (C.c_int, [C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
     "abz_symptr_rule_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),

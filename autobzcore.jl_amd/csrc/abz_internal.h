@@ -548,6 +548,11 @@ int launch_ltm_orbitals(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView 
 // band projectors P^b_pq = U_pb conj(U_qb) into the same block: one component for p == q, Re and Im for p != q
 int ltm_projector_components(const int32_t* pairs, int npairs);
 int launch_ltm_projectors(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, PlaneView A, const int32_t* pairs, int npairs);
+// Density matrix in the orbital basis (kernels_ltm_dens.hip): out_host [nE][n][n][2] = sum_k sum_b w_b(k; E_i) U_pb conj(U_qb) from the
+// weight block W (nE n planes, as launch_ltm_node_weights leaves it) and the H planes of the same whole grid (not read for one
+// band), U never in HBM; the lower triangle is the exact conjugate of the upper one.  1...32 bands.  Kernels under ABZ_K_EIG,
+// results through the mailbox, one synchronisation.
+int launch_ltm_density_matrix(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, PlaneView W, int nE, double* out_host);
 // Orbit map of an unfolded rule: node_of[x] = the node k of the list idx [d][nk] that is x or its first image under syms that
 // is a node; rank [npt^d] is scratch; *missing_dev counts the points without one (their node_of is -1).  Launches only.
 int launch_ltm_orbit_map(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, const int32_t* idx, int64_t nk, int32_t* rank,

@@ -2429,6 +2429,37 @@ int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out) try {
     return launch_ltm_node_weights_dot(ctx, r->s->n, r->npt, r->ntiles, r->NW, r->ltm_nodew_nE, r->A, r->ltm_ncomp, out);
 } ABZ_CATCH_ALL
 
+// rho_pq(E_i) from the resident weights and U(k) in one eigen-solve (kernels_ltm_dens.hip).  Nothing is attached and nothing
+// replaced: the rule's blocks are read only.  H(k) as in ltm_eigvec_attach: the rule's own planes, or a transient H-only rule.
+int abz_rule_ltm_density_matrix(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_density_matrix: null out");
+    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_density_matrix", "density matrices"))) return rc;
+    abz_series* s = r->s;
+    const int n = s->n;
+    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_density_matrix: the rule holds no integration weights (abz_rule_ltm_node_weights; "
+                                "abz_rule_rebuild drops them)");
+    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
+                "abz_rule_ltm_density_matrix: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
+    abz_ctx* ctx = s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: U = 1, no H needed)
+    if (!r->H.base && n > 1) {
+        abz_rule* built = nullptr;
+        if ((rc = rule_build(s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
+        tmp.reset(built);
+    }
+    // (synchronises once, at the delivery of the sums: nothing reads the transient rule after it)
+    rc = launch_ltm_density_matrix(ctx, n, r->npt, r->ntiles, tmp ? tmp->H : r->H, r->NW, r->ltm_nodew_nE, out);
+    if (tmp) {
+        if (rc) (void)hipStreamSynchronize(ctx->stream);  // a failure may have left launches behind
+        tmp.reset();
+        series_release(s);
+    }
+    return rc;
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out) try {
     int rc = check_rule(r);
     if (rc) return rc;

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib as L
 from .bz import SymmetricBZ
-from .series import FourierSeries
+from .series import FourierSeries, density_matrix_orbitals
 from .solver import NullParameters, checkkwargs
 
 
@@ -389,6 +389,43 @@ def integration_weights(prob_or_cache, E=None, nstates=None, kind="states", corr
     if fold:
         W = rule.ltm_node_weights_fold()
     return (W[0], float(Es[0])) if scalar else (W, Es)
+
+
+def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correction=False, orbitals=None):
+    """(rho, E): the density matrix rho_pq(E) = sum_k sum_b w_b(k; E) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
+    on the grid of an LTM cache or of a DOSProblem (solved with LTM()), and the energies it belongs to
+    (DeviceRule.ltm_density_matrix: Bloechl's weights contracted with the eigenvectors inside one eigen-solve of the grid).
+    Exactly one of `E` (at most 16 energies; rho is complex128 [nE, m, m], [m, m] for a scalar) and `nstates` (rho [m, m] at
+    `fermi_level`'s energy on the same rule: the occupation matrix of that filling, tr rho = nstates) is given.  `kind`:
+    "states" (occupations) or "dos" (the spectral-density matrix, tr rho = g(E)); `correction=True` (with "states") adds
+    Bloechl's curvature correction.  `orbitals` (None: all n) selects the sub-block.  The cache's attached elements stay as
+    they are; the rule's resident integration weights are replaced by those of E."""
+    if (E is None) == (nstates is None):
+        raise ValueError("density_matrix: give exactly one of E and nstates")
+    if kind not in ("states", "dos"):
+        raise ValueError(f"density_matrix: kind = {kind!r} is neither 'states' nor 'dos'")
+    if correction and kind != "states":
+        raise ValueError("density_matrix: correction=True corrects the state sum: it needs kind='states' (the DOS has no correction)")
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries):
+        density_matrix_orbitals(orbitals, H.n, "density_matrix")
+        if _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+            raise NotImplementedError("density_matrix on a k-sharded series is not implemented: a node's weight needs its whole "
+                                      "neighbourhood, which a slab with its halo plane does not hold")
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    if not isinstance(c.alg, LTM):
+        raise ValueError("density_matrix needs an LTM cache")
+    if c.alg.symmetric and c.p.syms is not None and len(c.p.syms) > 1:
+        raise ValueError("density_matrix needs symmetric=False (band projectors are not invariant under the zone's symmetries, and "
+                         "an unfolded rule stores no H(k))")
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    scalar = nstates is not None or np.ndim(E) == 0
+    Es = np.array([fermi_level(c, nstates)[0]]) if nstates is not None else np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
+    rho = c.cacheval.ltm_density_matrix(Es, states=kind == "states", correction=bool(correction), orbitals=orbitals)
+    return (rho[0], float(Es[0])) if scalar else (rho, Es)
 
 
 def solve(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):

@@ -384,6 +384,19 @@ def symptr_rule(npt, d, syms, ctx=None):
     return idx, w
 
 
+def density_matrix_orbitals(orbitals, n, who="ltm_density_matrix"):
+    """The orbital selection of a density matrix as an index array (None: all n); ValueError as in ltm_green_matrix, and for an
+    index outside 0..n-1 (the sub-block is cut on the host: no device call would refuse it)."""
+    orb = np.arange(n) if orbitals is None else np.asarray(orbitals).reshape(-1)
+    if orb.size < 1 or not np.issubdtype(orb.dtype, np.integer):
+        raise ValueError(f"{who}: orbitals = {orbitals!r} is not a sequence of orbital indices")
+    if len(set(orb.tolist())) != len(orb):
+        raise ValueError(f"{who}: orbitals = {orbitals!r} names an orbital twice")
+    if orb.min() < 0 or orb.max() >= n:
+        raise ValueError(f"{who}: orbitals = {orbitals!r} outside 0..{n - 1}")
+    return orb
+
+
 class DeviceRule:
     """abz_rule handle: FourierPTR (syms None) or FourierMonkhorstPack values resident in HBM.
     ref: src/fourier.jl:127-174,210-277."""
@@ -835,6 +848,30 @@ class DeviceRule:
         out = np.zeros((nE, self._ltm_ncomp))
         L.check(L.lib().abz_rule_ltm_node_weights_dot(h, out.ctypes.data_as(L.c_f64p)))
         return out
+
+    def ltm_density_matrix(self, Es=None, states=True, correction=False, orbitals=None):
+        """The density matrix rho_pq(E) = sum_k sum_b w_b(k; E) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
+        complex128 [nE, m, m] (abz_rule_ltm_density_matrix): the resident weights of `ltm_node_weights` contracted with the
+        eigenvectors inside one eigen-solve of the grid; U(k) and the band projectors never reach memory.  With `Es` the
+        weights are made first (`ltm_node_weights(Es, states, correction, export=False)`, at most 16 energies); with
+        `Es=None` the resident ones are used, and they say what rho is: the occupation matrix (`states`), the corrected one
+        (`correction`) or the spectral-density matrix (`states=False`).  Hermitian to the bit; tr rho is N(E) or g(E); two
+        calls return the same bits.  `orbitals` (None: all n) selects the sub-block rho[orbitals][:, orbitals] on the host.
+        Nothing is attached: elements and weights stay as they were.  1...32 bands, a whole periodic grid with H(k) (not an
+        unfolded rule); a k-sharded rule raises NotImplementedError."""
+        self._ltm_refuse_shard("ltm_density_matrix")
+        n = self.dev.s.n
+        orb = density_matrix_orbitals(orbitals, n)
+        if Es is not None:
+            self.ltm_node_weights(Es, states=states, correction=correction, export=False)
+        h = self.h  # (a stale rule is refilled here, which drops the weights it held)
+        _, _, nE = self.ltm_node_weights_ptr()
+        if nE < 1:
+            raise ValueError("ltm_density_matrix: the rule holds no weights (give Es, or call ltm_node_weights; a rebuild of the "
+                             "rule drops them)")
+        out = np.zeros((nE, n, n), dtype=np.complex128)
+        L.check(L.lib().abz_rule_ltm_density_matrix(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
+        return out if orbitals is None else np.ascontiguousarray(out[:, orb][:, :, orb])
 
     def ltm_fermi(self, nstates, tol=1e-10):
         """(E_F, N(E_F)): the Fermi level of `nstates` states per unit cell, 0 < nstates < n, to within `tol`

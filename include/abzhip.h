@@ -448,6 +448,25 @@ int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out /* [nE][ncomp] */);
  * map is made at the first call and kept (8 B per node, 4 B per grid point, counted by abz_mem_info).  No floating-point atomics:
  * two calls return the same bits.  ABZ_ERR_ARG: a rule that was not unfolded, no resident weights, out == NULL. */
 int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out /* [nE][nirr][n] */);
+/* The density matrix in the orbital basis from the resident weights and the eigenvectors U(k) of Hermitian(H(k)), bands ascending:
+ *      rho_pq(E_i) = sum_k sum_b w_b(k; E_i) U_pb(k) conj(U_qb(k)),      out [nE][n][n][2], per unit cell,
+ * for the nE energies of the last abz_rule_ltm_node_weights call, whose `what` says what rho is: the occupation matrix
+ * (ABZ_LTM_STATES; ABZ_LTM_STATES_CORRECTED: with the curvature correction) or the spectral-density matrix (ABZ_LTM_DOS).  The
+ * call takes no energies of its own, like abz_rule_ltm_node_weights_dot.  tr rho = N(E) (g(E)); rho = 0.0 exactly below the
+ * bands and I above them (ABZ_LTM_STATES).  One eigen-solve per node (and per group of up to 4 energies for 1...4 bands, per
+ * energy for 5...32): neither U nor the band projectors reach HBM, where abz_rule_ltm_projectors in groups of
+ * ABZ_LTM_MAX_COMP components + abz_rule_ltm_node_weights_dot repeats the solve of the whole grid for every group.  The upper
+ * triangle is summed in a fixed order without atomics (two calls return the same bits) and the lower one is filled as its exact
+ * conjugate: out is Hermitian to the bit.  No phase of an eigenvector changes rho; at a degenerate level U holds some
+ * orthonormal basis of the eigenspace, and rho is defined as far as the weights of the level's bands agree (the tetrahedron
+ * weights of exactly degenerate bands do).
+ * H(k) is read from the rule when it holds it (either layout), else from a transient rule of the series' CURRENT coefficients
+ * that lives for the call, as for abz_rule_ltm_orbitals.  Attached elements and the resident weights are left as they were, on
+ * success and on failure; one synchronisation; the results leave through the pinned mailbox.
+ * ABZ_ERR_ARG: out == NULL, no resident weights, a rule without eigenvalues, a series that is not Hermitian.
+ * ABZ_ERR_UNSUPPORTED: more than 32 bands, a rule of abz_rule_ltm_unfold (no H(k) at every grid point), slabs with or without a
+ * halo, lists of irreducible nodes, symmetric rules.  Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_density_matrix(abz_rule* r, double* out /* [nE][n][n][2] */);
 
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.

@@ -581,6 +581,26 @@ function ltm_green_matrix(r::HIPRule, zs::Vector{ComplexF64}, n::Integer; orbita
     return G
 end
 
+"""
+    ltm_density_matrix(r, n; orbitals=1:n)     -> Array{ComplexF64,3} [m, m, nE]
+
+The density matrix `rho[p, q](E) = sum_k sum_b w_b(k; E) U[p, b](k) conj(U[q, b](k))` on the listed orbitals of an `n`-band rule,
+per unit cell, at the energies of the rule's resident integration weights (`abz_rule_ltm_density_matrix`): the weights of the
+last `abz_rule_ltm_node_weights` call contracted with the eigenvectors inside one eigen-solve of the grid.  Those weights say
+what `rho` is: occupations, corrected occupations or the spectral-density matrix.  Hermitian to the bit; nothing is attached.
+"""
+function ltm_density_matrix(r::HIPRule, n::Integer; orbitals::AbstractVector{<:Integer}=1:n)
+    allunique(orbitals) || throw(ArgumentError("ltm_density_matrix: orbitals names an orbital twice"))
+    all(o -> 1 <= o <= n, orbitals) || throw(ArgumentError("ltm_density_matrix: orbitals outside 1:$n"))
+    nE = Ref{Cint}(0)
+    check(ccall((:abz_rule_ltm_node_weights_ptr, libabz), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Cint}), r.h, C_NULL, C_NULL, nE))
+    nE[] >= 1 || throw(ArgumentError("ltm_density_matrix: the rule holds no integration weights (abz_rule_ltm_node_weights)"))
+    out = Array{ComplexF64}(undef, n, n, nE[])  # the library's [nE][p][q] is column-major [q, p, iE]
+    GC.@preserve out check(ccall((:abz_rule_ltm_density_matrix, libabz), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}), r.h, out))
+    rho = permutedims(out, (2, 1, 3))
+    return rho[orbitals, orbitals, :]
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
