@@ -66,6 +66,11 @@ PROTOTYPES = {
     "abz_rule_ltm_node_weights_dot": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_rule_ltm_node_weights_fold": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_rule_ltm_density_matrix": (C.c_int, [C.c_void_p, c_f64p]),
+    "abz_rule_ltm_green_node_weights": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
+    "abz_rule_ltm_green_node_weights_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p, c_ip]),
+    "abz_rule_ltm_green_node_weights_dot": (C.c_int, [C.c_void_p, c_f64p]),
+    "abz_rule_ltm_green_node_weights_fold": (C.c_int, [C.c_void_p, c_f64p]),
+    "abz_rule_ltm_green_node_weights_matrix": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_mem_info": (C.c_int, [C.c_void_p, c_i64p]),
     "abz_symptr_rule": (C.c_int, [C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
     "abz_symptr_rule_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p]),
@@ -95,6 +100,7 @@ LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
 LTM_MAX_COMP = 16
 LTM_NODEW_MAX_E = 16
+LTM_GREEN_NODEW_MAX_Z = 8
 PIVOT_NONE, PIVOT_PARTIAL = 0, 1  # abz_series_set_pivoting
 ERR_ARG, ERR_HIP, ERR_NOGPU, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 

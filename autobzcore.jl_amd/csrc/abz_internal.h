@@ -307,6 +307,11 @@ struct abz_rule {
     abz::DevBuf ltm_nodew;
     int ltm_nodew_nE = 0;
     abz::PlaneView NW;       // view of ltm_nodew
+    // complex weights of abz_rule_ltm_green_node_weights: double [ntiles][2 ltm_gnodew_nz * n planes][row], plane (2 i + part) n + b =
+    // Re / Im of band b at z_i; a block of its own with the lifetime of ltm_nodew, untouched by the real weights' calls
+    abz::DevBuf ltm_gnodew;
+    int ltm_gnodew_nz = 0;
+    abz::PlaneView GW;       // view of ltm_gnodew
     // symmetric rules: double [nk] weights and int32 [d][nk] grid indices; of a device-built rule, views into the plan's arena
     abz::DevBuf w, idx;
     std::unique_ptr<abz::RulePlan> plan;  // (api.cpp): contraction plan + phase table, device resident
@@ -563,6 +568,9 @@ int launch_ltm_unfold(abz_ctx* ctx, PlaneView src, PlaneView dst, const int32_t*
 // plane i n + b = w_b(k; Es_host[i]), padding columns zero; 1 <= nE <= ABZ_LTM_NODEW_MAX_E.  Launches only.
 int launch_ltm_node_weights(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView W, const double* Es_host, int nE, int what);
 // out_host [nE][ncomp] = sum_k sum_b w_b(k; E_i) A_{c,b}(k), A an element block of ncomp components; one synchronisation
+// The complex weights of the Green's function (kernels_ltm_green_nodew.hip).  W: 2 nz n planes tiled like the eigenvalue planes with
+// pitch = row, plane (2 i + part) n + b; z_host [nz][2] with Im z != 0.  Launches only.
+int launch_ltm_green_node_weights(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView W, const double* z_host, int nz);
 int launch_ltm_node_weights_dot(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView W, int nE, PlaneView A, int ncomp, double* out_host);
 // host: the inverse of an orbit map node_of [N] with entries inside 0 .. nirr-1: start [nirr + 1], member [N] (ascending per orbit)
 void ltm_orbit_inverse(const int32_t* node_of, int64_t N, int64_t nirr, std::vector<int64_t>& start, std::vector<int32_t>& member);

@@ -1021,10 +1021,14 @@ static void rule_drop_ltm_elements(abz_rule* r) {
     r->A = PlaneView();
 }
 
+// both weight blocks: the real ones of abz_rule_ltm_node_weights and the complex ones of abz_rule_ltm_green_node_weights
 static void rule_drop_ltm_node_weights(abz_rule* r) {
     r->ltm_nodew = DevBuf();
     r->ltm_nodew_nE = 0;
     r->NW = PlaneView();
+    r->ltm_gnodew = DevBuf();
+    r->ltm_gnodew_nz = 0;
+    r->GW = PlaneView();
 }
 
 int abz_rule_destroy(abz_rule* r) try {
@@ -1452,7 +1456,7 @@ int abz_rule_rebuild(abz_rule* r) try {
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     RulePlan* rp = r->plan.get();
-    if (r->ltm_elems.p || r->ltm_nodew.p) {  // matrix elements and integration weights described the old eigenstates
+    if (r->ltm_elems.p || r->ltm_nodew.p || r->ltm_gnodew.p) {  // matrix elements and integration weights described the old eigenstates
         ABZ_HIP(hipStreamSynchronize(ctx->stream));
         rule_drop_ltm_elements(r);
         rule_drop_ltm_node_weights(r);
@@ -2460,27 +2464,23 @@ int abz_rule_ltm_density_matrix(abz_rule* r, double* out) try {
     return rc;
 } ABZ_CATCH_ALL
 
-int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_node_weights_fold: null out");
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights_fold"))) return rc;
-    ABZ_REQUIRE(r->node_of.p, "abz_rule_ltm_node_weights_fold: the rule was not made by abz_rule_ltm_unfold: it has no orbits to fold over");
-    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_node_weights_fold: the rule holds no integration weights (abz_rule_ltm_node_weights; a new "
-                                "gather drops them)");
+// out [nE][nirr][n] <- the orbit sums of the nE real weight sets of the block W of an unfolded rule.  The inverse of the orbit map
+// is made once per rule (the map does not change with the values) and serves the real and the complex weights.
+static int ltm_fold_sets(abz_rule* r, const char* who, PlaneView W, int nE, double* out) {
+    int rc = ABZ_OK;
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = r->s->n, nE = r->ltm_nodew_nE;
+    const int n = r->s->n;
     const int64_t N = r->nk, nirr = r->unfold_nk;
     const size_t start_bytes = sizeof(int64_t) * ((size_t)nirr + 1);
-    if (!r->unfold_inv.p) {  // once per rule: the map does not change with the values
+    if (!r->unfold_inv.p) {
         std::vector<int32_t> node_of((size_t)N), member;
         std::vector<int64_t> start;
         if ((rc = stage_d2h(ctx, node_of.data(), r->node_of.p, sizeof(int32_t) * (size_t)N))) return rc;
         for (int64_t x = 0; x < N; ++x)
             if (node_of[(size_t)x] < 0 || node_of[(size_t)x] >= nirr) {
-                set_error("abz_rule_ltm_node_weights_fold: the orbit map names node %d at grid point %lld (the source has %lld nodes)",
-                          node_of[(size_t)x], (long long)x, (long long)nirr);
+                set_error("%s: the orbit map names node %d at grid point %lld (the source has %lld nodes)", who, node_of[(size_t)x],
+                          (long long)x, (long long)nirr);
                 return ABZ_ERR_INTERNAL;
             }
         ltm_orbit_inverse(node_of.data(), N, nirr, start, member);
@@ -2494,8 +2494,172 @@ int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out) try {
     if ((rc = ctx->scratch[3].reserve(obytes))) return rc;
     const int64_t* start_dev = r->unfold_inv.as<int64_t>();
     const int32_t* member_dev = reinterpret_cast<const int32_t*>(static_cast<const char*>(r->unfold_inv.p) + start_bytes);
-    if ((rc = launch_ltm_node_weights_fold(ctx, n, r->NW, nE, start_dev, member_dev, nirr, ctx->scratch[3].as<double>()))) return rc;
+    if ((rc = launch_ltm_node_weights_fold(ctx, n, W, nE, start_dev, member_dev, nirr, ctx->scratch[3].as<double>()))) return rc;
     return stage_d2h(ctx, out, ctx->scratch[3].p, obytes);
+}
+
+int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_node_weights_fold: null out");
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights_fold"))) return rc;
+    ABZ_REQUIRE(r->node_of.p, "abz_rule_ltm_node_weights_fold: the rule was not made by abz_rule_ltm_unfold: it has no orbits to fold over");
+    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_node_weights_fold: the rule holds no integration weights (abz_rule_ltm_node_weights; a new "
+                                "gather drops them)");
+    return ltm_fold_sets(r, "abz_rule_ltm_node_weights_fold", r->NW, r->ltm_nodew_nE, out);
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_green_node_weights_fold(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_green_node_weights_fold: null out");
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights_fold"))) return rc;
+    ABZ_REQUIRE(r->node_of.p, "abz_rule_ltm_green_node_weights_fold: the rule was not made by abz_rule_ltm_unfold: it has no orbits to fold over");
+    ABZ_REQUIRE(r->ltm_gnodew.p, "abz_rule_ltm_green_node_weights_fold: the rule holds no complex integration weights "
+                                 "(abz_rule_ltm_green_node_weights; a new gather drops them)");
+    // [2 nz][nirr][n] of the real sets -> [nz][nirr][n][2]
+    const int nz = r->ltm_gnodew_nz;
+    const size_t per = (size_t)r->unfold_nk * (size_t)r->s->n;
+    std::vector<double> sets((size_t)2 * nz * per);
+    if ((rc = ltm_fold_sets(r, "abz_rule_ltm_green_node_weights_fold", r->GW, 2 * nz, sets.data()))) return rc;
+    for (int i = 0; i < nz; ++i)
+        for (size_t x = 0; x < per; ++x) {
+            out[2 * ((size_t)i * per + x)] = sets[(size_t)(2 * i) * per + x];
+            out[2 * ((size_t)i * per + x) + 1] = sets[(size_t)(2 * i + 1) * per + x];
+        }
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+// Complex integration weights W_b(k; z) of the Green's function per node and band (kernels_ltm_green_nodew.hip), resident in a
+// block of their own: 2 nz real weight sets to the dot, the fold and the density-matrix contraction, which are launched as they
+// are.  As for the real weights the new block is complete before it replaces the resident one.
+int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z, int nz, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(z, "abz_rule_ltm_green_node_weights: null z");
+    ABZ_REQUIRE(nz >= 1 && nz <= ABZ_LTM_GREEN_NODEW_MAX_Z, "abz_rule_ltm_green_node_weights: nz = %d outside 1..%d", nz,
+                ABZ_LTM_GREEN_NODEW_MAX_Z);
+    for (int i = 0; i < nz; ++i) {
+        const double re = z[2 * (size_t)i], im = z[2 * (size_t)i + 1];
+        ABZ_REQUIRE(std::isfinite(re) && std::isfinite(im), "abz_rule_ltm_green_node_weights: z[%d] = (%g, %g) is not finite", i, re, im);
+        ABZ_REQUIRE(im != 0.0, "abz_rule_ltm_green_node_weights: z[%d] = %g is real; G is computed off the real axis (Im z != 0)", i, re);
+    }
+    // (no slab_ok: a node needs the plane BEFORE it as well, which a halo does not give)
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights"))) return rc;
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = r->s->n;
+    const int planes = 2 * nz * n;
+    DevBuf block;
+    if ((rc = block.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row))) return rc;
+    PlaneView W = r->E;  // the tiling of the eigenvalue planes: same rows, same lines, 2 nz n planes per tile
+    W.base = block.as<double>();
+    W.tile = (int64_t)planes * r->E.row;
+    W.pitch = r->E.row;
+    W.compact = 0;
+    rc = launch_ltm_green_node_weights(ctx, n, r->s->d, r->npt, r->E, W, z, nz);
+    if (!rc && out) {
+        // one real set [nk][n] at a time through the staging of the export, interleaved on the host
+        std::vector<double> part((size_t)r->nk * (size_t)n);
+        for (int i = 0; i < 2 * nz && !rc; ++i) {
+            PlaneView v = W;
+            v.base += (int64_t)i * n * v.pitch;
+            rc = export_planes(ctx, v, n, r->nk, part.data());
+            double* o = out + (size_t)(i >> 1) * part.size() * 2 + (size_t)(i & 1);
+            for (size_t x = 0; x < part.size() && !rc; ++x) o[2 * x] = part[x];
+        }
+    }
+    // the block is complete, and nothing reads the old one any more
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_green_node_weights: the kernel failed");
+        rc = ABZ_ERR_HIP;
+    }
+    if (rc) return rc;
+    r->ltm_gnodew = std::move(block);  // (the previous complex weights go here)
+    r->ltm_gnodew_nz = nz;
+    r->GW = W;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nz) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    const bool have = r->ltm_gnodew.p != nullptr;
+    if (base) *base = r->ltm_gnodew.p;
+    if (nbytes)
+        *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * 2 * (size_t)r->ltm_gnodew_nz * (size_t)r->s->n * (size_t)r->GW.row) : 0;
+    if (nz) *nz = have ? r->ltm_gnodew_nz : 0;
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_green_node_weights_dot(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_green_node_weights_dot: null out");
+    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights_dot"))) return rc;
+    ABZ_REQUIRE(r->ltm_gnodew.p, "abz_rule_ltm_green_node_weights_dot: the rule holds no complex integration weights "
+                                 "(abz_rule_ltm_green_node_weights; abz_rule_rebuild drops them)");
+    ABZ_REQUIRE(r->ltm_elems.p, "abz_rule_ltm_green_node_weights_dot: no matrix elements are attached (abz_rule_ltm_elements, "
+                                "abz_rule_ltm_orbitals, abz_rule_ltm_projectors)");
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    // [2 nz][ncomp] of the real sets is [nz][Re, Im][ncomp]
+    const int nz = r->ltm_gnodew_nz, ncomp = r->ltm_ncomp;
+    std::vector<double> sets((size_t)2 * nz * ncomp);
+    if ((rc = launch_ltm_node_weights_dot(ctx, r->s->n, r->npt, r->ntiles, r->GW, 2 * nz, r->A, ncomp, sets.data()))) return rc;
+    for (int i = 0; i < nz; ++i)
+        for (int c = 0; c < ncomp; ++c) {
+            out[2 * ((size_t)i * ncomp + c)] = sets[(size_t)(2 * i) * ncomp + c];
+            out[2 * ((size_t)i * ncomp + c) + 1] = sets[(size_t)(2 * i + 1) * ncomp + c];
+        }
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+// G_pq(z_i) from the resident complex weights and U(k): the contraction of abz_rule_ltm_density_matrix over the 2 nz real sets,
+// X = rho[Re W] and Y = rho[Im W] paired on the host.  Nothing is attached and nothing replaced.
+int abz_rule_ltm_green_node_weights_matrix(abz_rule* r, double* out) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_green_node_weights_matrix: null out");
+    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_green_node_weights_matrix", "Green's function matrices"))) return rc;
+    abz_series* s = r->s;
+    const int n = s->n;
+    ABZ_REQUIRE(r->ltm_gnodew.p, "abz_rule_ltm_green_node_weights_matrix: the rule holds no complex integration weights "
+                                 "(abz_rule_ltm_green_node_weights; abz_rule_rebuild drops them)");
+    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
+                "abz_rule_ltm_green_node_weights_matrix: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of "
+                "a Hermitian H(k)");
+    abz_ctx* ctx = s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: U = 1, no H needed)
+    if (!r->H.base && n > 1) {
+        abz_rule* built = nullptr;
+        if ((rc = rule_build(s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
+        tmp.reset(built);
+    }
+    const int nz = r->ltm_gnodew_nz;
+    const size_t nn = (size_t)n * (size_t)n;
+    std::vector<double> sets((size_t)2 * nz * nn * 2);  // [2 nz][n][n][2]: X(z_0), Y(z_0), X(z_1), ...
+    // (synchronises once, at the delivery of the sums: nothing reads the transient rule after it)
+    rc = launch_ltm_density_matrix(ctx, n, r->npt, r->ntiles, tmp ? tmp->H : r->H, r->GW, 2 * nz, sets.data());
+    if (tmp) {
+        if (rc) (void)hipStreamSynchronize(ctx->stream);  // a failure may have left launches behind
+        tmp.reset();
+        series_release(s);
+    }
+    if (rc) return rc;
+    // X and Y are Hermitian as they come (the lower triangle the exact conjugate of the upper): entry (p, q) of either triangle
+    // is X_pq + i Y_pq, which is conj(X) + i conj(Y) of the mirrored entry
+    for (int i = 0; i < nz; ++i) {
+        const double* X = sets.data() + (size_t)(2 * i) * nn * 2;
+        const double* Y = X + nn * 2;
+        double* o = out + (size_t)i * nn * 2;
+        for (size_t e = 0; e < nn; ++e) {
+            o[2 * e] = X[2 * e] - Y[2 * e + 1];
+            o[2 * e + 1] = X[2 * e + 1] + Y[2 * e];
+        }
+    }
+    return ABZ_OK;
 } ABZ_CATCH_ALL
 
 // One eigenvalue per band is a scalar that the zone's symmetries leave alone, e_b(S k) = e_b(k): the planes of the whole grid
@@ -2529,7 +2693,7 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
                     r->npt, (long long)r->unfold_nk, npt, (long long)src->nk);
         ABZ_REQUIRE(r->unfold_syms.size() == (size_t)nsyms * d * d && std::equal(r->unfold_syms.begin(), r->unfold_syms.end(), syms),
                     "abz_rule_ltm_unfold: *out was unfolded under another symmetry set (its orbit map does not fit these %d matrices)", nsyms);
-        if (r->ltm_elems.p || r->ltm_nodew.p) {  // matrix elements and integration weights described the old eigenstates
+        if (r->ltm_elems.p || r->ltm_nodew.p || r->ltm_gnodew.p) {  // matrix elements and integration weights described the old eigenstates
             ABZ_HIP(hipStreamSynchronize(ctx->stream));
             rule_drop_ltm_elements(r);
             rule_drop_ltm_node_weights(r);

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib as L
 from .bz import SymmetricBZ
-from .series import FourierSeries, density_matrix_orbitals
+from .series import FourierSeries, density_matrix_orbitals, green_node_weight_zs
 from .solver import NullParameters, checkkwargs
 
 
@@ -320,27 +320,97 @@ def green_weighted(prob_or_cache, zs):
     return c.cacheval.ltm_green(zs, elements=el if isinstance(el, str) else "attached")
 
 
+def _green_local_check(c, who):
+    if not isinstance(c.alg, LTM):
+        raise ValueError(f"{who} needs an LTM cache")
+    if c.alg.symmetric and c.p.syms is not None and len(c.p.syms) > 1:
+        raise ValueError(f"{who} needs symmetric=False (band projectors are not invariant under the zone's symmetries, and "
+                         "an unfolded rule stores no H(k))")
+
+
+def _green_local(prob_or_cache, zs, orbitals, fused):
+    who = "green_local_fused" if fused else "green_local"
+    if fused and isinstance(prob_or_cache, DOSCache):  # (a cache says what it is without its series' device being asked)
+        _green_local_check(prob_or_cache, who)
+    H = getattr(prob_or_cache, "H", None)
+    if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
+        raise NotImplementedError(f"{who} on a k-sharded series is not implemented: the Green's function is computed on "
+                                  "whole grids")
+    c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
+    _green_local_check(c, who)
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+    if fused:
+        return c.cacheval.ltm_green_node_weights_matrix(zs, orbitals)
+    return c.cacheval.ltm_green_matrix(zs, orbitals)
+
+
 def green_local(prob_or_cache, zs, orbitals=None):
     """The local Green's function G_pq(z) = [int dk inv(z - H(k))]_pq on the orbitals `orbitals` (None: all n) at the complex
     energies `zs` (Im z != 0), per unit cell, complex128 [nz, m, m], on the grid of an LTM cache or of a DOSProblem (solved
     with LTM()): DeviceRule.ltm_green_matrix, the band projectors U_pb conj(U_qb) as elements of the tetrahedron method.  Its
     diagonal is `green_weighted` with orbital weights, its trace `green_trace`.  The cache's own elements are attached again by
-    its next solve."""
+    its next solve.
+    `green_local_fused` computes the same matrix from the complex node weights W_b(k; z) and U(k) without attaching projectors.
+    Crossover (measured on an MI355X, profiles/ltm_green_node_weights.txt): none in the number of z.  With ONE projector group of
+    16 components (up to 4 orbitals) the two routes are close, `green_local_fused` 1.25 times faster at one z and 1.05 times at 8
+    and 64 values (3 bands 48^3); with more groups it is faster at every number of z, 16...26 times for 16 bands (16 groups, 24^3)
+    and 27...55 times for 32 bands (64 groups, 16^3).  What this route keeps: it needs no weight block of 16 nz n bytes per node."""
+    return _green_local(prob_or_cache, zs, orbitals, False)
+
+
+def green_local_fused(prob_or_cache, zs, orbitals=None):
+    """`green_local` by the other route (DeviceRule.ltm_green_node_weights_matrix): the complex integration weights W_b(k; z)
+    are gathered per node, 8 values of z at a time, and contracted with the eigenvectors by the kernel of `density_matrix`;
+    no projector is attached and the cache's elements stay as they are.  Same solver, same basis, same arguments and refusals;
+    the two routes agree to rounding, not to the bit.
+    Cost: `green_local` repeats the eigen-solve of the grid and a scan of the simplices once per group of 16 projector
+    components (1 group up to 4 orbitals, 16 for 16, 64 for 32); this route gathers the weights once per z ((d+1) times the
+    simplices of a scan, one series per simplex where it is narrow) and solves the grid once per 4 weight sets for 1...4 bands,
+    twice per z for 5...32 bands.  Measured (profiles/ltm_green_node_weights.txt): 1.25 times faster than `green_local` for 3
+    bands at one z and 1.05 times at 8 and 64; 16...26 times faster for 16 bands and 27...55 times for 32 bands at 64...1 values.
+    It holds a weight block of 16 nz n bytes per node (8 values at a time) that `green_local` does not need."""
+    return _green_local(prob_or_cache, zs, orbitals, True)
+
+
+def green_weights(prob_or_cache, zs, fold=False):
+    """(W, zs): the complex integration weights W_b(k; z) of the Green's function on the grid of an LTM cache, or of a DOSProblem
+    (solved with LTM()), and the values of z they belong to: G_A(z) = sum_k sum_b W_b(k; z) A_b(k) for ANY A, complex or
+    matrix-valued (DeviceRule.ltm_green_node_weights).  At most 8 values, Im z != 0; W is complex128 [nz, nk, n], [nk, n] for a
+    scalar z.  Nodes and bands are ordered like the eigenvalues of the cache's rule (`cache.cacheval.export(eig=True)`).  With
+    `LTM(symmetric=True)` on a symmetric zone and `fold=True` the weights come back summed over orbits on the irreducible nodes
+    that were solved, [.., nirr, n] in the order of `cache.cacheval.source.export(eig=True)`: G_loc(z) is then a sum over
+    those nodes followed by the caller's own symmetrisation; anywhere else `fold=True` raises ValueError."""
+    scalar = np.ndim(zs) == 0
+    zs = green_node_weight_zs(zs, "green_weights")
+
+    def check(alg, p):
+        if not isinstance(alg, LTM):
+            raise ValueError("green_weights needs an LTM cache")
+        if fold and not (alg.symmetric and getattr(p, "syms", None) is not None and len(p.syms) > 1):
+            raise ValueError("green_weights: fold=True needs an LTM(symmetric=True) cache on a symmetric zone (nothing was unfolded)")
+
+    # (a cache says what it is, and a problem is solved with LTM(), without the series' device being asked)
+    if isinstance(prob_or_cache, DOSCache):
+        check(prob_or_cache.alg, prob_or_cache.p)
+    else:
+        check(LTM(), getattr(prob_or_cache, "p", None))
     H = getattr(prob_or_cache, "H", None)
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
-        raise NotImplementedError("green_local on a k-sharded series is not implemented: the Green's function is computed on "
-                                  "whole grids")
+        raise NotImplementedError("green_weights on a k-sharded series is not implemented: a node's weight needs its whole "
+                                  "neighbourhood, which a slab with its halo plane does not hold")
     c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
-    if not isinstance(c.alg, LTM):
-        raise ValueError("green_local needs an LTM cache")
-    if c.alg.symmetric and c.p.syms is not None and len(c.p.syms) > 1:
-        raise ValueError("green_local needs symmetric=False (band projectors are not invariant under the zone's symmetries, and "
-                         "an unfolded rule stores no H(k))")
     if c.isfresh:
         c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
-    return c.cacheval.ltm_green_matrix(zs, orbitals)
+    rule = c.cacheval
+    W = rule.ltm_green_node_weights(zs, export=not fold)
+    if fold:
+        W = rule.ltm_green_node_weights_fold()
+    return (W[0], complex(zs[0])) if scalar else (W, zs)
 
 
 def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):

@@ -397,6 +397,19 @@ def density_matrix_orbitals(orbitals, n, who="ltm_density_matrix"):
     return orb
 
 
+def green_node_weight_zs(zs, who="ltm_green_node_weights"):
+    """The values of z of one complex-weight call as a complex128 array; ValueError, before the library is called, for none or
+    more than 8 of them and for a real or non-finite one."""
+    zs = np.ascontiguousarray(np.asarray(zs, dtype=np.complex128).reshape(-1))
+    if not 1 <= len(zs) <= L.LTM_GREEN_NODEW_MAX_Z:
+        raise ValueError(f"{who}: {len(zs)} values of z, a call takes 1..{L.LTM_GREEN_NODEW_MAX_Z}")
+    if not (np.all(np.isfinite(zs.real)) and np.all(np.isfinite(zs.imag))):
+        raise ValueError(f"{who}: zs = {zs!r} holds a value that is not finite")
+    if np.any(zs.imag == 0.0):
+        raise ValueError(f"{who}: zs = {zs!r} holds a real value; G is computed off the real axis (Im z != 0)")
+    return zs
+
+
 class DeviceRule:
     """abz_rule handle: FourierPTR (syms None) or FourierMonkhorstPack values resident in HBM.
     ref: src/fourier.jl:127-174,210-277."""
@@ -873,6 +886,88 @@ class DeviceRule:
         L.check(L.lib().abz_rule_ltm_density_matrix(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out if orbitals is None else np.ascontiguousarray(out[:, orb][:, :, orb])
 
+    def ltm_green_node_weights(self, zs, export=True):
+        """The complex integration weights W_b(k; z) of the Green's function per grid point and band
+        (abz_rule_ltm_green_node_weights), complex128 [nz, nk, n] in the node and band order of export()'s eig: the numbers
+        with G_A(z) = sum_k sum_b W_b(k; z) A_b(k) for ANY A -- complex, matrix-valued, or not known yet -- where `ltm_green`
+        takes real elements attached before its scan.  At most 8 values per call, Im z != 0, in any order; Im z < 0 gives the
+        conjugate of the weights at conj z, to the bit; two calls return the same bits.  The weights also stay on the device in
+        a block of their own (the real weights of `ltm_node_weights` are untouched) until the next call, a rebuild of the rule
+        or `close`: `ltm_green_node_weights_dot` contracts them with attached elements, `ltm_green_node_weights_matrix` with
+        the eigenvectors, and `export=False` (returns None) skips the copy to the host.  The rule must be a whole periodic grid
+        (an unfolded rule is one); a k-sharded rule raises NotImplementedError, with or without its halo plane."""
+        self._ltm_refuse_shard("ltm_green_node_weights")
+        zs = green_node_weight_zs(zs)
+        h = self.h  # (a stale rule is refilled here, which drops the weights it held)
+        out = np.empty((len(zs), self.nk, self.dev.s.n), dtype=np.complex128) if export else None
+        L.check(L.lib().abz_rule_ltm_green_node_weights(h, zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs),
+                                                        out.view(np.float64).ctypes.data_as(L.c_f64p) if export else None))
+        return out
+
+    def ltm_green_node_weights_ptr(self):
+        """(device address, bytes, nz) of the resident block of `ltm_green_node_weights`; (0, 0, 0) when there is none."""
+        self._ltm_refuse_shard("ltm_green_node_weights_ptr")
+        base, nb, nz = C.c_void_p(), C.c_int64(0), C.c_int(0)
+        L.check(L.lib().abz_rule_ltm_green_node_weights_ptr(self.h, C.byref(base), C.byref(nb), C.byref(nz)))
+        return int(base.value or 0), int(nb.value), int(nz.value)
+
+    def ltm_green_node_weights_dot(self, elements="attached"):
+        """sum_k sum_b W_b(k; z_i) A_{c,b}(k) of the resident weights of `ltm_green_node_weights` as complex128 [nz, ncomp]
+        (abz_rule_ltm_green_node_weights_dot): `ltm_green(zs, elements="attached")` without another walk over the simplices.
+        `elements` as in `ltm_node_weights_dot`: "attached" or an array [ncomp, nk, n], attached first; attaching elements
+        leaves the weights in place."""
+        self._ltm_refuse_shard("ltm_green_node_weights_dot")
+        if isinstance(elements, str):
+            if elements != "attached":
+                raise ValueError(f"ltm_green_node_weights_dot: elements = {elements!r} is neither 'attached' nor an array")
+        else:
+            self.h  # (a stale rule is refilled first: it loses its weights, and the call below says so)
+            self.ltm_elements(elements)
+        h = self.h
+        _, _, nz = self.ltm_green_node_weights_ptr()
+        if nz < 1:
+            raise ValueError("ltm_green_node_weights_dot: the rule holds no weights (ltm_green_node_weights; a rebuild of the rule drops them)")
+        if self._ltm_ncomp < 1:
+            raise ValueError("ltm_green_node_weights_dot: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
+        out = np.zeros((nz, self._ltm_ncomp), dtype=np.complex128)
+        L.check(L.lib().abz_rule_ltm_green_node_weights_dot(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
+        return out
+
+    def ltm_green_node_weights_matrix(self, zs=None, orbitals=None):
+        """The local Green's function G_pq(z) = sum_k sum_b W_b(k; z) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
+        complex128 [nz, m, m] (abz_rule_ltm_green_node_weights_matrix): the resident weights of `ltm_green_node_weights`
+        contracted with the eigenvectors by the kernel of `ltm_density_matrix`; no projector is attached and attached elements
+        stay as they were.  With `zs` (any number) the weights are made first, in chunks of 8; with `zs=None` the resident ones
+        are used.  G(z)^dagger = G(conj z); two calls return the same bits.  `orbitals` (None: all n) selects the sub-block on
+        the host.  Against `ltm_green_matrix`, which repeats the eigen-solve of the grid once per group of 16 projector
+        components and scans the simplices per group: this route gathers the weights once per z and solves the grid once per 4
+        weight sets for 1...4 bands, twice per z for 5...32 (`abz.dos.green_local` has the measured crossover: the number of
+        projector groups).  1...32 bands, a whole periodic grid with H(k)
+        (not an unfolded rule); a k-sharded rule raises NotImplementedError."""
+        self._ltm_refuse_shard("ltm_green_node_weights_matrix")
+        n = self.dev.s.n
+        orb = density_matrix_orbitals(orbitals, n, "ltm_green_node_weights_matrix")
+        if zs is None:
+            chunks = [None]
+        else:
+            zs = np.ascontiguousarray(np.asarray(zs, dtype=np.complex128).reshape(-1))
+            step = L.LTM_GREEN_NODEW_MAX_Z
+            chunks = [green_node_weight_zs(zs[i:i + step], "ltm_green_node_weights_matrix") for i in range(0, max(len(zs), 1), step)]
+        parts = []
+        for chunk in chunks:
+            if chunk is not None:
+                self.ltm_green_node_weights(chunk, export=False)
+            h = self.h  # (a stale rule is refilled here, which drops the weights it held)
+            _, _, nz = self.ltm_green_node_weights_ptr()
+            if nz < 1:
+                raise ValueError("ltm_green_node_weights_matrix: the rule holds no weights (give zs, or call ltm_green_node_weights; a "
+                                 "rebuild of the rule drops them)")
+            out = np.zeros((nz, n, n), dtype=np.complex128)
+            L.check(L.lib().abz_rule_ltm_green_node_weights_matrix(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
+            parts.append(out)
+        G = parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0)
+        return G if orbitals is None else np.ascontiguousarray(G[:, orb][:, :, orb])
+
     def ltm_fermi(self, nstates, tol=1e-10):
         """(E_F, N(E_F)): the Fermi level of `nstates` states per unit cell, 0 < nstates < n, to within `tol`
         (abz_rule_ltm_fermi: a few N(E) scans of 512 energies each, no host bisection)."""
@@ -963,4 +1058,17 @@ class UnfoldedRule(DeviceRule):
             raise ValueError("ltm_node_weights_fold: the rule holds no weights (ltm_node_weights; a new gather drops them)")
         out = np.zeros((nE, len(self.source), self.dev.s.n))
         L.check(L.lib().abz_rule_ltm_node_weights_fold(h, out.ctypes.data_as(L.c_f64p)))
+        return out
+
+    def ltm_green_node_weights_fold(self):
+        """The resident weights of `ltm_green_node_weights` summed over each orbit onto the irreducible nodes of the source
+        rule, complex128 [nz, nirr, n] in the source's node order (abz_rule_ltm_green_node_weights_fold):
+        sum_j sum_b fold_b(j) A_b(j) is then the full-grid G_A(z) of any A that the zone's symmetries leave alone, from values
+        at the irreducible nodes only.  A sum over the orbit, not multiplicity x weight (`ltm_node_weights_fold`)."""
+        h = self.h
+        _, _, nz = self.ltm_green_node_weights_ptr()
+        if nz < 1:
+            raise ValueError("ltm_green_node_weights_fold: the rule holds no weights (ltm_green_node_weights; a new gather drops them)")
+        out = np.zeros((nz, len(self.source), self.dev.s.n), dtype=np.complex128)
+        L.check(L.lib().abz_rule_ltm_green_node_weights_fold(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out

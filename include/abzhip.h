@@ -468,6 +468,47 @@ int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out /* [nE][nirr][n] */)
  * halo, lists of irreducible nodes, symmetric rules.  Entry point added without a change of ABZ_VERSION. */
 int abz_rule_ltm_density_matrix(abz_rule* r, double* out /* [nE][n][n][2] */);
 
+/* The complex integration weights of the Green's function, per grid point and band: the numbers W_b(k; z) with
+ *      G_A(z) = sum_k sum_b W_b(k; z) A_b(k)
+ * for ANY A -- complex, matrix-valued, or not known when the weights are made -- on the mesh of abz_rule_ltm_green: what
+ * abz_rule_ltm_green_weighted forms inside its scan and contracts at once with real attached elements.
+ *      W_b(k; z) = w sum_{T contains k} W^T_{i(k)}(z),   w = 1 / (d! npt^d),   W^T_i = J[x_0 .. x_d, x_i](z) / (d + 1),
+ * over the (d+1)! Kuhn simplices that contain k (the geometry of abz_rule_ltm_node_weights), with the evaluation rule of
+ * abz_rule_ltm_green_weighted (rho = 1/2, Taylor series for narrow sub-ranges, principal logs of one half plane).
+ * z [nz][2] (re, im), 1 <= nz <= ABZ_LTM_GREEN_NODEW_MAX_Z, Im z != 0, in any order, duplicates allowed.  out [nz][nk][n][2]
+ * (or NULL: nothing is copied) is interleaved complex in the node and band order of abz_rule_export's eig.  Im z < 0: the
+ * conjugate of the value at conj(z), to the bit.  A gather without atomics: two calls write the same bits.
+ * The weights stay resident in HBM in a block of their own, 2 nz n planes tiled like the eigenvalue planes: plane
+ * (2 i + part) n + b of a grid line's tile is Re (part 0) or Im (part 1) of band b at z_i, padding columns zero -- 2 nz real
+ * weight sets to every consumer of a real weight block.  The block is separate from the one of abz_rule_ltm_node_weights:
+ * neither call touches the other's.  It lives as that one does: until the next call replaces it, abz_rule_rebuild, a new gather
+ * of abz_rule_ltm_unfold or abz_rule_destroy; attaching or dropping elements leaves it alone.  Counted by abz_mem_info.
+ * Takes full-grid rules and rules of abz_rule_ltm_unfold, d = 1...3, 1...64 bands.  ABZ_ERR_UNSUPPORTED: slabs, with or without
+ * a halo, lists of irreducible nodes, symmetric rules.  ABZ_ERR_ARG: a rule without eigenvalues, z == NULL, nz outside
+ * 1..ABZ_LTM_GREEN_NODEW_MAX_Z, any Im z == 0 or non-finite z.  A refusal or failure leaves both weight blocks and the attached
+ * elements as they were.  Entry points added without a change of ABZ_VERSION. */
+#define ABZ_LTM_GREEN_NODEW_MAX_Z 8   /* 2 nz real weight sets <= ABZ_LTM_NODEW_MAX_E */
+int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z /* [nz][2] */, int nz, double* out /* [nz][nk][n][2] or NULL */);
+/* The resident complex weights: device address, bytes and values of z of the block; NULL, 0, 0 when the rule holds none (any of
+ * the three pointers may be NULL). */
+int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nz);
+/* out [nz][ncomp][2] = sum_k sum_b W_b(k; z_i) A_{c,b}(k): the resident complex weights against the attached elements, i.e.
+ * abz_rule_ltm_green_weighted(r, ABZ_LTM_A_ELEMENTS, z, nz, out) without another walk over the simplices (the dot of
+ * abz_rule_ltm_node_weights_dot over the 2 nz real sets).  ABZ_ERR_ARG: no resident complex weights, nothing attached, out == NULL. */
+int abz_rule_ltm_green_node_weights_dot(abz_rule* r, double* out /* [nz][ncomp][2] */);
+/* For a rule of abz_rule_ltm_unfold: the resident complex weights summed over each orbit onto the nirr nodes of the source rule
+ * (the fold of abz_rule_ltm_node_weights_fold over the 2 nz real sets): sum_j sum_b fold_b(j) A_b(j) is the full-grid G_A(z) of
+ * every A that the zone's symmetries leave alone.  ABZ_ERR_ARG: a rule that was not unfolded, no resident complex weights,
+ * out == NULL. */
+int abz_rule_ltm_green_node_weights_fold(abz_rule* r, double* out /* [nz][nirr][n][2] */);
+/* The local Green's function in the orbital basis from the resident complex weights and the eigenvectors U(k):
+ *      G_pq(z_i) = sum_k sum_b W_b(k; z_i) U_pb(k) conj(U_qb(k)),      out [nz][n][n][2], per unit cell,
+ * by the contraction of abz_rule_ltm_density_matrix over the 2 nz real sets: with X = rho[Re W], Y = rho[Im W], both Hermitian,
+ * G_pq = X_pq + i Y_pq and G_qp = conj(X_pq) + i conj(Y_pq).  G is not Hermitian; G(z)^dagger = G(conj z).  Nothing is attached.
+ * H(k), refusals and codes as abz_rule_ltm_density_matrix (1...32 bands, not a rule of abz_rule_ltm_unfold, a Hermitian series);
+ * ABZ_ERR_ARG: no resident complex weights, out == NULL. */
+int abz_rule_ltm_green_node_weights_matrix(abz_rule* r, double* out /* [nz][n][n][2] */);
+
 /* Replaces: AutoSymPTR.symptr_rule as called at src/fourier.jl:271 (host, integer-exact).
  * syms [nsyms][d][d] row-major integer matrices acting on fractional coordinates.
  * First call with irr_idx = NULL to get *nirr; then with buffers irr_idx [nirr][d], wsym [nirr]. */

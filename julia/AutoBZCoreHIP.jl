@@ -601,6 +601,72 @@ function ltm_density_matrix(r::HIPRule, n::Integer; orbitals::AbstractVector{<:I
     return rho[orbitals, orbitals, :]
 end
 
+# values of z of the rule's resident complex weights (0: none)
+function ltm_green_node_weights_nz(r::HIPRule)
+    nz = Ref{Cint}(0)
+    check(ccall((:abz_rule_ltm_green_node_weights_ptr, libabz), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Cint}), r.h, C_NULL, C_NULL, nz))
+    return Int(nz[])
+end
+
+"""
+    ltm_green_node_weights!(r, zs, n; export_weights=true)  -> Array{ComplexF64,3} [n, nk, nz] or nothing
+
+The complex integration weights `W[b, k, i] = W_b(k; z_i)` of the Green's function of an `n`-band whole-grid rule
+(`abz_rule_ltm_green_node_weights`): `G_A(z) = sum_k sum_b W_b(k; z) A_b(k)` for any `A`.  At most 8 values, `imag(z) != 0`.  The
+weights stay resident on the rule for `ltm_green_node_weights_dot`, `_fold` and `_matrix`.
+"""
+function ltm_green_node_weights!(r::HIPRule, zs::Vector{ComplexF64}, n::Integer; export_weights::Bool=true)
+    1 <= length(zs) <= 8 || throw(ArgumentError("ltm_green_node_weights!: $(length(zs)) values of z, a call takes 1..8"))
+    out = export_weights ? Array{ComplexF64}(undef, n, r.nk, length(zs)) : nothing
+    GC.@preserve zs out check(ccall((:abz_rule_ltm_green_node_weights, libabz), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Cint, Ptr{ComplexF64}),
+                                    r.h, zs, length(zs), export_weights ? pointer(out) : C_NULL))
+    return out
+end
+
+"""
+    ltm_green_node_weights_dot(r, ncomp)  -> Matrix{ComplexF64} [ncomp, nz]
+
+The resident complex weights against the `ncomp` attached element components (`abz_rule_ltm_green_node_weights_dot`).
+"""
+function ltm_green_node_weights_dot(r::HIPRule, ncomp::Integer)
+    nz = ltm_green_node_weights_nz(r)
+    nz >= 1 || throw(ArgumentError("ltm_green_node_weights_dot: the rule holds no complex weights (ltm_green_node_weights!)"))
+    out = Matrix{ComplexF64}(undef, ncomp, nz)
+    GC.@preserve out check(ccall((:abz_rule_ltm_green_node_weights_dot, libabz), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}), r.h, out))
+    return out
+end
+
+"""
+    ltm_green_node_weights_fold(r, n, nirr)  -> Array{ComplexF64,3} [n, nirr, nz]
+
+For a rule of `abz_rule_ltm_unfold`: the resident complex weights summed over each orbit onto the `nirr` nodes of the source rule
+(`abz_rule_ltm_green_node_weights_fold`).
+"""
+function ltm_green_node_weights_fold(r::HIPRule, n::Integer, nirr::Integer)
+    nz = ltm_green_node_weights_nz(r)
+    nz >= 1 || throw(ArgumentError("ltm_green_node_weights_fold: the rule holds no complex weights (ltm_green_node_weights!)"))
+    out = Array{ComplexF64}(undef, n, nirr, nz)
+    GC.@preserve out check(ccall((:abz_rule_ltm_green_node_weights_fold, libabz), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}), r.h, out))
+    return out
+end
+
+"""
+    ltm_green_node_weights_matrix(r, n; orbitals=1:n)  -> Array{ComplexF64,3} [m, m, nz]
+
+The local Green's function `G[p, q](z) = sum_k sum_b W_b(k; z) U[p, b](k) conj(U[q, b](k))` from the resident complex weights and
+the eigenvectors (`abz_rule_ltm_green_node_weights_matrix`); nothing is attached.  `G(z)' == G(conj(z))`.
+"""
+function ltm_green_node_weights_matrix(r::HIPRule, n::Integer; orbitals::AbstractVector{<:Integer}=1:n)
+    allunique(orbitals) || throw(ArgumentError("ltm_green_node_weights_matrix: orbitals names an orbital twice"))
+    all(o -> 1 <= o <= n, orbitals) || throw(ArgumentError("ltm_green_node_weights_matrix: orbitals outside 1:$n"))
+    nz = ltm_green_node_weights_nz(r)
+    nz >= 1 || throw(ArgumentError("ltm_green_node_weights_matrix: the rule holds no complex weights (ltm_green_node_weights!)"))
+    out = Array{ComplexF64}(undef, n, n, nz)  # the library's [nz][p][q] is column-major [q, p, iz]
+    GC.@preserve out check(ccall((:abz_rule_ltm_green_node_weights_matrix, libabz), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}), r.h, out))
+    G = permutedims(out, (2, 1, 3))
+    return G[orbitals, orbitals, :]
+end
+
 # ---------------------------------------------------------------- cached rule -> the reference's own containers
 """
     export_rule(r, hs; H=true, eig=false, vel=false)
