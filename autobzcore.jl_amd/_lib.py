@@ -54,6 +54,7 @@ PROTOTYPES = {
     "abz_rule_ltm_elements": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
     "abz_rule_ltm_orbitals": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "abz_rule_ltm_projectors": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
+    "abz_rule_ltm_expectation": (C.c_int, [C.c_void_p, c_vpp, C.c_int, c_i32p, C.c_int]),
     "abz_rule_ltm_elements_export": (C.c_int, [C.c_void_p, c_ip, c_f64p]),
     "abz_rule_ltm_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_rule_ltm_fermi": (C.c_int, [C.c_void_p, C.c_double, C.c_double, c_f64p, c_f64p]),
@@ -99,6 +100,7 @@ K_EVAL_FUSED = 7  # launches only: the K_EVAL launches of the fused grid kernel
 LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
 LTM_MAX_COMP = 16
+LTM_EXPECT_MAX_OPS = 8  # operators of one abz_rule_ltm_expectation call
 LTM_NODEW_MAX_E = 16
 LTM_GREEN_NODEW_MAX_Z = 8
 PIVOT_NONE, PIVOT_PARTIAL = 0, 1  # abz_series_set_pivoting

@@ -553,6 +553,11 @@ int launch_ltm_orbitals(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView 
 // band projectors P^b_pq = U_pb conj(U_qb) into the same block: one component for p == q, Re and Im for p != q
 int ltm_projector_components(const int32_t* pairs, int npairs);
 int launch_ltm_projectors(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, PlaneView A, const int32_t* pairs, int npairs);
+// Band expectation values of operator series into the same block (kernels_ltm_expect.hip): q_i = Re u_b^H Hermitian(O_i) u_b from the H
+// planes of `ops[i]` (rules of the same whole grid, each full or compact); component c = q_{comps[2c]} when comps[2c+1] < 0, else
+// q_{comps[2c]} q_{comps[2c+1]}; comps == nullptr: the nops expectations in order.  nops <= ABZ_LTM_EXPECT_MAX_OPS.
+int launch_ltm_expectation(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, const PlaneView* ops, int nops, PlaneView A,
+                           const int32_t* comps, int ncomp);
 // Density matrix in the orbital basis (kernels_ltm_dens.hip): out_host [nE][n][n][2] = sum_k sum_b w_b(k; E_i) U_pb conj(U_qb) from the
 // weight block W (nE n planes, as launch_ltm_node_weights leaves it) and the H planes of the same whole grid (not read for one
 // band), U never in HBM; the lower triangle is the exact conjugate of the upper one.  1...32 bands.  Kernels under ABZ_K_EIG,

@@ -2297,6 +2297,53 @@ int abz_rule_ltm_projectors(abz_rule* r, const int32_t* pairs, int npairs) try {
     });
 } ABZ_CATCH_ALL
 
+int abz_rule_ltm_expectation(abz_rule* r, abz_rule* const* ops, int nops, const int32_t* comps, int ncomp) try {
+    const char* const who = "abz_rule_ltm_expectation";
+    int rc = check_rule(r);
+    if (rc) return rc;
+    if ((rc = ltm_eigvec_check_rule(r, who, "band expectation values"))) return rc;
+    const abz_series* s = r->s;
+    const int n = s->n;
+    ABZ_REQUIRE(ops, "abz_rule_ltm_expectation: null ops");
+    ABZ_REQUIRE(nops >= 1 && nops <= ABZ_LTM_EXPECT_MAX_OPS, "abz_rule_ltm_expectation: nops = %d outside 1..%d", nops, ABZ_LTM_EXPECT_MAX_OPS);
+    if (!comps) ncomp = nops;
+    ABZ_REQUIRE(ncomp >= 1 && ncomp <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_expectation: ncomp = %d outside 1..%d", ncomp, ABZ_LTM_MAX_COMP);
+    for (int c = 0; comps && c < ncomp; ++c)
+        ABZ_REQUIRE(comps[2 * c] >= 0 && comps[2 * c] < nops && comps[2 * c + 1] >= -1 && comps[2 * c + 1] < nops,
+                    "abz_rule_ltm_expectation: comps[%d] = (%d, %d): an operator index outside 0..%d (second: -1 for a single expectation)", c,
+                    comps[2 * c], comps[2 * c + 1], nops - 1);
+    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
+                "abz_rule_ltm_expectation: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
+    PlaneView O[ABZ_LTM_EXPECT_MAX_OPS];
+    for (int i = 0; i < nops; ++i) {
+        abz_rule* o = ops[i];
+        ABZ_REQUIRE(o, "abz_rule_ltm_expectation: ops[%d] is null", i);
+        if ((rc = check_rule(o))) return rc;
+        if (o->want & ABZ_WANT_H_ROW_MAJOR) {
+            set_error("abz_rule_ltm_expectation: ops[%d] was asked for in the row-major layout; operators are read from column-major or compact H planes", i);
+            return ABZ_ERR_UNSUPPORTED;
+        }
+        int64_t ogrid = 1;
+        for (int j = 0; j < o->s->d; ++j) ogrid *= o->npt;
+        if (!o->full || o->k_offset != 0 || o->nk != ogrid || o->node_of.p) {
+            set_error("abz_rule_ltm_expectation: ops[%d] is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, "
+                      "ABZ_WANT_H, ...)", i,
+                      !o->full ? "irreducible nodes of a symmetric rule" : (o->node_of.p ? "an unfolded rule" : "a slab of the outermost variable"));
+            return ABZ_ERR_UNSUPPORTED;
+        }
+        ABZ_REQUIRE(o->s->ctx == s->ctx, "abz_rule_ltm_expectation: ops[%d] lives on another context than the rule", i);
+        ABZ_REQUIRE(o->npt == r->npt && o->s->d == s->d && o->s->n == n && o->ntiles == r->ntiles,
+                    "abz_rule_ltm_expectation: ops[%d] has npt = %d, d = %d, n = %d; the rule has npt = %d, d = %d, n = %d", i, o->npt, o->s->d,
+                    o->s->n, r->npt, s->d, n);
+        ABZ_REQUIRE(o->H.base, "abz_rule_ltm_expectation: ops[%d] holds no H planes (build it with ABZ_WANT_H)", i);
+        ABZ_REQUIRE(o->s->hermitian && o->herm, "abz_rule_ltm_expectation: the series of ops[%d] is not Hermitian (c(-R) = c(R)^dagger)", i);
+        O[i] = o->H;
+    }
+    return ltm_eigvec_attach(r, who, ncomp, [&](PlaneView H, PlaneView A) {
+        return launch_ltm_expectation(s->ctx, n, r->npt, r->ntiles, H, O, nops, A, comps, ncomp);
+    });
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {
     int rc = check_rule(r);
     if (rc) return rc;

@@ -50,41 +50,7 @@ struct GgrRowsArgs {
 
 // (steps 2-5 -- kept reflectors, tridiagonal eigenvectors, back-transformation: rows_eigvec.h)
 
-// u^H D u for this lane's column u, D Hermitian: lane r parks the upper triangle of its row (D[r][c], c >= r) in the node's
-// room, every lane reads D[R][c] back (broadcast reads), column c at a time
-template <int NP>
-__device__ __forceinline__ void park_upper(int n, int r, double2* park, const double (&dr)[NP], const double (&di)[NP]) {
-#pragma unroll
-    for (int c = 0; c < NP; ++c)
-        if (c < n && r <= c) park[c * (c + 1) / 2 + r] = make_double2(dr[c], di[c]);
-}
-template <int NP, int C, int... RR>
-__device__ __forceinline__ void quad_col(int n, const double2* __restrict__ park, const double (&ur)[NP], const double (&ui)[NP], double& diag,
-                                         double (&offd)[2], std::integer_sequence<int, RR...>) {
-    if (C >= n) return;  // uniform
-    const double2* __restrict__ col = park + C * (C + 1) / 2;
-    // u_C through an opaque move: the products conj(u_R) u_C do not depend on the direction, and the compiler hoisted all
-    // n (n - 1) of them out of the loop over the directions -- through scratch memory (186 stores, 1.5 KB per lane)
-    double ucr = ur[C], uci = ui[C];
-    asm volatile("" : "+v"(ucr), "+v"(uci));
-    diag = fma(col[C].x, fma(ucr, ucr, uci * uci), diag);
-    ((void)([&] {
-         constexpr int R = RR;  // R < C
-         const double2 dv = col[R];
-         const double tr = fma(ur[R], ucr, ui[R] * uci);   // conj(u_R) u_C
-         const double ti = fma(ur[R], uci, -ui[R] * ucr);
-         offd[R & 1] = fma(dv.x, tr, offd[R & 1]);
-         offd[R & 1] = fma(-dv.y, ti, offd[R & 1]);
-     }()),
-     ...);
-}
-template <int NP, int... CC>
-__device__ __forceinline__ double quad_form(int n, const double2* __restrict__ park, const double (&ur)[NP], const double (&ui)[NP],
-                                            std::integer_sequence<int, CC...>) {
-    double diag = 0.0, offd[2] = {0.0, 0.0};
-    (quad_col<NP, CC>(n, park, ur, ui, diag, offd, std::make_integer_sequence<int, CC>()), ...);
-    return fma(2.0, offd[0] + offd[1], diag);
-}
+// (u^H D u from the node's LDS room -- park_upper, quad_form: rows_eigvec.h as well)
 
 // stage coefficients [m0, m0 + mcur) of one level-1 set; DERIV: times 2 pi i (first + m) on the way (d/dk_1)
 template <int NP, bool PAD>

@@ -2,7 +2,9 @@
 // Householder tridiagonalisation with the reflectors kept, the eigenvector of the real tridiagonal by inverse iteration in the
 // lane of its eigenvalue, and the back-transformation -- eigenvalue b (ascending) and column b of U end up in lane b
 // (rows_eigh_columns).  Steps (2)-(5) of the fused GGR build (kernels_ggr_rows.hip, which describes them); shared with the
-// orbital weights of the tetrahedron method (kernels_ltm_orb.hip).  gfx950 only.
+// orbital weights of the tetrahedron method (kernels_ltm_orb.hip).  Below them the Hermitian quadratic form u_b^H D u_b of a lane's
+// column from a matrix parked in the node's LDS room (park_upper, quad_form): the GGR velocities and the band expectation
+// values of kernels_ltm_expect.hip.  gfx950 only.
 #pragma once
 #include <utility>
 
@@ -295,6 +297,42 @@ __device__ __forceinline__ void rows_eigh_columns(int n, int r, int lane, double
     phase_apply<NP>(n, kp, z, ur, ui, std::make_integer_sequence<int, NP>());
     wave_sync_lds();  // the reflectors were written by other lanes of this wave
     if constexpr (NP >= 3) back_steps<NP>(n, kp, ur, ui, std::make_integer_sequence<int, NP - 2>());
+}
+
+// u^H D u for this lane's column u, D Hermitian: lane r parks the upper triangle of its row (D[r][c], c >= r) in the node's
+// room, every lane reads D[R][c] back (broadcast reads), column c at a time
+template <int NP>
+__device__ __forceinline__ void park_upper(int n, int r, double2* park, const double (&dr)[NP], const double (&di)[NP]) {
+#pragma unroll
+    for (int c = 0; c < NP; ++c)
+        if (c < n && r <= c) park[c * (c + 1) / 2 + r] = make_double2(dr[c], di[c]);
+}
+template <int NP, int C, int... RR>
+__device__ __forceinline__ void quad_col(int n, const double2* __restrict__ park, const double (&ur)[NP], const double (&ui)[NP], double& diag,
+                                         double (&offd)[2], std::integer_sequence<int, RR...>) {
+    if (C >= n) return;  // uniform
+    const double2* __restrict__ col = park + C * (C + 1) / 2;
+    // u_C through an opaque move: the products conj(u_R) u_C do not depend on the direction, and the compiler hoisted all
+    // n (n - 1) of them out of the loop over the directions -- through scratch memory (186 stores, 1.5 KB per lane)
+    double ucr = ur[C], uci = ui[C];
+    asm volatile("" : "+v"(ucr), "+v"(uci));
+    diag = fma(col[C].x, fma(ucr, ucr, uci * uci), diag);
+    ((void)([&] {
+         constexpr int R = RR;  // R < C
+         const double2 dv = col[R];
+         const double tr = fma(ur[R], ucr, ui[R] * uci);   // conj(u_R) u_C
+         const double ti = fma(ur[R], uci, -ui[R] * ucr);
+         offd[R & 1] = fma(dv.x, tr, offd[R & 1]);
+         offd[R & 1] = fma(-dv.y, ti, offd[R & 1]);
+     }()),
+     ...);
+}
+template <int NP, int... CC>
+__device__ __forceinline__ double quad_form(int n, const double2* __restrict__ park, const double (&ur)[NP], const double (&ui)[NP],
+                                            std::integer_sequence<int, CC...>) {
+    double diag = 0.0, offd[2] = {0.0, 0.0};
+    (quad_col<NP, CC>(n, park, ur, ui, diag, offd, std::make_integer_sequence<int, CC>()), ...);
+    return fma(2.0, offd[0] + offd[1], diag);
 }
 
 }  // namespace

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib as L
 from .bz import SymmetricBZ
-from .series import FourierSeries, density_matrix_orbitals, green_node_weight_zs
+from .series import FourierSeries, density_matrix_orbitals, expectation_components, green_node_weight_zs
 from .solver import NullParameters, checkkwargs
 
 
@@ -19,6 +19,52 @@ class GGR(DOSAlgorithm):
 
     def __init__(self, npt=50):
         self.npt = int(npt)
+
+
+def velocity_operators(h, basis=None):
+    """The d operator series O_a = sum_j M[a, j] dH/dkappa_j of the Hamiltonian series `h`, M = `basis` [d, d] or the identity:
+    kappa_j = x_j / t_j is the fractional coordinate of variable j (FourierSeries.derivative), so with the identity the band
+    expectations <u_b|O_j|u_b> are the rule's velocity planes, v_j = <dH/dx_j> t_j.  The linear combinations are taken on the
+    host coefficients; every O_a has the dims, `first` and period of `h` and is Hermitian when `h` is.
+    Cartesian velocities: a zone from load_bz(bz, A) holds the reciprocal basis B = 2 pi inv(A)^T, columns b_j (bz.py), and a
+    series of period 1 is a function of kappa with k = B kappa.  Then dH/dk_a = sum_j (d kappa_j / d k_a) dH/dkappa_j with
+    d kappa_j / d k_a = inv(B)[j, a], so M = inv(B)^T = A / (2 pi) gives O_a = dH/dk_a, the velocity operator in the Cartesian
+    direction a in units of (energy x length of A)."""
+    if not isinstance(h, FourierSeries):
+        raise ValueError("velocity_operators: h is not a FourierSeries")
+    d = h.d
+    M = np.eye(d) if basis is None else np.asarray(basis, dtype=np.float64)
+    if M.shape != (d, d):
+        raise ValueError(f"velocity_operators: basis of shape {M.shape}, expected [{d}, {d}]")
+    dh = [h.derivative(j) for j in range(d)]
+    out = []
+    for a in range(d):
+        c = sum(M[a, j] * dh[j].c for j in range(d))
+        o = FourierSeries(c, period=h.t, first=h.first, ndim=d)
+        o.scalar = h.scalar
+        out.append(o)
+    return out
+
+
+class BandExpectation:
+    """Band expectation values q_i = <u_b(k)| O_i(k) |u_b(k)> of 1..8 operator series in the Wannier basis of H as the
+    matrix elements of LTM(elements=BandExpectation(...)), computed on the device (DeviceRule.ltm_expectation).
+    `operators`: FourierSeries (or DeviceRule of the cache's grid that hold H planes); `components`: None for the
+    expectations in order, or at most 16 entries, each an operator index i (q_i) or a pair (i, j) (the product q_i q_j).
+    At a degenerate level only the sum of single expectations over the level is defined."""
+
+    def __init__(self, operators, components=None):
+        ops = list(operators) if isinstance(operators, (list, tuple)) else [operators]
+        if not 1 <= len(ops) <= L.LTM_EXPECT_MAX_OPS:
+            raise ValueError(f"BandExpectation: {len(ops)} operators, 1..{L.LTM_EXPECT_MAX_OPS} are taken")
+        self.operators = tuple(ops)
+        comps = expectation_components(components, len(ops), "BandExpectation")
+        self.components = None if comps is None else tuple((int(i), int(j)) for i, j in comps)
+
+
+def velocity_components(d):
+    """All pairs a <= b of the d directions, in the order (0,0), (0,1), (0,2), (1,1), (1,2), (2,2)."""
+    return tuple((a, b) for a in range(d) for b in range(a, d))
 
 
 class LTM(DOSAlgorithm):
@@ -37,7 +83,16 @@ class LTM(DOSAlgorithm):
                   1...32 bands, Hermitian series); `orbitals`, a sequence of orbital indices (at most 16, needed above 16
                   bands), then selects the columns of `u`.  At a degenerate level either route weighs with some
                   orthonormal basis of the eigenspace: sums over the level agree, single weights need not;
-      callable    f(x [nk, d], eig [nk, n]) -> [ncomp, nk, n] on the rule's exported nodes and eigenvalues.
+      callable    f(x [nk, d], eig [nk, n]) -> [ncomp, nk, n] on the rule's exported nodes and eigenvalues;
+      BandExpectation(operators, components)
+                  band expectation values <u_b|O_i|u_b> of operator series in the Wannier basis of H, and products of two of
+                  them, computed on the GPU into the resident element block (DeviceRule.ltm_expectation; 1...32 bands,
+                  Hermitian series; the rule keeps eigenvalues only);
+      "velocities"  the d fractional velocity operators dH/dkappa_j of the cache's own H (velocity_operators(H), rebuilt with
+                  the cache) with all products a <= b as components, in the order (0,0), (0,1), (0,2), (1,1), (1,2), (2,2):
+                  `u` [nE, d (d + 1) / 2] is the transport distribution sum_b int dk v_a v_b delta(E - e_b), with
+                  `cumulative` its integral, with `eta` the broadened one.  Like "orbitals" both need symmetric=False
+                  (expectation values are not invariant) and raise NotImplementedError on a k-sharded series.
     The elements are computed again whenever the cache rebuilds its eigenvalues.
 
     `symmetric=True` solves the eigenproblem at the irreducible nodes of the zone only and fills the full grid's eigenvalues
@@ -78,8 +133,9 @@ class LTM(DOSAlgorithm):
         self.eta = eta
         self.cumulative = bool(cumulative)
         self.symmetric = bool(symmetric)
-        if not (elements is None or callable(elements) or elements in ("energy", "orbitals")):
-            raise ValueError(f"LTM: elements = {elements!r} is neither 'energy', 'orbitals' nor a callable")
+        if not (elements is None or isinstance(elements, BandExpectation) or callable(elements)
+                or (isinstance(elements, str) and elements in ("energy", "orbitals", "velocities"))):
+            raise ValueError(f"LTM: elements = {elements!r} is neither 'energy', 'orbitals', 'velocities', a BandExpectation nor a callable")
         self.elements = elements
         self.correction = bool(correction)
         if self.correction and not self.cumulative:
@@ -146,16 +202,19 @@ def _init_cacheval(h, domain, p, alg):
         raise ValueError(f"{name} supports BZ parameters from load_bz")
     if p.ndim != h.d:
         raise ValueError(f"{name}: BZ and series dimensions differ")
-    if isinstance(alg, LTM) and alg.symmetric and alg.elements == "orbitals":
+    if isinstance(alg, LTM) and alg.symmetric and isinstance(alg.elements, str) and alg.elements == "orbitals":
         raise ValueError('LTM: elements = "orbitals" needs symmetric=False (orbital weights are not invariant under the zone\'s '
                          "symmetries, and an unfolded rule stores no H(k))")
+    if isinstance(alg, LTM) and alg.symmetric and _is_expectation(alg.elements) and p.syms is not None and len(p.syms) > 1:
+        raise ValueError("LTM: band expectation values (elements = 'velocities' or a BandExpectation) need symmetric=False (they "
+                         "are not invariant under the zone's symmetries, and an unfolded rule stores no H(k))")
     h.invalidate()  # coefficients may have been mutated in place (test/dos.jl:123): re-upload, rules refill lazily
     if isinstance(alg, LTM) and alg.eta is not None and _ksharded(h.device()):
         raise NotImplementedError("LTM(eta=...) on a k-sharded series is not implemented: the trace of the Green's function is "
                                   "computed on whole grids")
     if isinstance(alg, LTM) and _ksharded(h.device()):
         # slabs of the full grid, each with its halo plane; what needs more than a sum of partial scans is refused here
-        if alg.elements is not None and alg.elements != "energy":
+        if alg.elements is not None and not (isinstance(alg.elements, str) and alg.elements == "energy"):
             raise NotImplementedError('LTM on a k-sharded series: elements = "orbitals" or a callable are not implemented (a slab '
                                       'scans elements None or "energy")')
         if alg.symmetric and p.syms is not None and len(p.syms) > 1:
@@ -171,7 +230,7 @@ def _init_cacheval(h, domain, p, alg):
         # eigenvalues only, on the FULL grid whatever the zone's symmetries: the DOS is a scalar, so the full-zone sum is the
         # answer for every zone kind (symmetric=True above fills the same grid from the irreducible nodes; a symmetry-
         # reduced tetrahedron MESH is not implemented)
-        host_vectors = alg.elements == "orbitals" and alg.eigenvectors == "host"  # numpy diagonalises the exported H(k)
+        host_vectors = isinstance(alg.elements, str) and alg.elements == "orbitals" and alg.eigenvectors == "host"  # numpy diagonalises the exported H(k)
         return h.device().rule(alg.npt, None, (L.WANT_H | L.WANT_EIG) if host_vectors else L.WANT_EIG)
     return h.device().rule(alg.npt, p.syms, L.WANT_EIG | L.WANT_VEL)
 
@@ -187,11 +246,27 @@ class _DeviceOrbitals:
         self.orbitals = orbitals
 
 
+def _is_expectation(elements):
+    return isinstance(elements, BandExpectation) or (isinstance(elements, str) and elements == "velocities")
+
+
+class _DeviceExpectation:
+    """Band expectation values the rule computes itself (DeviceRule.ltm_expectation); one object per refresh of a cache: the
+    owner mark, and the operator series made from the Hamiltonian the cache held at that refresh."""
+
+    def __init__(self, operators, components):
+        self.operators, self.components = operators, components
+
+
 def _ltm_elements(rule, alg):
     """What an LTM cache hands DeviceRule.ltm as `elements`: None, "energy", the host array [ncomp, nk, n] computed
     from the rule's current values, or the request for orbital weights made on the device."""
     if not isinstance(alg, LTM) or alg.elements is None or rule is None:
         return None
+    if isinstance(alg.elements, BandExpectation):
+        return _DeviceExpectation(alg.elements.operators, alg.elements.components)
+    if isinstance(alg.elements, str) and alg.elements == "velocities":
+        return _DeviceExpectation(tuple(velocity_operators(rule.dev.s)), velocity_components(rule.dev.s.d))
     if alg.elements == "energy":
         return "energy"
     if alg.elements == "orbitals" and alg.eigenvectors == "device":
@@ -213,11 +288,13 @@ def _ltm_elements(rule, alg):
 
 
 def _ltm_attach(rule, el):
-    """The cache's elements `el` (an array or a _DeviceOrbitals) attached to its rule, unless they still are."""
+    """The cache's elements `el` (an array, a _DeviceOrbitals or a _DeviceExpectation) attached to its rule, unless they still are."""
     rule.h  # a stale rule refills here and loses its elements
     if rule._ltm_ncomp == 0 or getattr(rule, "_ltm_owner", None) is not el:  # (another cache on the same rule attached its own)
         if isinstance(el, _DeviceOrbitals):
             rule.ltm_orbitals(el.orbitals)
+        elif isinstance(el, _DeviceExpectation):
+            rule.ltm_expectation(list(el.operators), el.components)
         else:
             rule.ltm_elements(el)
         rule._ltm_owner = el

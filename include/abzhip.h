@@ -326,6 +326,27 @@ int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb);
  * as abz_rule_ltm_orbitals.  ABZ_ERR_ARG also for pairs == NULL, npairs < 1, an index outside 0..n-1, more than
  * ABZ_LTM_MAX_COMP components in all (attach them in groups).  Entry point added without a change of ABZ_VERSION. */
 int abz_rule_ltm_projectors(abz_rule* r, const int32_t* pairs /* [npairs][2] */, int npairs);
+/* Band expectation values of operator series as LTM matrix elements, computed on the device like the orbital weights and
+ * attached like them (replaces what was attached; dropped by the same events).  For operator i, band b and node k:
+ *      q_i = Re u_b(k)^H Hermitian(O_i(k)) u_b(k),   O_i(k) = sum_R e^{2 pi i k.R} O_{i,R} in the Wannier basis of H,
+ * the upper triangle of O_i read the way H is read, u_b the eigenvector the orbital and projector kernels use, bands ascending
+ * as in the rule's eigenvalue planes.  Component c with comps[c] = (i, j) is q_i for j == -1 and the product q_i q_j for
+ * 0 <= j < nops; comps == NULL: the nops expectations in order (ncomp = nops, the argument is ignored).  1 <= ncomp <=
+ * ABZ_LTM_MAX_COMP; duplicates are fine.  With O = S_z: the spin-resolved DOS; with O_a = dH/dk_a and products: the transport
+ * distribution sum_b int dk v_a v_b delta(E - e_b) from abz_rule_ltm_weighted.
+ * r: what abz_rule_ltm_orbitals takes (a whole periodic grid with eigenvalues, 1...32 bands, a Hermitian series, not a rule of
+ * abz_rule_ltm_unfold); H(k) from its own planes or a transient rule, as there.  ops[i]: rules that hold H planes (full or
+ * Hermitian-compact) of Hermitian series on whole periodic grids of the same context, npt, d and n as r; ops[i] == r is allowed
+ * when r holds H.  The caller keeps them current (abz_rule_rebuild after abz_series_update).
+ * At a degenerate level single expectations belong to some orthonormal basis of the eigenspace: only their sum over the level
+ * is defined, and products are not defined there at all.
+ * ABZ_ERR_UNSUPPORTED: slabs, node lists, symmetric rules, rules of abz_rule_ltm_unfold, more than 32 bands, the row-major
+ * layout.  ABZ_ERR_ARG: a NULL pointer, nops outside 1..ABZ_LTM_EXPECT_MAX_OPS, ncomp outside 1..ABZ_LTM_MAX_COMP, an operator
+ * index out of range, mismatched geometry or context, an operator without H planes, an operator series that is not Hermitian,
+ * r without eigenvalues.  Nothing is reserved or launched on a refusal; a refusal or failure leaves attached elements as they
+ * were.  Entry point added without a change of ABZ_VERSION. */
+#define ABZ_LTM_EXPECT_MAX_OPS 8
+int abz_rule_ltm_expectation(abz_rule* r, abz_rule* const* ops, int nops, const int32_t* comps /* [ncomp][2] or NULL */, int ncomp);
 /* Attached elements back to the host: *ncomp (0 if none), and, if A != NULL, A [ncomp][nk][n] in the order
  * abz_rule_ltm_elements takes them. */
 int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A);

@@ -420,6 +420,32 @@ function ltm_orbitals!(r::HIPRule; orbitals::Union{Nothing,AbstractVector{<:Inte
 end
 
 """
+    ltm_expectation!(r, ops; components=nothing)   -> number of components
+
+Attach the band expectation values `q_i = Re u_b' * Hermitian(O_i(k)) * u_b` of the operator rules `ops` (1 to 8 rules of the
+same grid that hold `H` planes, in the Wannier basis of `r`'s series) as matrix elements, computed on the device
+(`abz_rule_ltm_expectation`).  `components`: `nothing` for the expectations in order, or a vector of at most 16 entries, each an
+operator index `i` (1-based: `q_i`) or a pair `(i, j)` (the product `q_i q_j`).  At a degenerate level only the sum of single
+expectations over the level is defined.
+"""
+function ltm_expectation!(r::HIPRule, ops::AbstractVector{HIPRule}; components=nothing)
+    hs = Ptr{Cvoid}[o.h for o in ops]
+    if components === nothing
+        GC.@preserve ops check(ccall((:abz_rule_ltm_expectation, libabz), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cint}, Cint),
+                                     r.h, hs, length(hs), C_NULL, 0))
+        return length(hs)
+    end
+    comps = Cint[]
+    for c in components
+        i, j = c isa Integer ? (c, 0) : (c[1], c[2])
+        push!(comps, i - 1, j - 1)
+    end
+    GC.@preserve ops check(ccall((:abz_rule_ltm_expectation, libabz), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cint}, Cint),
+                                 r.h, hs, length(hs), comps, length(comps) ÷ 2))
+    return length(comps) ÷ 2
+end
+
+"""
     ltm_elements_export(r, n)                 -> A[b, k, c] or nothing
 
 The attached matrix elements back on the host, in the order `ltm_elements!` takes them (`abz_rule_ltm_elements_export`);
