@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import AbzError, Context
 from .bz import (FBZ, IBZ, Basis, CubicLimits, CubicSymIBZ, HyperCube, InversionSymIBZ, PolygonLimits, PolyhedralLimits, PuncturedInterval,
                  SymmetricBZ, TetrahedralLimits, canonical_reciprocal_basis, load_bz, nsyms)
-from .dos import BandExpectation, DOSProblem, DOSSolution, GGR, LTM, velocity_operators
+from .dos import BandExpectation, BandPairs, DOSProblem, DOSSolution, GGR, LTM, velocity_operators
 from . import dos
 from .interp import ChebInterp, hchebinterp
 from .io_w90 import load_w90_series, read_w90_hrdat, read_w90_wout

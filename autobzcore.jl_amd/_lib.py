@@ -56,10 +56,13 @@ PROTOTYPES = {
     "abz_rule_ltm_projectors": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "abz_rule_ltm_expectation": (C.c_int, [C.c_void_p, c_vpp, C.c_int, c_i32p, C.c_int]),
     "abz_rule_ltm_elements_export": (C.c_int, [C.c_void_p, c_ip, c_f64p]),
+    "abz_rule_ltm_elements_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p, c_ip]),
     "abz_rule_ltm_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_rule_ltm_fermi": (C.c_int, [C.c_void_p, C.c_double, C.c_double, c_f64p, c_f64p]),
     "abz_rule_ltm_unfold": (C.c_int, [C.c_void_p, c_i32p, C.c_int, c_vpp]),
     "abz_rule_ltm_halo": (C.c_int, [C.c_void_p]),
+    "abz_rule_ltm_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_vpp, C.c_int, c_i32p, C.c_int, c_vpp]),
+    "abz_rule_ltm_bands": (C.c_int, [C.c_void_p, c_ip]),
     "abz_rule_ltm_green": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
     "abz_rule_ltm_green_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, c_f64p]),
     "abz_rule_ltm_node_weights": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int, c_f64p]),
@@ -101,6 +104,8 @@ LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
 LTM_MAX_COMP = 16
 LTM_EXPECT_MAX_OPS = 8  # operators of one abz_rule_ltm_expectation call
+LTM_PAIRS_MAX_OPS = 4  # operators of one abz_rule_ltm_pairs call
+MAX_BANDS = 64  # bands a scan takes: the pairs of one pair rule
 LTM_NODEW_MAX_E = 16
 LTM_GREEN_NODEW_MAX_Z = 8
 PIVOT_NONE, PIVOT_PARTIAL = 0, 1  # abz_series_set_pivoting

@@ -291,6 +291,7 @@ int series_lane_views(abz_series* s, int count);
 struct abz_rule {
     abz_series* s = nullptr;
     int npt = 0, want = 0;
+    int nb = 0;           // bands of the E planes; 0: the series' n (a pair rule of abz_rule_ltm_pairs: its nv nc pseudo-bands)
     int64_t nk = 0;       // number of nodes
     int64_t ntiles = 0;   // tiles (grid lines, or 64-node groups of an irregular list)
     bool full = true;     // full grid (implicit nodes/weights) or explicit irregular list
@@ -325,11 +326,17 @@ struct abz_rule {
     // plane (outer_end mod npt) of the grid.  Owned by this rule (freed with it, refilled with it); holds no reference of
     // its own on the series.
     std::unique_ptr<abz_rule> ltm_halo;
+    // a pair rule (abz_rule_ltm_pairs): the band ranges of its source and the components of its elements, which a refill must repeat
+    int pair_v0 = 0, pair_nv = 0, pair_c0 = 0, pair_nc = 0, pair_nops = 0;
+    std::vector<int32_t> pair_comps;  // [ncomp][3]
     abz_rule();
     ~abz_rule();  // (api.cpp, where RulePlan is complete) on the owner's device, like every path that lets device blocks go
 };
 
 namespace abz {
+
+// bands of the rule's eigenvalue planes, attached elements and weight blocks
+inline int rule_bands(const abz_rule* r) { return r->nb ? r->nb : r->s->n; }
 
 // RAII-ish profiling bracket around launches of one logical kernel.  Its two events are bound to the kernel dispatches
 // made by launch() inside it, not recorded on the stream: an event record is a packet of its own, with a system-scope
@@ -558,6 +565,16 @@ int launch_ltm_projectors(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneVie
 // q_{comps[2c]} q_{comps[2c+1]}; comps == nullptr: the nops expectations in order.  nops <= ABZ_LTM_EXPECT_MAX_OPS.
 int launch_ltm_expectation(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, const PlaneView* ops, int nops, PlaneView A,
                            const int32_t* comps, int ncomp);
+// Pair rules (kernels_ltm_pairs.hip).  Pseudo-band p = (v - v0) nc + (c - c0) of the ranges [v0, v0 + nv) < [c0, c0 + nc) of the source's
+// ascending bands.
+// D (the nv nc eigenvalue planes of the pair rule, padding included) <- e_c - e_v of the planes E of the source; padding columns: 0.
+// Under ABZ_K_LTM, launches only.
+int launch_ltm_pair_energies(abz_ctx* ctx, int npt, int64_t nlines, PlaneView E, PlaneView D, int v0, int nv, int c0, int nc);
+// Interband products into an element block of ncomp nv nc planes: component c = Re (comps[3c+2] = 0) or Im (1) of
+// M^i_vc conj(M^j_vc), i = comps[3c], j = comps[3c+1], M^i_vc = u_v^H Hermitian(O_i) u_c from the H planes H of the source grid and of
+// the operators `ops` (as launch_ltm_expectation reads them).  2...32 bands, nops <= ABZ_LTM_PAIRS_MAX_OPS.  Under ABZ_K_EIG.
+int launch_ltm_pairs(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, const PlaneView* ops, int nops, PlaneView A, int v0, int nv,
+                     int c0, int nc, const int32_t* comps, int ncomp);
 // Density matrix in the orbital basis (kernels_ltm_dens.hip): out_host [nE][n][n][2] = sum_k sum_b w_b(k; E_i) U_pb conj(U_qb) from the
 // weight block W (nE n planes, as launch_ltm_node_weights leaves it) and the H planes of the same whole grid (not read for one
 // band), U never in HBM; the lower triangle is the exact conjugate of the upper one.  1...32 bands.  Kernels under ABZ_K_EIG,

@@ -1031,6 +1031,13 @@ static void rule_drop_ltm_node_weights(abz_rule* r) {
     r->GW = PlaneView();
 }
 
+// A pair rule (abz_rule_ltm_pairs) holds differences of eigenvalues and interband products: no H(k), no eigenvectors, no plan.
+static int refuse_pair_rule(const abz_rule* r, const char* who, const char* why) {
+    if (!r->nb) return ABZ_OK;
+    set_error("%s: the rule is a pair rule of abz_rule_ltm_pairs (%d pseudo-bands e_c - e_v): %s", who, r->nb, why);
+    return ABZ_ERR_UNSUPPORTED;
+}
+
 int abz_rule_destroy(abz_rule* r) try {
     if (!r) return ABZ_OK;
     abz_series* s = r->s;
@@ -1448,6 +1455,8 @@ int abz_ptr_rule_build_slab(abz_series* s, int npt, int outer_begin, int outer_e
 int abz_rule_rebuild(abz_rule* r) try {
     int rc0 = check_rule(r);
     if (rc0) return rc0;
+    if ((rc0 = refuse_pair_rule(r, "abz_rule_rebuild", "it has no plan of its own; rebuild the source and call abz_rule_ltm_pairs(src, ..., &rule) again")))
+        return rc0;
     if (r->node_of.p) {
         set_error("abz_rule_rebuild: the rule holds eigenvalues unfolded from another rule and no plan of its own; rebuild the source "
                   "and call abz_rule_ltm_unfold(src, syms, nsyms, &rule) again");
@@ -1479,6 +1488,7 @@ int abz_rule_rebuild(abz_rule* r) try {
 int abz_rule_ltm_halo(abz_rule* r) try {
     int rc = check_rule(r);
     if (rc) return rc;
+    if ((rc = refuse_pair_rule(r, "abz_rule_ltm_halo", "it is a whole grid and has no plan to build a plane from"))) return rc;
     if (!r->full) {
         set_error("abz_rule_ltm_halo: the rule holds irreducible nodes (a node list or a symmetric rule), not a slab of a full grid: "
                   "its simplices lack the mesh, not a plane");
@@ -1555,7 +1565,7 @@ int abz_rule_export(abz_rule* r, double* x, double* w, double* H, double* eig, d
     }
     if (eig) {
         ABZ_REQUIRE(r->E.base, "rule holds no eigenvalues (want lacked ABZ_WANT_EIG)");
-        int rc = export_planes(ctx, r->E, n, r->nk, eig);
+        int rc = export_planes(ctx, r->E, rule_bands(r), r->nk, eig);
         if (rc) return rc;
     }
     if (vel) {
@@ -1595,6 +1605,8 @@ static int rule_reduce(abz_rule* r, int integrand, const double* params, int npa
                        int nsyms, double* out_reim, bool device_io, double2* map_dev) {
     int rc0 = check_rule(r);
     if (rc0) return rc0;
+    if ((rc0 = refuse_pair_rule(r, "abz_rule_reduce", "the PTR integrands are functions of H(k) or of the n bands; its planes serve the tetrahedron scans")))
+        return rc0;
     ABZ_REQUIRE(out_reim || map_dev, "null out");
     ABZ_REQUIRE(nparams >= 0 && nparams <= 4, "nparams = %d not in 0..4", nparams);
     ABZ_REQUIRE(nsyms >= 1, "nsyms must be >= 1");
@@ -2135,7 +2147,7 @@ int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) tr
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     LtmSlab slab;
-    return launch_ltm(ctx, r->s->n, r->s->d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out, ltm_slab_of(r, slab) ? &slab : nullptr);
+    return launch_ltm(ctx, rule_bands(r), r->s->d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out, ltm_slab_of(r, slab) ? &slab : nullptr);
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_green(abz_rule* r, const double* z, int nz, double* out) try {
@@ -2151,7 +2163,7 @@ int abz_rule_ltm_green(abz_rule* r, const double* z, int nz, double* out) try {
     }
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    return launch_ltm_green(ctx, r->s->n, r->s->d, r->npt, r->E, z, nz, out);
+    return launch_ltm_green(ctx, rule_bands(r), r->s->d, r->npt, r->E, z, nz, out);
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
@@ -2165,7 +2177,7 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
     ABZ_HIP(hipStreamSynchronize(ctx->stream));
     rule_drop_ltm_elements(r);
     if (!A) return ABZ_OK;
-    const int n = r->s->n;
+    const int n = rule_bands(r);
     const int planes = ncomp * n;
     const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
     if ((rc = r->ltm_elems.alloc(bytes))) return rc;
@@ -2203,6 +2215,7 @@ int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
 static int ltm_eigvec_check_rule(abz_rule* r, const char* who, const char* what) {
     int rc = ltm_check_grid(r, who);
     if (rc) return rc;
+    if ((rc = refuse_pair_rule(r, who, "H(k) and eigenvectors belong to its source rule"))) return rc;
     if (r->node_of.p) {
         set_error("%s: the rule's eigenvalues were unfolded from irreducible nodes; eigenvectors at every grid "
                   "point are what such a rule avoids (build a full-grid rule with abz_ptr_rule_build)", who);
@@ -2215,8 +2228,10 @@ static int ltm_eigvec_check_rule(abz_rule* r, const char* who, const char* what)
     return ABZ_OK;
 }
 
-// allocate the block of ncomp components, fill it (`fill(H, A)` launches the kernel), wait once, attach
-static int ltm_eigvec_attach(abz_rule* r, const char* who, int ncomp, const std::function<int(PlaneView, PlaneView)>& fill) {
+// the block of `planes` planes tiled like the eigenvalue planes E, filled from H(k) of the grid of r (`fill(H, A)` launches the kernel;
+// H: r's own planes or a transient H-only rule), complete when this returns: the one synchronisation of the call
+static int ltm_eigvec_block(abz_rule* r, const char* who, PlaneView E, int planes, const std::function<int(PlaneView, PlaneView)>& fill,
+                            DevBuf& block, PlaneView& A) {
     const int n = r->s->n;
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
@@ -2227,14 +2242,12 @@ static int ltm_eigvec_attach(abz_rule* r, const char* who, int ncomp, const std:
         if ((rc = rule_build(r->s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
         tmp.reset(built);
     }
-    const int planes = ncomp * n;
-    const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
-    DevBuf block;
+    const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)E.row;
     rc = block.alloc(bytes);
-    PlaneView A = r->E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements)
+    A = E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements)
     A.base = block.as<double>();
-    A.tile = (int64_t)planes * r->E.row;
-    A.pitch = r->E.row;
+    A.tile = (int64_t)planes * E.row;
+    A.pitch = E.row;
     A.compact = 0;
     if (!rc) rc = fill(tmp ? tmp->H : r->H, A);
     // the one synchronisation of the call: the block is complete, nothing reads the old one or the transient rule any more
@@ -2246,6 +2259,14 @@ static int ltm_eigvec_attach(abz_rule* r, const char* who, int ncomp, const std:
         tmp.reset();
         series_release(r->s);
     }
+    return rc;
+}
+
+// allocate the block of ncomp components, fill it, wait once, attach
+static int ltm_eigvec_attach(abz_rule* r, const char* who, int ncomp, const std::function<int(PlaneView, PlaneView)>& fill) {
+    DevBuf block;
+    PlaneView A;
+    const int rc = ltm_eigvec_block(r, who, r->E, ncomp * r->s->n, fill, block, A);
     if (rc) return rc;
     r->ltm_elems = std::move(block);  // (what was attached goes here)
     r->ltm_ncomp = ncomp;
@@ -2297,6 +2318,39 @@ int abz_rule_ltm_projectors(abz_rule* r, const int32_t* pairs, int npairs) try {
     });
 } ABZ_CATCH_ALL
 
+// what the entry points that read operator rules (abz_rule_ltm_expectation, abz_rule_ltm_pairs) ask of ops[0 .. nops): H planes of
+// Hermitian series on whole periodic grids of the context, npt, d and n of r, not row-major; O[i] <- their planes
+static int ltm_check_operators(const char* who, const abz_rule* r, abz_rule* const* ops, int nops, PlaneView* O) {
+    const abz_series* s = r->s;
+    const int n = s->n;
+    int rc = ABZ_OK;
+    for (int i = 0; i < nops; ++i) {
+        abz_rule* o = ops[i];
+        ABZ_REQUIRE(o, "%s: ops[%d] is null", who, i);
+        if ((rc = check_rule(o))) return rc;
+        if (o->want & ABZ_WANT_H_ROW_MAJOR) {
+            set_error("%s: ops[%d] was asked for in the row-major layout; operators are read from column-major or compact H planes", who, i);
+            return ABZ_ERR_UNSUPPORTED;
+        }
+        int64_t ogrid = 1;
+        for (int j = 0; j < o->s->d; ++j) ogrid *= o->npt;
+        if (!o->full || o->k_offset != 0 || o->nk != ogrid || o->node_of.p) {
+            set_error("%s: ops[%d] is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, "
+                      "ABZ_WANT_H, ...)", who, i,
+                      !o->full ? "irreducible nodes of a symmetric rule" : (o->node_of.p ? "an unfolded rule" : "a slab of the outermost variable"));
+            return ABZ_ERR_UNSUPPORTED;
+        }
+        ABZ_REQUIRE(o->s->ctx == s->ctx, "%s: ops[%d] lives on another context than the rule", who, i);
+        ABZ_REQUIRE(o->npt == r->npt && o->s->d == s->d && o->s->n == n && o->ntiles == r->ntiles,
+                    "%s: ops[%d] has npt = %d, d = %d, n = %d; the rule has npt = %d, d = %d, n = %d", who, i, o->npt, o->s->d,
+                    o->s->n, r->npt, s->d, n);
+        ABZ_REQUIRE(o->H.base, "%s: ops[%d] holds no H planes (build it with ABZ_WANT_H)", who, i);
+        ABZ_REQUIRE(o->s->hermitian && o->herm, "%s: the series of ops[%d] is not Hermitian (c(-R) = c(R)^dagger)", who, i);
+        O[i] = o->H;
+    }
+    return ABZ_OK;
+}
+
 int abz_rule_ltm_expectation(abz_rule* r, abz_rule* const* ops, int nops, const int32_t* comps, int ncomp) try {
     const char* const who = "abz_rule_ltm_expectation";
     int rc = check_rule(r);
@@ -2315,30 +2369,7 @@ int abz_rule_ltm_expectation(abz_rule* r, abz_rule* const* ops, int nops, const 
     ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
                 "abz_rule_ltm_expectation: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
     PlaneView O[ABZ_LTM_EXPECT_MAX_OPS];
-    for (int i = 0; i < nops; ++i) {
-        abz_rule* o = ops[i];
-        ABZ_REQUIRE(o, "abz_rule_ltm_expectation: ops[%d] is null", i);
-        if ((rc = check_rule(o))) return rc;
-        if (o->want & ABZ_WANT_H_ROW_MAJOR) {
-            set_error("abz_rule_ltm_expectation: ops[%d] was asked for in the row-major layout; operators are read from column-major or compact H planes", i);
-            return ABZ_ERR_UNSUPPORTED;
-        }
-        int64_t ogrid = 1;
-        for (int j = 0; j < o->s->d; ++j) ogrid *= o->npt;
-        if (!o->full || o->k_offset != 0 || o->nk != ogrid || o->node_of.p) {
-            set_error("abz_rule_ltm_expectation: ops[%d] is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, "
-                      "ABZ_WANT_H, ...)", i,
-                      !o->full ? "irreducible nodes of a symmetric rule" : (o->node_of.p ? "an unfolded rule" : "a slab of the outermost variable"));
-            return ABZ_ERR_UNSUPPORTED;
-        }
-        ABZ_REQUIRE(o->s->ctx == s->ctx, "abz_rule_ltm_expectation: ops[%d] lives on another context than the rule", i);
-        ABZ_REQUIRE(o->npt == r->npt && o->s->d == s->d && o->s->n == n && o->ntiles == r->ntiles,
-                    "abz_rule_ltm_expectation: ops[%d] has npt = %d, d = %d, n = %d; the rule has npt = %d, d = %d, n = %d", i, o->npt, o->s->d,
-                    o->s->n, r->npt, s->d, n);
-        ABZ_REQUIRE(o->H.base, "abz_rule_ltm_expectation: ops[%d] holds no H planes (build it with ABZ_WANT_H)", i);
-        ABZ_REQUIRE(o->s->hermitian && o->herm, "abz_rule_ltm_expectation: the series of ops[%d] is not Hermitian (c(-R) = c(R)^dagger)", i);
-        O[i] = o->H;
-    }
+    if ((rc = ltm_check_operators(who, r, ops, nops, O))) return rc;
     return ltm_eigvec_attach(r, who, ncomp, [&](PlaneView H, PlaneView A) {
         return launch_ltm_expectation(s->ctx, n, r->npt, r->ntiles, H, O, nops, A, comps, ncomp);
     });
@@ -2354,12 +2385,22 @@ int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {
     if (!A || !r->ltm_elems.p) return ABZ_OK;
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = r->s->n;
+    const int n = rule_bands(r);
     for (int c = 0; c < r->ltm_ncomp; ++c) {  // one component [nk][n] at a time, the order they came in
         PlaneView v = r->A;
         v.base += (int64_t)c * n * v.pitch;
         if ((rc = export_planes(ctx, v, n, r->nk, A + (size_t)c * (size_t)r->nk * (size_t)n))) return rc;
     }
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_elements_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* ncomp) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    const bool have = r->ltm_elems.p != nullptr;
+    if (base) *base = r->ltm_elems.p;
+    if (nbytes) *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * (size_t)r->ltm_ncomp * (size_t)rule_bands(r) * (size_t)r->A.row) : 0;
+    if (ncomp) *ncomp = have ? r->ltm_ncomp : 0;
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
@@ -2378,7 +2419,7 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
     ABZ_HIP(hipSetDevice(ctx->device));
     const bool energy = source == ABZ_LTM_A_ENERGY;
     LtmSlab slab;
-    return launch_ltm_weighted(ctx, r->s->n, r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, E, nE,
+    return launch_ltm_weighted(ctx, rule_bands(r), r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, E, nE,
                                what, out, ltm_slab_of(r, slab) ? &slab : nullptr);
 } ABZ_CATCH_ALL
 
@@ -2400,7 +2441,7 @@ int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z, int nz
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     const bool energy = source == ABZ_LTM_A_ENERGY;
-    return launch_ltm_green_weighted(ctx, r->s->n, r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, z, nz, out);
+    return launch_ltm_green_weighted(ctx, rule_bands(r), r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, z, nz, out);
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {
@@ -2408,11 +2449,11 @@ int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, dou
     if (rc) return rc;
     ABZ_REQUIRE(E_F, "abz_rule_ltm_fermi: null E_F");
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_fermi"))) return rc;
-    ABZ_REQUIRE(nstates > 0.0 && nstates < (double)r->s->n, "abz_rule_ltm_fermi: nstates = %g outside (0, %d)", nstates, r->s->n);
+    ABZ_REQUIRE(nstates > 0.0 && nstates < (double)rule_bands(r), "abz_rule_ltm_fermi: nstates = %g outside (0, %d)", nstates, rule_bands(r));
     ABZ_REQUIRE(tol > 0.0, "abz_rule_ltm_fermi: tol = %g is not positive", tol);
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    return ltm_fermi(ctx, r->s->n, r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
+    return ltm_fermi(ctx, rule_bands(r), r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
 } ABZ_CATCH_ALL
 
 // Integration weights w_b(k; E) per node and band (kernels_ltm_nodew.hip).  The new block is complete before it replaces the
@@ -2429,7 +2470,7 @@ int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, do
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights"))) return rc;
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = r->s->n;
+    const int n = rule_bands(r);
     const int planes = nE * n;
     DevBuf block;
     if ((rc = block.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row))) return rc;
@@ -2461,7 +2502,7 @@ int abz_rule_ltm_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbyte
     if (rc) return rc;
     const bool have = r->ltm_nodew.p != nullptr;
     if (base) *base = r->ltm_nodew.p;
-    if (nbytes) *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * (size_t)r->ltm_nodew_nE * (size_t)r->s->n * (size_t)r->NW.row) : 0;
+    if (nbytes) *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * (size_t)r->ltm_nodew_nE * (size_t)rule_bands(r) * (size_t)r->NW.row) : 0;
     if (nE) *nE = have ? r->ltm_nodew_nE : 0;
     return ABZ_OK;
 } ABZ_CATCH_ALL
@@ -2477,7 +2518,7 @@ int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out) try {
                                 "abz_rule_ltm_projectors)");
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    return launch_ltm_node_weights_dot(ctx, r->s->n, r->npt, r->ntiles, r->NW, r->ltm_nodew_nE, r->A, r->ltm_ncomp, out);
+    return launch_ltm_node_weights_dot(ctx, rule_bands(r), r->npt, r->ntiles, r->NW, r->ltm_nodew_nE, r->A, r->ltm_ncomp, out);
 } ABZ_CATCH_ALL
 
 // rho_pq(E_i) from the resident weights and U(k) in one eigen-solve (kernels_ltm_dens.hip).  Nothing is attached and nothing
@@ -2595,7 +2636,7 @@ int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z, int nz, double
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights"))) return rc;
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = r->s->n;
+    const int n = rule_bands(r);
     const int planes = 2 * nz * n;
     DevBuf block;
     if ((rc = block.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row))) return rc;
@@ -2634,7 +2675,7 @@ int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t*
     const bool have = r->ltm_gnodew.p != nullptr;
     if (base) *base = r->ltm_gnodew.p;
     if (nbytes)
-        *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * 2 * (size_t)r->ltm_gnodew_nz * (size_t)r->s->n * (size_t)r->GW.row) : 0;
+        *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * 2 * (size_t)r->ltm_gnodew_nz * (size_t)rule_bands(r) * (size_t)r->GW.row) : 0;
     if (nz) *nz = have ? r->ltm_gnodew_nz : 0;
     return ABZ_OK;
 } ABZ_CATCH_ALL
@@ -2653,7 +2694,7 @@ int abz_rule_ltm_green_node_weights_dot(abz_rule* r, double* out) try {
     // [2 nz][ncomp] of the real sets is [nz][Re, Im][ncomp]
     const int nz = r->ltm_gnodew_nz, ncomp = r->ltm_ncomp;
     std::vector<double> sets((size_t)2 * nz * ncomp);
-    if ((rc = launch_ltm_node_weights_dot(ctx, r->s->n, r->npt, r->ntiles, r->GW, 2 * nz, r->A, ncomp, sets.data()))) return rc;
+    if ((rc = launch_ltm_node_weights_dot(ctx, rule_bands(r), r->npt, r->ntiles, r->GW, 2 * nz, r->A, ncomp, sets.data()))) return rc;
     for (int i = 0; i < nz; ++i)
         for (int c = 0; c < ncomp; ++c) {
             out[2 * ((size_t)i * ncomp + c)] = sets[(size_t)(2 * i) * ncomp + c];
@@ -2791,6 +2832,128 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
     }
     s->refs += 1;
     *out = r.release();  // (the handle: not a device block)
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+// Pair rule: the differences e_c - e_v of two band ranges of `src` as the eigenvalue planes of a whole-grid rule of its own, and
+// the interband products M^i_vc conj(M^j_vc) as its attached elements (kernels_ltm_pairs.hip).  Every scan that reads E, attached
+// elements or weight blocks sizes itself by rule_bands() and takes it as it takes an unfolded rule.  Both blocks are complete
+// before they replace anything: a refusal or a failure leaves *out and src as they were.
+int abz_rule_ltm_bands(const abz_rule* r, int* nb) try {
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(nb, "abz_rule_ltm_bands: null nb");
+    *nb = rule_bands(r);
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
+int abz_rule_ltm_pairs(abz_rule* src, int v0, int nv, int c0, int nc, abz_rule* const* ops, int nops, const int32_t* comps, int ncomp,
+                       abz_rule** out) try {
+    const char* const who = "abz_rule_ltm_pairs";
+    int rc = check_rule(src);
+    if (rc) return rc;
+    ABZ_REQUIRE(out, "abz_rule_ltm_pairs: null out");
+    ABZ_REQUIRE(nops >= 0 && nops <= ABZ_LTM_PAIRS_MAX_OPS, "abz_rule_ltm_pairs: nops = %d outside 0..%d", nops, ABZ_LTM_PAIRS_MAX_OPS);
+    if ((rc = refuse_pair_rule(src, who, "pairs are formed from the bands of a rule of the series"))) return rc;
+    // without operators: what abz_rule_ltm takes as a whole grid; with them: what abz_rule_ltm_expectation takes
+    if ((rc = nops ? ltm_eigvec_check_rule(src, who, "interband matrix elements") : ltm_check_grid(src, who))) return rc;
+    abz_series* s = src->s;
+    abz_ctx* ctx = s->ctx;
+    const int n = s->n, npt = src->npt;
+    ABZ_REQUIRE(!(nops && n == 1), "abz_rule_ltm_pairs: one band has no pairs");
+    ABZ_REQUIRE(v0 >= 0 && nv >= 1 && nc >= 1 && c0 >= 0 && (int64_t)v0 + nv <= c0 && (int64_t)c0 + nc <= n,
+                "abz_rule_ltm_pairs: ranges [%d, %d + %d) and [%d, %d + %d) of %d bands: 0 <= v0, nv >= 1, nc >= 1, v0 + nv <= c0, c0 + nc <= n",
+                v0, v0, nv, c0, c0, nc, n);
+    ABZ_REQUIRE((int64_t)nv * nc <= ABZ_MAX_BANDS, "abz_rule_ltm_pairs: %d x %d pairs are more than the %d pseudo-bands a scan takes; use a window of bands",
+                nv, nc, ABZ_MAX_BANDS);
+    const int nb = nv * nc;
+    PlaneView O[ABZ_LTM_PAIRS_MAX_OPS];
+    std::vector<int32_t> cv;  // [ncomp][3]
+    if (nops) {
+        ABZ_REQUIRE(ops, "abz_rule_ltm_pairs: null ops");
+        if (!comps) ncomp = nops;
+        ABZ_REQUIRE(ncomp >= 1 && ncomp <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_pairs: ncomp = %d outside 1..%d", ncomp, ABZ_LTM_MAX_COMP);
+        cv.resize((size_t)3 * ncomp);
+        for (int c = 0; c < ncomp; ++c) {
+            cv[3 * c] = comps ? comps[3 * c] : c;
+            cv[3 * c + 1] = comps ? comps[3 * c + 1] : c;
+            cv[3 * c + 2] = comps ? comps[3 * c + 2] : 0;
+            ABZ_REQUIRE(cv[3 * c] >= 0 && cv[3 * c] < nops && cv[3 * c + 1] >= 0 && cv[3 * c + 1] < nops && (cv[3 * c + 2] == 0 || cv[3 * c + 2] == 1),
+                        "abz_rule_ltm_pairs: comps[%d] = (%d, %d, %d): operator indices inside 0..%d, part 0 (Re) or 1 (Im)", c, cv[3 * c],
+                        cv[3 * c + 1], cv[3 * c + 2], nops - 1);
+        }
+        ABZ_REQUIRE(s->hermitian && (!src->H.base || src->herm),
+                    "abz_rule_ltm_pairs: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
+        if ((rc = ltm_check_operators(who, src, ops, nops, O))) return rc;
+    } else {
+        ncomp = 0;
+    }
+    abz_rule* const old = *out;
+    if (old) {
+        if ((rc = check_rule(old))) return rc;
+        ABZ_REQUIRE(old->nb && old != src, "abz_rule_ltm_pairs: *out is not a rule made by abz_rule_ltm_pairs (pass NULL to create one)");
+        ABZ_REQUIRE(old->s == s && old->npt == npt && old->pair_v0 == v0 && old->pair_nv == nv && old->pair_c0 == c0 && old->pair_nc == nc &&
+                        old->pair_nops == nops && old->pair_comps == cv,
+                    "abz_rule_ltm_pairs: *out was made for another series, npt, band ranges or components (npt = %d, [%d, %d + %d) x [%d, %d + %d), "
+                    "%d operators)", old->npt, old->pair_v0, old->pair_v0, old->pair_nv, old->pair_c0, old->pair_c0, old->pair_nc, old->pair_nops);
+    }
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int row = (npt + 15) / 16 * 16;
+    PlaneView E;  // the nb planes of the pair energies, tiled like the planes of an unfolded rule
+    E.tile = (int64_t)nb * row;
+    E.pitch = row;
+    E.line_len = npt;
+    E.row = row;
+    DevBuf vals, elems;
+    PlaneView A;
+    if ((rc = vals.alloc(sizeof(double) * (size_t)src->ntiles * (size_t)nb * (size_t)row))) return rc;
+    E.base = vals.as<double>();
+    // the energies always from the source's planes: the spectra sit on the eigenvalues the source's own scans see
+    rc = launch_ltm_pair_energies(ctx, npt, src->ntiles, src->E, E, v0, nv, c0, nc);
+    if (!rc && nops)
+        rc = ltm_eigvec_block(src, who, E, ncomp * nb, [&](PlaneView H, PlaneView Ab) {
+            return launch_ltm_pairs(ctx, n, npt, src->ntiles, H, O, nops, Ab, v0, nv, c0, nc, cv.data(), ncomp);
+        }, elems, A);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_pairs: the kernel failed");
+        rc = ABZ_ERR_HIP;
+    }
+    if (rc) return rc;
+    std::unique_ptr<abz_rule> made;
+    abz_rule* r = old;
+    if (!r) {
+        made.reset(new abz_rule());
+        r = made.get();
+        r->plan.reset(new RulePlan());  // empty: a pair rule has no contraction plan (abz_rule_rebuild refuses it)
+        r->s = s;
+        r->npt = npt;
+        r->want = ABZ_WANT_EIG;
+        r->full = true;
+        r->nb = nb;
+        r->nk = src->nk;
+        r->ntiles = src->ntiles;
+        r->planes = nb;
+        r->pair_v0 = v0;
+        r->pair_nv = nv;
+        r->pair_c0 = c0;
+        r->pair_nc = nc;
+        r->pair_nops = nops;
+        r->pair_comps = cv;
+    }
+    r->herm = src->herm;
+    r->vals = std::move(vals);  // (the old energies and elements go here)
+    r->E = E;
+    rule_drop_ltm_node_weights(r);  // they described the old energies
+    rule_drop_ltm_elements(r);
+    if (nops) {
+        r->ltm_elems = std::move(elems);
+        r->ltm_ncomp = ncomp;
+        r->A = A;
+    }
+    if (made) {
+        s->refs += 1;
+        *out = made.release();  // (the handle: not a device block)
+    }
     return ABZ_OK;
 } ABZ_CATCH_ALL
 

@@ -28,6 +28,7 @@
 #include "device_math.h"
 #include "rows_device.h"
 #include "rows_eigvec.h"
+#include "xp_select.h"
 
 namespace abz {
 
@@ -43,33 +44,6 @@ struct LtmExpectArgs {
     int n, npt, nops, ncomp;
     int ci[ABZ_LTM_MAX_COMP], cj[ABZ_LTM_MAX_COMP];  // component c: q[ci] (cj < 0) or q[ci] q[cj]
 };
-
-// plane of Re X[a][b], a <= b (Im: the next one; the diagonal of the compact layout has none)
-__device__ __forceinline__ int xp_plane(const PlaneView& v, int n, int a, int b) { return v.compact ? b * b + 2 * a : 2 * (a + n * b); }
-
-// q[i] of the register array and q[k] = v, i and k uniform: select chains over values that were read first (with the element
-// read inside the conditional expression the chain became a chain of addresses and one load at a run-time offset: the array
-// left the registers)
-template <int... M>
-__device__ __forceinline__ double xp_pick(const double (&q)[XOPS], int i, std::integer_sequence<int, M...>) {
-    double v = q[0];
-    ((void)([&] {
-         const double x = q[M + 1];
-         v = (i == M + 1) ? x : v;
-     }()),
-     ...);
-    return v;
-}
-__device__ __forceinline__ double xp_pick(const double (&q)[XOPS], int i) { return xp_pick(q, i, std::make_integer_sequence<int, XOPS - 1>()); }
-template <int... M>
-__device__ __forceinline__ void xp_put(double (&q)[XOPS], int k, double v, std::integer_sequence<int, M...>) {
-    ((void)([&] {
-         const double old = q[M];
-         q[M] = (k == M) ? v : old;
-     }()),
-     ...);
-}
-__device__ __forceinline__ void xp_put(double (&q)[XOPS], int k, double v) { xp_put(q, k, v, std::make_integer_sequence<int, XOPS>()); }
 
 template <int N>
 __global__ __launch_bounds__(256) void ltm_expect_lane_kernel(LtmExpectArgs a) {

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib as L
 from .bz import SymmetricBZ
-from .series import FourierSeries, density_matrix_orbitals, expectation_components, green_node_weight_zs
+from .series import FourierSeries, PairRule, density_matrix_orbitals, expectation_components, green_node_weight_zs, pair_components, pair_ranges
 from .solver import NullParameters, checkkwargs
 
 
@@ -60,6 +60,63 @@ class BandExpectation:
         self.operators = tuple(ops)
         comps = expectation_components(components, len(ops), "BandExpectation")
         self.components = None if comps is None else tuple((int(i), int(j)) for i, j in comps)
+
+
+class BandPairs:
+    """Pairs of a lower and an upper band as the "bands" of LTM(pairs=BandPairs(...)): the joint density of states
+    J(w) = sum_vc int dk delta(w - (e_c - e_v)) and, with operators, the interband spectra
+    S_ij(w) = sum_vc int dk M^i_vc conj(M^j_vc) delta(w - (e_c - e_v)), M^i_vc = <u_v|O_i|u_c> (DeviceRule.ltm_pairs).
+    Exactly one of `nocc` (the lowest nocc bands against all others: an insulator with nocc filled bands) and `lower` + `upper`
+    (each a `range` or (start, count); lower below upper) is given; at most 64 pairs, so a model of many bands takes a window
+    around the gap.  `operators`: None (energies only), 1..4 FourierSeries in the Wannier basis of H, or "velocities":
+    velocity_operators(H, basis) of the cache's own H with the real parts of all products a <= b as components, in the order of
+    velocity_components(d).  `components`: entries i (|M^i|^2), (i, j) (Re M^i conj(M^j)) or (i, j, "re" | "im"); None: |M^i|^2 of
+    every operator.  Whole bands only: no occupation factors, no 1 / w weights.  At a degenerate level only the sum of a
+    component over all pairs between two levels is defined."""
+
+    def __init__(self, nocc=None, lower=None, upper=None, operators=None, components=None, basis=None):
+        if (nocc is None) == (lower is None and upper is None) or (lower is None) != (upper is None):
+            raise ValueError("BandPairs: give exactly one of nocc and lower + upper")
+        if nocc is not None:
+            if not isinstance(nocc, (int, np.integer)) or nocc < 1:
+                raise ValueError(f"BandPairs: nocc = {nocc!r} is not a positive number of bands")
+            self.nocc, self.ranges = int(nocc), None
+        else:
+            self.nocc, self.ranges = None, pair_ranges(lower, upper, None, "BandPairs")
+        self.basis = basis
+        if isinstance(operators, str):
+            if operators != "velocities":
+                raise ValueError(f"BandPairs: operators = {operators!r} is neither 'velocities', None nor a sequence of FourierSeries")
+            if components is not None:
+                raise ValueError("BandPairs: operators = 'velocities' brings its own components (the real parts of all products a <= b)")
+            self.operators, self.components = "velocities", None
+            return
+        if basis is not None:
+            raise ValueError("BandPairs: basis goes with operators = 'velocities'")
+        if operators is None:
+            if components is not None:
+                raise ValueError("BandPairs: components without operators")
+            self.operators, self.components = None, None
+            return
+        ops = list(operators) if isinstance(operators, (list, tuple)) else [operators]
+        if not 1 <= len(ops) <= L.LTM_PAIRS_MAX_OPS:
+            raise ValueError(f"BandPairs: {len(ops)} operators, 1..{L.LTM_PAIRS_MAX_OPS} are taken")
+        self.operators = tuple(ops)
+        comps = pair_components(components, len(ops), "BandPairs")
+        self.components = None if comps is None else tuple((int(i), int(j), "im" if part else "re") for i, j, part in comps)
+
+    def resolve(self, h):
+        """((v0, nv), (c0, nc), operators, components) for the Hamiltonian series `h`; ValueError when the ranges do not fit its
+        bands or make more than 64 pairs."""
+        if self.nocc is not None:
+            if self.nocc >= h.n:
+                raise ValueError(f"BandPairs: nocc = {self.nocc} leaves no upper band of the {h.n} bands")
+            v0, nv, c0, nc = pair_ranges((0, self.nocc), (self.nocc, h.n - self.nocc), h.n, "BandPairs")
+        else:
+            v0, nv, c0, nc = pair_ranges((self.ranges[0], self.ranges[1]), (self.ranges[2], self.ranges[3]), h.n, "BandPairs")
+        if isinstance(self.operators, str):
+            return (v0, nv), (c0, nc), velocity_operators(h, self.basis), tuple((a, b, "re") for a, b in velocity_components(h.d))
+        return (v0, nv), (c0, nc), None if self.operators is None else list(self.operators), self.components
 
 
 def velocity_components(d):
@@ -119,11 +176,23 @@ class LTM(DOSAlgorithm):
     -Im G_A(E + i eta) / pi as [nE, ncomp] ([ncomp] for a scalar domain), from the corner weights of every simplex
     (DeviceRule.ltm_green with `elements`, `green_weighted`): with "orbitals" the diagonal G_aa of the local Green's function.
     `cumulative` and `correction` raise ValueError with `eta`, a k-sharded series NotImplementedError.  Without `eta`
-    nothing changes."""
+    nothing changes.
+
+    `pairs=BandPairs(...)` scans band PAIRS instead of bands: the domain is then the transition energies w, and the solution is
+    the joint density of states J(w) or, with operators, the interband spectra `u` [nw, ncomp] (DeviceRule.ltm_pairs: the pair
+    energies e_c - e_v are the eigenvalue planes of a rule of their own, the interband products its attached elements).
+    `cumulative`, `correction` and `eta` keep their meaning on the pair rule; with `eta` the solution is complex,
+    sum_vc int dk M M^* / (w + i eta - (e_c - e_v)): -Im / pi is the broadened spectrum, Re its Kramers-Kronig partner.
+    `correction` needs operators.  Refused when the cache is made: `pairs` with `elements`; `pairs` with operators and
+    symmetric=True (matrix elements are not invariant; without operators symmetric=True gives the JDOS from irreducible
+    nodes); a k-sharded series (NotImplementedError); more than 64 pairs."""
 
     def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None,
-                 correction=False, eta=None):
+                 correction=False, eta=None, pairs=None):
         self.npt = int(npt)
+        if pairs is not None and not isinstance(pairs, BandPairs):
+            raise ValueError(f"LTM: pairs = {pairs!r} is not a BandPairs")
+        self.pairs = pairs
         if eta is not None:
             eta = float(eta)
             if not (np.isfinite(eta) and eta > 0.0):
@@ -140,7 +209,7 @@ class LTM(DOSAlgorithm):
         self.correction = bool(correction)
         if self.correction and not self.cumulative:
             raise ValueError("LTM: correction=True corrects the state sum N_A: it needs cumulative=True (the DOS has no correction)")
-        if self.correction and elements is None:
+        if self.correction and elements is None and not (pairs is not None and pairs.operators is not None):
             raise ValueError("LTM: correction=True needs elements (the correction of the unweighted state count is zero)")
         if not (isinstance(eigenvectors, str) and eigenvectors in ("host", "device")):
             raise ValueError(f"LTM: eigenvectors = {eigenvectors!r} is neither 'host' nor 'device'")
@@ -190,7 +259,32 @@ class DOSCache:
         object.__setattr__(self, name, value)
 
 
-def _init_cacheval(h, domain, p, alg):
+def _pair_rule(h, p, alg, prev):
+    """The pair rule of an LTM(pairs=...) cache: made from the source rule the cache would scan without `pairs` (kept by the pair
+    rule as its `source`), or `prev`, the cache's pair rule so far, filled again from the series' current coefficients."""
+    pairs = alg.pairs
+    if alg.elements is not None:
+        raise ValueError("LTM: pairs and elements do not go together (the elements of a pair rule are its interband products)")
+    symmetric = alg.symmetric and p.syms is not None and len(p.syms) > 1
+    if pairs.operators is not None and alg.symmetric:
+        raise ValueError("LTM: pairs with operators need symmetric=False (interband matrix elements are not invariant under the "
+                         "zone's symmetries, and an unfolded rule stores no H(k))")
+    lower, upper, ops, comps = pairs.resolve(h)
+    if any(_ksharded(dev) for dev in h._dev.values()):  # (the copies the series has: no device is asked for the refusal)
+        raise NotImplementedError("LTM(pairs=...) on a k-sharded series is not implemented: a pair rule is made from a whole grid")
+    h.invalidate()  # coefficients may have been mutated in place: re-upload, rules refill lazily
+    dev = h.device()
+    if isinstance(prev, PairRule) and not prev._closed:
+        if prev.dev is dev and prev.npt == alg.npt and (prev.lower, prev.upper) == (range(lower[0], sum(lower)), range(upper[0], sum(upper))):
+            prev.operators = [] if ops is None else list(ops)  # ("velocities": those of the Hamiltonian the cache holds now)
+            prev.refill()
+            return prev
+        prev.close()  # another series, grid or ranges: its energies and elements leave the device now, not with the collector
+    src = dev.rule(alg.npt, p.syms, L.WANT_EIG).unfold() if symmetric else dev.rule(alg.npt, None, L.WANT_EIG)
+    return src.ltm_pairs(lower, upper, ops, comps)
+
+
+def _init_cacheval(h, domain, p, alg, prev=None):
     """get_ggr_data on the GPU: eigenvalues + band velocities at every (irreducible) PTR node stay
     resident in HBM.  ref: src/dos_ggr.jl:1-44."""
     if not isinstance(alg, (GGR, LTM)):
@@ -208,6 +302,8 @@ def _init_cacheval(h, domain, p, alg):
     if isinstance(alg, LTM) and alg.symmetric and _is_expectation(alg.elements) and p.syms is not None and len(p.syms) > 1:
         raise ValueError("LTM: band expectation values (elements = 'velocities' or a BandExpectation) need symmetric=False (they "
                          "are not invariant under the zone's symmetries, and an unfolded rule stores no H(k))")
+    if isinstance(alg, LTM) and alg.pairs is not None:
+        return _pair_rule(h, p, alg, prev)
     h.invalidate()  # coefficients may have been mutated in place (test/dos.jl:123): re-upload, rules refill lazily
     if isinstance(alg, LTM) and alg.eta is not None and _ksharded(h.device()):
         raise NotImplementedError("LTM(eta=...) on a k-sharded series is not implemented: the trace of the Green's function is "
@@ -261,6 +357,8 @@ class _DeviceExpectation:
 def _ltm_elements(rule, alg):
     """What an LTM cache hands DeviceRule.ltm as `elements`: None, "energy", the host array [ncomp, nk, n] computed
     from the rule's current values, or the request for orbital weights made on the device."""
+    if isinstance(alg, LTM) and alg.pairs is not None and rule is not None:
+        return None if alg.pairs.operators is None else "attached"  # (the pair rule made them itself)
     if not isinstance(alg, LTM) or alg.elements is None or rule is None:
         return None
     if isinstance(alg.elements, BandExpectation):
@@ -302,6 +400,8 @@ def _ltm_attach(rule, el):
 
 def _ltm_solve(c, Es):
     rule, el = c.cacheval, c.elements
+    if c.alg.eta is not None and c.alg.pairs is not None:  # the broadened spectrum (-Im / pi) with its Kramers-Kronig partner (Re)
+        return rule.ltm_green(Es + 1j * c.alg.eta, elements=el)
     if c.alg.eta is not None:
         zs = Es + 1j * c.alg.eta
         if el is None:
@@ -315,6 +415,14 @@ def _ltm_solve(c, Es):
     return rule.ltm(Es, states=c.alg.cumulative, elements="attached", correction=c.alg.correction)
 
 
+def _refresh(c):
+    """A cache whose H was assigned builds its eigen-data again (a pair rule is filled again in place) before its next use."""
+    if c.isfresh:
+        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg, c.cacheval)
+        c.elements = _ltm_elements(c.cacheval, c.alg)
+        c.isfresh = False
+
+
 def init(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):
     """ref: src/dos_interfaces.jl:82-86."""
     checkkwargs(kwargs)
@@ -323,10 +431,7 @@ def init(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):
 
 def solve_(c: DOSCache):
     """solve!(cache).  ref: src/dos_interfaces.jl:104-112, dos_solve src/dos_ggr.jl:46-56."""
-    if c.isfresh:
-        c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
-        c.elements = _ltm_elements(c.cacheval, c.alg)
-        c.isfresh = False
+    _refresh(c)
     if not isinstance(c.alg, (GGR, LTM)):
         raise ValueError("unknown DOS algorithm")
     scalar = np.ndim(c.domain) == 0
@@ -336,7 +441,7 @@ def solve_(c: DOSCache):
     u = _ltm_solve(c, Es) if isinstance(c.alg, LTM) else c.cacheval.ggr(Es)
     if u.ndim == 2:
         return DOSSolution(u[0].copy() if scalar else u, None, True, -1)
-    return DOSSolution(float(u[0]) if scalar else u, None, True, -1)
+    return DOSSolution(u[0].item() if scalar else u, None, True, -1)
 
 
 def fermi_level(prob_or_cache, nstates, tol=1e-10):
@@ -573,6 +678,52 @@ def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correctio
     Es = np.array([fermi_level(c, nstates)[0]]) if nstates is not None else np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
     rho = c.cacheval.ltm_density_matrix(Es, states=kind == "states", correction=bool(correction), orbitals=orbitals)
     return (rho[0], float(Es[0])) if scalar else (rho, Es)
+
+
+def _pairs_cache(prob_or_cache, who, npt, pairs, **alg):
+    if isinstance(prob_or_cache, DOSCache):
+        c = prob_or_cache
+        if not (isinstance(c.alg, LTM) and c.alg.pairs is not None):
+            raise ValueError(f"{who} needs an LTM(pairs=BandPairs(...)) cache")
+        if pairs is not None:
+            raise ValueError(f"{who}: a cache brings its own band pairs")
+        return c
+    if pairs is None:
+        raise ValueError(f"{who}: give the band pairs (nocc, or lower and upper)")
+    return init(prob_or_cache, LTM(npt=npt, pairs=pairs, **alg))
+
+
+def joint_dos(prob_or_cache, ws, nocc=None, lower=None, upper=None, npt=50, cumulative=False, symmetric=False):
+    """The joint density of states J(w) = sum_vc int dk delta(w - (e_c(k) - e_v(k))) at the transition energies `ws`, per unit
+    cell, [nw] (with `cumulative` its integral, the number of pairs below w): DeviceRule.ltm on the pair rule of an
+    LTM(pairs=BandPairs(...)) cache, or of a DOSProblem with the pairs `nocc` or `lower` + `upper` on a grid of `npt` points
+    (`symmetric=True`: eigenvalues from the irreducible nodes of the problem's zone)."""
+    pairs = None if nocc is None and lower is None and upper is None else BandPairs(nocc=nocc, lower=lower, upper=upper)
+    c = _pairs_cache(prob_or_cache, "joint_dos", npt, pairs, cumulative=cumulative, symmetric=symmetric)
+    _refresh(c)
+    ws = np.ascontiguousarray(np.asarray(ws, dtype=np.float64).reshape(-1))
+    return c.cacheval.ltm(ws, states=c.alg.cumulative)
+
+
+def interband(prob_or_cache, ws_or_zs, nocc=None, lower=None, upper=None, operators="velocities", components=None, basis=None, npt=50,
+              cumulative=False, correction=False):
+    """The interband spectra S_ij = sum_vc int dk M^i_vc conj(M^j_vc) delta(w - (e_c - e_v)) at real transition energies, [nw, ncomp]
+    (with `cumulative` their integrals, with `correction` Bloechl's curvature correction on those), or at complex energies z
+    (Im z != 0) sum_vc int dk M M^* / (z - (e_c - e_v)), complex128 [nz, ncomp]: -Im / pi at z = w + i eta is the spectrum
+    broadened by eta, Re its Kramers-Kronig partner.  DeviceRule.ltm / ltm_green with the attached interband products of the
+    pair rule of an LTM(pairs=BandPairs(..., operators=...)) cache, or of a DOSProblem with the pairs `nocc` or `lower` + `upper`
+    and `operators` ("velocities": velocity_operators(H, basis)) on a grid of `npt` points."""
+    pairs = None
+    if not (nocc is None and lower is None and upper is None):
+        pairs = BandPairs(nocc=nocc, lower=lower, upper=upper, operators=operators, components=components, basis=basis)
+    c = _pairs_cache(prob_or_cache, "interband", npt, pairs, cumulative=cumulative, correction=correction)
+    if c.alg.pairs.operators is None:
+        raise ValueError("interband needs band pairs with operators (joint_dos scans the energies alone)")
+    _refresh(c)
+    x = np.asarray(ws_or_zs).reshape(-1)
+    if np.iscomplexobj(x):
+        return c.cacheval.ltm_green(x, elements="attached")
+    return c.cacheval.ltm(np.ascontiguousarray(x, dtype=np.float64), states=c.alg.cumulative, elements="attached", correction=c.alg.correction)
 
 
 def solve(prob: DOSProblem, alg: DOSAlgorithm, **kwargs):

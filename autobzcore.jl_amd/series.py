@@ -444,6 +444,57 @@ def green_node_weight_zs(zs, who="ltm_green_node_weights"):
     return zs
 
 
+def band_range(r, who, name):
+    """A band range given as a `range` (step 1) or (start, count) -> (start, count); ValueError otherwise."""
+    if isinstance(r, range):
+        if r.step != 1 or len(r) < 1:
+            raise ValueError(f"{who}: {name} = {r!r} is not a non-empty range of consecutive bands")
+        return int(r.start), len(r)
+    try:
+        start, count = r
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {name} = {r!r} is neither a range nor (start, count)") from None
+    if not all(isinstance(v, (int, np.integer)) for v in (start, count)) or start < 0 or count < 1:
+        raise ValueError(f"{who}: {name} = {r!r} is neither a range nor (start, count) with start >= 0, count >= 1")
+    return int(start), int(count)
+
+
+def pair_ranges(lower, upper, n=None, who="ltm_pairs"):
+    """(v0, nv, c0, nc) of a lower and an upper band range; ValueError, before the library is called, for ranges that overlap
+    or are out of order, that leave the n bands, or that make more than 64 pairs."""
+    v0, nv = band_range(lower, who, "lower")
+    c0, nc = band_range(upper, who, "upper")
+    if v0 + nv > c0:
+        raise ValueError(f"{who}: the lower bands [{v0}, {v0 + nv}) must lie below the upper bands [{c0}, {c0 + nc})")
+    if n is not None and c0 + nc > n:
+        raise ValueError(f"{who}: the upper bands [{c0}, {c0 + nc}) leave the {n} bands of the series")
+    if nv * nc > L.MAX_BANDS:
+        raise ValueError(f"{who}: {nv} x {nc} = {nv * nc} pairs, a pair rule takes {L.MAX_BANDS}; take a window of bands around the gap")
+    return v0, nv, c0, nc
+
+
+def pair_components(components, nops, who="ltm_pairs"):
+    """The components of a pair rule as an int32 array [ncomp, 3] -- (i, j, part): Re (0) or Im (1) of M^i conj(M^j) -- or None
+    for |M^i|^2 of the nops operators in order.  Entries: i, (i, j) or (i, j, "re" | "im"); ValueError, before the library is
+    called, for none or more than 16 of them, a malformed entry and an operator index outside 0..nops-1."""
+    if components is None:
+        return None
+    out = []
+    for c in components:
+        t = (c, c, "re") if np.ndim(c) == 0 else tuple(c)
+        if len(t) == 2:
+            t = (t[0], t[1], "re")
+        if len(t) != 3 or not all(isinstance(v, (int, np.integer)) for v in t[:2]) or t[2] not in ("re", "im"):
+            raise ValueError(f"{who}: component {c!r} is neither an operator index i, a pair (i, j) nor (i, j, 're' | 'im')")
+        i, j = int(t[0]), int(t[1])
+        if not (0 <= i < nops and 0 <= j < nops):
+            raise ValueError(f"{who}: component {c!r} names an operator outside 0..{nops - 1}")
+        out.append((i, j, 0 if t[2] == "re" else 1))
+    if not 1 <= len(out) <= L.LTM_MAX_COMP:
+        raise ValueError(f"{who}: {len(out)} components, a call takes 1..{L.LTM_MAX_COMP}")
+    return np.ascontiguousarray(np.array(out, dtype=np.int32).reshape(-1, 3))
+
+
 class DeviceRule:
     """abz_rule handle: FourierPTR (syms None) or FourierMonkhorstPack values resident in HBM.
     ref: src/fourier.jl:127-174,210-277."""
@@ -541,6 +592,16 @@ class DeviceRule:
     def __len__(self):
         return self.nk
 
+    @property
+    def nbands(self):
+        """Bands of the rule's eigenvalue planes, attached elements and weight blocks (abz_rule_ltm_bands): the series' n, or
+        the nv nc pseudo-bands of a PairRule."""
+        if self._h is None:
+            return self.dev.s.n
+        nb = C.c_int(0)
+        L.check(L.lib().abz_rule_ltm_bands(self._h, C.byref(nb)))
+        return int(nb.value)
+
     def rebuild(self):
         """Re-evaluate all cached values in place from the series' current coefficients (async)."""
         if self._closed:
@@ -594,7 +655,7 @@ class DeviceRule:
         X = np.empty((nk, d)) if x else None
         W = np.empty(nk) if w else None
         Hb = np.empty((nk, n * n, 2)) if H else None
-        E = np.empty((nk, n)) if eig else None
+        E = np.empty((nk, self.nbands)) if eig else None
         V = np.empty((nk, d, n)) if vel else None
         ptr = lambda a: a.ctypes.data_as(L.c_f64p) if a is not None else None
         if self.h is not None:
@@ -662,8 +723,8 @@ class DeviceRule:
         A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
         if A.ndim == 2:
             A = A[None]
-        if A.ndim != 3 or A.shape[1:] != (self.nk, s.n):
-            raise ValueError(f"ltm_elements: elements of shape {A.shape}, expected [ncomp, {self.nk}, {s.n}]")
+        if A.ndim != 3 or A.shape[1:] != (self.nk, self.nbands):
+            raise ValueError(f"ltm_elements: elements of shape {A.shape}, expected [ncomp, {self.nk}, {self.nbands}]")
         L.check(L.lib().abz_rule_ltm_elements(self.h, A.ctypes.data_as(L.c_f64p), A.shape[0]))
         self._ltm_ncomp = A.shape[0]
 
@@ -703,6 +764,18 @@ class DeviceRule:
         L.check(L.lib().abz_rule_ltm_projectors(h, pr.ctypes.data_as(L.c_i32p), len(pr)))
         self._ltm_ncomp = int(np.where(pr[:, 0] == pr[:, 1], 1, 2).sum())
 
+    def _operator_rules(self, ops, who):
+        """The operators of `ltm_expectation` / `ltm_pairs` as rules with H planes on this rule's grid: a FourierSeries through
+        its copy on this rule's context and that copy's cached rule(npt, None, WANT_H), a DeviceRule as it is."""
+        rules = []
+        for i, op in enumerate(ops):
+            if isinstance(op, FourierSeries):
+                op = op.device(self.dev.ctx).rule(self.npt, None, L.WANT_H)
+            elif not isinstance(op, DeviceRule):
+                raise ValueError(f"{who}: operators[{i}] = {op!r} is neither a FourierSeries nor a DeviceRule")
+            rules.append(op)
+        return rules
+
     def ltm_expectation(self, operators, components=None):
         """Attach band expectation values of operator series as matrix elements, computed on the device from H(k) and the
         operators' values on the same grid (abz_rule_ltm_expectation): q_i = Re u_b^H Hermitian(O_i(k)) u_b for operator i, band b
@@ -726,13 +799,7 @@ class DeviceRule:
             raise ValueError(f"ltm_expectation: {len(ops)} operators, a call takes 1..{L.LTM_EXPECT_MAX_OPS}")
         comps = expectation_components(components, len(ops), "ltm_expectation")
         h = self.h  # (a stale rule is refilled here)
-        rules = []
-        for i, op in enumerate(ops):
-            if isinstance(op, FourierSeries):
-                op = op.device(self.dev.ctx).rule(self.npt, None, L.WANT_H)
-            elif not isinstance(op, DeviceRule):
-                raise ValueError(f"ltm_expectation: operators[{i}] = {op!r} is neither a FourierSeries nor a DeviceRule")
-            rules.append(op)
+        rules = self._operator_rules(ops, "ltm_expectation")
         handles = (C.c_void_p * len(rules))(*[getattr(r.h, "value", None) for r in rules])  # (stale operator rules are refilled here)
         L.check(L.lib().abz_rule_ltm_expectation(h, handles, len(rules), None if comps is None else comps.ctypes.data_as(L.c_i32p),
                                                  len(rules) if comps is None else len(comps)))
@@ -789,9 +856,18 @@ class DeviceRule:
         L.check(L.lib().abz_rule_ltm_elements_export(h, C.byref(nc), None))
         if nc.value == 0:
             return None
-        A = np.empty((nc.value, self.nk, self.dev.s.n))
+        A = np.empty((nc.value, self.nk, self.nbands))
         L.check(L.lib().abz_rule_ltm_elements_export(h, C.byref(nc), A.ctypes.data_as(L.c_f64p)))
         return A
+
+    def ltm_elements_ptr(self):
+        """(device address, bytes, ncomp) of the resident element block (abz_rule_ltm_elements_ptr): double
+        [nk / npt, ncomp * nbands, row], row = npt rounded up to a multiple of 16, zeros in the padding columns; (0, 0, 0) when
+        nothing is attached."""
+        self._ltm_refuse_shard("ltm_elements_ptr")
+        base, nb, nc = C.c_void_p(), C.c_int64(0), C.c_int(0)
+        L.check(L.lib().abz_rule_ltm_elements_ptr(self.h, C.byref(base), C.byref(nb), C.byref(nc)))
+        return int(base.value or 0), int(nb.value), int(nc.value)
 
     def ltm(self, Es, states=False, elements=None, correction=False):
         """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
@@ -897,7 +973,7 @@ class DeviceRule:
             raise ValueError(f"ltm_node_weights: {len(Es)} energies, a call takes 1..{L.LTM_NODEW_MAX_E}")
         what = L.LTM_STATES_CORRECTED if correction else (L.LTM_STATES if states else L.LTM_DOS)
         h = self.h  # (a stale rule is refilled here, which drops the weights it held)
-        out = np.empty((len(Es), self.nk, self.dev.s.n)) if export else None
+        out = np.empty((len(Es), self.nk, self.nbands)) if export else None
         L.check(L.lib().abz_rule_ltm_node_weights(h, Es.ctypes.data_as(L.c_f64p), len(Es), what,
                                                   out.ctypes.data_as(L.c_f64p) if export else None))
         return out
@@ -968,7 +1044,7 @@ class DeviceRule:
         self._ltm_refuse_shard("ltm_green_node_weights")
         zs = green_node_weight_zs(zs)
         h = self.h  # (a stale rule is refilled here, which drops the weights it held)
-        out = np.empty((len(zs), self.nk, self.dev.s.n), dtype=np.complex128) if export else None
+        out = np.empty((len(zs), self.nk, self.nbands), dtype=np.complex128) if export else None
         L.check(L.lib().abz_rule_ltm_green_node_weights(h, zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs),
                                                         out.view(np.float64).ctypes.data_as(L.c_f64p) if export else None))
         return out
@@ -1044,6 +1120,19 @@ class DeviceRule:
         ef, nf = C.c_double(0.0), C.c_double(0.0)
         L.check(L.lib().abz_rule_ltm_fermi(self.h, float(nstates), float(tol), C.byref(ef), C.byref(nf)))
         return ef.value, nf.value
+
+    def ltm_pairs(self, lower, upper, operators=None, components=None):
+        """The pair rule of two band ranges of this rule (abz_rule_ltm_pairs): a whole periodic grid whose "bands" are the
+        differences e_c(k) - e_v(k), v in `lower`, c in `upper` (each a `range` or (start, count); lower below upper, at most 64
+        pairs), pseudo-band (v - v0) nc + (c - c0).  Its `ltm(ws)` is the joint density of states.  With `operators` (1..4
+        FourierSeries in the Wannier basis of H, or DeviceRules with H planes, as for `ltm_expectation`) it carries the
+        interband products of M^i_vc = u_v^H Hermitian(O_i) u_c as attached elements: `components` entries i (|M^i|^2), (i, j)
+        (Re M^i conj(M^j)) or (i, j, "re" | "im"); None: |M^i|^2 for every operator.  `ltm(ws, elements="attached")` is then the
+        interband spectrum, `ltm_green(zs, elements="attached")` the broadened one (-Im / pi) with its Kramers-Kronig partner
+        (Re).  At a degenerate level only the sum of a component over all pairs between two levels is defined.  Whole bands
+        only: no occupation factors."""
+        self._ltm_refuse_shard("ltm_pairs")
+        return PairRule(self, lower, upper, operators, components)
 
     def unfold(self):
         """The full-grid eigenvalue rule of this symmetric rule (abz_rule_ltm_unfold): every grid point gets the
@@ -1141,3 +1230,82 @@ class UnfoldedRule(DeviceRule):
         out = np.zeros((nz, len(self.source), self.dev.s.n), dtype=np.complex128)
         L.check(L.lib().abz_rule_ltm_green_node_weights_fold(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out
+
+
+class PairRule(DeviceRule):
+    """Whole periodic grid of band-pair energies e_c(k) - e_v(k) with, optionally, interband products as attached elements
+    (DeviceRule.ltm_pairs, abz_rule_ltm_pairs).  `nbands` = nv nc pseudo-bands, `lower` / `upper` the ranges; `ltm`,
+    `ltm_green`, `ltm_elements`, `ltm_elements_export`, `ltm_node_weights`, `ltm_green_node_weights` with their dots, `ltm_fermi`
+    and `export(x, w, eig)` are those of a full-grid rule of nbands bands.  It holds no H(k), no eigenvectors and no plan: what
+    needs them (`ltm_orbitals`, `ltm_projectors`, `ltm_expectation`, `ltm_density_matrix`, `ltm_green_matrix`, `reduce`, a pair rule
+    of it) raises with the library's message.  It follows the series: when the coefficients changed, the source is refilled
+    and `refill` repeats the call into the same handle."""
+
+    def __init__(self, source: DeviceRule, lower, upper, operators=None, components=None):
+        dev = self.dev = source.dev
+        d = dev.s.d
+        self.source = source
+        self.npt = source.npt
+        self.want = L.WANT_EIG
+        self.syms = None  # a full grid to every reader
+        self.nsyms = 1
+        self.shard = None
+        self.nk = self.nk_local = self.npt ** d
+        v0, nv, c0, nc = pair_ranges(lower, upper, dev.s.n if not isinstance(source, PairRule) else None)
+        self.lower, self.upper = range(v0, v0 + nv), range(c0, c0 + nc)
+        ops = [] if operators is None else (list(operators) if isinstance(operators, (list, tuple)) else [operators])
+        if operators is not None and not 1 <= len(ops) <= L.LTM_PAIRS_MAX_OPS:
+            raise ValueError(f"ltm_pairs: {len(ops)} operators, a call takes 1..{L.LTM_PAIRS_MAX_OPS}")
+        if not ops and components is not None:
+            raise ValueError("ltm_pairs: components without operators")
+        self.operators = ops
+        self._comps = pair_components(components, len(ops)) if ops else None
+        self._hbox = C.c_void_p()
+        self._fill()
+        self._adopt(self._hbox)
+        self._ltm_ncomp = self._ncomp
+        self.nbytes = 8 * nv * nc * (1 + self._ncomp) * self.nk
+
+    @property
+    def _ncomp(self):
+        return 0 if not self.operators else (len(self.operators) if self._comps is None else len(self._comps))
+
+    def _fill(self):
+        src = self.source.h  # (a stale source is refilled here)
+        rules = self.source._operator_rules(self.operators, "ltm_pairs")
+        handles = (C.c_void_p * max(len(rules), 1))(*[getattr(r.h, "value", None) for r in rules])  # (stale operator rules are refilled here)
+        comps = self._comps
+        L.check(L.lib().abz_rule_ltm_pairs(src, self.lower.start, len(self.lower), self.upper.start, len(self.upper),
+                                           handles if rules else None, len(rules), None if comps is None else comps.ctypes.data_as(L.c_i32p),
+                                           self._ncomp, C.byref(self._hbox)))
+
+    def refill(self, source=None):
+        """Energies and elements again from `source` (default: the rule this one was made from) into the same handle: the call
+        to make after the series changed.  Weight blocks are dropped, elements attached by hand are replaced by the rule's own."""
+        if self._closed:
+            raise L.AbzError("DeviceRule was closed")
+        if source is not None:
+            self.source = source
+        elif self.source._closed:  # the series' rule cache let it go: the same grid again
+            self.source = self.dev.rule(self.npt, self.source.syms, self.source.want)
+        self.generation = self.dev.generation
+        self._fill()
+        self._ltm_ncomp = self._ncomp
+
+    @property
+    def h(self):
+        """The abz_rule handle; when the series moved on, the source is refilled and the pair rule filled again."""
+        if self._closed:
+            raise L.AbzError("DeviceRule was closed")
+        if self.generation != self.dev.generation:
+            self.refill()
+        return self._h
+
+    def rebuild(self):
+        if self._closed:
+            raise L.AbzError("DeviceRule was closed")
+        self.source.rebuild()
+        self.refill()
+
+    def unfold(self):
+        raise ValueError("unfold: the rule is a full grid already (no symmetries to unfold)")

@@ -350,6 +350,11 @@ int abz_rule_ltm_expectation(abz_rule* r, abz_rule* const* ops, int nops, const 
 /* Attached elements back to the host: *ncomp (0 if none), and, if A != NULL, A [ncomp][nk][n] in the order
  * abz_rule_ltm_elements takes them. */
 int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A);
+/* The resident element block as it lies on the device: *base (NULL if nothing is attached), *nbytes and *ncomp; any pointer may
+ * be NULL.  Layout: double [ntiles][ncomp * nb planes][row], ntiles = nk / npt grid lines, plane c * nb + b = component c of band
+ * b (nb: abz_rule_ltm_bands), row = npt rounded up to a multiple of 16; the padding columns npt .. row-1 hold zeros.  The address
+ * is valid until the elements are replaced or dropped.  Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_elements_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* ncomp);
 #define ABZ_LTM_A_ELEMENTS 0   /* the attached elements, ncomp components */
 #define ABZ_LTM_A_ENERGY 1     /* A_b(k) = e_b(k) itself, 1 component, nothing attached needed */
 /* out [nE][ncomp]: g_A(E) (ABZ_LTM_DOS) or N_A(E) (ABZ_LTM_STATES), per unit cell, summed over bands; A is interpolated
@@ -382,6 +387,53 @@ int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, dou
  * message counts the uncovered points).  ABZ_ERR_UNSUPPORTED: src is a full grid or a slab, or npt^d >= 2^31.  Costs 4 B
  * per grid point for the orbit map beside the n planes. */
 int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule** out);
+/* Pair rules: joint density of states and interband spectra from the scans above.
+ * The difference of two linearly interpolated bands is linear in a simplex, so Delta_p(k) = e_c(k) - e_v(k) of a lower band v and an
+ * upper band c is a pseudo-band the tetrahedron scans treat exactly like a band.  abz_rule_ltm_pairs makes, from the lower range
+ * [v0, v0 + nv) and the upper range [c0, c0 + nc) of the ascending bands of `src` (0 <= v0, nv >= 1, nc >= 1, v0 + nv <= c0,
+ * c0 + nc <= n, nv nc <= ABZ_MAX_BANDS), a whole periodic grid of nb = nv nc pseudo-bands p = (v - v0) nc + (c - c0), want =
+ * ABZ_WANT_EIG.  An insulator with nocc filled bands is (0, nocc, nocc, n - nocc); a model of many bands takes a window around the
+ * gap.  On the result
+ *      abz_rule_ltm                     J(w)    = sum_vc int dk delta(w - Delta_vc)                    (and its cumulative)
+ *      abz_rule_ltm_weighted            S_ij(w) = sum_vc int dk M^i_vc conj(M^j_vc) delta(w - Delta_vc) (cumulative, corrected)
+ *      abz_rule_ltm_green[_weighted]    sum_vc int dk M M^* / (z - Delta_vc): -Im / pi the broadened spectrum, Re its Kramers-Kronig partner
+ * and abz_rule_ltm_elements, _elements_export, _fermi, _node_weights(+ _ptr, _dot), _green_node_weights(+ _ptr, _dot) and
+ * abz_rule_export (x, w, eig [nk][nb]) work unchanged: they size themselves by abz_rule_ltm_bands, which is n for every other
+ * rule.  With O = dH/dk, S is the absorptive part of the optical conductivity up to prefactors and 1 / w.
+ * Energies: Delta = e_c - e_v, one subtraction per node from the eigenvalue planes of `src` as they are (never from another
+ * eigen-solve): the spectra sit on the eigenvalues the scans of `src` see.
+ * nops == 0: ops, comps and ncomp are ignored, the result has energies only, nothing with eigenvectors is launched; src is any
+ * whole grid abz_rule_ltm takes (1...64 bands, rules of abz_rule_ltm_unfold included).
+ * 1 <= nops <= ABZ_LTM_PAIRS_MAX_OPS: src and ops[i] are what abz_rule_ltm_expectation takes (src: 2...32 bands, a Hermitian
+ * series, a whole grid that was not unfolded, H(k) from its own planes or a transient rule of the series' CURRENT coefficients;
+ * ops[i]: H planes of Hermitian series of the same context, npt, d, n, not row-major).  Component (i, j, part) = comps[c][0..2] is
+ * Re (part 0) or Im (part 1) of M^i_vc conj(M^j_vc), M^i_vc = u_v^H Hermitian(O_i) u_c, which the phases of u_v and u_c do not
+ * change; comps == NULL: the nops components |M^i_vc|^2 (ncomp = nops).  1 <= ncomp <= ABZ_LTM_MAX_COMP; duplicates are fine.  The
+ * block is attached to the result as abz_rule_ltm_elements would attach it ([ncomp][nk][nb]).
+ * *out == NULL: a new rule; it holds its own reference on the series and does not depend on src afterwards.  *out != NULL: a pair
+ * rule of the same series, npt, ranges, operator count and components, filled again in place -- the call to make after
+ * abz_rule_rebuild(src); its weight blocks are dropped (they described the old energies).  Energies and elements are complete
+ * before they replace anything: a refusal or failure leaves *out, src and every attached block as they were.
+ * Degenerate levels: u_v, u_c are some orthonormal bases of their eigenspaces; only the SUM of a component over all pairs between
+ * two levels is defined (it is what a scan adds up, since those pairs share Delta).
+ * Not handled: partial occupations (the factor f_v (1 - f_c) of a metal restricts each simplex to its occupied part; the ranges
+ * here are whole bands), weights Delta^-m inside the elements (divide exported elements by exported energies and attach them
+ * with abz_rule_ltm_elements), the Berry-connection term of the Wannier velocity (operators are what the caller passes), 33...64
+ * bands with operators, slabs, more than ABZ_MAX_BANDS pairs per rule.
+ * A pair rule has no H(k), eigenvectors or plan: abz_rule_ltm_orbitals, _projectors, _expectation, _density_matrix,
+ * _green_node_weights_matrix, _halo, abz_rule_rebuild, abz_rule_reduce and abz_rule_ltm_pairs with a pair rule as src answer
+ * ABZ_ERR_UNSUPPORTED, launch nothing and leave it as it was.
+ * ABZ_ERR_ARG: range errors, one band with operators, nops outside 0..ABZ_LTM_PAIRS_MAX_OPS, ncomp outside 1..ABZ_LTM_MAX_COMP, an
+ * index or part out of range, NULL pointers, *out not a matching pair rule, the operator errors of abz_rule_ltm_expectation.
+ * ABZ_ERR_UNSUPPORTED: slabs, node lists, with operators more than 32 bands or an unfolded src.  Kernels: the energies under
+ * ABZ_K_LTM, the elements under ABZ_K_EIG.  Entry points added without a change of ABZ_VERSION. */
+#define ABZ_LTM_PAIRS_MAX_OPS 4
+int abz_rule_ltm_pairs(abz_rule* src, int v0, int nv, int c0, int nc, abz_rule* const* ops, int nops,
+                       const int32_t* comps /* [ncomp][3] or NULL */, int ncomp, abz_rule** out);
+/* *nb: bands of the rule's eigenvalue planes, attached elements and weight blocks: nv nc of a pair rule, n of any other.
+ * abz_rule_info keeps reporting the series' n (the bands of the source) for a pair rule: size the buffers of abz_rule_export's
+ * eig, abz_rule_ltm_elements(_export) and the node weights by *nb, not by that n. */
+int abz_rule_ltm_bands(const abz_rule* r, int* nb);
 /* Tetrahedron scans on a slab: attach the halo plane.  r: a rule of abz_ptr_rule_build_slab over [outer_begin, outer_end) that
  * holds eigenvalues (other `want` bits are fine).  The simplices of the cells of the slab's last plane reach into plane
  * outer_end mod npt; this builds that one plane, eigenvalues only, with the builder of the slab itself (1 / npt of the grid, no

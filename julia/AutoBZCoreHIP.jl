@@ -512,6 +512,63 @@ function ltm_unfold!(u::HIPRule, r::HIPRule, syms, ::Val{d}) where {d}
     return u
 end
 
+function _pair_comps(components)
+    components === nothing && return (C_NULL, 0, Cint[])
+    flat = Cint[]
+    for (i, j, part) in components
+        push!(flat, i - 1, j - 1, part)
+    end
+    return (pointer(flat), length(components), flat)
+end
+function _ltm_pairs(ref, r::HIPRule, lower::UnitRange, upper::UnitRange, ops::AbstractVector{HIPRule}, components)
+    hs = Ptr{Cvoid}[o.h for o in ops]
+    pc, nc, keep = _pair_comps(components)
+    GC.@preserve ops hs keep check(ccall((:abz_rule_ltm_pairs, libabz), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cint}, Cint, Ptr{Ptr{Cvoid}}),
+        r.h, first(lower) - 1, length(lower), first(upper) - 1, length(upper), isempty(hs) ? C_NULL : pointer(hs), length(hs), pc, nc, ref))
+end
+"""
+    ltm_pairs(r, lower, upper; ops=HIPRule[], components=nothing)        -> HIPRule
+    ltm_pairs!(p, r, lower, upper; ops=HIPRule[], components=nothing)    -> p
+    ltm_bands(r)                                                         -> Int
+
+Pair rule of the band ranges `lower` and `upper` (`UnitRange`s of 1-based ascending bands, `lower` below `upper`, at most 64 pairs)
+of the whole-grid rule `r` (`abz_rule_ltm_pairs`): its eigenvalue planes are the differences `e_c(k) - e_v(k)`, pseudo-band
+`(v - v0) nc + (c - c0)`, so `ltm_weighted` and the other tetrahedron scans on it give the joint density of states.  With `ops`
+(1..4 rules that hold H planes of operator series on the same grid, as for `ltm_expectation!`) it carries the interband products of
+`M^i_vc = u_v' Hermitian(O_i) u_c` as attached elements; `components`: `nothing` for `|M^i|^2` of every operator, or at most 16
+entries `(i, j, part)`, 1-based operators, `part` 0 for `Re` and 1 for `Im` of `M^i_vc conj(M^j_vc)`.  At a degenerate level only
+the sum of a component over all pairs between two levels is defined; the ranges are whole bands (no occupation factors).
+`ltm_pairs!` fills `p` again after `r` was rebuilt; `ltm_bands` is the number of bands a rule's planes hold (`nv nc` here).
+"""
+function ltm_pairs(r::HIPRule, lower::UnitRange, upper::UnitRange; ops::AbstractVector{HIPRule}=HIPRule[], components=nothing)
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    _ltm_pairs(ref, r, lower, upper, ops, components)
+    p = HIPRule(ref[], r.nk, r.npt, 1)
+    finalizer(x -> ccall((:abz_rule_destroy, libabz), Cint, (Ptr{Cvoid},), x.h), p)
+end
+function ltm_pairs!(p::HIPRule, r::HIPRule, lower::UnitRange, upper::UnitRange; ops::AbstractVector{HIPRule}=HIPRule[], components=nothing)
+    ref = Ref{Ptr{Cvoid}}(p.h)
+    _ltm_pairs(ref, r, lower, upper, ops, components)
+    return p
+end
+"""
+    ltm_elements_ptr(r) -> (base::Ptr{Cvoid}, nbytes::Int, ncomp::Int)
+
+The resident element block of `r` as it lies on the device (`abz_rule_ltm_elements_ptr`): `[nk / npt][ncomp * ltm_bands(r)][row]`
+doubles, `row` = `npt` rounded up to a multiple of 16, zeros in the padding columns; `(C_NULL, 0, 0)` when nothing is attached.
+"""
+function ltm_elements_ptr(r::HIPRule)
+    base = Ref{Ptr{Cvoid}}(C_NULL); nb = Ref{Int64}(0); nc = Ref{Cint}(0)
+    check(ccall((:abz_rule_ltm_elements_ptr, libabz), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Cint}), r.h, base, nb, nc))
+    return base[], Int(nb[]), Int(nc[])
+end
+function ltm_bands(r::HIPRule)
+    nb = Ref{Cint}(0)
+    check(ccall((:abz_rule_ltm_bands, libabz), Cint, (Ptr{Cvoid}, Ptr{Cint}), r.h, nb))
+    return Int(nb[])
+end
+
 """
     ltm_halo!(r)                              -> r
 
