@@ -12,6 +12,8 @@
 
 #include "../../include/abzhip.h"
 #include "dev_buf.h"
+#include "ltm_block.h"
+#include "plane_view.h"
 
 namespace abz {
 struct ProfScope;
@@ -137,25 +139,6 @@ int energies_deliver(abz_ctx* ctx, EnergyList& el, double* out_host);
 struct SymTables;
 int sym_tables_device(abz_ctx* ctx, int npt, int d, const int32_t* syms, int nsyms, SymTables& out);
 void preload_symptr_code();  // kernels_symptr.hip: force the lazy code-object load
-
-// Tiled planar addressing of rule values: nodes are grouped in tiles of `line_len` consecutive nodes
-// (a grid line, or 64 nodes of an irregular list); a tile stores all its planes back to back, each
-// plane row `pitch` doubles long (pitch >= line_len, multiple of 16 = 128 B).  Element (node k,
-// plane p) = base[(k / line_len) * tile + p * pitch + k % line_len].  One wave writes one tile: a
-// single contiguous ~27 KB HBM region instead of 21 streams 27 MB apart (1.7x the write bandwidth,
-// tools/micro/wtest.hip).
-// The same formula carries the PADDED PLANAR layout of full-grid rules (ABZ_RULE_PLANAR): tile = row (the stride from one
-// grid line to the next inside a plane), pitch = nlines * row (the stride from one plane to the next), so every plane is one
-// dense array of padded rows and all resident waves write it as one front (tools/micro/placement.hip).  `row` is the padded
-// row length either way (columns line_len .. row-1 of a row are padding).
-struct PlaneView {
-    double* base = nullptr;  // first plane of this array inside tile 0
-    int64_t tile = 0;        // doubles from one line (tile) to the next
-    int pitch = 0;           // doubles from one plane to the next
-    int line_len = 1;
-    int row = 0;             // padded row length (multiple of 16 doubles = 128 B)
-    int compact = 0;         // H planes of a Hermitian rule stored as the upper triangle only (ABZ_WANT_H_COMPACT): = n
-};
 
 // Device-resident description of the nodes of a symmetric (irreducible-node) rule: grid indices, weights and the
 // contraction plan (kernels_symptr.hip).  Integer tables: they do not depend on the series and are cached per context.
@@ -300,19 +283,14 @@ struct abz_rule {
     abz::DevBuf vals;  // double [ntiles][planes][pitch]: H planes 2*(a + n*b) + {re, im}, then E (n), then V (d*n)
     int planes = 0;
     abz::PlaneView H, E, V;  // views into vals (base == nullptr when absent)
-    abz::DevBuf ltm_elems;  // matrix elements of abz_rule_ltm_elements: double [ntiles][ltm_ncomp * n planes][row]
-    int ltm_ncomp = 0;
-    abz::PlaneView A;        // view of ltm_elems
-    // integration weights of abz_rule_ltm_node_weights: double [ntiles][ltm_nodew_nE * n planes][row], tiled like ltm_elems; they go
-    // where attached elements go (rebuild, a new gather of an unfolded rule, destroy), not with the elements themselves
-    abz::DevBuf ltm_nodew;
-    int ltm_nodew_nE = 0;
-    abz::PlaneView NW;       // view of ltm_nodew
-    // complex weights of abz_rule_ltm_green_node_weights: double [ntiles][2 ltm_gnodew_nz * n planes][row], plane (2 i + part) n + b =
-    // Re / Im of band b at z_i; a block of its own with the lifetime of ltm_nodew, untouched by the real weights' calls
-    abz::DevBuf ltm_gnodew;
-    int ltm_gnodew_nz = 0;
-    abz::PlaneView GW;       // view of ltm_gnodew
+    // blocks tiled like the eigenvalue planes (ltm_block.h), rule_bands() planes per set:
+    abz::LtmBlock elems;   // matrix elements of abz_rule_ltm_elements: one set per component
+    // integration weights of abz_rule_ltm_node_weights: one set per energy; they go where attached elements go (rebuild, a new
+    // gather of an unfolded rule, destroy), not with the elements themselves
+    abz::LtmBlock nodew;
+    // complex weights of abz_rule_ltm_green_node_weights: 2 nz sets, set 2 i + part = Re / Im at z_i; a block of its own with
+    // the lifetime of nodew, untouched by the real weights' calls
+    abz::LtmBlock gnodew;
     // symmetric rules: double [nk] weights and int32 [d][nk] grid indices; of a device-built rule, views into the plan's arena
     abz::DevBuf w, idx;
     std::unique_ptr<abz::RulePlan> plan;  // (api.cpp): contraction plan + phase table, device resident
@@ -337,6 +315,18 @@ namespace abz {
 
 // bands of the rule's eigenvalue planes, attached elements and weight blocks
 inline int rule_bands(const abz_rule* r) { return r->nb ? r->nb : r->s->n; }
+
+// ---- what ltm_api.cpp takes from api.cpp
+int check_rule(const abz_rule* r);
+void series_release(abz_series* s);
+int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_idx, const int64_t* wsym, int want, int outer0, int outer_n,
+               abz_rule** out, const SymTables* st = nullptr, bool wait = true);
+void rule_set_empty_plan(abz_rule* r);          // the plan of a rule without a contraction plan (abz_rule_rebuild refuses it)
+int rule_outer_planes(const abz_rule* r);       // planes of the outermost variable the rule's plan covers (a slab: fewer than npt)
+void rule_drop_ltm_elements(abz_rule* r);
+void rule_drop_ltm_node_weights(abz_rule* r);  // both weight blocks, real and complex
+// A pair rule (abz_rule_ltm_pairs) holds differences of eigenvalues and interband products: no H(k), no eigenvectors, no plan.
+int refuse_pair_rule(const abz_rule* r, const char* who, const char* why);
 
 // RAII-ish profiling bracket around launches of one logical kernel.  Its two events are bound to the kernel dispatches
 // made by launch() inside it, not recorded on the stream: an event record is a packet of its own, with a system-scope

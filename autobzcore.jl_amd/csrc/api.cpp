@@ -5,7 +5,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <numeric>
@@ -679,7 +678,7 @@ static int check_series(const abz_series* s) {
     return ABZ_OK;
 }
 
-static int check_rule(const abz_rule* r) {
+int check_rule(const abz_rule* r) {
     if (!r || !r->plan || !r->s) {
         set_error("null rule handle");
         return ABZ_ERR_ARG;
@@ -708,7 +707,7 @@ static void ctx_release(abz_ctx* ctx) {
     if (own) (void)hipStreamDestroy(own);
 }
 
-static void series_release(abz_series* s) {
+void series_release(abz_series* s) {
     if (--s->refs > 0) return;
     abz_ctx* ctx = s->ctx;
     (void)hipSetDevice(ctx->device);
@@ -998,6 +997,8 @@ int abz_series_drop_rules(abz_series* s) try {
 } ABZ_CATCH_ALL
 
 // ---------------------------------------------------------------- rules
+}  // extern "C"
+
 namespace abz {
 struct RulePlan {
     Plan plan;
@@ -1010,33 +1011,28 @@ struct RulePlan {
     DevBuf tri;
     int tri_state = 0;  // 0: not filled for the current values
 };
+
+void rule_set_empty_plan(abz_rule* r) { r->plan.reset(new RulePlan()); }
+int rule_outer_planes(const abz_rule* r) { return r->plan->plan.outer_n; }
+
+void rule_drop_ltm_elements(abz_rule* r) { r->elems.drop(); }
+
+void rule_drop_ltm_node_weights(abz_rule* r) {
+    r->nodew.drop();
+    r->gnodew.drop();
+}
+
+int refuse_pair_rule(const abz_rule* r, const char* who, const char* why) {
+    if (!r->nb) return ABZ_OK;
+    set_error("%s: the rule is a pair rule of abz_rule_ltm_pairs (%d pseudo-bands e_c - e_v): %s", who, r->nb, why);
+    return ABZ_ERR_UNSUPPORTED;
+}
 }  // namespace abz
 
 abz_rule::abz_rule() = default;
 abz_rule::~abz_rule() = default;  // the halo plane of abz_rule_ltm_halo goes with its slab (it holds no reference on the series)
 
-static void rule_drop_ltm_elements(abz_rule* r) {
-    r->ltm_elems = DevBuf();
-    r->ltm_ncomp = 0;
-    r->A = PlaneView();
-}
-
-// both weight blocks: the real ones of abz_rule_ltm_node_weights and the complex ones of abz_rule_ltm_green_node_weights
-static void rule_drop_ltm_node_weights(abz_rule* r) {
-    r->ltm_nodew = DevBuf();
-    r->ltm_nodew_nE = 0;
-    r->NW = PlaneView();
-    r->ltm_gnodew = DevBuf();
-    r->ltm_gnodew_nz = 0;
-    r->GW = PlaneView();
-}
-
-// A pair rule (abz_rule_ltm_pairs) holds differences of eigenvalues and interband products: no H(k), no eigenvectors, no plan.
-static int refuse_pair_rule(const abz_rule* r, const char* who, const char* why) {
-    if (!r->nb) return ABZ_OK;
-    set_error("%s: the rule is a pair rule of abz_rule_ltm_pairs (%d pseudo-bands e_c - e_v): %s", who, r->nb, why);
-    return ABZ_ERR_UNSUPPORTED;
-}
+extern "C" {
 
 int abz_rule_destroy(abz_rule* r) try {
     if (!r) return ABZ_OK;
@@ -1242,8 +1238,10 @@ static int rule_fill(abz_rule* r) {
     return ABZ_OK;
 }
 
-static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_idx, const int64_t* wsym, int want,
-                      int outer0, int outer_n, abz_rule** out, const SymTables* st = nullptr, bool wait = true) {
+}  // extern "C"
+
+int abz::rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_idx, const int64_t* wsym, int want, int outer0, int outer_n,
+                    abz_rule** out, const SymTables* st, bool wait) {
     int rc = check_series(s);
     if (rc) return rc;
     ABZ_REQUIRE(out, "null out");
@@ -1398,6 +1396,8 @@ static int rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_i
     return ABZ_OK;
 }
 
+extern "C" {
+
 int abz_ptr_rule_build(abz_series* s, int npt, int64_t nirr, const int32_t* irr_idx, const int64_t* wsym, int want,
                        abz_rule** out) try {
     return rule_build(s, npt, nirr, irr_idx, wsym, want, 0, npt, out);
@@ -1465,7 +1465,7 @@ int abz_rule_rebuild(abz_rule* r) try {
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     RulePlan* rp = r->plan.get();
-    if (r->ltm_elems.p || r->ltm_nodew.p || r->ltm_gnodew.p) {  // matrix elements and integration weights described the old eigenstates
+    if (r->elems.buf.p || r->nodew.buf.p || r->gnodew.buf.p) {  // matrix elements and integration weights described the old eigenstates
         ABZ_HIP(hipStreamSynchronize(ctx->stream));
         rule_drop_ltm_elements(r);
         rule_drop_ltm_node_weights(r);
@@ -2101,860 +2101,6 @@ int abz_rule_ggr(abz_rule* r, const double* E, int nE, double* out) try {
     abz_ctx* ctx = r->s->ctx;
     ABZ_HIP(hipSetDevice(ctx->device));
     return launch_ggr(ctx, r->s->n, r->s->d, r->npt, r->E, r->V, r->w.as<double>(), r->nk, E, nE, out);
-} ABZ_CATCH_ALL
-
-// The rule is a whole periodic grid with eigenvalues -- or, where the caller scans slabs (`slab_ok`: abz_rule_ltm and the
-// energy-weighted abz_rule_ltm_weighted), a slab with its halo plane attached.  The simplices of a cell need all its 2^d
-// corners: a slab lacks one halo plane, a list of irreducible nodes the mesh.
-static int ltm_check_grid(const abz_rule* r, const char* who, bool slab_ok = false) {
-    if (!r->E.base) {
-        set_error("LTM needs a rule built with ABZ_WANT_EIG");
-        return ABZ_ERR_ARG;
-    }
-    int64_t ngrid = 1;
-    for (int j = 0; j < r->s->d; ++j) ngrid *= r->npt;
-    if (!r->full || r->k_offset != 0 || r->nk != ngrid) {
-        if (r->full && r->ltm_halo) {
-            if (slab_ok) return ABZ_OK;
-            set_error("%s: the rule is not a whole periodic grid (a slab of the outermost variable; its halo plane serves abz_rule_ltm and "
-                      "abz_rule_ltm_weighted with ABZ_LTM_A_ENERGY only: attached elements, orbital weights, the Fermi level and unfolding "
-                      "are not implemented on slabs); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)", who);
-            return ABZ_ERR_UNSUPPORTED;
-        }
-        set_error("%s: the rule is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, ...)%s", who,
-                  r->full ? "a slab of the outermost variable" : "irreducible nodes of a symmetric rule",
-                  r->full && slab_ok ? ", or give the slab its halo plane: attach it with abz_rule_ltm_halo" : "");
-        return ABZ_ERR_UNSUPPORTED;
-    }
-    return ABZ_OK;
-}
-
-// the slab arguments of a scan when the rule is a slab with its halo (ltm_check_grid let it through), else false
-static bool ltm_slab_of(const abz_rule* r, LtmSlab& slab) {
-    if (!r->ltm_halo) return false;
-    slab.E = slab.A = r->ltm_halo->E;  // (the energy is the only element of a slab scan)
-    slab.nz = r->plan->plan.outer_n;
-    return true;
-}
-
-int abz_rule_ltm(abz_rule* r, const double* E, int nE, int what, double* out) try {
-    int rc0 = check_rule(r);
-    if (rc0) return rc0;
-    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm: bad arguments");
-    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES, "abz_rule_ltm: what = %d is neither ABZ_LTM_DOS nor ABZ_LTM_STATES", what);
-    int rc = ltm_check_grid(r, "abz_rule_ltm", true);
-    if (rc) return rc;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    LtmSlab slab;
-    return launch_ltm(ctx, rule_bands(r), r->s->d, r->npt, r->E, E, nE, what == ABZ_LTM_STATES, out, ltm_slab_of(r, slab) ? &slab : nullptr);
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_green(abz_rule* r, const double* z, int nz, double* out) try {
-    int rc0 = check_rule(r);
-    if (rc0) return rc0;
-    ABZ_REQUIRE(z && out && nz >= 1, "abz_rule_ltm_green: bad arguments");
-    int rc = ltm_check_grid(r, "abz_rule_ltm_green");
-    if (rc) return rc;
-    for (int i = 0; i < nz; ++i) {
-        const double re = z[2 * (size_t)i], im = z[2 * (size_t)i + 1];
-        ABZ_REQUIRE(std::isfinite(re) && std::isfinite(im), "abz_rule_ltm_green: z[%d] = (%g, %g) is not finite", i, re, im);
-        ABZ_REQUIRE(im != 0.0, "abz_rule_ltm_green: z[%d] = %g is real; the trace is computed off the real axis (Im z != 0)", i, re);
-    }
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    return launch_ltm_green(ctx, rule_bands(r), r->s->d, r->npt, r->E, z, nz, out);
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_elements(abz_rule* r, const double* A, int ncomp) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE((A == nullptr) == (ncomp == 0), "abz_rule_ltm_elements: elements and ncomp = %d do not go together (drop with NULL, 0)", ncomp);
-    ABZ_REQUIRE(ncomp >= 0 && ncomp <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_elements: ncomp = %d outside 1..%d", ncomp, ABZ_LTM_MAX_COMP);
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_elements"))) return rc;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    ABZ_HIP(hipStreamSynchronize(ctx->stream));
-    rule_drop_ltm_elements(r);
-    if (!A) return ABZ_OK;
-    const int n = rule_bands(r);
-    const int planes = ncomp * n;
-    const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row;
-    if ((rc = r->ltm_elems.alloc(bytes))) return rc;
-    r->ltm_ncomp = ncomp;
-    r->A = r->E;  // the tiling of the eigenvalue planes: same rows, same lines, ncomp n planes per tile
-    r->A.base = r->ltm_elems.as<double>();
-    r->A.tile = (int64_t)planes * r->E.row;
-    r->A.pitch = r->E.row;
-    r->A.compact = 0;
-    DevBuf stage;  // one component at a time in the host's order
-    const size_t cbytes = sizeof(double) * (size_t)r->nk * (size_t)n;
-    rc = stage.reserve(cbytes);
-    if (!rc && hipMemsetAsync(r->ltm_elems.p, 0, bytes, ctx->stream) != hipSuccess) {  // the padding columns hold finite numbers
-        set_error("abz_rule_ltm_elements: hipMemsetAsync failed");
-        rc = ABZ_ERR_HIP;
-    }
-    for (int c = 0; c < ncomp && !rc; ++c) {
-        rc = stage_h2d(ctx, stage.p, A + (size_t)c * (size_t)r->nk * (size_t)n, cbytes);
-        if (!rc) rc = launch_ltm_repack(ctx, stage.as<double>(), r->A, c * n, n, r->nk);
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_elements: the upload failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) rule_drop_ltm_elements(r);
-    return rc;
-} ABZ_CATCH_ALL
-
-// The same block filled on the device from the eigenvectors U(k) (kernels_ltm_orb.hip): |U_ab|^2 (abz_rule_ltm_orbitals) or the
-// band projectors U_pb conj(U_qb) (abz_rule_ltm_projectors).  H(k) comes from the rule's own planes or, for a rule of
-// eigenvalues only, from a transient H-only rule of the same grid that lives for this call.  Whatever was attached stays in
-// place until the new block is complete: a refusal or a failure leaves it untouched.
-
-// what both entry points ask of the rule, before they look at their selection
-static int ltm_eigvec_check_rule(abz_rule* r, const char* who, const char* what) {
-    int rc = ltm_check_grid(r, who);
-    if (rc) return rc;
-    if ((rc = refuse_pair_rule(r, who, "H(k) and eigenvectors belong to its source rule"))) return rc;
-    if (r->node_of.p) {
-        set_error("%s: the rule's eigenvalues were unfolded from irreducible nodes; eigenvectors at every grid "
-                  "point are what such a rule avoids (build a full-grid rule with abz_ptr_rule_build)", who);
-        return ABZ_ERR_UNSUPPORTED;
-    }
-    if (!ltm_orbitals_supported(r->s->n)) {
-        set_error("%s: %d bands; %s are computed for 1...32", who, r->s->n, what);
-        return ABZ_ERR_UNSUPPORTED;
-    }
-    return ABZ_OK;
-}
-
-// the block of `planes` planes tiled like the eigenvalue planes E, filled from H(k) of the grid of r (`fill(H, A)` launches the kernel;
-// H: r's own planes or a transient H-only rule), complete when this returns: the one synchronisation of the call
-static int ltm_eigvec_block(abz_rule* r, const char* who, PlaneView E, int planes, const std::function<int(PlaneView, PlaneView)>& fill,
-                            DevBuf& block, PlaneView& A) {
-    const int n = r->s->n;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    int rc = ABZ_OK;
-    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: U = 1, no H needed)
-    if (!r->H.base && n > 1) {
-        abz_rule* built = nullptr;
-        if ((rc = rule_build(r->s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
-        tmp.reset(built);
-    }
-    const size_t bytes = sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)E.row;
-    rc = block.alloc(bytes);
-    A = E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements)
-    A.base = block.as<double>();
-    A.tile = (int64_t)planes * E.row;
-    A.pitch = E.row;
-    A.compact = 0;
-    if (!rc) rc = fill(tmp ? tmp->H : r->H, A);
-    // the one synchronisation of the call: the block is complete, nothing reads the old one or the transient rule any more
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("%s: the kernel failed", who);
-        rc = ABZ_ERR_HIP;
-    }
-    if (tmp) {
-        tmp.reset();
-        series_release(r->s);
-    }
-    return rc;
-}
-
-// allocate the block of ncomp components, fill it, wait once, attach
-static int ltm_eigvec_attach(abz_rule* r, const char* who, int ncomp, const std::function<int(PlaneView, PlaneView)>& fill) {
-    DevBuf block;
-    PlaneView A;
-    const int rc = ltm_eigvec_block(r, who, r->E, ncomp * r->s->n, fill, block, A);
-    if (rc) return rc;
-    r->ltm_elems = std::move(block);  // (what was attached goes here)
-    r->ltm_ncomp = ncomp;
-    r->A = A;
-    return ABZ_OK;
-}
-
-int abz_rule_ltm_orbitals(abz_rule* r, const int32_t* orb, int norb) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_orbitals", "orbital weights"))) return rc;
-    const abz_series* s = r->s;
-    const int n = s->n;
-    if (orb) {
-        ABZ_REQUIRE(norb >= 1 && norb <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: norb = %d outside 1..%d", norb, ABZ_LTM_MAX_COMP);
-        for (int c = 0; c < norb; ++c)
-            ABZ_REQUIRE(orb[c] >= 0 && orb[c] < n, "abz_rule_ltm_orbitals: orb[%d] = %d outside 0..%d", c, orb[c], n - 1);
-    } else {
-        ABZ_REQUIRE(n <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_orbitals: all %d orbitals are more than %d components; select some (orb, norb)", n,
-                    ABZ_LTM_MAX_COMP);
-    }
-    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
-                "abz_rule_ltm_orbitals: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
-    const int ncomp = orb ? norb : n;
-    return ltm_eigvec_attach(r, "abz_rule_ltm_orbitals", ncomp, [&](PlaneView H, PlaneView A) {
-        return launch_ltm_orbitals(s->ctx, n, r->npt, r->ntiles, H, A, orb, ncomp);
-    });
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_projectors(abz_rule* r, const int32_t* pairs, int npairs) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_projectors", "band projectors"))) return rc;
-    const abz_series* s = r->s;
-    const int n = s->n;
-    ABZ_REQUIRE(pairs, "abz_rule_ltm_projectors: null pairs");
-    ABZ_REQUIRE(npairs >= 1 && npairs <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_projectors: npairs = %d outside 1..%d", npairs, ABZ_LTM_MAX_COMP);
-    for (int i = 0; i < npairs; ++i)
-        ABZ_REQUIRE(pairs[2 * i] >= 0 && pairs[2 * i] < n && pairs[2 * i + 1] >= 0 && pairs[2 * i + 1] < n,
-                    "abz_rule_ltm_projectors: pairs[%d] = (%d, %d) outside 0..%d", i, pairs[2 * i], pairs[2 * i + 1], n - 1);
-    const int ncomp = ltm_projector_components(pairs, npairs);
-    ABZ_REQUIRE(ncomp <= ABZ_LTM_MAX_COMP,
-                "abz_rule_ltm_projectors: %d pairs are %d components (one for p == q, two for p != q), more than %d; attach them in groups",
-                npairs, ncomp, ABZ_LTM_MAX_COMP);
-    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
-                "abz_rule_ltm_projectors: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
-    return ltm_eigvec_attach(r, "abz_rule_ltm_projectors", ncomp, [&](PlaneView H, PlaneView A) {
-        return launch_ltm_projectors(s->ctx, n, r->npt, r->ntiles, H, A, pairs, npairs);
-    });
-} ABZ_CATCH_ALL
-
-// what the entry points that read operator rules (abz_rule_ltm_expectation, abz_rule_ltm_pairs) ask of ops[0 .. nops): H planes of
-// Hermitian series on whole periodic grids of the context, npt, d and n of r, not row-major; O[i] <- their planes
-static int ltm_check_operators(const char* who, const abz_rule* r, abz_rule* const* ops, int nops, PlaneView* O) {
-    const abz_series* s = r->s;
-    const int n = s->n;
-    int rc = ABZ_OK;
-    for (int i = 0; i < nops; ++i) {
-        abz_rule* o = ops[i];
-        ABZ_REQUIRE(o, "%s: ops[%d] is null", who, i);
-        if ((rc = check_rule(o))) return rc;
-        if (o->want & ABZ_WANT_H_ROW_MAJOR) {
-            set_error("%s: ops[%d] was asked for in the row-major layout; operators are read from column-major or compact H planes", who, i);
-            return ABZ_ERR_UNSUPPORTED;
-        }
-        int64_t ogrid = 1;
-        for (int j = 0; j < o->s->d; ++j) ogrid *= o->npt;
-        if (!o->full || o->k_offset != 0 || o->nk != ogrid || o->node_of.p) {
-            set_error("%s: ops[%d] is not a whole periodic grid (%s); build it with abz_ptr_rule_build(s, npt, 0, NULL, NULL, "
-                      "ABZ_WANT_H, ...)", who, i,
-                      !o->full ? "irreducible nodes of a symmetric rule" : (o->node_of.p ? "an unfolded rule" : "a slab of the outermost variable"));
-            return ABZ_ERR_UNSUPPORTED;
-        }
-        ABZ_REQUIRE(o->s->ctx == s->ctx, "%s: ops[%d] lives on another context than the rule", who, i);
-        ABZ_REQUIRE(o->npt == r->npt && o->s->d == s->d && o->s->n == n && o->ntiles == r->ntiles,
-                    "%s: ops[%d] has npt = %d, d = %d, n = %d; the rule has npt = %d, d = %d, n = %d", who, i, o->npt, o->s->d,
-                    o->s->n, r->npt, s->d, n);
-        ABZ_REQUIRE(o->H.base, "%s: ops[%d] holds no H planes (build it with ABZ_WANT_H)", who, i);
-        ABZ_REQUIRE(o->s->hermitian && o->herm, "%s: the series of ops[%d] is not Hermitian (c(-R) = c(R)^dagger)", who, i);
-        O[i] = o->H;
-    }
-    return ABZ_OK;
-}
-
-int abz_rule_ltm_expectation(abz_rule* r, abz_rule* const* ops, int nops, const int32_t* comps, int ncomp) try {
-    const char* const who = "abz_rule_ltm_expectation";
-    int rc = check_rule(r);
-    if (rc) return rc;
-    if ((rc = ltm_eigvec_check_rule(r, who, "band expectation values"))) return rc;
-    const abz_series* s = r->s;
-    const int n = s->n;
-    ABZ_REQUIRE(ops, "abz_rule_ltm_expectation: null ops");
-    ABZ_REQUIRE(nops >= 1 && nops <= ABZ_LTM_EXPECT_MAX_OPS, "abz_rule_ltm_expectation: nops = %d outside 1..%d", nops, ABZ_LTM_EXPECT_MAX_OPS);
-    if (!comps) ncomp = nops;
-    ABZ_REQUIRE(ncomp >= 1 && ncomp <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_expectation: ncomp = %d outside 1..%d", ncomp, ABZ_LTM_MAX_COMP);
-    for (int c = 0; comps && c < ncomp; ++c)
-        ABZ_REQUIRE(comps[2 * c] >= 0 && comps[2 * c] < nops && comps[2 * c + 1] >= -1 && comps[2 * c + 1] < nops,
-                    "abz_rule_ltm_expectation: comps[%d] = (%d, %d): an operator index outside 0..%d (second: -1 for a single expectation)", c,
-                    comps[2 * c], comps[2 * c + 1], nops - 1);
-    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
-                "abz_rule_ltm_expectation: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
-    PlaneView O[ABZ_LTM_EXPECT_MAX_OPS];
-    if ((rc = ltm_check_operators(who, r, ops, nops, O))) return rc;
-    return ltm_eigvec_attach(r, who, ncomp, [&](PlaneView H, PlaneView A) {
-        return launch_ltm_expectation(s->ctx, n, r->npt, r->ntiles, H, O, nops, A, comps, ncomp);
-    });
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_elements_export(abz_rule* r, int* ncomp, double* A) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(ncomp, "abz_rule_ltm_elements_export: null ncomp");
-    // a slab made scannable by abz_rule_ltm_halo names its limit here too (any other rule without elements answers 0 components)
-    if (r->ltm_halo && (rc = ltm_check_grid(r, "abz_rule_ltm_elements_export"))) return rc;
-    *ncomp = r->ltm_elems.p ? r->ltm_ncomp : 0;
-    if (!A || !r->ltm_elems.p) return ABZ_OK;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    for (int c = 0; c < r->ltm_ncomp; ++c) {  // one component [nk][n] at a time, the order they came in
-        PlaneView v = r->A;
-        v.base += (int64_t)c * n * v.pitch;
-        if ((rc = export_planes(ctx, v, n, r->nk, A + (size_t)c * (size_t)r->nk * (size_t)n))) return rc;
-    }
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_elements_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* ncomp) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    const bool have = r->ltm_elems.p != nullptr;
-    if (base) *base = r->ltm_elems.p;
-    if (nbytes) *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * (size_t)r->ltm_ncomp * (size_t)rule_bands(r) * (size_t)r->A.row) : 0;
-    if (ncomp) *ncomp = have ? r->ltm_ncomp : 0;
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int what, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm_weighted: bad arguments");
-    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES || what == ABZ_LTM_STATES_CORRECTED,
-                "abz_rule_ltm_weighted: what = %d is neither ABZ_LTM_DOS, ABZ_LTM_STATES nor ABZ_LTM_STATES_CORRECTED", what);
-    ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
-                "abz_rule_ltm_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_weighted", source == ABZ_LTM_A_ENERGY))) return rc;
-    ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems.p,
-                "abz_rule_ltm_weighted: no matrix elements are attached (abz_rule_ltm_elements; abz_rule_rebuild drops them)");
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const bool energy = source == ABZ_LTM_A_ENERGY;
-    LtmSlab slab;
-    return launch_ltm_weighted(ctx, rule_bands(r), r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, E, nE,
-                               what, out, ltm_slab_of(r, slab) ? &slab : nullptr);
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z, int nz, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(z && out && nz >= 1, "abz_rule_ltm_green_weighted: bad arguments");
-    ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ENERGY,
-                "abz_rule_ltm_green_weighted: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ENERGY", source);
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_weighted"))) return rc;
-    ABZ_REQUIRE(source == ABZ_LTM_A_ENERGY || r->ltm_elems.p,
-                "abz_rule_ltm_green_weighted: no matrix elements are attached (abz_rule_ltm_elements, abz_rule_ltm_orbitals; "
-                "abz_rule_rebuild drops them)");
-    for (int i = 0; i < nz; ++i) {
-        const double re = z[2 * (size_t)i], im = z[2 * (size_t)i + 1];
-        ABZ_REQUIRE(std::isfinite(re) && std::isfinite(im), "abz_rule_ltm_green_weighted: z[%d] = (%g, %g) is not finite", i, re, im);
-        ABZ_REQUIRE(im != 0.0, "abz_rule_ltm_green_weighted: z[%d] = %g is real; G_A is computed off the real axis (Im z != 0)", i, re);
-    }
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const bool energy = source == ABZ_LTM_A_ENERGY;
-    return launch_ltm_green_weighted(ctx, rule_bands(r), r->s->d, r->npt, r->E, energy ? r->E : r->A, energy ? 1 : r->ltm_ncomp, z, nz, out);
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(E_F, "abz_rule_ltm_fermi: null E_F");
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_fermi"))) return rc;
-    ABZ_REQUIRE(nstates > 0.0 && nstates < (double)rule_bands(r), "abz_rule_ltm_fermi: nstates = %g outside (0, %d)", nstates, rule_bands(r));
-    ABZ_REQUIRE(tol > 0.0, "abz_rule_ltm_fermi: tol = %g is not positive", tol);
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    return ltm_fermi(ctx, rule_bands(r), r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
-} ABZ_CATCH_ALL
-
-// Integration weights w_b(k; E) per node and band (kernels_ltm_nodew.hip).  The new block is complete before it replaces the
-// resident one: a refusal or a failure leaves that one as it was, and the half-made block goes with its DevBuf.
-int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(E, "abz_rule_ltm_node_weights: null energies");
-    ABZ_REQUIRE(nE >= 1 && nE <= ABZ_LTM_NODEW_MAX_E, "abz_rule_ltm_node_weights: nE = %d outside 1..%d", nE, ABZ_LTM_NODEW_MAX_E);
-    ABZ_REQUIRE(what == ABZ_LTM_DOS || what == ABZ_LTM_STATES || what == ABZ_LTM_STATES_CORRECTED,
-                "abz_rule_ltm_node_weights: what = %d is neither ABZ_LTM_DOS, ABZ_LTM_STATES nor ABZ_LTM_STATES_CORRECTED", what);
-    for (int i = 0; i < nE; ++i) ABZ_REQUIRE(std::isfinite(E[i]), "abz_rule_ltm_node_weights: E[%d] = %g is not finite", i, E[i]);
-    // (no slab_ok: a node needs the plane BEFORE it as well, which a halo does not give)
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights"))) return rc;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    const int planes = nE * n;
-    DevBuf block;
-    if ((rc = block.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row))) return rc;
-    PlaneView W = r->E;  // the tiling of the eigenvalue planes (abz_rule_ltm_elements): same rows, same lines, nE n planes per tile
-    W.base = block.as<double>();
-    W.tile = (int64_t)planes * r->E.row;
-    W.pitch = r->E.row;
-    W.compact = 0;
-    rc = launch_ltm_node_weights(ctx, n, r->s->d, r->npt, r->E, W, E, nE, what);
-    for (int i = 0; i < nE && !rc && out; ++i) {  // one energy [nk][n] at a time, in the node and band order of abz_rule_export's eig
-        PlaneView v = W;
-        v.base += (int64_t)i * n * v.pitch;
-        rc = export_planes(ctx, v, n, r->nk, out + (size_t)i * (size_t)r->nk * (size_t)n);
-    }
-    // the block is complete, and nothing reads the old one any more
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_node_weights: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) return rc;
-    r->ltm_nodew = std::move(block);  // (the previous weights go here)
-    r->ltm_nodew_nE = nE;
-    r->NW = W;
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nE) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    const bool have = r->ltm_nodew.p != nullptr;
-    if (base) *base = r->ltm_nodew.p;
-    if (nbytes) *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * (size_t)r->ltm_nodew_nE * (size_t)rule_bands(r) * (size_t)r->NW.row) : 0;
-    if (nE) *nE = have ? r->ltm_nodew_nE : 0;
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_node_weights_dot: null out");
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights_dot"))) return rc;
-    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_node_weights_dot: the rule holds no integration weights (abz_rule_ltm_node_weights; "
-                                "abz_rule_rebuild drops them)");
-    ABZ_REQUIRE(r->ltm_elems.p, "abz_rule_ltm_node_weights_dot: no matrix elements are attached (abz_rule_ltm_elements, abz_rule_ltm_orbitals, "
-                                "abz_rule_ltm_projectors)");
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    return launch_ltm_node_weights_dot(ctx, rule_bands(r), r->npt, r->ntiles, r->NW, r->ltm_nodew_nE, r->A, r->ltm_ncomp, out);
-} ABZ_CATCH_ALL
-
-// rho_pq(E_i) from the resident weights and U(k) in one eigen-solve (kernels_ltm_dens.hip).  Nothing is attached and nothing
-// replaced: the rule's blocks are read only.  H(k) as in ltm_eigvec_attach: the rule's own planes, or a transient H-only rule.
-int abz_rule_ltm_density_matrix(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_density_matrix: null out");
-    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_density_matrix", "density matrices"))) return rc;
-    abz_series* s = r->s;
-    const int n = s->n;
-    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_density_matrix: the rule holds no integration weights (abz_rule_ltm_node_weights; "
-                                "abz_rule_rebuild drops them)");
-    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
-                "abz_rule_ltm_density_matrix: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
-    abz_ctx* ctx = s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: U = 1, no H needed)
-    if (!r->H.base && n > 1) {
-        abz_rule* built = nullptr;
-        if ((rc = rule_build(s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
-        tmp.reset(built);
-    }
-    // (synchronises once, at the delivery of the sums: nothing reads the transient rule after it)
-    rc = launch_ltm_density_matrix(ctx, n, r->npt, r->ntiles, tmp ? tmp->H : r->H, r->NW, r->ltm_nodew_nE, out);
-    if (tmp) {
-        if (rc) (void)hipStreamSynchronize(ctx->stream);  // a failure may have left launches behind
-        tmp.reset();
-        series_release(s);
-    }
-    return rc;
-} ABZ_CATCH_ALL
-
-// out [nE][nirr][n] <- the orbit sums of the nE real weight sets of the block W of an unfolded rule.  The inverse of the orbit map
-// is made once per rule (the map does not change with the values) and serves the real and the complex weights.
-static int ltm_fold_sets(abz_rule* r, const char* who, PlaneView W, int nE, double* out) {
-    int rc = ABZ_OK;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = r->s->n;
-    const int64_t N = r->nk, nirr = r->unfold_nk;
-    const size_t start_bytes = sizeof(int64_t) * ((size_t)nirr + 1);
-    if (!r->unfold_inv.p) {
-        std::vector<int32_t> node_of((size_t)N), member;
-        std::vector<int64_t> start;
-        if ((rc = stage_d2h(ctx, node_of.data(), r->node_of.p, sizeof(int32_t) * (size_t)N))) return rc;
-        for (int64_t x = 0; x < N; ++x)
-            if (node_of[(size_t)x] < 0 || node_of[(size_t)x] >= nirr) {
-                set_error("%s: the orbit map names node %d at grid point %lld (the source has %lld nodes)", who, node_of[(size_t)x],
-                          (long long)x, (long long)nirr);
-                return ABZ_ERR_INTERNAL;
-            }
-        ltm_orbit_inverse(node_of.data(), N, nirr, start, member);
-        DevBuf inv;
-        if ((rc = inv.alloc(start_bytes + sizeof(int32_t) * (size_t)N))) return rc;
-        if ((rc = stage_h2d(ctx, inv.p, start.data(), start_bytes))) return rc;
-        if ((rc = stage_h2d(ctx, static_cast<char*>(inv.p) + start_bytes, member.data(), sizeof(int32_t) * (size_t)N))) return rc;
-        r->unfold_inv = std::move(inv);
-    }
-    const size_t obytes = sizeof(double) * (size_t)nE * (size_t)nirr * (size_t)n;
-    if ((rc = ctx->scratch[3].reserve(obytes))) return rc;
-    const int64_t* start_dev = r->unfold_inv.as<int64_t>();
-    const int32_t* member_dev = reinterpret_cast<const int32_t*>(static_cast<const char*>(r->unfold_inv.p) + start_bytes);
-    if ((rc = launch_ltm_node_weights_fold(ctx, n, W, nE, start_dev, member_dev, nirr, ctx->scratch[3].as<double>()))) return rc;
-    return stage_d2h(ctx, out, ctx->scratch[3].p, obytes);
-}
-
-int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_node_weights_fold: null out");
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights_fold"))) return rc;
-    ABZ_REQUIRE(r->node_of.p, "abz_rule_ltm_node_weights_fold: the rule was not made by abz_rule_ltm_unfold: it has no orbits to fold over");
-    ABZ_REQUIRE(r->ltm_nodew.p, "abz_rule_ltm_node_weights_fold: the rule holds no integration weights (abz_rule_ltm_node_weights; a new "
-                                "gather drops them)");
-    return ltm_fold_sets(r, "abz_rule_ltm_node_weights_fold", r->NW, r->ltm_nodew_nE, out);
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_green_node_weights_fold(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_green_node_weights_fold: null out");
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights_fold"))) return rc;
-    ABZ_REQUIRE(r->node_of.p, "abz_rule_ltm_green_node_weights_fold: the rule was not made by abz_rule_ltm_unfold: it has no orbits to fold over");
-    ABZ_REQUIRE(r->ltm_gnodew.p, "abz_rule_ltm_green_node_weights_fold: the rule holds no complex integration weights "
-                                 "(abz_rule_ltm_green_node_weights; a new gather drops them)");
-    // [2 nz][nirr][n] of the real sets -> [nz][nirr][n][2]
-    const int nz = r->ltm_gnodew_nz;
-    const size_t per = (size_t)r->unfold_nk * (size_t)r->s->n;
-    std::vector<double> sets((size_t)2 * nz * per);
-    if ((rc = ltm_fold_sets(r, "abz_rule_ltm_green_node_weights_fold", r->GW, 2 * nz, sets.data()))) return rc;
-    for (int i = 0; i < nz; ++i)
-        for (size_t x = 0; x < per; ++x) {
-            out[2 * ((size_t)i * per + x)] = sets[(size_t)(2 * i) * per + x];
-            out[2 * ((size_t)i * per + x) + 1] = sets[(size_t)(2 * i + 1) * per + x];
-        }
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-// Complex integration weights W_b(k; z) of the Green's function per node and band (kernels_ltm_green_nodew.hip), resident in a
-// block of their own: 2 nz real weight sets to the dot, the fold and the density-matrix contraction, which are launched as they
-// are.  As for the real weights the new block is complete before it replaces the resident one.
-int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z, int nz, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(z, "abz_rule_ltm_green_node_weights: null z");
-    ABZ_REQUIRE(nz >= 1 && nz <= ABZ_LTM_GREEN_NODEW_MAX_Z, "abz_rule_ltm_green_node_weights: nz = %d outside 1..%d", nz,
-                ABZ_LTM_GREEN_NODEW_MAX_Z);
-    for (int i = 0; i < nz; ++i) {
-        const double re = z[2 * (size_t)i], im = z[2 * (size_t)i + 1];
-        ABZ_REQUIRE(std::isfinite(re) && std::isfinite(im), "abz_rule_ltm_green_node_weights: z[%d] = (%g, %g) is not finite", i, re, im);
-        ABZ_REQUIRE(im != 0.0, "abz_rule_ltm_green_node_weights: z[%d] = %g is real; G is computed off the real axis (Im z != 0)", i, re);
-    }
-    // (no slab_ok: a node needs the plane BEFORE it as well, which a halo does not give)
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights"))) return rc;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    const int planes = 2 * nz * n;
-    DevBuf block;
-    if ((rc = block.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)planes * (size_t)r->E.row))) return rc;
-    PlaneView W = r->E;  // the tiling of the eigenvalue planes: same rows, same lines, 2 nz n planes per tile
-    W.base = block.as<double>();
-    W.tile = (int64_t)planes * r->E.row;
-    W.pitch = r->E.row;
-    W.compact = 0;
-    rc = launch_ltm_green_node_weights(ctx, n, r->s->d, r->npt, r->E, W, z, nz);
-    if (!rc && out) {
-        // one real set [nk][n] at a time through the staging of the export, interleaved on the host
-        std::vector<double> part((size_t)r->nk * (size_t)n);
-        for (int i = 0; i < 2 * nz && !rc; ++i) {
-            PlaneView v = W;
-            v.base += (int64_t)i * n * v.pitch;
-            rc = export_planes(ctx, v, n, r->nk, part.data());
-            double* o = out + (size_t)(i >> 1) * part.size() * 2 + (size_t)(i & 1);
-            for (size_t x = 0; x < part.size() && !rc; ++x) o[2 * x] = part[x];
-        }
-    }
-    // the block is complete, and nothing reads the old one any more
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_green_node_weights: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) return rc;
-    r->ltm_gnodew = std::move(block);  // (the previous complex weights go here)
-    r->ltm_gnodew_nz = nz;
-    r->GW = W;
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nz) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    const bool have = r->ltm_gnodew.p != nullptr;
-    if (base) *base = r->ltm_gnodew.p;
-    if (nbytes)
-        *nbytes = have ? (int64_t)(sizeof(double) * (size_t)r->ntiles * 2 * (size_t)r->ltm_gnodew_nz * (size_t)rule_bands(r) * (size_t)r->GW.row) : 0;
-    if (nz) *nz = have ? r->ltm_gnodew_nz : 0;
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_green_node_weights_dot(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_green_node_weights_dot: null out");
-    if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights_dot"))) return rc;
-    ABZ_REQUIRE(r->ltm_gnodew.p, "abz_rule_ltm_green_node_weights_dot: the rule holds no complex integration weights "
-                                 "(abz_rule_ltm_green_node_weights; abz_rule_rebuild drops them)");
-    ABZ_REQUIRE(r->ltm_elems.p, "abz_rule_ltm_green_node_weights_dot: no matrix elements are attached (abz_rule_ltm_elements, "
-                                "abz_rule_ltm_orbitals, abz_rule_ltm_projectors)");
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    // [2 nz][ncomp] of the real sets is [nz][Re, Im][ncomp]
-    const int nz = r->ltm_gnodew_nz, ncomp = r->ltm_ncomp;
-    std::vector<double> sets((size_t)2 * nz * ncomp);
-    if ((rc = launch_ltm_node_weights_dot(ctx, rule_bands(r), r->npt, r->ntiles, r->GW, 2 * nz, r->A, ncomp, sets.data()))) return rc;
-    for (int i = 0; i < nz; ++i)
-        for (int c = 0; c < ncomp; ++c) {
-            out[2 * ((size_t)i * ncomp + c)] = sets[(size_t)(2 * i) * ncomp + c];
-            out[2 * ((size_t)i * ncomp + c) + 1] = sets[(size_t)(2 * i + 1) * ncomp + c];
-        }
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-// G_pq(z_i) from the resident complex weights and U(k): the contraction of abz_rule_ltm_density_matrix over the 2 nz real sets,
-// X = rho[Re W] and Y = rho[Im W] paired on the host.  Nothing is attached and nothing replaced.
-int abz_rule_ltm_green_node_weights_matrix(abz_rule* r, double* out) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_green_node_weights_matrix: null out");
-    if ((rc = ltm_eigvec_check_rule(r, "abz_rule_ltm_green_node_weights_matrix", "Green's function matrices"))) return rc;
-    abz_series* s = r->s;
-    const int n = s->n;
-    ABZ_REQUIRE(r->ltm_gnodew.p, "abz_rule_ltm_green_node_weights_matrix: the rule holds no complex integration weights "
-                                 "(abz_rule_ltm_green_node_weights; abz_rule_rebuild drops them)");
-    ABZ_REQUIRE(s->hermitian && (!r->H.base || r->herm),
-                "abz_rule_ltm_green_node_weights_matrix: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of "
-                "a Hermitian H(k)");
-    abz_ctx* ctx = s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<abz_rule> tmp;  // H(k) of a rule that keeps eigenvalues only (one band: U = 1, no H needed)
-    if (!r->H.base && n > 1) {
-        abz_rule* built = nullptr;
-        if ((rc = rule_build(s, r->npt, 0, nullptr, nullptr, ABZ_WANT_H | ABZ_WANT_H_COMPACT, 0, r->npt, &built, nullptr, false))) return rc;
-        tmp.reset(built);
-    }
-    const int nz = r->ltm_gnodew_nz;
-    const size_t nn = (size_t)n * (size_t)n;
-    std::vector<double> sets((size_t)2 * nz * nn * 2);  // [2 nz][n][n][2]: X(z_0), Y(z_0), X(z_1), ...
-    // (synchronises once, at the delivery of the sums: nothing reads the transient rule after it)
-    rc = launch_ltm_density_matrix(ctx, n, r->npt, r->ntiles, tmp ? tmp->H : r->H, r->GW, 2 * nz, sets.data());
-    if (tmp) {
-        if (rc) (void)hipStreamSynchronize(ctx->stream);  // a failure may have left launches behind
-        tmp.reset();
-        series_release(s);
-    }
-    if (rc) return rc;
-    // X and Y are Hermitian as they come (the lower triangle the exact conjugate of the upper): entry (p, q) of either triangle
-    // is X_pq + i Y_pq, which is conj(X) + i conj(Y) of the mirrored entry
-    for (int i = 0; i < nz; ++i) {
-        const double* X = sets.data() + (size_t)(2 * i) * nn * 2;
-        const double* Y = X + nn * 2;
-        double* o = out + (size_t)i * nn * 2;
-        for (size_t e = 0; e < nn; ++e) {
-            o[2 * e] = X[2 * e] - Y[2 * e + 1];
-            o[2 * e + 1] = X[2 * e + 1] + Y[2 * e];
-        }
-    }
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-// One eigenvalue per band is a scalar that the zone's symmetries leave alone, e_b(S k) = e_b(k): the planes of the whole grid
-// are a gather from the irreducible nodes.  The orbit map depends on (npt, d, syms, node list) only and stays with the rule.
-int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule** out) try {
-    int rc = check_rule(src);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_unfold: null out");
-    ABZ_REQUIRE(syms && nsyms >= 1, "abz_rule_ltm_unfold: no symmetries (syms = %s, nsyms = %d)", syms ? "given" : "NULL", nsyms);
-    ABZ_REQUIRE(src->E.base, "abz_rule_ltm_unfold: the source rule holds no eigenvalues (build it with ABZ_WANT_EIG)");
-    if (src->full) {
-        set_error("abz_rule_ltm_unfold: the source rule is %s, not a list of irreducible nodes: there is nothing to unfold",
-                  src->node_of.p ? "an unfolded grid" : "a full grid or a slab of one");
-        return ABZ_ERR_UNSUPPORTED;
-    }
-    abz_series* s = src->s;
-    abz_ctx* ctx = s->ctx;
-    const int d = s->d, n = s->n, npt = src->npt;
-    int64_t N = 1;
-    for (int j = 0; j < d; ++j) N *= npt;
-    if (N >= ((int64_t)1 << 31)) {
-        set_error("abz_rule_ltm_unfold: a grid of %lld points does not fit the 32-bit orbit map", (long long)N);
-        return ABZ_ERR_UNSUPPORTED;
-    }
-    ABZ_HIP(hipSetDevice(ctx->device));
-    if (abz_rule* const r = *out) {  // gather again through the map the rule has
-        if ((rc = check_rule(r))) return rc;
-        ABZ_REQUIRE(r->node_of.p && r != src, "abz_rule_ltm_unfold: *out is not a rule made by abz_rule_ltm_unfold (pass NULL to create one)");
-        ABZ_REQUIRE(r->s == s && r->npt == npt && r->unfold_nk == src->nk,
-                    "abz_rule_ltm_unfold: *out was unfolded from another geometry (series, npt = %d, %lld nodes; the source has npt = %d, %lld nodes)",
-                    r->npt, (long long)r->unfold_nk, npt, (long long)src->nk);
-        ABZ_REQUIRE(r->unfold_syms.size() == (size_t)nsyms * d * d && std::equal(r->unfold_syms.begin(), r->unfold_syms.end(), syms),
-                    "abz_rule_ltm_unfold: *out was unfolded under another symmetry set (its orbit map does not fit these %d matrices)", nsyms);
-        if (r->ltm_elems.p || r->ltm_nodew.p || r->ltm_gnodew.p) {  // matrix elements and integration weights described the old eigenstates
-            ABZ_HIP(hipStreamSynchronize(ctx->stream));
-            rule_drop_ltm_elements(r);
-            rule_drop_ltm_node_weights(r);
-        }
-        r->herm = src->herm;
-        if ((rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of.as<int32_t>(), n, npt, r->ntiles))) return rc;
-        ABZ_HIP(hipStreamSynchronize(ctx->stream));
-        return ABZ_OK;
-    }
-    std::unique_ptr<abz_rule> r(new abz_rule());
-    r->plan.reset(new RulePlan());  // empty: an unfolded rule has no contraction plan (abz_rule_rebuild refuses it)
-    r->s = s;
-    r->npt = npt;
-    r->want = ABZ_WANT_EIG;
-    r->full = true;
-    r->herm = src->herm;
-    r->nk = N;
-    r->ntiles = N / npt;
-    r->planes = n;
-    r->unfold_nk = src->nk;
-    r->unfold_syms.assign(syms, syms + (size_t)nsyms * d * d);
-    const int row = (npt + 15) / 16 * 16;
-    r->E.tile = (int64_t)n * row;
-    r->E.pitch = row;
-    r->E.line_len = npt;
-    r->E.row = row;
-    DevBuf rank;  // scratch: int32 [N] node of a point, then the counter of points without one
-    int missing = 0;
-    if ((rc = r->vals.alloc(sizeof(double) * (size_t)r->ntiles * (size_t)n * (size_t)row))) return rc;
-    if ((rc = r->node_of.alloc(sizeof(int32_t) * (size_t)N))) return rc;
-    if ((rc = rank.alloc(sizeof(int32_t) * ((size_t)N + 1)))) return rc;
-    r->E.base = r->vals.as<double>();
-    int* const missing_dev = reinterpret_cast<int*>(rank.as<int32_t>() + N);
-    rc = launch_ltm_orbit_map(ctx, npt, d, syms, nsyms, src->idx.as<int32_t>(), src->nk, rank.as<int32_t>(), r->node_of.as<int32_t>(), missing_dev);
-    if (!rc) rc = launch_ltm_unfold(ctx, src->E, r->E, r->node_of.as<int32_t>(), n, npt, r->ntiles);
-    // the call's one synchronisation: the counter, the map and the planes have arrived
-    hipError_t e = hipMemcpyAsync(&missing, missing_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_unfold: %s", hipGetErrorString(e));
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) return rc;
-    if (missing != 0) {
-        set_error("abz_rule_ltm_unfold: %d of the %lld grid points have no image under the %d symmetries among the %lld nodes of the source rule "
-                  "(the node list does not cover every orbit)", missing, (long long)N, nsyms, (long long)src->nk);
-        return ABZ_ERR_ARG;
-    }
-    s->refs += 1;
-    *out = r.release();  // (the handle: not a device block)
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-// Pair rule: the differences e_c - e_v of two band ranges of `src` as the eigenvalue planes of a whole-grid rule of its own, and
-// the interband products M^i_vc conj(M^j_vc) as its attached elements (kernels_ltm_pairs.hip).  Every scan that reads E, attached
-// elements or weight blocks sizes itself by rule_bands() and takes it as it takes an unfolded rule.  Both blocks are complete
-// before they replace anything: a refusal or a failure leaves *out and src as they were.
-int abz_rule_ltm_bands(const abz_rule* r, int* nb) try {
-    int rc = check_rule(r);
-    if (rc) return rc;
-    ABZ_REQUIRE(nb, "abz_rule_ltm_bands: null nb");
-    *nb = rule_bands(r);
-    return ABZ_OK;
-} ABZ_CATCH_ALL
-
-int abz_rule_ltm_pairs(abz_rule* src, int v0, int nv, int c0, int nc, abz_rule* const* ops, int nops, const int32_t* comps, int ncomp,
-                       abz_rule** out) try {
-    const char* const who = "abz_rule_ltm_pairs";
-    int rc = check_rule(src);
-    if (rc) return rc;
-    ABZ_REQUIRE(out, "abz_rule_ltm_pairs: null out");
-    ABZ_REQUIRE(nops >= 0 && nops <= ABZ_LTM_PAIRS_MAX_OPS, "abz_rule_ltm_pairs: nops = %d outside 0..%d", nops, ABZ_LTM_PAIRS_MAX_OPS);
-    if ((rc = refuse_pair_rule(src, who, "pairs are formed from the bands of a rule of the series"))) return rc;
-    // without operators: what abz_rule_ltm takes as a whole grid; with them: what abz_rule_ltm_expectation takes
-    if ((rc = nops ? ltm_eigvec_check_rule(src, who, "interband matrix elements") : ltm_check_grid(src, who))) return rc;
-    abz_series* s = src->s;
-    abz_ctx* ctx = s->ctx;
-    const int n = s->n, npt = src->npt;
-    ABZ_REQUIRE(!(nops && n == 1), "abz_rule_ltm_pairs: one band has no pairs");
-    ABZ_REQUIRE(v0 >= 0 && nv >= 1 && nc >= 1 && c0 >= 0 && (int64_t)v0 + nv <= c0 && (int64_t)c0 + nc <= n,
-                "abz_rule_ltm_pairs: ranges [%d, %d + %d) and [%d, %d + %d) of %d bands: 0 <= v0, nv >= 1, nc >= 1, v0 + nv <= c0, c0 + nc <= n",
-                v0, v0, nv, c0, c0, nc, n);
-    ABZ_REQUIRE((int64_t)nv * nc <= ABZ_MAX_BANDS, "abz_rule_ltm_pairs: %d x %d pairs are more than the %d pseudo-bands a scan takes; use a window of bands",
-                nv, nc, ABZ_MAX_BANDS);
-    const int nb = nv * nc;
-    PlaneView O[ABZ_LTM_PAIRS_MAX_OPS];
-    std::vector<int32_t> cv;  // [ncomp][3]
-    if (nops) {
-        ABZ_REQUIRE(ops, "abz_rule_ltm_pairs: null ops");
-        if (!comps) ncomp = nops;
-        ABZ_REQUIRE(ncomp >= 1 && ncomp <= ABZ_LTM_MAX_COMP, "abz_rule_ltm_pairs: ncomp = %d outside 1..%d", ncomp, ABZ_LTM_MAX_COMP);
-        cv.resize((size_t)3 * ncomp);
-        for (int c = 0; c < ncomp; ++c) {
-            cv[3 * c] = comps ? comps[3 * c] : c;
-            cv[3 * c + 1] = comps ? comps[3 * c + 1] : c;
-            cv[3 * c + 2] = comps ? comps[3 * c + 2] : 0;
-            ABZ_REQUIRE(cv[3 * c] >= 0 && cv[3 * c] < nops && cv[3 * c + 1] >= 0 && cv[3 * c + 1] < nops && (cv[3 * c + 2] == 0 || cv[3 * c + 2] == 1),
-                        "abz_rule_ltm_pairs: comps[%d] = (%d, %d, %d): operator indices inside 0..%d, part 0 (Re) or 1 (Im)", c, cv[3 * c],
-                        cv[3 * c + 1], cv[3 * c + 2], nops - 1);
-        }
-        ABZ_REQUIRE(s->hermitian && (!src->H.base || src->herm),
-                    "abz_rule_ltm_pairs: the series is not Hermitian (c(-R) = c(R)^dagger): U(k) is the eigenvector matrix of a Hermitian H(k)");
-        if ((rc = ltm_check_operators(who, src, ops, nops, O))) return rc;
-    } else {
-        ncomp = 0;
-    }
-    abz_rule* const old = *out;
-    if (old) {
-        if ((rc = check_rule(old))) return rc;
-        ABZ_REQUIRE(old->nb && old != src, "abz_rule_ltm_pairs: *out is not a rule made by abz_rule_ltm_pairs (pass NULL to create one)");
-        ABZ_REQUIRE(old->s == s && old->npt == npt && old->pair_v0 == v0 && old->pair_nv == nv && old->pair_c0 == c0 && old->pair_nc == nc &&
-                        old->pair_nops == nops && old->pair_comps == cv,
-                    "abz_rule_ltm_pairs: *out was made for another series, npt, band ranges or components (npt = %d, [%d, %d + %d) x [%d, %d + %d), "
-                    "%d operators)", old->npt, old->pair_v0, old->pair_v0, old->pair_nv, old->pair_c0, old->pair_c0, old->pair_nc, old->pair_nops);
-    }
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int row = (npt + 15) / 16 * 16;
-    PlaneView E;  // the nb planes of the pair energies, tiled like the planes of an unfolded rule
-    E.tile = (int64_t)nb * row;
-    E.pitch = row;
-    E.line_len = npt;
-    E.row = row;
-    DevBuf vals, elems;
-    PlaneView A;
-    if ((rc = vals.alloc(sizeof(double) * (size_t)src->ntiles * (size_t)nb * (size_t)row))) return rc;
-    E.base = vals.as<double>();
-    // the energies always from the source's planes: the spectra sit on the eigenvalues the source's own scans see
-    rc = launch_ltm_pair_energies(ctx, npt, src->ntiles, src->E, E, v0, nv, c0, nc);
-    if (!rc && nops)
-        rc = ltm_eigvec_block(src, who, E, ncomp * nb, [&](PlaneView H, PlaneView Ab) {
-            return launch_ltm_pairs(ctx, n, npt, src->ntiles, H, O, nops, Ab, v0, nv, c0, nc, cv.data(), ncomp);
-        }, elems, A);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_pairs: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) return rc;
-    std::unique_ptr<abz_rule> made;
-    abz_rule* r = old;
-    if (!r) {
-        made.reset(new abz_rule());
-        r = made.get();
-        r->plan.reset(new RulePlan());  // empty: a pair rule has no contraction plan (abz_rule_rebuild refuses it)
-        r->s = s;
-        r->npt = npt;
-        r->want = ABZ_WANT_EIG;
-        r->full = true;
-        r->nb = nb;
-        r->nk = src->nk;
-        r->ntiles = src->ntiles;
-        r->planes = nb;
-        r->pair_v0 = v0;
-        r->pair_nv = nv;
-        r->pair_c0 = c0;
-        r->pair_nc = nc;
-        r->pair_nops = nops;
-        r->pair_comps = cv;
-    }
-    r->herm = src->herm;
-    r->vals = std::move(vals);  // (the old energies and elements go here)
-    r->E = E;
-    rule_drop_ltm_node_weights(r);  // they described the old energies
-    rule_drop_ltm_elements(r);
-    if (nops) {
-        r->ltm_elems = std::move(elems);
-        r->ltm_ncomp = ncomp;
-        r->A = A;
-    }
-    if (made) {
-        s->refs += 1;
-        *out = made.release();  // (the handle: not a device block)
-    }
-    return ABZ_OK;
 } ABZ_CATCH_ALL
 
 // ---------------------------------------------------------------- arbitrary nodes

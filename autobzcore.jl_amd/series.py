@@ -865,9 +865,13 @@ class DeviceRule:
         [nk / npt, ncomp * nbands, row], row = npt rounded up to a multiple of 16, zeros in the padding columns; (0, 0, 0) when
         nothing is attached."""
         self._ltm_refuse_shard("ltm_elements_ptr")
-        base, nb, nc = C.c_void_p(), C.c_int64(0), C.c_int(0)
-        L.check(L.lib().abz_rule_ltm_elements_ptr(self.h, C.byref(base), C.byref(nb), C.byref(nc)))
-        return int(base.value or 0), int(nb.value), int(nc.value)
+        return self._ltm_ptr(L.lib().abz_rule_ltm_elements_ptr)
+
+    def _ltm_ptr(self, fn):
+        """(device address, bytes, count) of a resident block from its C entry point `fn`."""
+        base, nb, count = C.c_void_p(), C.c_int64(0), C.c_int(0)
+        L.check(fn(self.h, C.byref(base), C.byref(nb), C.byref(count)))
+        return int(base.value or 0), int(nb.value), int(count.value)
 
     def ltm(self, Es, states=False, elements=None, correction=False):
         """Linear tetrahedron method on the rule's eigenvalues (abz_rule_ltm): the DOS g(E) or, with `states`, the
@@ -981,30 +985,34 @@ class DeviceRule:
     def ltm_node_weights_ptr(self):
         """(device address, bytes, nE) of the resident weight block of `ltm_node_weights`; (0, 0, 0) when there is none."""
         self._ltm_refuse_shard("ltm_node_weights_ptr")
-        base, nb, ne = C.c_void_p(), C.c_int64(0), C.c_int(0)
-        L.check(L.lib().abz_rule_ltm_node_weights_ptr(self.h, C.byref(base), C.byref(nb), C.byref(ne)))
-        return int(base.value or 0), int(nb.value), int(ne.value)
+        return self._ltm_ptr(L.lib().abz_rule_ltm_node_weights_ptr)
 
     def ltm_node_weights_dot(self, elements="attached"):
         """sum_k sum_b w_b(k; E_i) A_{c,b}(k) of the resident weights of `ltm_node_weights` as [nE, ncomp]
         (abz_rule_ltm_node_weights_dot): one pass over the two blocks, no walk over the simplices.  `elements`: "attached"
         (what ltm_elements, ltm_orbitals or ltm_projectors attached) or an array [ncomp, nk, n], attached first; attaching
         elements leaves the weights in place."""
-        self._ltm_refuse_shard("ltm_node_weights_dot")
+        return self._node_weights_dot(False, elements)
+
+    def _node_weights_dot(self, green, elements):
+        """The resident real weights (float64 [nE, ncomp]) or, with `green`, complex ones (complex128 [nz, ncomp]) against the
+        attached elements."""
+        weights = "ltm_green_node_weights" if green else "ltm_node_weights"
+        self._ltm_refuse_shard(f"{weights}_dot")
         if isinstance(elements, str):
             if elements != "attached":
-                raise ValueError(f"ltm_node_weights_dot: elements = {elements!r} is neither 'attached' nor an array")
+                raise ValueError(f"{weights}_dot: elements = {elements!r} is neither 'attached' nor an array")
         else:
             self.h  # (a stale rule is refilled first: it loses its weights, and the call below says so)
             self.ltm_elements(elements)
         h = self.h
-        _, _, nE = self.ltm_node_weights_ptr()
-        if nE < 1:
-            raise ValueError("ltm_node_weights_dot: the rule holds no weights (ltm_node_weights; a rebuild of the rule drops them)")
+        _, _, count = getattr(self, f"{weights}_ptr")()
+        if count < 1:
+            raise ValueError(f"{weights}_dot: the rule holds no weights ({weights}; a rebuild of the rule drops them)")
         if self._ltm_ncomp < 1:
-            raise ValueError("ltm_node_weights_dot: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
-        out = np.zeros((nE, self._ltm_ncomp))
-        L.check(L.lib().abz_rule_ltm_node_weights_dot(h, out.ctypes.data_as(L.c_f64p)))
+            raise ValueError(f"{weights}_dot: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
+        out = np.zeros((count, self._ltm_ncomp), dtype=np.complex128 if green else np.float64)
+        L.check(getattr(L.lib(), f"abz_rule_{weights}_dot")(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out
 
     def ltm_density_matrix(self, Es=None, states=True, correction=False, orbitals=None):
@@ -1052,31 +1060,14 @@ class DeviceRule:
     def ltm_green_node_weights_ptr(self):
         """(device address, bytes, nz) of the resident block of `ltm_green_node_weights`; (0, 0, 0) when there is none."""
         self._ltm_refuse_shard("ltm_green_node_weights_ptr")
-        base, nb, nz = C.c_void_p(), C.c_int64(0), C.c_int(0)
-        L.check(L.lib().abz_rule_ltm_green_node_weights_ptr(self.h, C.byref(base), C.byref(nb), C.byref(nz)))
-        return int(base.value or 0), int(nb.value), int(nz.value)
+        return self._ltm_ptr(L.lib().abz_rule_ltm_green_node_weights_ptr)
 
     def ltm_green_node_weights_dot(self, elements="attached"):
         """sum_k sum_b W_b(k; z_i) A_{c,b}(k) of the resident weights of `ltm_green_node_weights` as complex128 [nz, ncomp]
         (abz_rule_ltm_green_node_weights_dot): `ltm_green(zs, elements="attached")` without another walk over the simplices.
         `elements` as in `ltm_node_weights_dot`: "attached" or an array [ncomp, nk, n], attached first; attaching elements
         leaves the weights in place."""
-        self._ltm_refuse_shard("ltm_green_node_weights_dot")
-        if isinstance(elements, str):
-            if elements != "attached":
-                raise ValueError(f"ltm_green_node_weights_dot: elements = {elements!r} is neither 'attached' nor an array")
-        else:
-            self.h  # (a stale rule is refilled first: it loses its weights, and the call below says so)
-            self.ltm_elements(elements)
-        h = self.h
-        _, _, nz = self.ltm_green_node_weights_ptr()
-        if nz < 1:
-            raise ValueError("ltm_green_node_weights_dot: the rule holds no weights (ltm_green_node_weights; a rebuild of the rule drops them)")
-        if self._ltm_ncomp < 1:
-            raise ValueError("ltm_green_node_weights_dot: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
-        out = np.zeros((nz, self._ltm_ncomp), dtype=np.complex128)
-        L.check(L.lib().abz_rule_ltm_green_node_weights_dot(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
-        return out
+        return self._node_weights_dot(True, elements)
 
     def ltm_green_node_weights_matrix(self, zs=None, orbitals=None):
         """The local Green's function G_pq(z) = sum_k sum_b W_b(k; z) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
