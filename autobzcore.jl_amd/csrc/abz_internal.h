@@ -80,6 +80,7 @@ enum Switch {
     SW_IAI_LANE_MIN,     // ABZ_IAI_LANE_MIN    solves a lane needs before a sweep is split further
     SW_CHAIN_FUSED,      // ABZ_CHAIN_FUSED     3-D full grids: variables 3 and 2 contracted in one launch (0: one launch per level)
     SW_EVAL_FUSED,       // ABZ_EVAL_FUSED      3-D full grids, n <= 4: the grid kernel contracts variable 2 itself (0: level-1 sets in memory)
+    SW_EVAL_PAIRS,       // ABZ_EVAL_PAIRS      fused grid kernel: one grid line per half-wave where that takes fewer lane-rounds (0: never, 2: wherever supported)
     SW_COUNT
 };
 int abz_switch(Switch s);  // the switch's integer value from the environment, or its default
@@ -425,7 +426,8 @@ struct EvalSpec {
 };
 int launch_eval(abz_ctx* ctx, const EvalSpec& es);
 bool eval_packed_supported(int n, int M, int npt);
-bool eval_fused_supported(int n, int64_t mnn, int M2, int npt);  // mnn: numbers per line (packed_row_elems or M n n)
+// mnn: numbers per line (packed_row_elems or M n n); pairs: the LDS of the pair mapping (one grid line per half-wave)
+bool eval_fused_supported(int n, int64_t mnn, int M2, int npt, bool pairs = false);
 // rows [nrows][M n n] of full coefficients (innermost variable fastest) -> packed rows [nrows][P] (packed_herm.h)
 int launch_pack_rows(abz_ctx* ctx, int n, int M, const double2* src, int64_t nrows, double2* out);
 size_t packed_row_elems(int n, int M);

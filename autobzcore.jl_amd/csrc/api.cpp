@@ -90,6 +90,7 @@ const SwitchDef g_switches[SW_COUNT] = {
     {"ABZ_IAI_LANE_MIN", 16, "solves per lane below which a sweep is not split further"},
     {"ABZ_CHAIN_FUSED", 1, "0: 3-D full-grid chains contract variables 3 and 2 in two launches instead of contract_chain_kernel"},
     {"ABZ_EVAL_FUSED", 1, "0: 3-D full-grid rules (n <= 4) build level-1 sets with contract_chain_kernel instead of contracting variable 2 inside the grid kernel"},
+    {"ABZ_EVAL_PAIRS", 1, "fused grid kernel, one grid line per half-wave: 1 where it takes fewer lane-rounds per line (Hermitian series), 0 never, 2 wherever supported (tests: same values)"},
 };
 }  // namespace
 

@@ -41,6 +41,9 @@ __device__ __forceinline__ void cmul(double ar, double ai, double br, double bi,
 //   a_rp' = c a_rp - s g a_rq ; a_rq' = s a_rp + c g a_rq ; a_pp -= t b ; a_qq += t b
 template <int N, bool VEC>
 __device__ __forceinline__ void herm_eig(const CMat<N>& h, double (&e)[N], CMat<N>& V) {
+    // products fused as written, the same in every inlined copy (see herm_eig3_values): two kernel instances give one
+    // matrix the same eigenvectors to the bit by construction, not by the optimiser's choice
+#pragma clang fp contract(on)
     if constexpr (N == 1) {
         e[0] = h.re[0][0];
         if constexpr (VEC) {
@@ -190,6 +193,10 @@ __device__ __forceinline__ void sort3(double a, double b, double c, double (&e)[
 // (3) the other two eigenvalues from the 2 x 2 projection of A on the orthogonal complement, which
 // is stable for (near-)degenerate pairs where the closed form alone loses half the digits.
 __device__ __forceinline__ void herm_eig3_values(const CMat<3>& h, double (&e)[3]) {
+    // Products are fused into fma as each expression is written, not wherever the optimiser finds a pair: left to it,
+    // sums such as br br + bi bi were rounded differently from one inlined copy to the next (even between the columns
+    // of one lane), so the eigenvalues of a node depended on the lane slot it was computed in.
+#pragma clang fp contract(on)
     const double a00 = h.re[0][0], a11 = h.re[1][1], a22 = h.re[2][2];
     const double br = h.re[0][1], bi = h.im[0][1];  // a01
     const double cr = h.re[0][2], ci = h.im[0][2];  // a02

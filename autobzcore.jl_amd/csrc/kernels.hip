@@ -628,10 +628,24 @@ __device__ __forceinline__ void eval_epilogue(const EvalArgs& a, CMat<N>& H, int
 // No block-level barrier: a wave only ever reads the LDS bytes it wrote itself.
 constexpr int EVAL_MAX_MNN = 256;  // complex coefficients per line held in LDS (M * N * N)
 
+// Phase recurrence of the grid kernels, p <- p z.  The roundings are spelled out: written as p.x z.x - p.y z.y and
+// p.x z.y + p.y z.x, the compiler chose which product to fuse per instance (one column per lane: fma(p.y, z.x, p.x z.y);
+// three: fma(p.x, z.y, p.y z.x)), so two work mappings of one grid agreed only by chance.  This is the form of the
+// three-column instances (the 150^3 grid), now the same in every instance.
+__device__ __forceinline__ void phase_step(double& pr, double& pi, double zr, double zi) {
+    const double nr = fma(pr, zr, -(pi * zi));
+    const double ni = fma(pr, zi, pi * zr);
+    pr = nr;
+    pi = ni;
+}
+
 // One unit of work of the grid kernels: pass `pass` (64 KPL nodes starting at i0) of line `line`, from the
 // line's coefficients c1 (LDS).  `mid` runs between the m-loop and the stores: the place where the next
 // unit's coefficients are handed to the other LDS buffer.
-template <int N, int KPL, bool HERM, class MID, bool PK = false>
+// LW = 32 (pair mapping of the fused instance): a unit is a pass of TWO lines, one per half-wave; `lane` is then the
+// lane's index within its half, c1 its half's set, and a lane owns the columns i0 + lane + 32 j.  Per node the
+// arithmetic is the same either way.
+template <int N, int KPL, bool HERM, class MID, bool PK = false, int LW = 64>
 __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2* __restrict__ c1, const double2* tab_l, int fm,
                                                const int (&iz0)[KPL], const int (&iw0)[KPL], int npass, int i0, int lane,
                                                MID&& mid, CMat<N> (&H)[KPL]) {
@@ -645,7 +659,7 @@ __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2*
         for (int j = 0; j < KPL; ++j) {
             int ic = iz0[j];
             if (npass > 1) {
-                const int i1 = i0 + lane + 64 * j;
+                const int i1 = i0 + lane + LW * j;
                 ic = i1 < a.npt ? i1 : 0;
             }
             const double2 z = tab_l[ic];
@@ -669,10 +683,7 @@ __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2*
         for (int f = 1; f <= F; ++f) {
 #pragma unroll
             for (int j = 0; j < KPL; ++j) {
-                const double nr = pr[j] * zr[j] - pi[j] * zi[j];
-                const double ni = pr[j] * zi[j] + pi[j] * zr[j];
-                pr[j] = nr;
-                pi[j] = ni;
+                phase_step(pr[j], pi[j], zr[j], zi[j]);
             }
             const double2* __restrict__ cf = c1 + Pk<N>::blk(1) + (f - 1) * (N * N);
 #pragma unroll
@@ -719,7 +730,7 @@ __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2*
     for (int j = 0; j < KPL; ++j) {
         int ic = iz0[j], iw = iw0[j];
         if (npass > 1) {
-            const int i1 = i0 + lane + 64 * j;
+            const int i1 = i0 + lane + LW * j;
             ic = i1 < a.npt ? i1 : 0;
             iw = (int)(((unsigned)fm * (unsigned)ic) % (unsigned)a.npt);
         }
@@ -758,12 +769,7 @@ __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2*
             }
         }
 #pragma unroll
-        for (int j = 0; j < KPL; ++j) {
-            const double nr = pr[j] * zr[j] - pi[j] * zi[j];
-            const double ni = pr[j] * zi[j] + pi[j] * zr[j];
-            pr[j] = nr;
-            pi[j] = ni;
-        }
+        for (int j = 0; j < KPL; ++j) phase_step(pr[j], pi[j], zr[j], zi[j]);
     }
     mid();
 #pragma unroll
@@ -782,9 +788,14 @@ __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2*
 }
 
 // The store epilogue of a unit: values of its 64 KPL nodes into the tiled-planar rule arrays.
-template <int N, int KPL, bool VEC>
-__device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[KPL], int i0, int lane, int64_t line) {
+// Pair mapping (LW = 32): `line` is the pair's first line and the second half-wave adds one tile to its lane offset
+// (off_h, off_e: 0 or the tile of the H and of the eigenvalue planes), so every plane row keeps its scalar base; a
+// half without a line of its own (odd npt) has `on` false and stores nothing.
+template <int N, int KPL, bool VEC, int LW = 64>
+__device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[KPL], int i0, int lane, int64_t line, int off_h = 0,
+                                                int off_e = 0, bool on = true) {
     if constexpr (VEC) {
+        static_assert(LW == 64, "the pair mapping stores values and eigenvalues only");
 #pragma unroll
         for (int j = 0; j < KPL; ++j) {
             const int i1 = i0 + lane + 64 * j;
@@ -806,19 +817,19 @@ __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[
             if (a.H.base) {
 #pragma unroll
                 for (int j = 0; j < KPL; ++j) {
-                    const int i1 = i0 + lane + 64 * j;
-                    if (i1 < pitch) store_planes_at<N, NT, HC>(H[j], a.H, line, i1);
+                    const int i1 = i0 + lane + LW * j;
+                    if (i1 < pitch && on) store_planes_at<N, NT, HC>(H[j], a.H, line, i1 + off_h);
                 }
             }
             if (a.E.base) {
 #pragma unroll
                 for (int j = 0; j < KPL; ++j) {
-                    const int i1 = i0 + lane + 64 * j;
-                    if (i1 < pitch) {
+                    const int i1 = i0 + lane + LW * j;
+                    if (i1 < pitch && on) {
                         double e[N];
                         herm_eig_values<N>(H[j], e);
                         double* __restrict__ row = a.E.base + line * a.E.tile;
-                        const unsigned u = (unsigned)i1;
+                        const unsigned u = (unsigned)(i1 + off_e);
 #pragma unroll
                         for (int b = 0; b < N; ++b) store_f64<NT>((row + (int64_t)b * a.E.pitch) + u, e[b]);
                     }
@@ -837,13 +848,13 @@ __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[
     }
 }
 
-template <int N, int KPL, bool HERM, bool VEC, class MID, bool PK = false>
+template <int N, int KPL, bool HERM, bool VEC, class MID, bool PK = false, int LW = 64>
 __device__ __forceinline__ void eval_unit(const EvalArgs& a, const double2* __restrict__ c1, const double2* tab_l, int fm,
                                           const int (&iz0)[KPL], const int (&iw0)[KPL], int npass, int i0, int lane,
-                                          int64_t line, MID&& mid) {
+                                          int64_t line, MID&& mid, int off_h = 0, int off_e = 0, bool on = true) {
     CMat<N> H[KPL];
-    eval_unit_core<N, KPL, HERM, MID&, PK>(a, c1, tab_l, fm, iz0, iw0, npass, i0, lane, mid, H);
-    eval_unit_store<N, KPL, VEC>(a, H, i0, lane, line);
+    eval_unit_core<N, KPL, HERM, MID&, PK, LW>(a, c1, tab_l, fm, iz0, iw0, npass, i0, lane, mid, H);
+    eval_unit_store<N, KPL, VEC, LW>(a, H, i0, lane, line, off_h, off_e, on);
 }
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -897,9 +908,20 @@ __device__ __forceinline__ void contract_line_m(int M2, const double2* s2, const
 // stepping by 4 bpk, of that index; it stages the level-2 set of k3 next to the phase table (one round trip) and
 // every wave contracts its next line into its other LDS buffer where the plain kernel hands over prefetched
 // registers: the work loop holds no vector load at all.
-template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false>
+// PAIR (with FUSE): one grid line per half-wave.  A wave's unit is the pair of lines (k2, k2 + 1), k2 = 2 (4 seg + wave)
+// stepping by 8 bpk: lanes 0-31 own line k2, lanes 32-63 line k2 + 1, a lane the columns (lane & 31) + 32 j.  Five
+// rounds cover a 160-double row exactly where the 64-lane mapping issues 3 x 64 = 192 slots per line.  The rounds of
+// a pair, ceil(npt / 32), are run as passes of KPL with a last pass of KT <= KPL (150 points: 3 + 2; five rounds in one
+// pass spill at three waves per SIMD), so no round is idle.  Both lines'
+// level-1 sets lie side by side in the wave's LDS room, [buffer][half][MNN]; k3, the pair and the pass stay scalars,
+// only the half is per lane (the set's address and one tile added to the store offset).  The last pair of an odd npt
+// has one line: its second half evaluates line npt - 1 again and stores nothing.
+template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false, bool PAIR = false, int KT = KPL>
 __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
-    extern __shared__ double2 lds_c[];  // [4 waves][2 buffers][MNN], phase table [npt], FUSE: level-2 set [M2][MNN]
+    static_assert(FUSE || !PAIR, "the pair mapping exists in the fused instance only");
+    static_assert(KT >= 1 && KT <= KPL && (PAIR || KT == KPL), "a shorter last pass exists in the pair mapping only");
+    constexpr int LPU = PAIR ? 2 : 1;  // lines per unit of work
+    extern __shared__ double2 lds_c[];  // [4 waves][2 buffers][LPU][MNN], phase table [npt], FUSE: level-2 set [M2][MNN]
     // the wave index is made an SGPR value: every per-line quantity (tile base, coefficient row) is
     // then scalar arithmetic
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -910,7 +932,7 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
         const double f = 6.283185307179586476925286766559 * (double)(a.first + idx / (N * N));
         return make_double2(-f * c.y, f * c.x);
     };
-    double2* const mybuf = lds_c + (size_t)wave * 2 * MNN;
+    double2* const mybuf = lds_c + (size_t)wave * 2 * LPU * MNN;
     int fm = a.first % a.npt;
     if (fm < 0) fm += a.npt;
     // Every global load issued inside the work loop shares the in-order vmcnt with the stores, and a
@@ -918,8 +940,9 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
     // line code with exactly one group of loads (the next unit's coefficients) and one wait, placed
     // right after the m-loop when the previous unit's stores are a whole m-loop old; phase seeds
     // come from an LDS copy of the table.  A unit of work is one pass (64 KPL nodes) of one line.
-    const int npass = (a.npt + 64 * KPL - 1) / (64 * KPL);
-    double2* const tab_l = lds_c + (size_t)4 * 2 * MNN;  // LDS copy of the phase table, shared by the block
+    constexpr int LW = 64 / LPU;  // lanes per line
+    const int npass = (a.npt + LW * KPL - 1) / (LW * KPL);
+    double2* const tab_l = lds_c + (size_t)4 * 2 * LPU * MNN;  // LDS copy of the phase table, shared by the block
     if constexpr (FUSE) {
         static_assert(!VEC, "the fused instance stores values and eigenvalues only");
         const int k3 = blockIdx.y, seg = blockIdx.x;  // grid (bpk, outermost indices): both scalars
@@ -929,7 +952,7 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
         // the phases of the wave's first line: in flight across the copy and the barrier (a wave beyond the last line
         // reads row 0)
         const int kstride = 4 * a.bpk;
-        int k2 = 4 * seg + wave;
+        int k2 = LPU * (4 * seg + wave);
         LinePhases ph;
         load_line_phases(as_const(a.phs2 + (int64_t)(k2 < a.npt ? k2 : 0) * a.M2), ph);
         // phase table and level-2 set in one round trip: the loads are unconditional, from clamped 32-bit indices off
@@ -953,6 +976,65 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
         __syncthreads();
         if (k2 >= a.npt) return;
         contract_line_m(a.M2, s2, ph, mybuf, MNN, lane);
+        if constexpr (PAIR) {
+            const int half = lane >> 5, col = lane & 31;
+            // both lines of a pair, one after the other, lane = column as above; line k2 + 1 clamped to the last line
+            load_line_phases(as_const(a.phs2 + (int64_t)min(k2 + 1, a.npt - 1) * a.M2), ph);
+            contract_line_m(a.M2, s2, ph, mybuf + MNN, MNN, lane);
+            // seeds of pass 0, read when it is the only pass: then it is the last one, of KT rounds
+            int iz0[KPL], iw0[KPL], izt[KT], iwt[KT];
+#pragma unroll
+            for (int j = 0; j < KPL; ++j) {
+                const int i1 = col + 32 * j;
+                iz0[j] = i1 < a.npt ? i1 : 0;
+                iw0[j] = (int)(((unsigned)fm * (unsigned)iz0[j]) % (unsigned)a.npt);
+                if (j < KT) {
+                    izt[j] = iz0[j];
+                    iwt[j] = iw0[j];
+                }
+            }
+            const int off_h = half * (int)a.H.tile, off_e = half * (int)a.E.tile;  // launch_eval: the tiles fit 31 bits
+            int cur = 0, pass = 0;
+            while (k2 < a.npt) {
+                // the next unit is the same pair again (its sets stay where they are) or the wave's next pair
+                const bool last_pass = pass + 1 >= npass;
+                const int nk2 = last_pass ? k2 + 2 * kstride : k2;
+                const bool contract_next = last_pass && nk2 < a.npt;
+                wave_lds_sync();
+                // (kept inline, so the phases stay in registers)
+                auto mid_fn = [&]() __attribute__((always_inline)) {
+                    if (contract_next) {
+                        // the LDS addresses of the contraction are formed here, from a lane index the compiler cannot see
+                        // through: hoisted out of the work loop they were spilled to scratch at three waves per SIMD
+                        int ln = lane;
+                        asm volatile("" : "+v"(ln));
+                        double2* const dst = mybuf + (size_t)(cur ^ 1) * 2 * MNN;
+                        load_line_phases(as_const(a.phs2 + (int64_t)nk2 * a.M2), ph);
+                        contract_line_m(a.M2, s2, ph, dst, MNN, ln);
+                        load_line_phases(as_const(a.phs2 + (int64_t)min(nk2 + 1, a.npt - 1) * a.M2), ph);
+                        contract_line_m(a.M2, s2, ph, dst + MNN, MNN, ln);
+                    }
+                };
+                const double2* const c1 = mybuf + (size_t)(2 * cur + half) * MNN;
+                const int64_t line = (int64_t)k3 * a.npt + k2;
+                const bool on = half == 0 || k2 + 1 < a.npt;
+                if constexpr (KT == KPL) {
+                    eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK, 32>(a, c1, tab_l, fm, iz0, iw0, npass, pass * (32 * KPL), col, line, mid_fn,
+                                                                            off_h, off_e, on);
+                } else if (!last_pass) {  // nothing to contract before the pair's last pass
+                    auto no_mid = []() {};
+                    eval_unit<N, KPL, HERM, VEC, decltype(no_mid)&, PK, 32>(a, c1, tab_l, fm, iz0, iw0, npass, pass * (32 * KPL), col, line, no_mid,
+                                                                            off_h, off_e, on);
+                } else {
+                    eval_unit<N, KT, HERM, VEC, decltype(mid_fn)&, PK, 32>(a, c1, tab_l, fm, izt, iwt, npass, pass * (32 * KPL), col, line, mid_fn,
+                                                                           off_h, off_e, on);
+                }
+                if (last_pass) cur ^= 1;
+                pass = last_pass ? 0 : pass + 1;
+                k2 = nk2;
+            }
+            return;
+        }
         int iz0[KPL], iw0[KPL];
 #pragma unroll
         for (int j = 0; j < KPL; ++j) {
@@ -1114,9 +1196,11 @@ bool eval_packed_supported(int n, int M, int npt) {
 
 // Can the grid kernel contract variable 2 itself (EvalSpec::src2)?  Its LDS-staged path with the level-2 set of one
 // outermost index next to the four waves' double buffers and the phase table; `mnn` numbers per line.
-bool eval_fused_supported(int n, int64_t mnn, int M2, int npt) {
+// `pairs`: the pair mapping (one line per half-wave), whose waves hold two lines' sets in each buffer.
+bool eval_fused_supported(int n, int64_t mnn, int M2, int npt, bool pairs) {
+    const size_t lpu = pairs ? 2 : 1;
     return n >= 1 && n <= 4 && mnn >= 1 && mnn <= EVAL_MAX_MNN && M2 >= 1 && M2 <= ABZ_CONTRACT_GRID_MAXM && npt >= 1 &&
-           npt < 65536 && sizeof(double2) * ((size_t)M2 * mnn + 4 * 2 * (size_t)mnn + (size_t)npt) <= 64 * 1024;
+           npt < 65536 && sizeof(double2) * ((size_t)M2 * mnn + 4 * 2 * lpu * (size_t)mnn + (size_t)npt) <= 64 * 1024;
 }
 
 int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
@@ -1222,6 +1306,48 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
             a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(es.npt, 4), cdiv(blocks, gcnt)));
             a.bpk = (int)cdiv(es.npt, 4 * cdiv(es.npt, 4 * a.bpk));
             const size_t flds = lds + sizeof(double2) * (size_t)es.M2 * mnn;
+            // Pair mapping (one line per half-wave): the same count over rounds of 32 lanes, for two lines at once.  Its
+            // passes are of KP rounds -- the most the instance holds without scratch in its work loop: 3, with 4 bands 2,
+            // non-Hermitian 1 -- and the last pass of the rest, kt, so a pair costs ceil(npt / 32) lane-rounds.  It is taken
+            // where that is fewer than two lines of the 64-lane mapping cost (150 points: 5 against 2 x 3); ties keep the
+            // 64-lane mapping (measured slower or equal there: +6 % at 64 and 250 points), and so do non-Hermitian series
+            // (3 bands: +7 % at 80 points, +4 % at 200, -2 % at 150).  ABZ_EVAL_PAIRS: 0 never,
+            // 2 wherever the kernel supports it.
+            const int sw_pairs = abz_switch(SW_EVAL_PAIRS);
+            const int rounds = (int)cdiv(es.npt, 32);
+            const bool pairs = sw_pairs != 0 && eval_fused_supported(es.n, mnn, es.M2, es.npt, true) && es.H.tile < INT32_MAX &&
+                               es.E.tile < INT32_MAX && (sw_pairs >= 2 || (a.herm && rounds < 2 * cdiv(es.npt, 64 * kpl) * kpl));
+            if (pairs) {
+                const int kp = es.n < 4 ? 3 : (a.herm ? 2 : 1);
+                const int kt = rounds - (int)(cdiv(rounds, kp) - 1) * kp;  // 1 ... kp
+                // blocks per index by the rule above, counted in pairs (150 points: 19 blocks, one pair per wave; two pairs
+                // per wave measured 9 % slower there and 7 % at 200 points)
+                const int64_t npairs = cdiv(es.npt, 2);
+                a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(npairs, 4), cdiv(blocks, gcnt)));
+                a.bpk = (int)cdiv(npairs, 4 * cdiv(npairs, 4 * a.bpk));
+                const size_t plds = flds + sizeof(double2) * 4 * 2 * (size_t)mnn;
+                const dim3 grid((unsigned)a.bpk, (unsigned)gcnt);
+#define LKP(NN, KT)                                                                                                          \
+    {                                                                                                                        \
+        constexpr int OO = NN == 3 ? 3 : 2;                                                                                  \
+        constexpr int KH = NN < 4 ? 3 : 2, KG = NN < 4 ? 3 : 1; /* kp above */                                               \
+        if (a.pk)                                                                                                            \
+            launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, true, true, true, KT <= KH ? KT : KH>, grid, dim3(256), plds, a);  \
+        else if (a.herm)                                                                                                     \
+            launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, false, true, true, KT <= KH ? KT : KH>, grid, dim3(256), plds, a); \
+        else                                                                                                                 \
+            launch(ctx, eval_grid_kernel<NN, KG, false, false, 2, false, true, true, KT <= KG ? KT : KG>, grid, dim3(256), plds, a); \
+    }
+#define FN(NN)                     \
+    switch (kt) {                  \
+        case 1: LKP(NN, 1) break;  \
+        case 2: LKP(NN, 2) break;  \
+        default: LKP(NN, 3) break; \
+    }
+                ABZ_DISPATCH_N(es.n, FN)
+#undef FN
+#undef LKP
+            } else {
 #define LK(NN, KK)                                                                                                                         \
     {                                                                                                                                      \
         constexpr int OO = NN == 3 ? 3 : 2;                                                                                                \
@@ -1241,6 +1367,7 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
             ABZ_DISPATCH_N(es.n, FN)
 #undef FN
 #undef LK
+            }
         } else if (mnn <= EVAL_MAX_MNN && lds <= 64 * 1024 && a.npt < 65536) {
             // waves per SIMD the register allocator is asked for: 3 on the Hermitian 3-band paths (2 and 4 measured
             // slower there), 2 elsewhere

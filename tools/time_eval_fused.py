@@ -1,7 +1,10 @@
 """Rebuild pass of a 3-D SVO rule (H + eigenvalues) with the last contraction inside the grid kernel (the default) and
 with level-1 sets in memory (ABZ_EVAL_FUSED=0): wall time per pass over back-to-back rebuilds, arms alternated.
 
-    python3 tools/time_eval_fused.py [--ref-layout] [svo | n3gen | n4herm | n2herm ...] [npt ...]
+    python3 tools/time_eval_fused.py [--ref-layout] [--pairs] [svo | n3gen | n4herm | n2herm ...] [npt ...]
+
+--pairs: the arms are the two work mappings of the fused grid kernel instead, one grid line per wave (ABZ_EVAL_PAIRS=0)
+and one per half-wave wherever the kernel supports it (ABZ_EVAL_PAIRS=2).
 """
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,9 +41,13 @@ def per_pass(ctx, rule, n):
 
 args = sys.argv[1:]
 ref_layout = "--ref-layout" in args  # full matrices (168 B per k-point at 3 bands) instead of the upper triangle of Hermitian rules
-args = [a for a in args if a != "--ref-layout"]
+pairs = "--pairs" in args
+args = [a for a in args if a not in ("--ref-layout", "--pairs")]
 names = [a for a in args if a in SERIES] or ["svo"]
 npts = [int(a) for a in args if a not in SERIES] or [64, 100, 128, 150, 200, 250, 400]
+# (switch, value of the base arm, value of the new arm, their names)
+switch, base, new, base_name, new_name = (("ABZ_EVAL_PAIRS", "0", "2", "line per wave", "line per half-wave") if pairs else
+                                          ("ABZ_EVAL_FUSED", "0", "1", "level-1 sets in memory", "fused"))
 for name in names:
     dev = SERIES[name]().device()
     herm = name != "n3gen"
@@ -48,16 +55,16 @@ for name in names:
         want = L.WANT_H | (L.WANT_EIG if herm else 0)
         rule = abz.DeviceRule(dev, npt, None, want if ref_layout else dev._layout_want(want))
         n = max(8, min(256, int(2e9 / npt**3)))
-        res = {"1": [], "0": []}
+        res = {new: [], base: []}
         for rep in range(4):  # the first round warms up
-            for arm in ("0", "1"):
-                os.environ["ABZ_EVAL_FUSED"] = arm
+            for arm in (base, new):
+                os.environ[switch] = arm
                 t = per_pass(dev.ctx, rule, n)
                 if rep:
                     res[arm].append(t)
-        del os.environ["ABZ_EVAL_FUSED"]
-        off, on = sorted(res["0"]), sorted(res["1"])
-        print(f"{name}{' ref-layout' if ref_layout else ''} npt {npt}: level-1 sets in memory {off[0]:.4f} {off[1]:.4f} {off[2]:.4f} ms, fused {on[0]:.4f} {on[1]:.4f} {on[2]:.4f} ms "
+        del os.environ[switch]
+        off, on = sorted(res[base]), sorted(res[new])
+        print(f"{name}{' ref-layout' if ref_layout else ''} npt {npt}: {base_name} {off[0]:.4f} {off[1]:.4f} {off[2]:.4f} ms, {new_name} {on[0]:.4f} {on[1]:.4f} {on[2]:.4f} ms "
               f"per pass ({n} passes per sample); medians {off[1]:.4f} -> {on[1]:.4f} ({100 * (on[1] / off[1] - 1):+.1f} %)", flush=True)
         rule.close()
     dev.drop_rules()
