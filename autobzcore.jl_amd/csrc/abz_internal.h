@@ -81,6 +81,7 @@ enum Switch {
     SW_CHAIN_FUSED,      // ABZ_CHAIN_FUSED     3-D full grids: variables 3 and 2 contracted in one launch (0: one launch per level)
     SW_EVAL_FUSED,       // ABZ_EVAL_FUSED      3-D full grids, n <= 4: the grid kernel contracts variable 2 itself (0: level-1 sets in memory)
     SW_EVAL_PAIRS,       // ABZ_EVAL_PAIRS      fused grid kernel: one grid line per half-wave where that takes fewer lane-rounds (0: never, 2: wherever supported)
+    SW_EVAL_MIRROR,      // ABZ_EVAL_MIRROR     3-D full grids, real Hermitian series: planes k3 <= npt/2 evaluated, H(-k) = conj H(k) stored with them, where the launch writes at most 600 MB (0: never, 2: wherever supported)
     SW_COUNT
 };
 int abz_switch(Switch s);  // the switch's integer value from the environment, or its default
@@ -230,6 +231,7 @@ struct abz_series {
     int first[ABZ_MAX_DIM] = {0, 0, 0};
     double period[ABZ_MAX_DIM] = {1, 1, 1};
     bool hermitian = false;   // c(-R) == c(R)^dagger exactly  =>  H(k) Hermitian: half the Fourier work
+    bool real_coef = false;   // every Im c(R) == 0.0 exactly; with `hermitian`: H(-k) == conj H(k), eigenvalues at -k those at k
     int pivoting = ABZ_PIVOT_NONE;  // abz_series_set_pivoting: read at every launch of a resolvent integrand (series_pivots below)
     abz::DevBuf coef_pk;       // Hermitian series, n <= 4: the coefficients with the innermost variable packed (packed_herm.h)
     bool coef_pk_valid = false;
@@ -419,6 +421,10 @@ struct EvalSpec {
     const double2* src2 = nullptr;
     const double2* phs2 = nullptr;
     int M2 = 0;
+    // grid mode, nlines == npt * npt (a whole 3-D grid) of a real Hermitian series, no eigenvectors: the lines of the planes
+    // k3 <= npt / 2 are evaluated and every node of a plane that is not its own mirror image is stored a second time, conjugated,
+    // at -k (eval_mirror_supported; the scalar fallback kernel evaluates every line as before)
+    bool mirror = false;
     // outputs (tiled planar views), base == nullptr when not wanted
     PlaneView H;
     PlaneView E;
@@ -426,6 +432,7 @@ struct EvalSpec {
 };
 int launch_eval(abz_ctx* ctx, const EvalSpec& es);
 bool eval_packed_supported(int n, int M, int npt);
+bool eval_mirror_supported(const EvalSpec& es);
 // mnn: numbers per line (packed_row_elems or M n n); pairs: the LDS of the pair mapping (one grid line per half-wave)
 bool eval_fused_supported(int n, int64_t mnn, int M2, int npt, bool pairs = false);
 // rows [nrows][M n n] of full coefficients (innermost variable fastest) -> packed rows [nrows][P] (packed_herm.h)

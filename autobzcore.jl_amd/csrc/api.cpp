@@ -91,6 +91,7 @@ const SwitchDef g_switches[SW_COUNT] = {
     {"ABZ_CHAIN_FUSED", 1, "0: 3-D full-grid chains contract variables 3 and 2 in two launches instead of contract_chain_kernel"},
     {"ABZ_EVAL_FUSED", 1, "0: 3-D full-grid rules (n <= 4) build level-1 sets with contract_chain_kernel instead of contracting variable 2 inside the grid kernel"},
     {"ABZ_EVAL_PAIRS", 1, "fused grid kernel, one grid line per half-wave: 1 where it takes fewer lane-rounds per line (Hermitian series), 0 never, 2 wherever supported (tests: same values)"},
+    {"ABZ_EVAL_MIRROR", 1, "3-D full-grid rules (n <= 4) of a real Hermitian series evaluate the planes k3 <= npt/2 and store H(-k) = conj H(k) beside them: 1 where the launch writes at most 600 MB, 0 never (every plane evaluated), 2 wherever supported"},
 };
 }  // namespace
 
@@ -846,6 +847,7 @@ int abz_prof_read(abz_ctx* ctx, int kernel_id, double* total_ms, int64_t* launch
 
 // ---------------------------------------------------------------- series
 static bool detect_hermitian(const abz_series* s, const double* coef_reim);
+static bool detect_real(const abz_series* s, const double* coef_reim);
 
 int abz_series_create(abz_ctx* ctx, const double* coef_reim, int d, const int32_t* dims, const int32_t* first,
                       const double* period, int n, abz_series** out) try {
@@ -873,6 +875,7 @@ int abz_series_create(abz_ctx* ctx, const double* coef_reim, int d, const int32_
         return ABZ_ERR_HIP;
     }
     s->hermitian = detect_hermitian(s.get(), coef_reim);
+    s->real_coef = detect_real(s.get(), coef_reim);
     ctx->refs += 1;
     *out = s.release();  // (the handle: not a device block)
     return ABZ_OK;
@@ -907,6 +910,14 @@ static bool detect_hermitian(const abz_series* s, const double* coef_reim) {
     return true;
 }
 
+// Im c(R) == 0.0 for every R and entry (exact comparison; -0.0 counts as zero)
+static bool detect_real(const abz_series* s, const double* coef_reim) {
+    const int64_t cnt = s->elems(s->d);
+    for (int64_t i = 0; i < cnt; ++i)
+        if (coef_reim[2 * i + 1] != 0.0) return false;
+    return true;
+}
+
 int abz_series_update(abz_series* s, const double* coef_reim) try {
     int rc = check_series(s);
     if (rc) return rc;
@@ -916,11 +927,13 @@ int abz_series_update(abz_series* s, const double* coef_reim) try {
                            s->ctx->stream));
     ABZ_HIP(hipStreamSynchronize(s->ctx->stream));
     s->hermitian = detect_hermitian(s, coef_reim);
+    s->real_coef = detect_real(s, coef_reim);
     s->coef_pk_valid = false;
     s->generation += 1;  // rules kept by the series refill themselves at their next use
     for (int64_t& u : s->iai_used) u = 0;  // sets contracted from the old coefficients (abz_contract_nodes) are dead
     for (abz_series* v : s->lanes) {
         v->hermitian = s->hermitian;
+        v->real_coef = s->real_coef;
         v->coef_pk_valid = false;
         v->generation += 1;
     }
@@ -962,6 +975,7 @@ int series_lane_views(abz_series* s, int count) {
             v->period[j] = s->period[j];
         }
         v->hermitian = s->hermitian;
+        v->real_coef = s->real_coef;
         v->pivoting = s->pivoting;
         v->coef = DevBuf::view_of(s->coef.p);
         c->refs += 1;
@@ -1195,6 +1209,18 @@ static int rule_fill(abz_rule* r) {
         es.deriv = deriv;
         es.herm = s->hermitian;
         es.packed = packed_chain && !deriv && !Uout.base;
+        // whole 3-D grids of a real Hermitian series, values / eigenvalues only (a slab's mirror planes belong to another rank).
+        // Size rule (profiles/eval_mirror_trace_gaps.txt): by the bytes the launch writes, padding
+        // included.  Every measured shape up to 597 MB was faster mirrored (3 and 4 bands, both layouts: 3-32 %), 605 MB tied
+        // (+2 %) and 665 MB and more lost 9-50 % with 3 bands -- the mirrored stores are temporal, and beyond that they no
+        // longer leave L2 as whole lines.  (4 bands still won 15 % at 814 MB and lost at 1331 MB; the limit is not tuned per
+        // band count.)  ABZ_EVAL_MIRROR=2 takes the route wherever it is supported.
+        const int sw_mirror = abz_switch(SW_EVAL_MIRROR);
+        const PlaneView& pv = Hout.base ? Hout : Eout;
+        const double out_bytes = 8.0 * ((Hout.base ? (Hout.compact ? 1.0 : 2.0) * n * n : 0.0) + (Eout.base ? (double)n : 0.0)) *
+                                 (double)pv.row * (double)es.nlines;
+        es.mirror = s->hermitian && s->real_coef && r->full && d == 3 && plan.outer_n == r->npt && !deriv && !Uout.base &&
+                    !(r->want & ABZ_WANT_VEL) && (sw_mirror >= 2 || (sw_mirror == 1 && out_bytes <= 600e6));
         es.H = Hout;
         es.E = Eout;
         es.U = Uout;

@@ -558,6 +558,9 @@ struct EvalArgs {
     const double2* src2 = nullptr;
     const double2* phs2 = nullptr;
     int M2 = 0, bpk = 0;
+    // nlines == npt^2, real Hermitian series: the lines of planes k3 <= npt / 2 are evaluated, the rest stored as their mirror
+    // images (eval_unit_store)
+    int mirror = 0;
 };
 
 // planes of one node at column i1 of tile `line`; with a wave-uniform line every plane row is a scalar
@@ -570,7 +573,9 @@ __device__ __forceinline__ void store_f64(double* p, double v) {
     else
         *p = v;
 }
-template <int N, bool NT = false, bool HC = false>
+// CONJ: the conjugate is stored (the imaginary planes with their sign flipped; the diagonal's stay as they are, +0.0 in
+// Hermitian instances either way)
+template <int N, bool NT = false, bool HC = false, bool CONJ = false>
 __device__ __forceinline__ void store_planes_at(const CMat<N>& H, const PlaneView& v, int64_t line, int i1) {
     double* __restrict__ row = v.base + line * v.tile;
     const unsigned u = (unsigned)i1;
@@ -580,7 +585,7 @@ __device__ __forceinline__ void store_planes_at(const CMat<N>& H, const PlaneVie
 #pragma unroll
             for (int a = 0; a <= b; ++a) {
                 store_f64<NT>((row + (int64_t)(b * b + 2 * a) * v.pitch) + u, H.re[a][b]);
-                if (a < b) store_f64<NT>((row + (int64_t)(b * b + 2 * a + 1) * v.pitch) + u, H.im[a][b]);
+                if (a < b) store_f64<NT>((row + (int64_t)(b * b + 2 * a + 1) * v.pitch) + u, CONJ ? -H.im[a][b] : H.im[a][b]);
             }
         }
     } else {
@@ -589,7 +594,7 @@ __device__ __forceinline__ void store_planes_at(const CMat<N>& H, const PlaneVie
 #pragma unroll
             for (int a = 0; a < N; ++a) {
                 store_f64<NT>((row + (int64_t)(2 * (a + N * b)) * v.pitch) + u, H.re[a][b]);
-                store_f64<NT>((row + (int64_t)(2 * (a + N * b) + 1) * v.pitch) + u, H.im[a][b]);
+                store_f64<NT>((row + (int64_t)(2 * (a + N * b) + 1) * v.pitch) + u, (CONJ && a != b) ? -H.im[a][b] : H.im[a][b]);
             }
         }
     }
@@ -787,13 +792,30 @@ __device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2*
     }
 }
 
+// Where a unit's values go a second time when the rule is built from the planes k3 <= npt / 2 alone (EvalArgs::mirror): the
+// row of -k.  `line` is a line of the mirrored plane and t0 / t1 the offset from it in tiles for the lanes of the first and
+// of the second half-wave (the pair mapping: line = first line of the mirrored plane, t0 / t1 = the mirrored k2 of the half's
+// line; the two are not neighbours at k2 = 0).  All three are scalars.
+// line < 0: nothing is mirrored (the unit's plane is its own mirror image, or the launch evaluates every plane).
+struct MirrorTo {
+    int64_t line = -1;
+    int t0 = 0, t1 = 0;
+};
+
 // The store epilogue of a unit: values of its 64 KPL nodes into the tiled-planar rule arrays.
 // Pair mapping (LW = 32): `line` is the pair's first line and the second half-wave adds one tile to its lane offset
 // (off_h, off_e: 0 or the tile of the H and of the eigenvalue planes), so every plane row keeps its scalar base; a
 // half without a line of its own (odd npt) has `on` false and stores nothing.
+// Mirror (mt.line >= 0): H(-k) = conj H(k) of a real Hermitian series, from the same registers -- column i1 of the row goes
+// to column (npt - i1) % npt of the mirrored row, padding columns to themselves, with the sign of the off-diagonal imaginary
+// planes flipped and the same eigenvalues.  Every column of the mirrored tile is written exactly once, like the unit's own.
+// A half-wave's mirrored run is contiguous but descends with the lane and starts off a 128-B line ((npt - 32 j - 31) 8 B:
+// 56 B off at 150 points), so it leaves lines partial until the next round or, across a pass seam, the next pass fills them.
+// These stores are therefore always temporal, so that L2 merges the parts before the line goes out: with the unit's own
+// non-temporal policy the 150^3 launch took 141 us instead of 62 (every line written to memory twice, in parts).
 template <int N, int KPL, bool VEC, int LW = 64>
 __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[KPL], int i0, int lane, int64_t line, int off_h = 0,
-                                                int off_e = 0, bool on = true) {
+                                                int off_e = 0, bool on = true, const MirrorTo mt = MirrorTo()) {
     if constexpr (VEC) {
         static_assert(LW == 64, "the pair mapping stores values and eigenvalues only");
 #pragma unroll
@@ -811,6 +833,20 @@ __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[
         // Cache this is worth 19 % at 150^3 (neither change alone is: the interleaved order leaves the
         // store queue empty during every eigensolve, and temporal stores make the 605 MB fight for L2/MALL).
         const int pitch = a.H.base ? a.H.row : a.E.row;
+        const bool mir = mt.line >= 0;  // wave-uniform
+        // the lane's offset in the mirrored row for its column j, formed where it is used from a thread index the compiler
+        // cannot see through: hoisted out of the work loop (one register per column and pass) these offsets were spilled to
+        // scratch at three waves per SIMD (the benchmark's instance, <3, 3, true, false, 3, true, true, true, 2>: 168 VGPRs and
+        // 12 B of scratch per lane, reloaded in the work loop; formed here: 168 VGPRs, no scratch, three waves per SIMD).
+        // This relies on what every caller passes: lane == threadIdx.x & (LW - 1), and with LW == 32 bit 5 of threadIdx.x
+        // is the lane's half (eval_grid_kernel: lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5).
+        auto moffset = [&](int j, int64_t tile) {
+            int tx = threadIdx.x;
+            asm volatile("" : "+v"(tx));
+            const int i1 = i0 + (tx & (LW - 1)) + LW * j;
+            const int mc = (i1 == 0 || i1 >= a.npt) ? i1 : a.npt - i1;
+            return mc + (LW == 32 && (tx & 32) ? mt.t1 : mt.t0) * (int)tile;
+        };
         auto epilogue = [&](auto nt, auto hc) {
             constexpr bool NT = decltype(nt)::value;
             constexpr bool HC = decltype(hc)::value;
@@ -819,6 +855,13 @@ __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[
                 for (int j = 0; j < KPL; ++j) {
                     const int i1 = i0 + lane + LW * j;
                     if (i1 < pitch && on) store_planes_at<N, NT, HC>(H[j], a.H, line, i1 + off_h);
+                }
+                if (mir) {
+#pragma unroll
+                    for (int j = 0; j < KPL; ++j) {
+                        const int i1 = i0 + lane + LW * j;
+                        if (i1 < pitch && on) store_planes_at<N, false, HC, true>(H[j], a.H, mt.line, moffset(j, a.H.tile));
+                    }
                 }
             }
             if (a.E.base) {
@@ -832,6 +875,12 @@ __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[
                         const unsigned u = (unsigned)(i1 + off_e);
 #pragma unroll
                         for (int b = 0; b < N; ++b) store_f64<NT>((row + (int64_t)b * a.E.pitch) + u, e[b]);
+                        if (mir) {
+                            double* __restrict__ mrow = a.E.base + mt.line * a.E.tile;
+                            const unsigned mu = (unsigned)moffset(j, a.E.tile);
+#pragma unroll
+                            for (int b = 0; b < N; ++b) store_f64<false>((mrow + (int64_t)b * a.E.pitch) + mu, e[b]);
+                        }
                     }
                 }
             }
@@ -851,10 +900,11 @@ __device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[
 template <int N, int KPL, bool HERM, bool VEC, class MID, bool PK = false, int LW = 64>
 __device__ __forceinline__ void eval_unit(const EvalArgs& a, const double2* __restrict__ c1, const double2* tab_l, int fm,
                                           const int (&iz0)[KPL], const int (&iw0)[KPL], int npass, int i0, int lane,
-                                          int64_t line, MID&& mid, int off_h = 0, int off_e = 0, bool on = true) {
+                                          int64_t line, MID&& mid, int off_h = 0, int off_e = 0, bool on = true,
+                                          const MirrorTo mt = MirrorTo()) {
     CMat<N> H[KPL];
     eval_unit_core<N, KPL, HERM, MID&, PK, LW>(a, c1, tab_l, fm, iz0, iw0, npass, i0, lane, mid, H);
-    eval_unit_store<N, KPL, VEC, LW>(a, H, i0, lane, line, off_h, off_e, on);
+    eval_unit_store<N, KPL, VEC, LW>(a, H, i0, lane, line, off_h, off_e, on, mt);
 }
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -916,8 +966,12 @@ __device__ __forceinline__ void contract_line_m(int M2, const double2* s2, const
 // level-1 sets lie side by side in the wave's LDS room, [buffer][half][MNN]; k3, the pair and the pass stay scalars,
 // only the half is per lane (the set's address and one tile added to the store offset).  The last pair of an odd npt
 // has one line: its second half evaluates line npt - 1 again and stores nothing.
-template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false, bool PAIR = false, int KT = KPL>
+// MIR: the instance of a mirrored launch (EvalArgs::mirror, Hermitian series only).  A template parameter, so the instances of
+// every other launch hold none of its code: with a run-time flag alone the benchmark's instance measured 5 % slower with the
+// mirror switched off.
+template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false, bool PAIR = false, int KT = KPL, bool MIR = false>
 __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
+    static_assert(!MIR || (HERM && !VEC), "mirrored launches: values and eigenvalues of a Hermitian series");
     static_assert(FUSE || !PAIR, "the pair mapping exists in the fused instance only");
     static_assert(KT >= 1 && KT <= KPL && (PAIR || KT == KPL), "a shorter last pass exists in the pair mapping only");
     constexpr int LPU = PAIR ? 2 : 1;  // lines per unit of work
@@ -946,6 +1000,8 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
     if constexpr (FUSE) {
         static_assert(!VEC, "the fused instance stores values and eigenvalues only");
         const int k3 = blockIdx.y, seg = blockIdx.x;  // grid (bpk, outermost indices): both scalars
+        // mirror: the grid's rows are the planes k3 <= npt / 2; the plane of -k3, or -1 where k3 is its own (0 and npt / 2)
+        const int mk3 = (MIR && k3 != 0 && 2 * k3 != a.npt) ? a.npt - k3 : -1;
         const int L2 = a.M2 * MNN;
         const double2* __restrict__ src2 = a.src2 + (int64_t)k3 * L2;
         double2* const s2 = tab_l + a.npt;
@@ -1018,16 +1074,22 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
                 const double2* const c1 = mybuf + (size_t)(2 * cur + half) * MNN;
                 const int64_t line = (int64_t)k3 * a.npt + k2;
                 const bool on = half == 0 || k2 + 1 < a.npt;
+                MirrorTo mt;
+                if (mk3 >= 0) {
+                    mt.line = (int64_t)mk3 * a.npt;
+                    mt.t0 = k2 ? a.npt - k2 : 0;
+                    mt.t1 = k2 + 1 < a.npt ? a.npt - k2 - 1 : 0;  // (a half without a line: nothing is stored)
+                }
                 if constexpr (KT == KPL) {
                     eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK, 32>(a, c1, tab_l, fm, iz0, iw0, npass, pass * (32 * KPL), col, line, mid_fn,
-                                                                            off_h, off_e, on);
+                                                                            off_h, off_e, on, mt);
                 } else if (!last_pass) {  // nothing to contract before the pair's last pass
                     auto no_mid = []() {};
                     eval_unit<N, KPL, HERM, VEC, decltype(no_mid)&, PK, 32>(a, c1, tab_l, fm, iz0, iw0, npass, pass * (32 * KPL), col, line, no_mid,
-                                                                            off_h, off_e, on);
+                                                                            off_h, off_e, on, mt);
                 } else {
                     eval_unit<N, KT, HERM, VEC, decltype(mid_fn)&, PK, 32>(a, c1, tab_l, fm, izt, iwt, npass, pass * (32 * KPL), col, line, mid_fn,
-                                                                           off_h, off_e, on);
+                                                                           off_h, off_e, on, mt);
                 }
                 if (last_pass) cur ^= 1;
                 pass = last_pass ? 0 : pass + 1;
@@ -1055,8 +1117,10 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
                     contract_line_m(a.M2, s2, ph, mybuf + (size_t)(cur ^ 1) * MNN, MNN, lane);
                 }
             };
+            MirrorTo mt;
+            if (mk3 >= 0) mt.line = (int64_t)mk3 * a.npt + (k2 ? a.npt - k2 : 0);
             eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK>(a, mybuf + (size_t)cur * MNN, tab_l, fm, iz0, iw0, npass, pass * (64 * KPL), lane,
-                                                                (int64_t)k3 * a.npt + k2, mid_fn);
+                                                                (int64_t)k3 * a.npt + k2, mid_fn, 0, 0, true, mt);
             if (last_pass) cur ^= 1;
             pass = last_pass ? 0 : pass + 1;
             k2 = nk2;
@@ -1115,8 +1179,13 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
                 }
             }
         };
+        MirrorTo mt;
+        if constexpr (MIR) {  // a.nlines: the lines of the planes k3 <= npt / 2, fewer than 2^31 (eval_mirror_supported)
+            const unsigned k3 = (unsigned)line / (unsigned)a.npt, k2 = (unsigned)line - k3 * (unsigned)a.npt;
+            if (k3 != 0 && 2 * (int)k3 != a.npt) mt.line = (int64_t)(a.npt - (int)k3) * a.npt + (k2 ? a.npt - (int)k2 : 0);
+        }
         eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK>(a, mybuf + (size_t)cur * MNN, tab_l, fm, iz0, iw0, npass, pass * (64 * KPL), lane, line,
-                                                            mid_fn);
+                                                            mid_fn, 0, 0, true, mt);
         cur ^= 1;
         pass = last_pass ? 0 : pass + 1;
         line = nline;
@@ -1201,6 +1270,27 @@ bool eval_fused_supported(int n, int64_t mnn, int M2, int npt, bool pairs) {
     const size_t lpu = pairs ? 2 : 1;
     return n >= 1 && n <= 4 && mnn >= 1 && mnn <= EVAL_MAX_MNN && M2 >= 1 && M2 <= ABZ_CONTRACT_GRID_MAXM && npt >= 1 &&
            npt < 65536 && sizeof(double2) * ((size_t)M2 * mnn + 4 * 2 * lpu * (size_t)mnn + (size_t)npt) <= 64 * 1024;
+}
+
+// f(std::bool_constant<p>{}, std::bool_constant<q>{}): the template flags of the launch ladders below from run-time values
+template <class F>
+static void with_flags(bool p, bool q, F&& f) {
+    if (p)
+        q ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    else
+        q ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+
+// Can a launch evaluate the planes k3 <= npt / 2 alone and store the rest as their mirror images (EvalSpec::mirror)?  A whole
+// 3-D grid, values / eigenvalues of a Hermitian series; the mirrored row is addressed from the first line of its plane by a
+// 32-bit lane offset.
+bool eval_mirror_supported(const EvalSpec& es) {
+    if (!es.mirror || !es.grid || !es.herm || es.deriv || es.U.base || es.n < 1 || es.n > 4 || es.npt < 1 || es.npt >= 65536 ||
+        es.nlines != (int64_t)es.npt * es.npt || es.nlines >= INT32_MAX)
+        return false;
+    for (const PlaneView* v : {&es.H, &es.E})
+        if (v->base && ((int64_t)es.npt * v->tile + v->row >= INT32_MAX || v->tile < 0)) return false;
+    return true;
 }
 
 int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
@@ -1297,6 +1387,9 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
                 return ABZ_ERR_UNSUPPORTED;
             }
             const int64_t gcnt = es.nlines / es.npt;
+            // mirror: the launch grid's rows are the planes k3 <= npt / 2; blocks per plane as for the whole grid
+            a.mirror = eval_mirror_supported(es) ? 1 : 0;
+            const unsigned grows = a.mirror ? (unsigned)(es.npt / 2 + 1) : (unsigned)gcnt;
             a.src2 = es.src2;
             a.phs2 = es.phs2;
             a.M2 = es.M2;
@@ -1326,15 +1419,15 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
                 a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(npairs, 4), cdiv(blocks, gcnt)));
                 a.bpk = (int)cdiv(npairs, 4 * cdiv(npairs, 4 * a.bpk));
                 const size_t plds = flds + sizeof(double2) * 4 * 2 * (size_t)mnn;
-                const dim3 grid((unsigned)a.bpk, (unsigned)gcnt);
+                const dim3 grid((unsigned)a.bpk, grows);
 #define LKP(NN, KT)                                                                                                          \
     {                                                                                                                        \
         constexpr int OO = NN == 3 ? 3 : 2;                                                                                  \
         constexpr int KH = NN < 4 ? 3 : 2, KG = NN < 4 ? 3 : 1; /* kp above */                                               \
-        if (a.pk)                                                                                                            \
-            launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, true, true, true, KT <= KH ? KT : KH>, grid, dim3(256), plds, a);  \
-        else if (a.herm)                                                                                                     \
-            launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, false, true, true, KT <= KH ? KT : KH>, grid, dim3(256), plds, a); \
+        if (a.herm)                                                                                                          \
+            with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                    \
+                launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, pk(), true, true, KT <= KH ? KT : KH, mir()>, grid, dim3(256), plds, a); \
+            });                                                                                                              \
         else                                                                                                                 \
             launch(ctx, eval_grid_kernel<NN, KG, false, false, 2, false, true, true, KT <= KG ? KT : KG>, grid, dim3(256), plds, a); \
     }
@@ -1351,12 +1444,12 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
 #define LK(NN, KK)                                                                                                                         \
     {                                                                                                                                      \
         constexpr int OO = NN == 3 ? 3 : 2;                                                                                                \
-        if (a.pk)                                                                                                                          \
-            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, true, true>, dim3((unsigned)a.bpk, (unsigned)gcnt), dim3(256), flds, a);  \
-        else if (a.herm)                                                                                                                   \
-            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, false, true>, dim3((unsigned)a.bpk, (unsigned)gcnt), dim3(256), flds, a); \
+        if (a.herm)                                                                                                                        \
+            with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                                  \
+                launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, pk(), true, false, KK, mir()>, dim3((unsigned)a.bpk, grows), dim3(256), flds, a); \
+            });                                                                                                                            \
         else                                                                                                                               \
-            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2, false, true>, dim3((unsigned)a.bpk, (unsigned)gcnt), dim3(256), flds, a); \
+            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2, false, true>, dim3((unsigned)a.bpk, grows), dim3(256), flds, a); \
     }
 #define FN(NN)                    \
     switch (kpl) {                \
@@ -1371,17 +1464,23 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
         } else if (mnn <= EVAL_MAX_MNN && lds <= 64 * 1024 && a.npt < 65536) {
             // waves per SIMD the register allocator is asked for: 3 on the Hermitian 3-band paths (2 and 4 measured
             // slower there), 2 elsewhere
+            // mirror: the lines of the planes k3 <= npt / 2, which come first
+            if (eval_mirror_supported(es)) {
+                a.mirror = 1;
+                a.nlines = (int64_t)(es.npt / 2 + 1) * es.npt;
+            }
+            const unsigned lblocks = (unsigned)std::min<int64_t>(blocks, cdiv(a.nlines, 4));
 #define LK(NN, KK)                                                                                                             \
     {                                                                                                                          \
         constexpr int OO = NN == 3 ? 3 : 2;                                                                                    \
-        if (a.pk)                                                                                                              \
-            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, true>, dim3((unsigned)blocks), dim3(256), lds, a); \
-        else if (a.U.base)                                                                                                     \
-            launch(ctx, eval_grid_kernel<NN, KK, false, true, 2>, dim3((unsigned)blocks), dim3(256), lds, a);  \
+        if (a.U.base && !a.pk)                                                                                                 \
+            launch(ctx, eval_grid_kernel<NN, KK, false, true, 2>, dim3(lblocks), dim3(256), lds, a);                           \
         else if (a.herm)                                                                                                       \
-            launch(ctx, eval_grid_kernel<NN, KK, true, false, OO>, dim3((unsigned)blocks), dim3(256), lds, a); \
+            with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                      \
+                launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, pk(), false, false, KK, mir()>, dim3(lblocks), dim3(256), lds, a); \
+            });                                                                                                                \
         else                                                                                                                   \
-            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2>, dim3((unsigned)blocks), dim3(256), lds, a); \
+            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2>, dim3(lblocks), dim3(256), lds, a);                          \
     }
 #define FN(NN)                    \
     switch (kpl) {                \
