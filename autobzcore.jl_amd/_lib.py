@@ -63,6 +63,7 @@ PROTOTYPES = {
     "abz_rule_ltm_halo": (C.c_int, [C.c_void_p]),
     "abz_rule_ltm_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_vpp, C.c_int, c_i32p, C.c_int, c_vpp]),
     "abz_rule_ltm_bands": (C.c_int, [C.c_void_p, c_ip]),
+    "abz_rule_ltm_pairs_occupied": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_rule_ltm_green": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
     "abz_rule_ltm_green_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, c_f64p]),
     "abz_rule_ltm_node_weights": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int, c_f64p]),
@@ -102,6 +103,7 @@ K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
 K_EVAL_FUSED = 7  # launches only: the K_EVAL launches of the fused grid kernel
 LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
+LTM_A_ONE = 2  # A = 1, the joint DOS: abz_rule_ltm_pairs_occupied only
 LTM_MAX_COMP = 16
 LTM_EXPECT_MAX_OPS = 8  # operators of one abz_rule_ltm_expectation call
 LTM_PAIRS_MAX_OPS = 4  # operators of one abz_rule_ltm_pairs call

@@ -551,6 +551,9 @@ int launch_ltm_repack(abz_ctx* ctx, const double* src_dev, PlaneView A, int plan
 // The last step of every tetrahedron sum: out[c * ostride + i] = scale * sum_rows partial[c * cnt + i][row] for the `ncols` columns
 // (c, i) of transposed partials [ncols][nrows], in a fixed order
 int launch_ltm_final(abz_ctx* ctx, const double* partial, int64_t nrows, double scale, int ncols, int cnt, int64_t ostride, double* out);
+// The last step of a state sum's chunk (nE <= 512), one block per component: out[c * ostride + i] = weight * (sums[c][i] + steps[c][0] +
+// ... + steps[c][i]) from col = [nc][nE] sums | [nc][nE] steps, the prefix sum in index order
+int launch_ltm_prefix(abz_ctx* ctx, const double* col, int nE, int nc, double weight, int64_t ostride, double* out);
 // Orbital weights as matrix elements (kernels_ltm_orb.hip): plane c n + b of A (ncomp n planes tiled like the eigenvalue planes,
 // padding columns included) <- |U_{orb[c], b}|^2 from the H planes of the same whole grid (full or compact); orb == nullptr:
 // orbital c.  1...32 bands.  Launches only, under ABZ_K_EIG.
@@ -574,6 +577,12 @@ int launch_ltm_pair_energies(abz_ctx* ctx, int npt, int64_t nlines, PlaneView E,
 // the operators `ops` (as launch_ltm_expectation reads them).  2...32 bands, nops <= ABZ_LTM_PAIRS_MAX_OPS.  Under ABZ_K_EIG.
 int launch_ltm_pairs(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, const PlaneView* ops, int nops, PlaneView A, int v0, int nv,
                      int c0, int nc, const int32_t* comps, int ncomp);
+// The scans of a pair rule with the occupation factor theta(E_F - e_v) theta(e_c - E_F) inside every simplex
+// (kernels_ltm_pairs_occ.hip): out_host [nE][ncomp], g (states = false) or N.  Esrc: the eigenvalue planes of the SOURCE grid; pseudo-band
+// p < nb is the pair v = v0 + p / pnc, c = c0 + p % pnc of its bands.  A: the element block of the pair rule (ncomp nb planes), or
+// nullptr with ncomp = 1: A = 1, the joint DOS.  Under ABZ_K_LTM.
+int launch_ltm_pairs_occupied(abz_ctx* ctx, int d, int npt, PlaneView Esrc, const PlaneView* A, int ncomp, int nb, int v0, int c0, int pnc,
+                              double E_F, const double* Es_host, int nE, bool states, double* out_host);
 // Density matrix in the orbital basis (kernels_ltm_dens.hip): out_host [nE][n][n][2] = sum_k sum_b w_b(k; E_i) U_pb conj(U_qb) from the
 // weight block W (nE n planes, as launch_ltm_node_weights leaves it) and the H planes of the same whole grid (not read for one
 // band), U never in HBM; the lower triangle is the exact conjugate of the upper one.  1...32 bands.  Kernels under ABZ_K_EIG,

@@ -799,4 +799,37 @@ int abz_rule_ltm_pairs(abz_rule* src, int v0, int nv, int c0, int nc, abz_rule* 
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
+// The scans of a pair rule with the occupations of a metal (kernels_ltm_pairs_occ.hip).  Every check comes before anything is reserved
+// or launched; nothing is attached, replaced or dropped on either rule.
+int abz_rule_ltm_pairs_occupied(abz_rule* src, abz_rule* pairs, double E_F, int source, const double* w, int nw, int what, double* out) try {
+    const char* const who = "abz_rule_ltm_pairs_occupied";
+    int rc = check_rule(src);
+    if (rc || (rc = check_rule(pairs))) return rc;
+    ABZ_REQUIRE(w && out && nw >= 1, "abz_rule_ltm_pairs_occupied: bad arguments (w = %s, out = %s, nw = %d)", w ? "given" : "NULL",
+                out ? "given" : "NULL", nw);
+    ABZ_REQUIRE(pairs->nb, "abz_rule_ltm_pairs_occupied: `pairs` is not a rule made by abz_rule_ltm_pairs");
+    if ((rc = refuse_pair_rule(src, who, "the occupations are those of the bands of the pair rule's source"))) return rc;
+    if (what == ABZ_LTM_STATES_CORRECTED) {
+        set_error("abz_rule_ltm_pairs_occupied: ABZ_LTM_STATES_CORRECTED: the curvature correction is not defined on cut simplices");
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if ((rc = ltm_check_what(who, what, false))) return rc;
+    ABZ_REQUIRE(source == ABZ_LTM_A_ELEMENTS || source == ABZ_LTM_A_ONE, "%s: source = %d is neither ABZ_LTM_A_ELEMENTS nor ABZ_LTM_A_ONE", who,
+                source);
+    if ((rc = ltm_check_grid(src, who)) || (rc = ltm_check_grid(pairs, who))) return rc;
+    ABZ_REQUIRE(src->s == pairs->s && src->npt == pairs->npt,
+                "abz_rule_ltm_pairs_occupied: the rules differ in their series or grid (src: npt = %d, pairs: npt = %d)", src->npt, pairs->npt);
+    ABZ_REQUIRE(pairs->pair_c0 + pairs->pair_nc <= rule_bands(src), "abz_rule_ltm_pairs_occupied: the upper range [%d, %d + %d) leaves the %d bands of src",
+                pairs->pair_c0, pairs->pair_c0, pairs->pair_nc, rule_bands(src));
+    ABZ_REQUIRE(source == ABZ_LTM_A_ONE || pairs->elems.buf.p,
+                "abz_rule_ltm_pairs_occupied: the pair rule has no elements (abz_rule_ltm_pairs with operators, abz_rule_ltm_elements); "
+                "ABZ_LTM_A_ONE gives the joint DOS");
+    ABZ_REQUIRE(std::isfinite(E_F), "abz_rule_ltm_pairs_occupied: E_F = %g is not finite", E_F);
+    abz_ctx* ctx = src->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const bool one = source == ABZ_LTM_A_ONE;
+    return launch_ltm_pairs_occupied(ctx, src->s->d, src->npt, src->E, one ? nullptr : &pairs->elems.view, one ? 1 : pairs->elems.sets, pairs->nb,
+                                     pairs->pair_v0, pairs->pair_c0, pairs->pair_nc, E_F, w, nw, what == ABZ_LTM_STATES, out);
+} ABZ_CATCH_ALL
+
 }  // extern "C"

@@ -71,8 +71,10 @@ class BandPairs:
     around the gap.  `operators`: None (energies only), 1..4 FourierSeries in the Wannier basis of H, or "velocities":
     velocity_operators(H, basis) of the cache's own H with the real parts of all products a <= b as components, in the order of
     velocity_components(d).  `components`: entries i (|M^i|^2), (i, j) (Re M^i conj(M^j)) or (i, j, "re" | "im"); None: |M^i|^2 of
-    every operator.  Whole bands only: no occupation factors, no 1 / w weights.  At a degenerate level only the sum of a
-    component over all pairs between two levels is defined."""
+    every operator.  The ranges are whole bands and carry no 1 / w weights; the occupation factors of a metal,
+    theta(E_F - e_v) theta(e_c - E_F) inside every simplex, come from `joint_dos` / `interband` with `fermi=` or `nstates=`
+    (PairRule.ltm_occupied on the cache's pair rule).  At a degenerate level only the sum of a component over all pairs between
+    two levels is defined."""
 
     def __init__(self, nocc=None, lower=None, upper=None, operators=None, components=None, basis=None):
         if (nocc is None) == (lower is None and upper is None) or (lower is None) != (upper is None):
@@ -693,12 +695,67 @@ def _pairs_cache(prob_or_cache, who, npt, pairs, **alg):
     return init(prob_or_cache, LTM(npt=npt, pairs=pairs, **alg))
 
 
-def joint_dos(prob_or_cache, ws, nocc=None, lower=None, upper=None, npt=50, cumulative=False, symmetric=False):
+def _occupied_check(who, fermi, nstates, correction=False, x=None):
+    """What `fermi` / `nstates` of joint_dos and interband do not go with; True when occupations were asked for."""
+    if fermi is None and nstates is None:
+        return False
+    if fermi is not None and nstates is not None:
+        raise ValueError(f"{who}: give at most one of fermi and nstates")
+    if correction:
+        raise ValueError(f"{who}: correction=True does not go with fermi / nstates (the curvature correction is not defined on the "
+                         "cut simplices of the occupied region)")
+    if x is not None and np.iscomplexobj(x):
+        raise NotImplementedError(f"{who}: complex energies with fermi / nstates are not implemented (the broadened, Kramers-Kronig "
+                                  "form of the spectra has no occupation factors; pass real transition energies)")
+    return True
+
+
+def _occupied_scan(c, who, ws, fermi, nstates, elements):
+    """(u, E_F): PairRule.ltm_occupied on the pair rule of the cache `c`, at `fermi` or at the source grid's own level of `nstates`."""
+    if c.alg.correction:
+        raise ValueError(f"{who}: correction=True does not go with fermi / nstates (the curvature correction is not defined on the "
+                         "cut simplices of the occupied region)")
+    _refresh(c)
+    pr = c.cacheval
+    pr.h  # (a stale pair rule is refilled here, and its source with it)
+    E_F = float(fermi) if fermi is not None else pr.source.ltm_fermi(nstates)[0]
+    return pr.ltm_occupied(ws, E_F, states=c.alg.cumulative, elements=elements), E_F
+
+
+def _occupied_all_pairs(prob, who, ws, fermi, nstates, npt, elements, pair_kw, alg_kw):
+    """All pairs v < c of a DOSProblem as a staircase of pair rules lower = (v, 1), upper = (v + 1, n - v - 1), results added."""
+    n = getattr(prob.H, "n", None)
+    if not isinstance(prob.H, FourierSeries) or n < 2:
+        raise ValueError(f"{who}: all pairs v < c need a Fourier series Hamiltonian of at least two bands")
+    total, E_F = None, fermi
+    for v in range(n - 1):
+        c = init(prob, LTM(npt=npt, pairs=BandPairs(lower=(v, 1), upper=(v + 1, n - v - 1), **pair_kw), **alg_kw))
+        try:
+            u, E_F = _occupied_scan(c, who, ws, E_F, None if E_F is not None else nstates, elements)
+        finally:
+            c.cacheval.close()  # this step's energies and elements leave the device now, not with the collector
+        total = u if total is None else total + u
+    return total
+
+
+def joint_dos(prob_or_cache, ws, nocc=None, lower=None, upper=None, npt=50, cumulative=False, symmetric=False, fermi=None, nstates=None):
     """The joint density of states J(w) = sum_vc int dk delta(w - (e_c(k) - e_v(k))) at the transition energies `ws`, per unit
     cell, [nw] (with `cumulative` its integral, the number of pairs below w): DeviceRule.ltm on the pair rule of an
     LTM(pairs=BandPairs(...)) cache, or of a DOSProblem with the pairs `nocc` or `lower` + `upper` on a grid of `npt` points
-    (`symmetric=True`: eigenvalues from the irreducible nodes of the problem's zone)."""
+    (`symmetric=True`: eigenvalues from the irreducible nodes of the problem's zone).
+
+    `fermi` or `nstates` (at most one): the occupied joint DOS of a metal at T = 0, with theta(E_F - e_v) theta(e_c - E_F) under the
+    integral (PairRule.ltm_occupied: every simplex restricted to its occupied part).  `nstates` finds E_F with `ltm_fermi` on the
+    source rule, the grid's own Fermi level.  On a DOSProblem without `nocc`, `lower`, `upper` all pairs v < c are taken, as a
+    staircase of pair rules lower = (v, 1), upper = (v + 1, n - v - 1) whose results are added: n - 1 pair rules, each filled and
+    scanned once.  Without `fermi` / `nstates` nothing changes."""
     pairs = None if nocc is None and lower is None and upper is None else BandPairs(nocc=nocc, lower=lower, upper=upper)
+    if _occupied_check("joint_dos", fermi, nstates):
+        ws = np.ascontiguousarray(np.asarray(ws, dtype=np.float64).reshape(-1))
+        if pairs is None and not isinstance(prob_or_cache, DOSCache):
+            return _occupied_all_pairs(prob_or_cache, "joint_dos", ws, fermi, nstates, npt, None, {}, dict(cumulative=cumulative, symmetric=symmetric))
+        c = _pairs_cache(prob_or_cache, "joint_dos", npt, pairs, cumulative=cumulative, symmetric=symmetric)
+        return _occupied_scan(c, "joint_dos", ws, fermi, nstates, None)[0]
     c = _pairs_cache(prob_or_cache, "joint_dos", npt, pairs, cumulative=cumulative, symmetric=symmetric)
     _refresh(c)
     ws = np.ascontiguousarray(np.asarray(ws, dtype=np.float64).reshape(-1))
@@ -706,19 +763,35 @@ def joint_dos(prob_or_cache, ws, nocc=None, lower=None, upper=None, npt=50, cumu
 
 
 def interband(prob_or_cache, ws_or_zs, nocc=None, lower=None, upper=None, operators="velocities", components=None, basis=None, npt=50,
-              cumulative=False, correction=False):
+              cumulative=False, correction=False, fermi=None, nstates=None):
     """The interband spectra S_ij = sum_vc int dk M^i_vc conj(M^j_vc) delta(w - (e_c - e_v)) at real transition energies, [nw, ncomp]
     (with `cumulative` their integrals, with `correction` Bloechl's curvature correction on those), or at complex energies z
     (Im z != 0) sum_vc int dk M M^* / (z - (e_c - e_v)), complex128 [nz, ncomp]: -Im / pi at z = w + i eta is the spectrum
     broadened by eta, Re its Kramers-Kronig partner.  DeviceRule.ltm / ltm_green with the attached interband products of the
     pair rule of an LTM(pairs=BandPairs(..., operators=...)) cache, or of a DOSProblem with the pairs `nocc` or `lower` + `upper`
-    and `operators` ("velocities": velocity_operators(H, basis)) on a grid of `npt` points."""
+    and `operators` ("velocities": velocity_operators(H, basis)) on a grid of `npt` points.
+
+    `fermi` or `nstates` (at most one): the spectra of a metal at T = 0, with theta(E_F - e_v) theta(e_c - E_F) under the integral
+    (PairRule.ltm_occupied).  `nstates` finds E_F with `ltm_fermi` on the source rule, the grid's own Fermi level.  Complex
+    energies raise NotImplementedError with them (the broadened form has no occupation factors), `correction=True` ValueError.  On
+    a DOSProblem without `nocc`, `lower`, `upper` all pairs v < c are taken, as a staircase of pair rules lower = (v, 1),
+    upper = (v + 1, n - v - 1) whose results are added.  Cost: one element build (an eigen-solve of the grid) per step, n - 1 in
+    all.  Without `fermi` / `nstates` nothing changes."""
+    if _occupied_check("interband", fermi, nstates, correction, np.asarray(ws_or_zs)):
+        ws = np.ascontiguousarray(np.asarray(ws_or_zs, dtype=np.float64).reshape(-1))
+        if nocc is None and lower is None and upper is None and not isinstance(prob_or_cache, DOSCache):
+            if operators is None:
+                raise ValueError("interband needs band pairs with operators (joint_dos scans the energies alone)")
+            return _occupied_all_pairs(prob_or_cache, "interband", ws, fermi, nstates, npt, "attached",
+                                       dict(operators=operators, components=components, basis=basis), dict(cumulative=cumulative))
     pairs = None
     if not (nocc is None and lower is None and upper is None):
         pairs = BandPairs(nocc=nocc, lower=lower, upper=upper, operators=operators, components=components, basis=basis)
     c = _pairs_cache(prob_or_cache, "interband", npt, pairs, cumulative=cumulative, correction=correction)
     if c.alg.pairs.operators is None:
         raise ValueError("interband needs band pairs with operators (joint_dos scans the energies alone)")
+    if fermi is not None or nstates is not None:
+        return _occupied_scan(c, "interband", np.ascontiguousarray(np.asarray(ws_or_zs, dtype=np.float64).reshape(-1)), fermi, nstates, "attached")[0]
     _refresh(c)
     x = np.asarray(ws_or_zs).reshape(-1)
     if np.iscomplexobj(x):

@@ -1120,8 +1120,8 @@ class DeviceRule:
         interband products of M^i_vc = u_v^H Hermitian(O_i) u_c as attached elements: `components` entries i (|M^i|^2), (i, j)
         (Re M^i conj(M^j)) or (i, j, "re" | "im"); None: |M^i|^2 for every operator.  `ltm(ws, elements="attached")` is then the
         interband spectrum, `ltm_green(zs, elements="attached")` the broadened one (-Im / pi) with its Kramers-Kronig partner
-        (Re).  At a degenerate level only the sum of a component over all pairs between two levels is defined.  Whole bands
-        only: no occupation factors."""
+        (Re).  At a degenerate level only the sum of a component over all pairs between two levels is defined.  These scans
+        take whole bands; the occupation factors of a metal are `PairRule.ltm_occupied(ws, fermi)`."""
         self._ltm_refuse_shard("ltm_pairs")
         return PairRule(self, lower, upper, operators, components)
 
@@ -1297,6 +1297,39 @@ class PairRule(DeviceRule):
             raise L.AbzError("DeviceRule was closed")
         self.source.rebuild()
         self.refill()
+
+    def ltm_occupied(self, ws, fermi, states=False, elements=None):
+        """The scans of this pair rule with the T = 0 occupations of a metal (abz_rule_ltm_pairs_occupied): the factor
+        theta(fermi - e_v) theta(e_c - fermi) restricts every simplex to its occupied part -- the simplex cut by two planes, since
+        e_v, e_c and e_c - e_v are all linear inside it -- which is split into sub-simplices that go through the closed forms of
+        `ltm`.  `elements` None: the occupied joint density of states J^occ(w) as [nw]; "attached": the occupied interband spectra
+        S^occ_ij(w) of the attached products as [nw, ncomp].  `states`: the cumulative forms (theta(w - Delta) for delta).  The band
+        energies are read from `self.source` (refilled like `h` when the series moved on); a corner is occupied iff e_v <= fermi and
+        empty iff e_c > fermi, the half-open rule of the scans.  `fermi` is the caller's: `self.source.ltm_fermi(nstates)` gives
+        the grid's own level.  No curvature correction, no finite temperature, no broadened form."""
+        if elements is not None and not (isinstance(elements, str) and elements == "attached"):
+            raise ValueError(f"ltm_occupied: elements = {elements!r} is neither None nor 'attached'")
+        fermi = float(fermi)
+        if not np.isfinite(fermi):
+            raise ValueError(f"ltm_occupied: fermi = {fermi!r} is not finite")
+        ws = np.ascontiguousarray(np.asarray(ws, dtype=np.float64).reshape(-1))
+        if len(ws) < 1:
+            raise ValueError("ltm_occupied: no transition energies")
+        if not self._closed and self.source._closed:  # the series' rule cache let the source go: the same grid again
+            self.refill()
+        h = self.h  # (a stale rule is refilled here, and its source with it)
+        src = self.source.h
+        if elements is None:
+            out = np.zeros(len(ws))
+            source = L.LTM_A_ONE
+        else:
+            if self._ltm_ncomp < 1:
+                raise ValueError("ltm_occupied: the pair rule has no elements (ltm_pairs with operators, ltm_elements)")
+            out = np.zeros((len(ws), self._ltm_ncomp))
+            source = L.LTM_A_ELEMENTS
+        L.check(L.lib().abz_rule_ltm_pairs_occupied(src, h, fermi, source, ws.ctypes.data_as(L.c_f64p), len(ws),
+                                                    L.LTM_STATES if states else L.LTM_DOS, out.ctypes.data_as(L.c_f64p)))
+        return out
 
     def unfold(self):
         raise ValueError("unfold: the rule is a full grid already (no symmetries to unfold)")

@@ -416,8 +416,9 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
  * before they replace anything: a refusal or failure leaves *out, src and every attached block as they were.
  * Degenerate levels: u_v, u_c are some orthonormal bases of their eigenspaces; only the SUM of a component over all pairs between
  * two levels is defined (it is what a scan adds up, since those pairs share Delta).
- * Not handled: partial occupations (the factor f_v (1 - f_c) of a metal restricts each simplex to its occupied part; the ranges
- * here are whole bands), weights Delta^-m inside the elements (divide exported elements by exported energies and attach them
+ * The scans above take whole bands; partial occupations (the factor f_v (1 - f_c) of a metal restricts each simplex to its occupied
+ * part) are what abz_rule_ltm_pairs_occupied below adds at T = 0.
+ * Not handled: weights Delta^-m inside the elements (divide exported elements by exported energies and attach them
  * with abz_rule_ltm_elements), the Berry-connection term of the Wannier velocity (operators are what the caller passes), 33...64
  * bands with operators, slabs, more than ABZ_MAX_BANDS pairs per rule.
  * A pair rule has no H(k), eigenvectors or plan: abz_rule_ltm_orbitals, _projectors, _expectation, _density_matrix,
@@ -430,6 +431,27 @@ int abz_rule_ltm_unfold(abz_rule* src, const int32_t* syms, int nsyms, abz_rule*
 #define ABZ_LTM_PAIRS_MAX_OPS 4
 int abz_rule_ltm_pairs(abz_rule* src, int v0, int nv, int c0, int nc, abz_rule* const* ops, int nops,
                        const int32_t* comps /* [ncomp][3] or NULL */, int ncomp, abz_rule** out);
+/* Interband spectra of a metal: the scans of a pair rule with the T = 0 occupation factor inside every simplex,
+ *      J^occ(w)    = sum_vc int dk theta(E_F - e_v) theta(e_c - E_F) delta(w - Delta_vc)                    (ABZ_LTM_A_ONE)
+ *      S^occ_ij(w) = sum_vc int dk theta(E_F - e_v) theta(e_c - E_F) M^i_vc conj(M^j_vc) delta(w - Delta_vc)  (ABZ_LTM_A_ELEMENTS)
+ * for what = ABZ_LTM_DOS, and with theta(w - Delta_vc) in place of delta for ABZ_LTM_STATES; out [nw][ncomp], ncomp = 1 for
+ * ABZ_LTM_A_ONE.  `pairs` is a rule of abz_rule_ltm_pairs, `src` the whole grid it was made from (same series and npt, at least
+ * c0 + nc bands; a rule of abz_rule_ltm_unfold is fine: only its eigenvalues are read, as they are now -- after abz_rule_rebuild(src)
+ * fill the pair rule again first).  Inside a simplex e_v, e_c and Delta are linear, so the occupied region is the simplex cut by two
+ * planes; it is split into sub-simplices of non-negative volume (at most 1, 2 x 2, 3 x 3 for d = 1, 2, 3) and each goes through the
+ * closed forms of abz_rule_ltm_weighted with interpolated corner values, weight 1 / (d! npt^d) per simplex as everywhere.
+ * Ties follow the half-open rule of the scans (N(E) counts e <= E): a corner is occupied iff e_v <= E_F and empty iff e_c > E_F.
+ * E_F is the caller's (abz_rule_ltm_fermi on src gives the grid's own).  Nothing is attached, replaced or dropped on either rule.
+ * Not handled: finite temperature, the broadened (Green's function) form with occupations, node weights of the cut, slabs, and
+ * Bloechl's correction: ABZ_LTM_STATES_CORRECTED answers ABZ_ERR_UNSUPPORTED (the curvature correction is not defined on cut
+ * simplices).
+ * ABZ_ERR_ARG: NULL pointers, nw < 1, `pairs` not a pair rule, another `what` or `source`, rules of different series or npt, an upper
+ * range outside the bands of src, ABZ_LTM_A_ELEMENTS without elements on `pairs`, E_F not finite, src without eigenvalues.
+ * ABZ_ERR_UNSUPPORTED: src a slab, a node list or a pair rule.  A refusal launches nothing and leaves both rules as they were.
+ * Kernels under ABZ_K_LTM.  Entry point added without a change of ABZ_VERSION. */
+#define ABZ_LTM_A_ONE 2   /* A = 1: the joint DOS; accepted by abz_rule_ltm_pairs_occupied only */
+int abz_rule_ltm_pairs_occupied(abz_rule* src, abz_rule* pairs, double E_F, int source, const double* w, int nw, int what,
+                                double* out /* [nw][ncomp], ncomp = 1 for A_ONE */);
 /* *nb: bands of the rule's eigenvalue planes, attached elements and weight blocks: nv nc of a pair rule, n of any other.
  * abz_rule_info keeps reporting the series' n (the bands of the source) for a pair rule: size the buffers of abz_rule_export's
  * eig, abz_rule_ltm_elements(_export) and the node weights by *nb, not by that n. */

@@ -32,6 +32,7 @@ const WANT_HC = WANT_H | WANT_H_COMPACT
 const F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = Cint.(0:6)
 const LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = Cint(0), Cint(1), Cint(2), Cint(3)
 const LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = Cint(0), Cint(1), Cint(2)  # `what` of abz_rule_ltm / abz_rule_ltm_weighted
+const LTM_A_ELEMENTS, LTM_A_ENERGY, LTM_A_ONE = Cint(0), Cint(1), Cint(2)    # `source`; LTM_A_ONE: abz_rule_ltm_pairs_occupied only
 
 # (kind, lim_a, lim_b) of the reference's limits types for abz_iai_solve(_many); the SymmetryReduceBZ
 # extension's Polyhedron3 travels as packed faces [nv, x y z ...] with lim_b = [length(lim_a)]
@@ -551,6 +552,22 @@ function ltm_pairs!(p::HIPRule, r::HIPRule, lower::UnitRange, upper::UnitRange; 
     ref = Ref{Ptr{Cvoid}}(p.h)
     _ltm_pairs(ref, r, lower, upper, ops, components)
     return p
+end
+"""
+    ltm_pairs_occupied(r, p, ws, fermi; ncomp=0, cumulative=false)       -> Matrix [max(ncomp, 1), nw]
+
+The scans of the pair rule `p` of the whole-grid rule `r` with the T = 0 occupations of a metal inside every simplex
+(`abz_rule_ltm_pairs_occupied`): `theta(fermi - e_v) theta(e_c - fermi)` restricts each simplex to its occupied part, which is cut
+into sub-simplices and goes through the closed forms of `ltm_weighted`.  `ncomp = 0`: the occupied joint density of states
+(`A = 1`, `LTM_A_ONE`); `ncomp > 0`: the `ncomp` attached interband products of `p`.  `cumulative`: `theta(w - Delta)` in place of
+`delta`.  A corner is occupied iff `e_v <= fermi` and empty iff `e_c > fermi`; `ltm_fermi(r, nstates)` gives the grid's own level.
+"""
+function ltm_pairs_occupied(r::HIPRule, p::HIPRule, ws::Vector{Float64}, fermi::Real; ncomp::Integer=0, cumulative::Bool=false)
+    out = Matrix{Float64}(undef, max(ncomp, 1), length(ws))
+    check(ccall((:abz_rule_ltm_pairs_occupied, libabz), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Float64}, Cint, Cint, Ptr{Float64}),
+        r.h, p.h, Float64(fermi), ncomp > 0 ? LTM_A_ELEMENTS : LTM_A_ONE, ws, length(ws), cumulative ? LTM_STATES : LTM_DOS, out))
+    return out
 end
 """
     ltm_elements_ptr(r) -> (base::Ptr{Cvoid}, nbytes::Int, ncomp::Int)
