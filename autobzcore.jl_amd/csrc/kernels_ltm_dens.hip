@@ -3,9 +3,9 @@
 // from the resident integration weights of abz_rule_ltm_node_weights (plane i n + b of a grid line's tile: band b at E[i], padding
 // columns zero) and the H planes of the same whole grid, in ONE eigen-solve per node (and group of energies): neither U nor the
 // band projectors reach HBM.  The weights say what rho is: occupations, corrected occupations or the spectral-density matrix.
-// U(k), the H layouts and the treatment of degenerate levels are those of kernels_ltm_orb.hip, whose loads are restated here on
-// purpose (that file and its objects stay what they were): a degenerate level gets some orthonormal basis, and only sums over a
-// level with equal weights are defined.  The corrected weights do go negative: nothing here assumes w >= 0.
+// U(k), the H layouts and the treatment of degenerate levels are those of kernels_ltm_orb.hip (lane load, pass head, products and
+// launch: the frame of ltm_eig_device.h): a degenerate level gets some orthonormal basis, and only sums over a level with
+// equal weights are defined.  The corrected weights do go negative: nothing here assumes w >= 0.
 //   1...4 bands   ltm_dens_lane_kernel<N, NE>: one grid point per lane over a fixed grid-stride, herm_eig<N, true>, the weights of
 //                 the launch's NE = 1 or 4 energies from the resident block, the upper triangle of sum_b w_b u_b u_b^dagger in
 //                 registers as N^2 reals per energy (N diagonal entries, then Re and Im of every p < q, p outer), in the
@@ -25,13 +25,9 @@
 // the problem's sizes alone, so two calls return the same bits.  No register array is indexed at run time.
 #include <algorithm>
 #include <cstring>
-#include <utility>
 #include <vector>
 
-#include "abz_internal.h"
-#include "device_math.h"
-#include "rows_device.h"
-#include "rows_eigvec.h"
+#include "ltm_eig_device.h"
 
 namespace abz {
 
@@ -47,14 +43,6 @@ struct LtmDensArgs {
     double* partial;  // [nE ncol][nrows]
     int64_t nrows;
 };
-
-// plane of Re H[a][b], a <= b (Im: the next one; the diagonal of the compact layout has none)
-__device__ __forceinline__ int dens_hplane(const PlaneView& v, int n, int a, int b) { return v.compact ? b * b + 2 * a : 2 * (a + n * b); }
-
-// the expressions of the projector kernels (kernels_ltm_orb.hip)
-__device__ __forceinline__ double dens_diag(double re, double im) { return fma(re, re, im * im); }
-__device__ __forceinline__ double dens_re(double pr, double pi, double qr, double qi) { return fma(pr, qr, pi * qi); }
-__device__ __forceinline__ double dens_im(double pr, double pi, double qr, double qi) { return fma(pi, qr, -(pr * qi)); }
 
 template <int N, int NE>
 __global__ __launch_bounds__(256) void ltm_dens_lane_kernel(LtmDensArgs a) {
@@ -78,21 +66,8 @@ __global__ __launch_bounds__(256) void ltm_dens_lane_kernel(LtmDensArgs a) {
             ur[0][0] = 1.0;
             ui[0][0] = 0.0;
         } else {
-            const double* __restrict__ const in = a.H.base + line * a.H.tile + i;
             CMat<N> h, V;
-#pragma unroll
-            for (int p = 0; p < N; ++p) {
-#pragma unroll
-                for (int q = 0; q < N; ++q) {
-                    h.re[p][q] = 0.0;
-                    h.im[p][q] = 0.0;
-                    if (p <= q) {
-                        const int64_t pl = dens_hplane(a.H, N, p, q);
-                        h.re[p][q] = in[pl * a.H.pitch];
-                        if (p < q) h.im[p][q] = in[(pl + 1) * a.H.pitch];
-                    }
-                }
-            }
+            herm_lane_load<N>(a.H, line, i, h);
             double e[N];
             herm_eig<N, true>(h, e, V);
 #pragma unroll
@@ -111,14 +86,14 @@ __global__ __launch_bounds__(256) void ltm_dens_lane_kernel(LtmDensArgs a) {
             for (int b = 0; b < N; ++b) {
                 const double w = wp[(int64_t)(e * N + b) * a.W.pitch];
 #pragma unroll
-                for (int p = 0; p < N; ++p) acc[e][p] += w * dens_diag(ur[b][p], ui[b][p]);
+                for (int p = 0; p < N; ++p) acc[e][p] += w * proj_diag(ur[b][p], ui[b][p]);
                 int c = N;
 #pragma unroll
                 for (int p = 0; p < N; ++p) {
 #pragma unroll
                     for (int q = p + 1; q < N; ++q) {
-                        acc[e][c] += w * dens_re(ur[b][p], ui[b][p], ur[b][q], ui[b][q]);
-                        acc[e][c + 1] += w * dens_im(ur[b][p], ui[b][p], ur[b][q], ui[b][q]);
+                        acc[e][c] += w * proj_re(ur[b][p], ui[b][p], ur[b][q], ui[b][q]);
+                        acc[e][c + 1] += w * proj_im(ur[b][p], ui[b][p], ur[b][q], ui[b][q]);
                         c += 2;
                     }
                 }
@@ -150,37 +125,29 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_dens_rows_kernel(Lt
     constexpr int HALF = NP / 2;
     constexpr int RS = NP + 1;  // row stride of the transposed half of U
     static_assert(HALF * RS <= PARK_STRIDE<NP>, "half of U fits the reflector room");
-    const int slot = threadIdx.x / NP, r0 = threadIdx.x % NP, lane = threadIdx.x & 63;
-    double2* const park = lds_dens + (size_t)slot * PARK_STRIDE<NP>;            // this node's reflectors, then half of U
+    const int slot = threadIdx.x / NP, r0 = threadIdx.x % NP;
     double2* const acc = lds_dens + (size_t)(SLOTS + slot) * PARK_STRIDE<NP>;   // this slot's upper triangle, entry q (q + 1) / 2 + p
     double* const wts = reinterpret_cast<double*>(lds_dens + (size_t)2 * SLOTS * PARK_STRIDE<NP>) + slot * NP;  // w_b of this node
     const int npt = a.npt;
     const int iE = (int)blockIdx.y;
     // lane q owns the entries (p, q), p <= q, of its slot
     for (int p = 0; p <= r0; ++p) acc[r0 * (r0 + 1) / 2 + p] = make_double2(0.0, 0.0);
-    const int ppl = (npt + SLOTS - 1) / SLOTS;  // passes per line
-    for (int64_t item = blockIdx.x; item < a.nlines * ppl; item += gridDim.x) {
-        const int64_t line = item / ppl;
-        const int i0 = (int)(item - line * ppl) * SLOTS;
-        // (see ggr_rows_kernel: what depends on n and r alone must not be hoisted out of the loop and kept alive through it)
-        int n = a.n, r = r0;
-        asm volatile("" : "+s"(n));
-        asm volatile("" : "+v"(r));
-        const bool wave_on = i0 + (int)(threadIdx.x >> 6) * (64 / NP) < npt;  // a wave without a node has nothing to add
-        const int i1 = i0 + slot;
-        const bool act = i1 < npt;
-        if (!wave_on) continue;
-        // row r of Hermitian(H): (r, j) of the upper triangle for j >= r, the conjugate of (j, r) below the diagonal
-        const double* __restrict__ const in = a.H.base + line * a.H.tile + (act ? i1 : 0);
-        const int rr = r < n ? r : n - 1;
+    for (int64_t item = blockIdx.x; item < a.nlines * rows_passes_per_line<NP>(npt); item += gridDim.x) {
+        const RowsPass<NP> ps = rows_pass<NP>(lds_dens, item, npt, a.n);
+        const int n = ps.n, r = ps.r;
+        double2* const park = ps.park;  // this node's reflectors, then half of U
+        if (!ps.wave_on) continue;      // a wave without a node has nothing to add
         double hr[NP], hi[NP];
+        // herm_row_load written out (see there: behind the call this kernel's results move in the last bit at NP = 16)
+        const double* __restrict__ const in = a.H.base + ps.line * a.H.tile + (ps.act ? ps.i1 : 0);
+        const int rr = r < n ? r : n - 1;
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
             hr[j] = 0.0;
             hi[j] = 0.0;
             if (j < n) {  // uniform
                 const int lo = rr < j ? rr : j, up = rr < j ? j : rr;
-                const int64_t pl = dens_hplane(a.H, n, lo, up);
+                const int64_t pl = herm_plane(a.H, n, lo, up);
                 const double re = in[pl * a.H.pitch];
                 const double im = in[(pl + (lo != up ? 1 : 0)) * a.H.pitch];
                 hr[j] = r < n ? re : 0.0;
@@ -188,10 +155,10 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_dens_rows_kernel(Lt
             }
         }
         double myeig, ur[NP], ui[NP];
-        rows_eigh_columns<NP>(n, r, lane, park, hr, hi, myeig, ur, ui);
-        const bool mine = act && r < n;  // this lane holds column r of a node of the grid
+        rows_eigh_columns<NP>(n, r, ps.lane, park, hr, hi, myeig, ur, ui);
+        const bool mine = ps.act && r < n;  // this lane holds column r of a node of the grid
         wave_sync_lds();  // the back-transformation has read the reflectors: the room is free
-        wts[r] = mine ? a.W.base[line * a.W.tile + (int64_t)(iE * n + r) * a.W.pitch + i1] : 0.0;
+        wts[r] = mine ? a.W.base[ps.line * a.W.tile + (int64_t)(iE * n + r) * a.W.pitch + ps.i1] : 0.0;
         // U through the room in two halves of the orbital index, the upper one first: the lanes of the half take their own row,
         // scaled by the weights of its bands, into registers, and every lane q forms (p, q) for the p <= q of the half
         double vr[NP], vi[NP];
@@ -220,8 +187,8 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_dens_rows_kernel(Lt
                     for (int b = 0; b < NP; ++b) {
                         if (b < n) {  // uniform
                             const double2 x = xp[b];
-                            sr += dens_re(x.x, x.y, vr[b], vi[b]);
-                            si += dens_im(x.x, x.y, vr[b], vi[b]);
+                            sr += proj_re(x.x, x.y, vr[b], vi[b]);
+                            si += proj_im(x.x, x.y, vr[b], vi[b]);
                         }
                     }
                     double2 s = acc[r * (r + 1) / 2 + p];
@@ -250,20 +217,6 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_dens_rows_kernel(Lt
     }
 }
 
-template <int NP>
-constexpr size_t dens_rows_lds_bytes() {
-    return sizeof(double2) * (size_t)(2 * (256 / NP)) * (size_t)PARK_STRIDE<NP> + sizeof(double) * 256;
-}
-
-using DensLaneFn = void (*)(LtmDensArgs);
-// [n - 1][NE == 4]
-constexpr DensLaneFn LTM_DENS_LANE[4][2] = {
-    {ltm_dens_lane_kernel<1, 1>, ltm_dens_lane_kernel<1, 4>},
-    {ltm_dens_lane_kernel<2, 1>, ltm_dens_lane_kernel<2, 4>},
-    {ltm_dens_lane_kernel<3, 1>, ltm_dens_lane_kernel<3, 4>},
-    {ltm_dens_lane_kernel<4, 1>, ltm_dens_lane_kernel<4, 4>},
-};
-
 }  // namespace
 
 // out_host [nE][n][n][2] = rho(E_i) per unit cell from the weights W (nE energies) and the H planes; the lower triangle is the exact
@@ -277,9 +230,8 @@ int launch_ltm_density_matrix(abz_ctx* ctx, int n, int npt, int64_t nlines, Plan
     if (lanes) {
         nblocks = std::max<int64_t>(1, std::min<int64_t>((nlines * W.row + 255) / 256, 2048));
     } else {
-        np = n <= 8 ? 8 : (n <= 16 ? 16 : 32);
-        const int slots = 256 / np;
-        nblocks = std::max<int64_t>(1, std::min<int64_t>(nlines * ((npt + slots - 1) / slots), std::max(128, 1024 / nE)));
+        np = rows_np(n);
+        nblocks = std::max<int64_t>(1, rows_blocks(np, npt, nlines, std::max(128, 1024 / nE)));
     }
     int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nblocks * (size_t)ntot);
     if (rc) return rc;
@@ -306,20 +258,18 @@ int launch_ltm_density_matrix(abz_ctx* ctx, int n, int npt, int64_t nlines, Plan
             for (int i0 = 0; i0 < nE;) {
                 const int ne = nE - i0 >= 4 ? 4 : 1;
                 a.e0 = i0;
-                launch(ctx, LTM_DENS_LANE[n - 1][ne == 4], dim3((unsigned)nblocks), dim3(256), 0, a);
+                const dim3 grid((unsigned)nblocks);
+                lanes_dispatch(n, [&](auto N) {
+                    launch(ctx, ne == 1 ? ltm_dens_lane_kernel<decltype(N)::value, 1> : ltm_dens_lane_kernel<decltype(N)::value, 4>, grid, dim3(256), 0, a);
+                    return ABZ_OK;
+                });
                 i0 += ne;
             }
         } else {
-#define ABZ_LD(NPV)                                                                                                        \
-    {                                                                                                                      \
-        constexpr size_t lds = dens_rows_lds_bytes<NPV>();                                                                 \
-        ABZ_HIP(hipFuncSetAttribute((const void*)ltm_dens_rows_kernel<NPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        launch(ctx, (ltm_dens_rows_kernel<NPV>), dim3((unsigned)nblocks, (unsigned)nE), dim3(256), lds, a);               \
-    }
-            if (np == 8) ABZ_LD(8)
-            else if (np == 16) ABZ_LD(16)
-            else ABZ_LD(32)
-#undef ABZ_LD
+            // its own grid: blockIdx.y = energy.  Behind the rooms: as much again for the slots' accumulators, and 256 weights
+            const size_t lds = rows_lds_bytes(np, rows_room_bytes(np) + sizeof(double) * 256);
+            const dim3 grid((unsigned)nblocks, (unsigned)nE);
+            if ((rc = rows_dispatch(np, [&](auto NP) { return launch_rows(ctx, ltm_dens_rows_kernel<decltype(NP)::value>, grid, lds, a); }))) return rc;
         }
         ABZ_HIP(hipGetLastError());
     }

@@ -2,8 +2,8 @@
 //   q_i(b, k) = Re u_b(k)^H Hermitian(O_i(k)) u_b(k),   component c = q_i (single) or q_i q_j (product),
 // the H planes of a whole periodic grid and the planes of up to ABZ_LTM_EXPECT_MAX_OPS operator rules of the same grid in,
 // the element block of abz_rule_ltm_elements out (plane c n + b of a grid line's tile, padded rows, the padding columns
-// written as zeros).  Siblings of the two orbital kernels (kernels_ltm_orb.hip): the same loads of H, the same solves, the
-// same stores; neither U nor O u reaches HBM, no atomics, no dependence on the launch geometry: two calls write the same bits.
+// written as zeros).  Loads, pass head, write-out and launch are the frame of ltm_eig_device.h.  Neither U nor O u reaches HBM,
+// no atomics, no dependence on the launch geometry: two calls write the same bits.
 // Of every operator the upper triangle is read, the way H is read (either plane layout, each rule with its own tiling).
 //   1...4 bands   one grid point per lane: herm_eig<N, true>, then per operator its N (N + 1) / 2 upper-triangle entries and
 //                 the form sum_p O_pp |u_p|^2 + 2 Re sum_{p<q} conj(u_p) O_pq u_q in registers;
@@ -22,13 +22,7 @@
 // would end the spills and halve the nodes in flight; the orbital kernel made the same choice.
 // At a degenerate level u_b is some orthonormal basis of the eigenspace: the sum of single expectations over the level is
 // defined, single values and products are not.
-#include <utility>
-
-#include "abz_internal.h"
-#include "device_math.h"
-#include "rows_device.h"
-#include "rows_eigvec.h"
-#include "xp_select.h"
+#include "ltm_eig_device.h"
 
 namespace abz {
 
@@ -64,21 +58,8 @@ __global__ __launch_bounds__(256) void ltm_expect_lane_kernel(LtmExpectArgs a) {
             V.re[0][0] = 1.0;
             V.im[0][0] = 0.0;
         } else {
-            const double* __restrict__ const in = a.H.base + line * a.H.tile + i;
             CMat<N> h;
-#pragma unroll
-            for (int p = 0; p < N; ++p) {
-#pragma unroll
-                for (int s = 0; s < N; ++s) {
-                    h.re[p][s] = 0.0;
-                    h.im[p][s] = 0.0;
-                    if (p <= s) {
-                        const int64_t pl = xp_plane(a.H, N, p, s);
-                        h.re[p][s] = in[pl * a.H.pitch];
-                        if (p < s) h.im[p][s] = in[(pl + 1) * a.H.pitch];
-                    }
-                }
-            }
+            herm_lane_load<N>(a.H, line, i, h);
             double e[N];
             herm_eig<N, true>(h, e, V);
         }
@@ -92,7 +73,7 @@ __global__ __launch_bounds__(256) void ltm_expect_lane_kernel(LtmExpectArgs a) {
             for (int s = 0; s < N; ++s) {
 #pragma unroll
                 for (int p = 0; p <= s; ++p) {
-                    const int64_t pl = xp_plane(O, N, p, s);
+                    const int64_t pl = herm_plane(O, N, p, s);
                     const double ore = in[pl * O.pitch];
                     if (p == s) {
 #pragma unroll
@@ -128,79 +109,43 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_expect_rows_kernel(
     extern __shared__ double2 lds_xp[];
     constexpr int SLOTS = 256 / NP;
     constexpr int TS = SLOTS + 1;
-    const int slot = threadIdx.x / NP, r0 = threadIdx.x % NP, lane = threadIdx.x & 63;
-    double2* const park = lds_xp + (size_t)slot * PARK_STRIDE<NP>;                     // this node's reflectors, then its operator
     double* const tile = reinterpret_cast<double*>(lds_xp + SLOTS * PARK_STRIDE<NP>);  // [component][NP bands][TS]
     const int npt = a.npt, nplanes = a.ncomp * a.n;
-    const int ppl = (npt + SLOTS - 1) / SLOTS;  // passes per line
-    for (int64_t item = blockIdx.x; item < a.nlines * ppl; item += gridDim.x) {
-        const int64_t line = item / ppl;
-        const int i0 = (int)(item - line * ppl) * SLOTS;
-        // (see ggr_rows_kernel: what depends on n and r alone must not be hoisted out of the loop and kept alive through it)
-        int n = a.n, r = r0;
-        asm volatile("" : "+s"(n));
-        asm volatile("" : "+v"(r));
-        const bool wave_on = i0 + (int)(threadIdx.x >> 6) * (64 / NP) < npt;  // a wave without a node keeps the barriers only
-        const int i1 = i0 + slot;
-        const bool act = i1 < npt;
-        if (wave_on) {
-            const int rr = r < n ? r : n - 1;
+    for (int64_t item = blockIdx.x; item < a.nlines * rows_passes_per_line<NP>(npt); item += gridDim.x) {
+        const RowsPass<NP> ps = rows_pass<NP>(lds_xp, item, npt, a.n);  // ps.park: the node's reflectors, then its operator
+        const int n = ps.n, r = ps.r;
+        if (ps.wave_on) {
+            const int column = ps.act ? ps.i1 : 0;
             double hr[NP], hi[NP];
-            // row r of Hermitian(X): (r, j) of the upper triangle for j >= r, the conjugate of (j, r) below the diagonal
-            auto load_row = [&](const PlaneView& X) {
-                const double* __restrict__ const in = X.base + line * X.tile + (act ? i1 : 0);
-#pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    hr[j] = 0.0;
-                    hi[j] = 0.0;
-                    if (j < n) {  // uniform
-                        const int lo = rr < j ? rr : j, up = rr < j ? j : rr;
-                        const int64_t pl = xp_plane(X, n, lo, up);
-                        const double re = in[pl * X.pitch];
-                        const double im = in[(pl + (lo != up ? 1 : 0)) * X.pitch];
-                        hr[j] = r < n ? re : 0.0;
-                        hi[j] = (r < n && lo != up) ? (rr < j ? im : -im) : 0.0;
-                    }
-                }
-            };
+            // (a local closure over the shared load, as in kernels_ltm_pairs.hip: the register counts are the ones these
+            // kernels had with their own closures)
+            auto load_row = [&](const PlaneView& X) { herm_row_load<NP>(X, n, r, ps.line, column, hr, hi); };
             load_row(a.H);
             double myeig, ur[NP], ui[NP];
-            rows_eigh_columns<NP>(n, r, lane, park, hr, hi, myeig, ur, ui);
+            rows_eigh_columns<NP>(n, r, ps.lane, ps.park, hr, hi, myeig, ur, ui);
             double q[XOPS];
 #pragma unroll
             for (int m = 0; m < XOPS; ++m) q[m] = 0.0;
             for (int k = 0; k < a.nops; ++k) {  // (uniform)
                 load_row(a.O[k]);
                 wave_sync_lds();  // every lane of the node is done reading the room (reflectors, the operator before)
-                park_upper<NP>(n, r, park, hr, hi);
+                park_upper<NP>(n, r, ps.park, hr, hi);
                 wave_sync_lds();
-                const double v = quad_form<NP>(n, park, ur, ui, std::make_integer_sequence<int, NP>());
+                const double v = quad_form<NP>(n, ps.park, ur, ui, std::make_integer_sequence<int, NP>());
                 xp_put(q, k, v);
             }
-            if (act && r < n) {
+            if (ps.act && r < n) {
                 for (int c = 0; c < a.ncomp; ++c) {
                     const int ki = a.ci[c], kj = a.cj[c];  // (uniform)
                     const double x = xp_pick(q, ki);
-                    tile[(c * NP + r) * TS + slot] = kj < 0 ? x : x * xp_pick(q, kj);
+                    tile[(c * NP + r) * TS + ps.slot] = kj < 0 ? x : x * xp_pick(q, kj);
                 }
             }
         }
         __syncthreads();
-        // the pass's columns of every plane; the line's last pass takes the padding columns along, as zeros
-        const int width = (i0 + SLOTS >= npt) ? a.A.row - i0 : SLOTS;
-        double* __restrict__ const out = a.A.base + line * a.A.tile + i0;
-        for (int idx = threadIdx.x; idx < nplanes * width; idx += 256) {
-            const int pl = idx / width, sl = idx - pl * width;
-            const int c = pl / a.n, b = pl - c * a.n;
-            out[(int64_t)pl * a.A.pitch + sl] = (i0 + sl < npt) ? tile[(c * NP + b) * TS + sl] : 0.0;
-        }
+        rows_tile_write<NP>(a.A, ps.line, ps.i0, npt, a.n, nplanes, tile, [](int c, int b) { return c * NP + b; });
         __syncthreads();  // the tile is free for the next pass
     }
-}
-
-size_t ltm_expect_lds_bytes(int np, int ncomp) {
-    const size_t slots = (size_t)(256 / np);
-    return sizeof(double2) * slots * (size_t)(np * (np + 1) / 2 + 1) + sizeof(double) * (size_t)ncomp * np * (slots + 1);
 }
 
 }  // namespace
@@ -222,28 +167,16 @@ int launch_ltm_expectation(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneVi
         a.cj[c] = c < ncomp ? (comps ? comps[2 * c + 1] : -1) : -1;
     }
     ProfScope ps(ctx, ABZ_K_EIG);
+    int rc;
     if (n <= 4) {
-        const dim3 grid((unsigned)((nlines * A.row + 255) / 256));
-        switch (n) {
-            case 1: launch(ctx, ltm_expect_lane_kernel<1>, grid, dim3(256), 0, a); break;
-            case 2: launch(ctx, ltm_expect_lane_kernel<2>, grid, dim3(256), 0, a); break;
-            case 3: launch(ctx, ltm_expect_lane_kernel<3>, grid, dim3(256), 0, a); break;
-            default: launch(ctx, ltm_expect_lane_kernel<4>, grid, dim3(256), 0, a); break;
-        }
+        rc = lanes_dispatch(n, [&](auto N) { return launch_lanes(ctx, ltm_expect_lane_kernel<decltype(N)::value>, nlines, A.row, a); });
     } else {
-        const int np = n <= 8 ? 8 : (n <= 16 ? 16 : 32);
-        const size_t lds = ltm_expect_lds_bytes(np, ncomp);
-        const int64_t blocks = std::min<int64_t>(nlines * ((npt + 256 / np - 1) / (256 / np)), 256 * 64);
-#define ABZ_LX(NPV)                                                                                                              \
-    {                                                                                                                            \
-        ABZ_HIP(hipFuncSetAttribute((const void*)ltm_expect_rows_kernel<NPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        launch(ctx, (ltm_expect_rows_kernel<NPV>), dim3((unsigned)blocks), dim3(256), lds, a);                                   \
+        const int np = rows_np(n);
+        const size_t lds = rows_lds_bytes(np, rows_tile_bytes(np, ncomp));
+        const dim3 grid((unsigned)rows_blocks(np, npt, nlines, 256 * 64));
+        rc = rows_dispatch(np, [&](auto NP) { return launch_rows(ctx, ltm_expect_rows_kernel<decltype(NP)::value>, grid, lds, a); });
     }
-        if (np == 8) ABZ_LX(8)
-        else if (np == 16) ABZ_LX(16)
-        else ABZ_LX(32)
-#undef ABZ_LX
-    }
+    if (rc) return rc;
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }

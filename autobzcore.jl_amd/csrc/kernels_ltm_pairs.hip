@@ -4,9 +4,9 @@
 //   the element kernels      M^i_vc = u_v(k)^H Hermitian(O_i(k)) u_c(k) for up to ABZ_LTM_PAIRS_MAX_OPS operator rules of the same grid,
 //                            component c = Re or Im of M^i_vc conj(M^j_vc) -- no phase of u_v or u_c changes it -- into the element
 //                            block of abz_rule_ltm_elements (plane c nb + p of a grid line's tile, padded rows, padding columns 0.0).
-// The element kernels are siblings of kernels_ltm_expect.hip: the same loads of H and O (upper triangles, either plane layout, each
-// rule with its own tiling), the same solves, the same write-out; neither U nor O u reaches HBM, no atomics, no dependence on
-// the launch geometry: two calls write the same bits.
+// The element kernels read H and O (upper triangles, either plane layout, each rule with its own tiling) through the frame of
+// ltm_eig_device.h, which also has their pass head and their launch; neither U nor O u reaches HBM, no atomics, no dependence
+// on the launch geometry: two calls write the same bits.
 //   2...4 bands   one grid point per lane: herm_eig<N, true>, then per operator y_c = O u_c and M_vc = u_v^H y_c for the
 //                 N (N - 1) / 2 pairs v < c in registers (all indices compile-time; the pairs outside the ranges are computed and
 //                 not stored); the products are formed at the store.
@@ -18,19 +18,13 @@
 //                 side form their min(nv, nc) dot products from broadcast reads: no cross-lane shuffles.  The complex M^i_vc leave
 //                 the lanes into an LDS tile [operator][pair][node]; Re / Im (M^i conj M^j) are formed during the write-out of
 //                 contiguous row segments, so no lane keeps nv nops complex values alive and no register array is indexed at run
-//                 time (xp_select.h).
+//                 time (xp_pick, xp_put).
 // LDS per workgroup: the rooms (18.5 / 34.3 / 66.1 KB at NP = 8 / 16 / 32) plus 16 B nops npairs (256 / NP + 1) for the tile, sized by
 // the call: at most 33 KB (NP = 8, 4 x 4 pairs), 68 KB (NP = 16, 64 pairs) and 36 KB (NP = 32, 64 pairs) with 4 operators.  NP = 16
 // with 4 operators and 64 pairs is one workgroup per CU (102 KB of 160); up to 2 operators, or up to 32 pairs, leave room for two.
 // At a degenerate level u_v, u_c are some orthonormal bases of their eigenspaces: only the sum of a component over all pairs
 // between two levels is defined.
-#include <utility>
-
-#include "abz_internal.h"
-#include "device_math.h"
-#include "rows_device.h"
-#include "rows_eigvec.h"
-#include "xp_select.h"
+#include "ltm_eig_device.h"
 
 namespace abz {
 
@@ -109,21 +103,8 @@ __global__ __launch_bounds__(256) void ltm_pairs_lane_kernel(LtmPairsArgs a) {
     if (i < a.npt) {
         CMat<N> V;
         {
-            const double* __restrict__ const in = a.H.base + line * a.H.tile + i;
             CMat<N> h;
-#pragma unroll
-            for (int p = 0; p < N; ++p) {
-#pragma unroll
-                for (int s = 0; s < N; ++s) {
-                    h.re[p][s] = 0.0;
-                    h.im[p][s] = 0.0;
-                    if (p <= s) {
-                        const int64_t pl = xp_plane(a.H, N, p, s);
-                        h.re[p][s] = in[pl * a.H.pitch];
-                        if (p < s) h.im[p][s] = in[(pl + 1) * a.H.pitch];
-                    }
-                }
-            }
+            herm_lane_load<N>(a.H, line, i, h);
             double e[N];
             herm_eig<N, true>(h, e, V);
         }
@@ -143,7 +124,7 @@ __global__ __launch_bounds__(256) void ltm_pairs_lane_kernel(LtmPairsArgs a) {
             for (int s = 0; s < N; ++s) {
 #pragma unroll
                 for (int p = 0; p <= s; ++p) {
-                    const int64_t pl = xp_plane(O, N, p, s);
+                    const int64_t pl = herm_plane(O, N, p, s);
                     const double ore = in[pl * O.pitch];
                     if (p == s) {
 #pragma unroll
@@ -252,45 +233,22 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_pairs_rows_kernel(L
     extern __shared__ double2 lds_pr[];
     constexpr int SLOTS = 256 / NP;
     constexpr int TS = SLOTS + 1;
-    const int slot = threadIdx.x / NP, r0 = threadIdx.x % NP, lane = threadIdx.x & 63;
-    double2* const park = lds_pr + (size_t)slot * PARK_STRIDE<NP>;  // this node's reflectors, then its operator, then the parked columns
-    double2* const tile = lds_pr + SLOTS * PARK_STRIDE<NP>;          // [operator][pair][TS]
+    double2* const tile = lds_pr + SLOTS * PARK_STRIDE<NP>;  // [operator][pair][TS]
     const int npt = a.npt, nb = a.nv * a.nc;
-    const int ppl = (npt + SLOTS - 1) / SLOTS;  // passes per line
-    const bool lowpark = a.nv <= a.nc;          // the lower range's u_v are parked (else the upper range's y_c)
-    for (int64_t item = blockIdx.x; item < a.nlines * ppl; item += gridDim.x) {
-        const int64_t line = item / ppl;
-        const int i0 = (int)(item - line * ppl) * SLOTS;
-        // (see ggr_rows_kernel: what depends on n and r alone must not be hoisted out of the loop and kept alive through it)
-        int n = a.n, r = r0;
-        asm volatile("" : "+s"(n));
-        asm volatile("" : "+v"(r));
-        const bool wave_on = i0 + (int)(threadIdx.x >> 6) * (64 / NP) < npt;  // a wave without a node keeps the barriers only
-        const int i1 = i0 + slot;
-        const bool act = i1 < npt;
-        if (wave_on) {
-            const int rr = r < n ? r : n - 1;
+    const bool lowpark = a.nv <= a.nc;  // the lower range's u_v are parked (else the upper range's y_c)
+    for (int64_t item = blockIdx.x; item < a.nlines * rows_passes_per_line<NP>(npt); item += gridDim.x) {
+        const RowsPass<NP> ps = rows_pass<NP>(lds_pr, item, npt, a.n);
+        const int n = ps.n, r = ps.r, i0 = ps.i0;
+        double2* const park = ps.park;  // this node's reflectors, then its operator, then the parked columns
+        if (ps.wave_on) {
+            const int column = ps.act ? ps.i1 : 0;
             double hr[NP], hi[NP];
-            // row r of Hermitian(X): (r, j) of the upper triangle for j >= r, the conjugate of (j, r) below the diagonal
-            auto load_row = [&](const PlaneView& X) {
-                const double* __restrict__ const in = X.base + line * X.tile + (act ? i1 : 0);
-#pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    hr[j] = 0.0;
-                    hi[j] = 0.0;
-                    if (j < n) {  // uniform
-                        const int lo = rr < j ? rr : j, up = rr < j ? j : rr;
-                        const int64_t pl = xp_plane(X, n, lo, up);
-                        const double re = in[pl * X.pitch];
-                        const double im = in[(pl + (lo != up ? 1 : 0)) * X.pitch];
-                        hr[j] = r < n ? re : 0.0;
-                        hi[j] = (r < n && lo != up) ? (rr < j ? im : -im) : 0.0;
-                    }
-                }
-            };
+            // (a local closure over the shared load, as these kernels had one over their own: with the direct calls the
+            // NP = 16 kernel spills 624 B instead of 520)
+            auto load_row = [&](const PlaneView& X) { herm_row_load<NP>(X, n, r, ps.line, column, hr, hi); };
             load_row(a.H);
             double myeig, ur[NP], ui[NP];
-            rows_eigh_columns<NP>(n, r, lane, park, hr, hi, myeig, ur, ui);
+            rows_eigh_columns<NP>(n, r, ps.lane, park, hr, hi, myeig, ur, ui);
             const bool in_v = r >= a.v0 && r < a.v0 + a.nv, in_c = r >= a.c0 && r < a.c0 + a.nc;
             for (int k = 0; k < a.nops; ++k) {  // (uniform)
                 load_row(a.O[k]);
@@ -306,18 +264,18 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_pairs_rows_kernel(L
                         if (j < n) mine[j] = lowpark ? make_double2(ur[j], ui[j]) : make_double2(hr[j], hi[j]);
                 }
                 wave_sync_lds();
-                double2* const trow = tile + (size_t)k * nb * TS + slot;
+                double2* const trow = tile + (size_t)k * nb * TS + ps.slot;
                 if (lowpark) {  // lane c: M_vc = conj(u_v) . y_c over the parked u_v
                     for (int m = 0; m < a.nv; ++m) {
                         double sr, si;
                         parked_dot<NP>(n, park + m * n, hr, hi, sr, si);
-                        if (act && in_c) trow[(m * a.nc + (r - a.c0)) * TS] = make_double2(sr, si);
+                        if (ps.act && in_c) trow[(m * a.nc + (r - a.c0)) * TS] = make_double2(sr, si);
                     }
                 } else {  // lane v: conj(M_vc) = conj(y_c) . u_v over the parked y_c
                     for (int m = 0; m < a.nc; ++m) {
                         double sr, si;
                         parked_dot<NP>(n, park + m * n, ur, ui, sr, si);
-                        if (act && in_v) trow[((r - a.v0) * a.nc + m) * TS] = make_double2(sr, -si);
+                        if (ps.act && in_v) trow[((r - a.v0) * a.nc + m) * TS] = make_double2(sr, -si);
                     }
                 }
             }
@@ -325,7 +283,7 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_pairs_rows_kernel(L
         __syncthreads();
         // the pass's columns of every plane; the line's last pass takes the padding columns along, as zeros
         const int width = (i0 + SLOTS >= npt) ? a.A.row - i0 : SLOTS;
-        double* __restrict__ const out = a.A.base + line * a.A.tile + i0;
+        double* __restrict__ const out = a.A.base + ps.line * a.A.tile + i0;
         for (int cc = 0; cc < a.ncomp; ++cc) {
             const int part = a.part[cc];  // (uniform)
             const double2* __restrict__ const ti = tile + (size_t)a.ci[cc] * nb * TS;
@@ -342,11 +300,6 @@ __global__ __launch_bounds__(256, NP <= 16 ? 2 : 1) void ltm_pairs_rows_kernel(L
         }
         __syncthreads();  // the tile is free for the next pass
     }
-}
-
-size_t ltm_pairs_lds_bytes(int np, int nops, int nb) {
-    const size_t slots = (size_t)(256 / np);
-    return sizeof(double2) * (slots * (size_t)(np * (np + 1) / 2 + 1) + (size_t)nops * nb * (slots + 1));
 }
 
 }  // namespace
@@ -388,27 +341,19 @@ int launch_ltm_pairs(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView H, 
         a.part[c] = c < ncomp ? comps[3 * c + 2] : 0;
     }
     ProfScope ps(ctx, ABZ_K_EIG);
+    int rc;
     if (n <= 4) {
-        const dim3 grid((unsigned)((nlines * A.row + 255) / 256));
-        switch (n) {
-            case 2: launch(ctx, ltm_pairs_lane_kernel<2>, grid, dim3(256), 0, a); break;
-            case 3: launch(ctx, ltm_pairs_lane_kernel<3>, grid, dim3(256), 0, a); break;
-            default: launch(ctx, ltm_pairs_lane_kernel<4>, grid, dim3(256), 0, a); break;
-        }
+        rc = lanes_dispatch(n, [&](auto N) {
+            if constexpr (decltype(N)::value >= 2) return launch_lanes(ctx, ltm_pairs_lane_kernel<decltype(N)::value>, nlines, A.row, a);
+            return (int)ABZ_ERR_INTERNAL;  // (n >= 2 was checked)
+        });
     } else {
-        const int np = n <= 8 ? 8 : (n <= 16 ? 16 : 32);
-        const size_t lds = ltm_pairs_lds_bytes(np, nops, nv * nc);
-        const int64_t blocks = std::min<int64_t>(nlines * ((npt + 256 / np - 1) / (256 / np)), 256 * 64);
-#define ABZ_LP(NPV)                                                                                                             \
-    {                                                                                                                           \
-        ABZ_HIP(hipFuncSetAttribute((const void*)ltm_pairs_rows_kernel<NPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        launch(ctx, (ltm_pairs_rows_kernel<NPV>), dim3((unsigned)blocks), dim3(256), lds, a);                                   \
+        const int np = rows_np(n);
+        const size_t lds = rows_lds_bytes(np, sizeof(double2) * (size_t)nops * nv * nc * (256 / np + 1));  // the tile: complex M^i_vc
+        const dim3 grid((unsigned)rows_blocks(np, npt, nlines, 256 * 64));
+        rc = rows_dispatch(np, [&](auto NP) { return launch_rows(ctx, ltm_pairs_rows_kernel<decltype(NP)::value>, grid, lds, a); });
     }
-        if (np == 8) ABZ_LP(8)
-        else if (np == 16) ABZ_LP(16)
-        else ABZ_LP(32)
-#undef ABZ_LP
-    }
+    if (rc) return rc;
     ABZ_HIP(hipGetLastError());
     return ABZ_OK;
 }

@@ -110,7 +110,7 @@ def test_expectation_of_a_scalar_series_is_the_operator(abz):
 
 
 # ---------------------------------------------------------------- 3. layouts
-@pytest.mark.parametrize("n", [3, 12])
+@pytest.mark.parametrize("n", [3, 6, 12, 17])
 def test_expectations_do_not_depend_on_the_plane_layouts(abz, n):
     L = abz._lib
     s = product_series(abz, orc.synthetic_wannier(n, rmax=2, seed=7))
@@ -119,7 +119,8 @@ def test_expectations_do_not_depend_on_the_plane_layouts(abz, n):
     ref, bound = None, None
     for owant in (L.WANT_H, L.WANT_H | L.WANT_H_COMPACT):
         orules = [abz.DeviceRule(o.device(), npt, None, owant) for o in ops]
-        assert all(r.want == owant for r in orules)  # the library built the layout asked for
+        # the library built the layout asked for; above 16 bands there is no compact layout and it drops the bit (abzhip.h)
+        assert all(r.want == (owant if n <= 16 else L.WANT_H) for r in orules)
         if ref is None:
             O = [r.export(x=False, w=False, H=True)["H"] for r in orules]
             ref, bound = xn.elements(exported_h(abz, s, npt), O, MIXED), xn.bounds(O, MIXED)

@@ -176,8 +176,10 @@ def test_diagonal_pairs_equal_the_orbital_weights_to_the_bit(abz, n):
 
 
 # ---------------------------------------------------------------- 3. layouts, repeatability
-@pytest.mark.parametrize("n", [3, 9])
+@pytest.mark.parametrize("n", [3, 6, 9, 17])
 def test_projectors_do_not_depend_on_the_h_layout(abz, n):
+    """3: lane kernel; 6, 9, 17: 8, 16 and 32 lanes per node.  Above 16 bands the library has no compact layout and drops the bit
+    (abzhip.h): at n = 17 the third rule is a second full-layout one."""
     L = abz._lib
     s, npt = make_series(abz, n)
     pairs = groups_of(all_pairs(n))[0]

@@ -97,17 +97,23 @@ def test_orbital_weight_of_a_scalar_series_is_one(abz):
 
 
 # ---------------------------------------------------------------- 2. layouts
-@pytest.mark.parametrize("n", [3, 12])
+@pytest.mark.parametrize("n", [3, 6, 12, 17])
 def test_orbital_weights_do_not_depend_on_the_h_layout(abz, n):
+    """One lane kernel and the row kernels of 8, 16 and 32 lanes per node; above 16 bands the selection of sixteen orbitals of
+    test_orbital_weights_match_lapack_17_to_32_bands.  The library has no compact layout above 16 bands and drops the bit
+    (abzhip.h): at n = 17 the third rule is a second full-layout one, so the case checks the transient H against the resident
+    one at 32 lanes per node, not the compact branch."""
     L = abz._lib
     s = product_series(abz, orc.synthetic_wannier(n, rmax=2, seed=7))
+    orbitals = None if n <= 16 else [n - 1, 0, 5, 3] + list(range(6, 17)) + [1]
     blocks = []
     for want in (L.WANT_EIG, L.WANT_H | L.WANT_EIG, L.WANT_H | L.WANT_EIG | L.WANT_H_COMPACT):
         rule = abz.DeviceRule(s.device(), 12, None, want)
-        W = device_weights(rule)
-        assert np.array_equal(W, device_weights(rule)), want  # two calls on one rule
+        W = device_weights(rule, orbitals)
+        assert np.array_equal(W, device_weights(rule, orbitals)), want  # two calls on one rule
         if want == L.WANT_EIG:
-            sel = device_weights(rule, [2, 0, 2])
+            asked = list(range(n)) if orbitals is None else orbitals
+            sel = device_weights(rule, [asked[2], asked[0], asked[2]])
             assert np.array_equal(sel, W[[2, 0, 2]])
         blocks.append(W)
         rule.close()
