@@ -58,6 +58,7 @@ PROTOTYPES = {
     "abz_rule_ltm_elements_export": (C.c_int, [C.c_void_p, c_ip, c_f64p]),
     "abz_rule_ltm_elements_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p, c_ip]),
     "abz_rule_ltm_weighted": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
+    "abz_rule_ltm_optimized": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int, C.c_int, c_f64p]),
     "abz_rule_ltm_fermi": (C.c_int, [C.c_void_p, C.c_double, C.c_double, c_f64p, c_f64p]),
     "abz_rule_ltm_unfold": (C.c_int, [C.c_void_p, c_i32p, C.c_int, c_vpp]),
     "abz_rule_ltm_halo": (C.c_int, [C.c_void_p]),
@@ -103,7 +104,7 @@ K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
 K_EVAL_FUSED = 7  # launches only: the K_EVAL launches of the fused grid kernel
 LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
-LTM_A_ONE = 2  # A = 1, the joint DOS: abz_rule_ltm_pairs_occupied only
+LTM_A_ONE = 2  # A = 1: the joint DOS of abz_rule_ltm_pairs_occupied, g and N of abz_rule_ltm_optimized
 LTM_MAX_COMP = 16
 LTM_EXPECT_MAX_OPS = 8  # operators of one abz_rule_ltm_expectation call
 LTM_PAIRS_MAX_OPS = 4  # operators of one abz_rule_ltm_pairs call

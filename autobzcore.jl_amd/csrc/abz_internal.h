@@ -540,6 +540,11 @@ int launch_ltm(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* E
 // (a slab: one component only)
 int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView A, int ncomp, const double* Es_host, int nE,
                         int what, double* out_host, const LtmSlab* slab = nullptr);
+// Optimized tetrahedron scan (kernels_ltm_opt.hip; Kawamura et al.) over the eigenvalue planes of a whole periodic 3-d grid: the sums of
+// launch_ltm_weighted on the effective corner values of every simplex.  A: ncomp n element planes tiled like E, out_host [nE][ncomp];
+// A == nullptr: one component, A = 1 (g, N) or, with `energy`, A = e.  Under ABZ_K_LTM.
+int launch_ltm_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneView* A, bool energy, int ncomp, const double* Es_host, int nE,
+                         bool states, double* out_host);
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 // tr G(z) by the tetrahedron method on a whole grid (abz_rule_ltm_green): z_host [nz][2] with Im z != 0, out_host [nz][2]
 int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* z_host, int nz, double* out_host);

@@ -1,0 +1,306 @@
+// Optimized tetrahedron method (gfx950 only): g(E), N(E), g_A(E), N_A(E) from the cached eigenvalues of a full 3-d grid with the
+// leading O(1/npt^2) interpolation error of the linear method removed.
+//
+// Kawamura, Gohda, Tsuneyuki, PRB 89, 094515 (2014).  The reference has no counterpart (src/dos_algorithms.jl:1-7 plans "LTM").
+//
+//  * Definition (d = 3).  A Kuhn simplex of cell i is the path v1 = i (corner 0), v2 = v1 + e_a, v3 = v2 + e_b, v4 = v3 + e_c (corner 7)
+//    over a permutation (a, b, c) of the axes: the six (0, a, b, 7) of kernels_ltm.hip.  The band is taken at 20 grid points,
+//      p1..p4   = v1..v4
+//      p5..p16  = 2 v_i - v_j,  (i, j) = (1,2) (2,3) (3,4) (4,1) (1,3) (2,4) (3,1) (4,2) (1,4) (2,1) (3,2) (4,3)
+//      p17..p20 = v4 - v1 + v2,  v1 - v2 + v3,  v2 - v3 + v4,  v3 - v4 + v1,
+//    all inside i + [-1, 2]^3, every index wrapped mod npt (any npt >= 1; below 4 the stencil wraps onto itself).  The cubic through
+//    the 20 values is fitted, and the 4 corner values are replaced by those of the linear function closest to it in the
+//    least-squares sense over the simplex: x'_m = sum_j P[m][j] x(p_j), OPT_K = 1260 P below (rows sum to 1260; derived in exact
+//    rationals by tests/optltm_numpy.py, which does not read this table).  For band b, x is the b-th ascending eigenvalue at each
+//    point (no band unfolding); elements A_b take the same P at the same points.  Every closed form of the linear method
+//    (ltm_simplex_device.h) then applies unchanged to (e'_1..e'_4; A'_1..A'_4), with the weight 1 / (6 npt^3) per simplex; a simplex
+//    wholly below E adds the mean of its A' to the step histogram at the first energy >= max e'.
+//  * Rows sum to one, so x'_m = x_m + sum_{j != m} P[m][j] (x_j - x_m): this is the form evaluated.  A flat band keeps its value
+//    to the bit (g = 0, a unit step), A = 1 gives A' = 1 exactly, and the rounding error scales with the variation of the band
+//    over the stencil instead of its absolute value.
+//  * Shape (ltm_opt_kernel<STATES, SRC, NC>).  Energies ascending in LDS, blockIdx.y the band, one histogram per wave and kind,
+//    fixed-order reduction into transposed partials, then ltm_final_kernel / ltm_prefix_kernel of kernels_ltm.hip as they are:
+//    two calls return the same bits.  A block walks 256 cells at a time, one cell per thread, and every thread takes the six
+//    simplices of its cell one after the other: the permutation is uniform over the wave, so the 20 loads of a simplex are 20
+//    shifted copies of the same run of a grid line (consecutive lanes, consecutive i_1), and the 4^3 neighbourhood that the six
+//    simplices and the neighbouring cells share is served by the caches.  Per axis the thread keeps the 4 wrapped indices
+//    i - 1 .. i + 2 as (column, line) contributions; a simplex picks its three tables by compares on the permutation and every
+//    point is three constant-index entries of them: nothing is indexed by a run-time value, nothing goes to scratch.
+//  * Window.  e' can leave the range of the cell's 8 corners (sum_j |P[m][j]| = 1836 / 1260), so the window [min e', max e') is
+//    that of the effective energies of each simplex, taken after the product.  A simplex with no energy at or above min e' is
+//    done; without STATES one with no energy below max e' too, before its elements are loaded.  Everything else goes to
+//    ltm_simplex3 of the element payload, which walks the energies of the window and places the step.  There is no queue: the
+//    20 loads and the 4 x 17 product of every simplex come before the window is known, and they, not the walk, set the time
+//    (DESIGN section 4e).
+//  * Sources.  OPT_ONE: A' = 1, nothing loaded.  OPT_ENERGY: A' = e', nothing loaded.  OPT_ELEMS: NC = 1, 2 or 4 components per
+//    launch, 20 loads and one product per component, after the window test.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "abz_internal.h"
+#include "ltm_device.h"
+#include "ltm_simplex_device.h"
+
+namespace abz {
+
+namespace {
+
+// The 20 points in path coordinates: p = v1 + al e_a + be e_b + ga e_c.
+constexpr int OPT_NPT = 20;
+__device__ constexpr int OPT_PT[OPT_NPT][3] = {
+    {0, 0, 0},    {1, 0, 0},   {1, 1, 0},   {1, 1, 1},                                                   // v1 .. v4
+    {-1, 0, 0},   {1, -1, 0},  {1, 1, -1},  {2, 2, 2},                                                   // 2 v_i - v_j: (1,2) (2,3) (3,4) (4,1)
+    {-1, -1, 0},  {1, -1, -1}, {2, 2, 0},   {1, 2, 2},                                                   // (1,3) (2,4) (3,1) (4,2)
+    {-1, -1, -1}, {2, 0, 0},   {1, 2, 0},   {1, 1, 2},                                                   // (1,4) (2,1) (3,2) (4,3)
+    {2, 1, 1},    {0, 1, 0},   {1, 0, 1},   {0, 0, -1},                                                  // v4 - v1 + v2, ...
+};
+// 1260 P
+__device__ constexpr int OPT_K[4][OPT_NPT] = {
+    {1440, 0, 30, 0, -38, 7, 17, -28, -56, 9, -46, 9, -38, -28, 17, 7, -18, -18, 12, -18},
+    {0, 1440, 0, 30, -28, -38, 7, 17, 9, -56, 9, -46, 7, -38, -28, 17, -18, -18, -18, 12},
+    {30, 0, 1440, 0, 17, -28, -38, 7, -46, 9, -56, 9, 17, 7, -38, -28, 12, -18, -18, -18},
+    {0, 30, 0, 1440, 7, 17, -28, -38, 9, -46, 9, -56, -28, 17, 7, -38, -18, 12, -18, -18},
+};
+constexpr bool opt_rows_ok() {
+    for (int m = 0; m < 4; ++m) {
+        int s = 0;
+        for (int j = 0; j < OPT_NPT; ++j) s += OPT_K[m][j];
+        if (s != 1260) return false;
+    }
+    return true;
+}
+static_assert(opt_rows_ok(), "the rows of 1260 P sum to 1260");
+
+// x'_m = x_m + sum_{j != m} P[m][j] (x_j - x_m)
+__device__ __forceinline__ void opt_project(const double (&x)[OPT_NPT], double (&y)[4]) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < OPT_NPT; ++j)
+            if (j != m && OPT_K[m][j] != 0) s = fma((double)OPT_K[m][j] / 1260.0, x[j] - x[m], s);
+        y[m] = x[m] + s;
+    }
+}
+
+enum { OPT_ONE = 0, OPT_ENERGY = 1, OPT_ELEMS = 2 };
+
+struct OptArgs {
+    PlaneView E, A;
+    const double* Es;  // device, ascending
+    int64_t ncell;     // npt^3
+    int64_t acomp;     // doubles from a band's plane of one component to its plane of the next: n * A.pitch
+    int npt, nE;
+    int aplane0;       // first element plane of this launch: (its first component) * n
+    double inv_step = 0.0;
+};
+
+// what ltm_simplex3 asks of its payload
+template <int NC_>
+struct OptPayload {
+    static constexpr int NC = NC_;
+    static constexpr bool CORR = false;
+};
+
+// index i + o of a periodic axis of npt >= 1 points, o in -1 .. 2
+__device__ __forceinline__ int opt_wrap(int i, int o, int npt) {
+    int j = i + o;
+    j += j < 0 ? npt : 0;
+    j -= j >= npt ? npt : 0;
+    j -= j >= npt ? npt : 0;  // npt = 1: i + 2 is two periods away
+    return j;
+}
+
+// partial [(STATES ? 2 : 1) NC nE][nrows]: columns c nE + i the formula sums of component c, NC nE + c nE + i its steps
+template <bool STATES, int SRC, int NC>
+__global__ __launch_bounds__(256) void ltm_opt_kernel(OptArgs a, double* __restrict__ partial, int64_t nrows) {
+    static_assert(SRC == OPT_ELEMS || NC == 1, "one component without attached elements");
+    // [nE] energies | [4 waves][NC][nE] sums | STATES: [4 waves][NC][nE] steps
+    extern __shared__ __attribute__((aligned(16))) double ldsl[];
+    using Pay = OptPayload<NC>;
+    using Vec = LtmVec<NC>;
+    const int wave = threadIdx.x >> 6;
+    const int nE = a.nE;
+    constexpr int NH = (STATES ? 8 : 4) * NC;
+    const double* const Esl = ldsl;
+    double* const hist = ldsl + (size_t)(1 + wave * NC) * nE;
+    double* const step = ldsl + (size_t)(1 + (4 + wave) * NC) * nE;  // STATES only
+    for (int i = threadIdx.x; i < nE; i += 256) ldsl[i] = a.Es[i];
+    for (int i = threadIdx.x; i < NH * nE; i += 256) ldsl[nE + i] = 0.0;
+    __syncthreads();
+    const int npt = a.npt;
+    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
+    // the strides between lines as 32-bit factors (the host checks them): line * tile is then ONE 32 x 32 -> 64 bit multiply-add per point,
+    // where the 64 x 64 bit product took three quarter-rate multiplies and set the kernel's time
+    const int tileE = (int)a.E.tile;
+    [[maybe_unused]] const double* __restrict__ Ab = nullptr;
+    [[maybe_unused]] int tileA = 0;
+    [[maybe_unused]] int64_t acomp = 0;
+    if constexpr (SRC == OPT_ELEMS) {
+        Ab = a.A.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.A.pitch;
+        tileA = (int)a.A.tile;
+        acomp = a.acomp;
+    }
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
+        const int64_t k = base + threadIdx.x;
+        if (k >= a.ncell) continue;  // (no barrier inside the walk)
+        const LtmCell cell = ltm_cell<3>(k, npt);
+        // the wrapped indices i - 1 .. i + 2 of every axis: a column (axis 1) or a line number (axis 2; axis 3 in units of npt lines)
+        int j1[4], j2[4], j3[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            j1[o] = opt_wrap(cell.i1, o - 1, npt);
+            j2[o] = opt_wrap(cell.i2, o - 1, npt);
+            j3[o] = opt_wrap(cell.i3, o - 1, npt) * npt;
+        }
+#pragma unroll 1
+        for (int t = 0; t < 6; ++t) {
+            // the permutation (X, Y, Z) of the axes, as in the queue of ltm_window_kernel: corners 0, e_X, e_X + e_Y, (1,1,1)
+            const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3, Z = 3 - X - Y;
+            // what a step of o - 1 along the path's first, second and third axis adds to the column and to the line
+            int col[3][4], line[3][4];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                col[0][o] = X == 0 ? j1[o] : 0;
+                col[1][o] = Y == 0 ? j1[o] : 0;
+                col[2][o] = Z == 0 ? j1[o] : 0;
+                line[0][o] = X == 1 ? j2[o] : (X == 2 ? j3[o] : 0);
+                line[1][o] = Y == 1 ? j2[o] : (Y == 2 ? j3[o] : 0);
+                line[2][o] = Z == 1 ? j2[o] : (Z == 2 ? j3[o] : 0);
+            }
+            // point j of the stencil: column and line inside 0 .. npt-1 and 0 .. npt^2-1, as for a corner of the linear scan
+            auto at = [&](const double* __restrict__ planes, int tile, int j) -> double {
+                const int c = col[0][OPT_PT[j][0] + 1] + col[1][OPT_PT[j][1] + 1] + col[2][OPT_PT[j][2] + 1];
+                const int l = line[0][OPT_PT[j][0] + 1] + line[1][OPT_PT[j][1] + 1] + line[2][OPT_PT[j][2] + 1];
+                return planes[(int64_t)l * tile + c];
+            };
+            double x[OPT_NPT], e[4];
+#pragma unroll
+            for (int j = 0; j < OPT_NPT; ++j) x[j] = at(Eb, tileE, j);
+            opt_project(x, e);
+            const double emin = fmin(fmin(e[0], e[1]), fmin(e[2], e[3])), emax = fmax(fmax(e[0], e[1]), fmax(e[2], e[3]));
+            const int i0 = ltm_first(Esl, nE, a.inv_step, emin);
+            if (i0 >= nE) continue;                       // every energy lies below the simplex
+            if (!STATES && !(Esl[i0] < emax)) continue;   // no energy inside the window: nothing for g
+            Vec A[4];
+            if constexpr (SRC == OPT_ONE) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) A[m].v[0] = 1.0;
+            } else if constexpr (SRC == OPT_ENERGY) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) A[m].v[0] = e[m];
+            } else {
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    double y[4];
+#pragma unroll
+                    for (int j = 0; j < OPT_NPT; ++j) x[j] = at(Ab + (int64_t)c * acomp, tileA, j);
+                    opt_project(x, y);
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) A[m].v[c] = y[m];
+                }
+            }
+            ltm_simplex3<STATES, Pay>(e[0], e[1], e[2], e[3], A[0], A[1], A[2], A[3], Esl, nE, i0, hist, step);
+        }
+    }
+    __syncthreads();
+    const int64_t prow = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const double* h = ldsl + nE;
+    // transposed partials [column][row], as ltm_window_kernel writes them
+    for (int t = threadIdx.x; t < NC * nE; t += 256) {
+        const size_t w = (size_t)NC * nE;  // from one wave's histograms to the next
+        partial[(int64_t)t * nrows + prow] = (h[t] + h[w + t]) + (h[2 * w + t] + h[3 * w + t]);
+        if (STATES) partial[((int64_t)NC * nE + t) * nrows + prow] = (h[4 * w + t] + h[5 * w + t]) + (h[6 * w + t] + h[7 * w + t]);
+    }
+}
+
+using OptFn = void (*)(abz_ctx*, dim3, size_t, const OptArgs&, double*, int64_t);
+template <bool STATES, int SRC, int NC>
+void opt_launch(abz_ctx* ctx, dim3 grid, size_t lds, const OptArgs& a, double* partial, int64_t nrows) {
+    launch(ctx, (ltm_opt_kernel<STATES, SRC, NC>), grid, dim3(256), (unsigned)lds, a, partial, nrows);
+}
+
+// the compiled kernels: [states][source][NC]
+OptFn opt_fn(bool states, int src, int nc) {
+    if (src == OPT_ONE) return states ? opt_launch<true, OPT_ONE, 1> : opt_launch<false, OPT_ONE, 1>;
+    if (src == OPT_ENERGY) return states ? opt_launch<true, OPT_ENERGY, 1> : opt_launch<false, OPT_ENERGY, 1>;
+    switch (nc) {
+        case 1: return states ? opt_launch<true, OPT_ELEMS, 1> : opt_launch<false, OPT_ELEMS, 1>;
+        case 2: return states ? opt_launch<true, OPT_ELEMS, 2> : opt_launch<false, OPT_ELEMS, 2>;
+        case 4: return states ? opt_launch<true, OPT_ELEMS, 4> : opt_launch<false, OPT_ELEMS, 4>;
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+// The host side of ltm_scan (kernels_ltm.hip) for the optimized kernel: chunks of energies, groups of 4, 2, 1 components, the same
+// final and prefix kernels.  A == nullptr: one component, A = 1 (`energy` false) or A = e (`energy` true).
+int launch_ltm_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneView* A, bool energy, int ncomp, const double* Es_host, int nE,
+                         bool states, double* out_host) {
+    const int src = A ? OPT_ELEMS : (energy ? OPT_ENERGY : OPT_ONE);
+    if (!A) ncomp = 1;
+    if (E.tile > INT32_MAX || (A && A->tile > INT32_MAX)) {
+        set_error("abz_rule_ltm_optimized: a stride of %lld doubles between grid lines does not fit the kernel's 32-bit factor",
+                  (long long)std::max(E.tile, A ? A->tile : 0));
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    OptArgs a;
+    a.E = E;
+    a.npt = npt;
+    a.ncell = (int64_t)npt * npt * npt;
+    if (A) {
+        a.A = *A;
+        a.acomp = (int64_t)n * A->pitch;
+    }
+    const double weight = 1.0 / (6.0 * (double)a.ncell);
+    const int ncol = states ? 2 : 1;
+    // energies per launch of NC components, as in ltm_scan: 8 (1 + 4 NC ncol) B of LDS each within LTM_LDS_MAX, at most 512 where
+    // the prefix kernel holds a chunk's steps
+    auto chunk = [&](int nc) {
+        const size_t fit = LTM_LDS_MAX / (sizeof(double) * (size_t)(1 + 4 * nc * ncol));
+        return (int)std::min<size_t>(fit, states ? 512 : 1024);
+    };
+    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
+    const int64_t nrows = nblocks * n;
+    size_t pmax = 0;
+    for (int nc : {1, 2, 4})
+        if (nc <= ncomp) pmax = std::max(pmax, (size_t)std::min(nE, chunk(nc)) * (size_t)(nc * ncol));
+    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax);
+    if (rc) return rc;
+    double* partial = ctx->scratch[1].as<double>();
+    EnergyList el;
+    // behind the energies: the column sums of a launch, [nc][cnt] sums | [nc][cnt] steps (states)
+    if ((rc = energies_to_device(ctx, Es_host, nE, true, 2 * 4 * (size_t)512, el, ncomp))) return rc;
+    double* col = el.extra;
+    a.inv_step = el.inv_step;
+    const dim3 grid((unsigned)nblocks, (unsigned)n);
+    for (int c0 = 0; c0 < ncomp;) {
+        const int nc = ncomp - c0 >= 4 ? 4 : (ncomp - c0 >= 2 ? 2 : 1);
+        const int CH = chunk(nc);
+        const OptFn fn = opt_fn(states, src, nc);
+        a.aplane0 = c0 * n;
+        for (int s0 = 0; s0 < nE; s0 += CH) {
+            const int cnt = std::min(CH, nE - s0);
+            a.Es = el.dev + s0;
+            a.nE = cnt;
+            ProfScope ps(ctx, ABZ_K_LTM);
+            const size_t lds = sizeof(double) * (size_t)(1 + 4 * nc * ncol) * (size_t)cnt;
+            double* const o = el.out + (size_t)c0 * nE + s0;  // results [ncomp][nE] in sorted order
+            fn(ctx, grid, lds, a, partial, nrows);
+            ABZ_HIP(hipGetLastError());
+            if (states) {
+                if ((rc = launch_ltm_final(ctx, partial, nrows, 1.0, 2 * nc * cnt, 2 * nc * cnt, 0, col))) return rc;
+                if ((rc = launch_ltm_prefix(ctx, col, cnt, nc, weight, (int64_t)nE, o))) return rc;
+            } else if ((rc = launch_ltm_final(ctx, partial, nrows, weight, nc * cnt, cnt, nE, o))) {
+                return rc;
+            }
+        }
+        c0 += nc;
+    }
+    return energies_deliver(ctx, el, out_host);
+}
+
+}  // namespace abz

@@ -354,6 +354,31 @@ int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int 
                                what, out, ltm_slab_of(r, slab) ? &slab : nullptr);
 } ABZ_CATCH_ALL
 
+// The optimized tetrahedron method (kernels_ltm_opt.hip).  Every check comes before anything is reserved or launched.
+int abz_rule_ltm_optimized(abz_rule* r, int source, const double* E, int nE, int what, double* out) try {
+    const char* const who = "abz_rule_ltm_optimized";
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm_optimized: bad arguments");
+    ABZ_REQUIRE(what != ABZ_LTM_STATES_CORRECTED,
+                "abz_rule_ltm_optimized: ABZ_LTM_STATES_CORRECTED: the optimized rule replaces the curvature correction (ask for ABZ_LTM_STATES)");
+    if ((rc = ltm_check_what(who, what, false))) return rc;
+    ABZ_REQUIRE(source == ABZ_LTM_A_ONE || source == ABZ_LTM_A_ENERGY || source == ABZ_LTM_A_ELEMENTS,
+                "%s: source = %d is neither ABZ_LTM_A_ONE, ABZ_LTM_A_ENERGY nor ABZ_LTM_A_ELEMENTS", who, source);
+    if (r->s->d != 3) {
+        set_error("abz_rule_ltm_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
+    ABZ_REQUIRE(source != ABZ_LTM_A_ELEMENTS || r->elems.buf.p,
+                "abz_rule_ltm_optimized: no matrix elements are attached (abz_rule_ltm_elements; abz_rule_rebuild drops them)");
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const bool elems = source == ABZ_LTM_A_ELEMENTS;
+    return launch_ltm_optimized(ctx, rule_bands(r), r->npt, r->E, elems ? &r->elems.view : nullptr, source == ABZ_LTM_A_ENERGY,
+                                elems ? r->elems.sets : 1, E, nE, what == ABZ_LTM_STATES, out);
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z, int nz, double* out) try {
     int rc = check_rule(r);
     if (rc) return rc;

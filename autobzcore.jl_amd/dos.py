@@ -163,7 +163,7 @@ class LTM(DOSAlgorithm):
     `correction=True` (with `cumulative=True` and `elements`) adds Bloechl's curvature correction (eq. 22 of the paper)
     to N_A on every route above.  It removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING, i.e. at the Fermi
     level of the same grid (`fermi_level`, `band_energy`); at a fixed energy the misplaced Fermi surface leaves an error
-    of the same order.  The plain state count and the DOS have no correction.
+    of the same order (`optimized=True` below has no such limit).  The plain state count and the DOS have no correction.
 
     On a k-sharded series (dist.kshard) every rank builds its slab of the grid and the one halo plane behind it
     (DeviceRule.ltm_halo), scans the cells of its slab, and the partial sums are summed over the ranks: `elements` None or
@@ -187,11 +187,27 @@ class LTM(DOSAlgorithm):
     sum_vc int dk M M^* / (w + i eta - (e_c - e_v)): -Im / pi is the broadened spectrum, Re its Kramers-Kronig partner.
     `correction` needs operators.  Refused when the cache is made: `pairs` with `elements`; `pairs` with operators and
     symmetric=True (matrix elements are not invariant; without operators symmetric=True gives the JDOS from irreducible
-    nodes); a k-sharded series (NotImplementedError); more than 64 pairs."""
+    nodes); a k-sharded series (NotImplementedError); more than 64 pairs.
+
+    `optimized=True` (d = 3) scans with the optimized tetrahedron method of Kawamura, Gohda and Tsuneyuki, PRB 89, 094515
+    (2014) instead (DeviceRule.ltm_optimized): every simplex takes the band, and the elements, at its 4 corners and at 16
+    neighbouring grid points, and the closed forms run on the corner values of the linear function closest to the cubic
+    through the 20 values.  Same eigenvalues, no further eigen-solve; the error falls like a higher power of 1/npt at ANY
+    energy, for the DOS, `cumulative`, and `elements` "energy", "orbitals", a callable or a BandExpectation, with or without
+    `symmetric` -- the rule at npt compares with the linear rule at 2 npt.  It replaces the curvature correction:
+    `correction`, `eta` and `pairs` raise ValueError with it; a k-sharded series and d < 3 raise NotImplementedError when
+    the cache is made.  `fermi_level` and `band_energy` follow the cache's rule."""
 
     def __init__(self, npt=50, cumulative=False, elements=None, symmetric=False, eigenvectors="host", orbitals=None,
-                 correction=False, eta=None, pairs=None):
+                 correction=False, eta=None, pairs=None, optimized=False):
         self.npt = int(npt)
+        self.optimized = bool(optimized)
+        if self.optimized and correction:
+            raise ValueError("LTM: optimized=True replaces the curvature correction: it does not go with correction=True")
+        if self.optimized and eta is not None:
+            raise ValueError("LTM: optimized=True does not go with eta (the Green's functions use the linear rule)")
+        if self.optimized and pairs is not None:
+            raise ValueError("LTM: optimized=True does not go with pairs (pair rules are scanned with the linear rule)")
         if pairs is not None and not isinstance(pairs, BandPairs):
             raise ValueError(f"LTM: pairs = {pairs!r} is not a BandPairs")
         self.pairs = pairs
@@ -306,7 +322,12 @@ def _init_cacheval(h, domain, p, alg, prev=None):
                          "are not invariant under the zone's symmetries, and an unfolded rule stores no H(k))")
     if isinstance(alg, LTM) and alg.pairs is not None:
         return _pair_rule(h, p, alg, prev)
+    if isinstance(alg, LTM) and alg.optimized and h.d != 3:
+        raise NotImplementedError(f"LTM(optimized=True) is implemented for d = 3 (the series has d = {h.d})")
     h.invalidate()  # coefficients may have been mutated in place (test/dos.jl:123): re-upload, rules refill lazily
+    if isinstance(alg, LTM) and alg.optimized and _ksharded(h.device()):
+        raise NotImplementedError("LTM(optimized=True) on a k-sharded series is not implemented: the 20-point stencil of a simplex "
+                                  "needs three halo planes")
     if isinstance(alg, LTM) and alg.eta is not None and _ksharded(h.device()):
         raise NotImplementedError("LTM(eta=...) on a k-sharded series is not implemented: the trace of the Green's function is "
                                   "computed on whole grids")
@@ -411,10 +432,12 @@ def _ltm_solve(c, Es):
         if not isinstance(el, str):
             _ltm_attach(rule, el)
         return -rule.ltm_green(zs, elements=el if isinstance(el, str) else "attached").imag / np.pi
-    if el is None or isinstance(el, str):
-        return rule.ltm(Es, states=c.alg.cumulative, elements=el, correction=c.alg.correction)
-    _ltm_attach(rule, el)
-    return rule.ltm(Es, states=c.alg.cumulative, elements="attached", correction=c.alg.correction)
+    if not (el is None or isinstance(el, str)):
+        _ltm_attach(rule, el)
+        el = "attached"
+    if c.alg.optimized:
+        return rule.ltm_optimized(Es, states=c.alg.cumulative, elements=el)
+    return rule.ltm(Es, states=c.alg.cumulative, elements=el, correction=c.alg.correction)
 
 
 def _refresh(c):
@@ -446,9 +469,12 @@ def solve_(c: DOSCache):
     return DOSSolution(u[0].item() if scalar else u, None, True, -1)
 
 
-def fermi_level(prob_or_cache, nstates, tol=1e-10):
+def fermi_level(prob_or_cache, nstates, tol=1e-10, optimized=None):
     """(E_F, N(E_F)) of `nstates` states per unit cell (0 < nstates < n) from the eigenvalues of an LTM cache, or of a
-    DOSProblem (solved with LTM()): E_F is the upper end of an interval no wider than `tol` that N crosses `nstates` in."""
+    DOSProblem (solved with LTM()): E_F is the upper end of an interval no wider than `tol` that N crosses `nstates` in.
+    `optimized`: True for the level of the optimized tetrahedron rule's state count (DeviceRule.ltm_fermi_optimized, d = 3:
+    a host search over device scans, the same contract), False for the linear rule's, None (the default) for the rule of
+    the cache's algorithm, LTM(optimized=...)."""
     H = getattr(prob_or_cache, "H", None)
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
         raise NotImplementedError("fermi_level / band_energy on a k-sharded series are not implemented: the search for the level "
@@ -460,6 +486,8 @@ def fermi_level(prob_or_cache, nstates, tol=1e-10):
         c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
+    if c.alg.optimized if optimized is None else optimized:
+        return c.cacheval.ltm_fermi_optimized(nstates, tol)
     return c.cacheval.ltm_fermi(nstates, tol)
 
 
@@ -601,9 +629,12 @@ def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):
     """(E_band, E_F): the band energy sum_b int e_b theta(E_F - e_b) of `nstates` states per unit cell.  E_F is
     `fermi_level`'s on the same grid; one single-energy scan with the energy as the element follows, with Bloechl's
     curvature correction unless `correction=False`.  The correction is made for exactly this use -- a sum at the grid's own
-    Fermi level: it removes the leading O(1/npt^2) error of the linear interpolation."""
+    Fermi level: it removes the leading O(1/npt^2) error of the linear interpolation.  On a cache of LTM(optimized=True) the
+    level and the scan are those of the optimized rule, which takes no correction (`correction` is not read)."""
     c = prob_or_cache if isinstance(prob_or_cache, DOSCache) else init(prob_or_cache, LTM())
     E_F, _ = fermi_level(c, nstates, tol)
+    if c.alg.optimized:
+        return float(c.cacheval.ltm_optimized(np.array([E_F]), states=True, elements="energy")[0, 0]), E_F
     u = c.cacheval.ltm(np.array([E_F]), states=True, elements="energy", correction=bool(correction))
     return float(u[0, 0]), E_F
 

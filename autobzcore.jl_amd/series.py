@@ -887,8 +887,8 @@ class DeviceRule:
         `correction` (with `states` and `elements`): N_A with Bloechl's curvature correction (ABZ_LTM_STATES_CORRECTED),
         N_A + w sum_T g_T(E) kappa_T, kappa_T = sum_i A_i (sum_l e_l - (d+1) e_i) / (2 (d+1)(d+2)), in the same launches.  It
         removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING -- at the level `ltm_fermi` finds on the same
-        grid; at a fixed energy the misplaced Fermi surface leaves an error of that order.  The plain state count has no
-        correction (kappa_T = 0 for A = 1)."""
+        grid; at a fixed energy the misplaced Fermi surface leaves an error of that order (`ltm_optimized` has no such
+        limit).  The plain state count has no correction (kappa_T = 0 for A = 1)."""
         sharded = bool(self.shard and self.shard[1] > 1)
         if sharded and not self._ltm_halo:
             self._ltm_refuse_shard()
@@ -922,6 +922,107 @@ class DeviceRule:
             L.check(L.lib().abz_rule_ltm_weighted(h, L.LTM_A_ENERGY if elements == "energy" else L.LTM_A_ELEMENTS,
                                                   Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
         return self._sum_over_ranks(out)
+
+    def ltm_optimized(self, Es, states=False, elements=None):
+        """`ltm(Es, states, elements)` by the optimized tetrahedron method of Kawamura, Gohda and Tsuneyuki, PRB 89, 094515
+        (abz_rule_ltm_optimized; d = 3): every simplex takes the band at its 4 corners and at 16 neighbouring grid points and
+        replaces the corner values by those of the linear function closest, in the least-squares sense over the simplex, to
+        the cubic through the 20 values; the closed forms of `ltm` then apply to these effective corner values.  Same
+        eigenvalues, no further eigen-solve, and the error falls like a higher power of 1/npt AT ANY ENERGY: the rule at npt
+        compares with the linear rule at 2 npt.  `elements`: None (g, N as [nE]), "energy", "attached" or an array
+        [ncomp, nk, n] as for `ltm` ([nE, ncomp]); they take the same 20-point fit.  There is no `correction`: this rule
+        replaces it.  NotImplementedError on a k-sharded rule (the stencil needs three halo planes) and for d < 3."""
+        self._ltm_refuse_optimized("ltm_optimized")
+        Es = np.ascontiguousarray(np.asarray(Es, dtype=np.float64).reshape(-1))
+        what = L.LTM_STATES if states else L.LTM_DOS
+        if elements is None:
+            source, ncomp = L.LTM_A_ONE, 1
+        elif isinstance(elements, str):
+            if elements not in ("energy", "attached"):
+                raise ValueError(f"ltm_optimized: elements = {elements!r} is neither 'energy' nor 'attached'")
+            source = L.LTM_A_ENERGY if elements == "energy" else L.LTM_A_ELEMENTS
+        else:
+            self.ltm_elements(elements)
+            source = L.LTM_A_ELEMENTS
+        h = self.h  # (a stale rule is refilled here, which drops the attached elements)
+        if source == L.LTM_A_ELEMENTS:
+            ncomp = self._ltm_ncomp
+            if ncomp < 1:
+                raise ValueError("ltm_optimized: no matrix elements are attached (ltm_elements; a rebuild of the rule drops them)")
+        elif source == L.LTM_A_ENERGY:
+            ncomp = 1
+        out = np.zeros((len(Es), ncomp))
+        L.check(L.lib().abz_rule_ltm_optimized(h, source, Es.ctypes.data_as(L.c_f64p), len(Es), what, out.ctypes.data_as(L.c_f64p)))
+        return out[:, 0] if elements is None else out
+
+    def _ltm_refuse_optimized(self, who):
+        if self.shard and self.shard[1] > 1:
+            raise NotImplementedError(f"{who} on a k-sharded (slab) rule is not implemented: the 20-point stencil of a simplex "
+                                      "needs three halo planes")
+        if self.dev.s.d != 3:
+            raise NotImplementedError(f"{who}: the optimized tetrahedron rule is implemented for d = 3 (the series has d = {self.dev.s.d})")
+
+    def ltm_fermi_optimized(self, nstates, tol=1e-10):
+        """(E_F, N(E_F)) as `ltm_fermi` returns them, for the state count of `ltm_optimized`: E_F is the upper end of an
+        interval no wider than `tol` with N(E_F) >= nstates (1 - 1e-12) and N below that at its lower end; below a gap it is
+        moved up to the lowest energy with g(E_F) = 0.  The search runs on the host and brackets with device scans of 512
+        energies each, 511 times narrower per scan: the optimized N is monotone like the linear one (every simplex adds a
+        non-decreasing function of E)."""
+        self._ltm_refuse_optimized("ltm_fermi_optimized")
+        n = self.nbands
+        nstates, tol = float(nstates), float(tol)
+        if not (0.0 < nstates < n):
+            raise ValueError(f"ltm_fermi_optimized: nstates = {nstates} outside (0, {n})")
+        if not tol > 0.0:
+            raise ValueError(f"ltm_fermi_optimized: tol = {tol} is not positive")
+        eig = self.export(x=False, w=False, eig=True)["eig"]
+        # the effective corner energies leave the range of the eigenvalues by less than (1836 / 1260 - 1) / 2 of its width
+        width = float(eig.max() - eig.min())
+        lo, hi = float(eig.min()) - 0.25 * width, float(eig.max()) + 0.25 * width
+        top = hi
+        M = 512
+        target = nstates * (1.0 - 1e-12)
+
+        def narrow(a, b, states, reached):
+            """the sub-interval (E_{i-1}, E_i] of M samples of [a, b] with `reached` first true at E_i -> (a', b', value at b', i)"""
+            Es = a + (b - a) * (np.arange(M) / (M - 1.0))
+            Es[-1] = b
+            u = self.ltm_optimized(Es, states=states)
+            hit = np.flatnonzero(reached(u[:-1]))
+            i = int(hit[0]) if len(hit) else M - 1  # the upper end stands for "none": it was seen to qualify before
+            return (float(Es[i - 1]) if i > 0 else a), float(Es[i]), float(u[i]), i
+
+        Nhi = float(n)
+        for _ in range(64):
+            if not hi - lo > 0.0:
+                break
+            a, b, Nhi, i = narrow(lo, hi, True, lambda N: N >= target)
+            shrunk = b - a < hi - lo
+            lo, hi = a, b
+            if i == 0 or hi - lo <= tol or not shrunk:
+                break
+        # below a gap N cannot tell the band top from a point 1e-4 below it, g can: the search of abz_rule_ltm_fermi on g == 0
+        if top > hi:
+            a, b, gap = hi, top, False
+            for it in range(64):
+                na, nb, g_at, i = narrow(a, b, False, lambda g: g == 0.0)
+                if it == 0:
+                    if g_at != 0.0 or i == 0:
+                        break  # no zero of g above hi, or hi itself already has one
+                    if self.ltm_optimized(np.array([nb]), states=True)[0] > nstates * (1.0 + 1e-12):
+                        break  # states in between: the zero belongs to a higher gap
+                    gap = True
+                if i == 0:
+                    b = a
+                    break
+                shrunk = nb - na < b - a
+                a, b = na, nb
+                if b - a <= tol or not shrunk:
+                    break
+            if gap:
+                hi = b
+                Nhi = float(self.ltm_optimized(np.array([hi]), states=True)[0])
+        return hi, Nhi
 
     def ltm_green(self, zs, elements=None):
         """Trace of the Green's function tr G(z) = sum_b int dk / (z - e_b(k)) at the complex energies `zs`, per unit cell and

@@ -364,7 +364,8 @@ int abz_rule_ltm_elements_ptr(const abz_rule* r, void** base, int64_t* nbytes, i
  * over the simplices T with e_1 <= E < e_{d+1}, g_T the simplex's own DOS, w = 1 / (d! npt^d); f_3 = 1/40 is eq. 22 of
  * the paper, f_2 = 1/24, f_1 = 1/12.  It removes the leading O(1/npt^2) error of a sum taken at FIXED FILLING, i.e. at
  * the Fermi level of the same grid (abz_rule_ltm_fermi: for A = 1 the correction vanishes, the level has none); at a
- * fixed energy the misplaced Fermi surface leaves an error of the same order.  Any other `what`: ABZ_ERR_ARG. */
+ * fixed energy the misplaced Fermi surface leaves an error of the same order (abz_rule_ltm_optimized below has no such limit).
+ * Any other `what`: ABZ_ERR_ARG. */
 #define ABZ_LTM_STATES_CORRECTED 2
 int abz_rule_ltm_weighted(abz_rule* r, int source, const double* E, int nE, int what, double* out);
 /* Fermi level: E_F with N(E_F) >= nstates (1 - 1e-12) and N(E) below that for every sampled E <= E_F - tol;
@@ -449,13 +450,36 @@ int abz_rule_ltm_pairs(abz_rule* src, int v0, int nv, int c0, int nc, abz_rule* 
  * range outside the bands of src, ABZ_LTM_A_ELEMENTS without elements on `pairs`, E_F not finite, src without eigenvalues.
  * ABZ_ERR_UNSUPPORTED: src a slab, a node list or a pair rule.  A refusal launches nothing and leaves both rules as they were.
  * Kernels under ABZ_K_LTM.  Entry point added without a change of ABZ_VERSION. */
-#define ABZ_LTM_A_ONE 2   /* A = 1: the joint DOS; accepted by abz_rule_ltm_pairs_occupied only */
+#define ABZ_LTM_A_ONE 2   /* A = 1: the joint DOS of abz_rule_ltm_pairs_occupied; g and N of abz_rule_ltm_optimized */
 int abz_rule_ltm_pairs_occupied(abz_rule* src, abz_rule* pairs, double E_F, int source, const double* w, int nw, int what,
                                 double* out /* [nw][ncomp], ncomp = 1 for A_ONE */);
 /* *nb: bands of the rule's eigenvalue planes, attached elements and weight blocks: nv nc of a pair rule, n of any other.
  * abz_rule_info keeps reporting the series' n (the bands of the source) for a pair rule: size the buffers of abz_rule_export's
  * eig, abz_rule_ltm_elements(_export) and the node weights by *nb, not by that n. */
 int abz_rule_ltm_bands(const abz_rule* r, int* nb);
+/* Optimized tetrahedron method (Kawamura, Gohda, Tsuneyuki, PRB 89, 094515 (2014)), d = 3: the sums of abz_rule_ltm and
+ * abz_rule_ltm_weighted without the leading O(1/npt^2) error of linear interpolation, at any energy, from the same eigenvalue
+ * planes and with no further eigen-solve.  A Kuhn simplex of cell i is the path v1 = i, v2 = v1 + e_a, v3 = v2 + e_b, v4 = v3 + e_c
+ * over a permutation (a, b, c) of the axes.  The band is taken at the 20 grid points
+ *      p1..p4   = v1..v4
+ *      p5..p16  = 2 v_i - v_j,  (i, j) = (1,2) (2,3) (3,4) (4,1) (1,3) (2,4) (3,1) (4,2) (1,4) (2,1) (3,2) (4,3)
+ *      p17..p20 = v4 - v1 + v2,  v1 - v2 + v3,  v2 - v3 + v4,  v3 - v4 + v1
+ * (indices mod npt, any npt >= 1), the cubic through the 20 values is fitted, and the 4 corner values are replaced by those of the
+ * linear function closest to it in the least-squares sense over the simplex, x'_m = sum_j P[m][j] x(p_j); P is 4 x 20 with rows
+ * summing to 1 (DESIGN section 4e has 1260 P).  For band b, x is the b-th ascending eigenvalue at each point; elements A_b take
+ * the same P at the same points.  The closed forms of abz_rule_ltm_weighted then apply to (e'; A'), weight 1 / (6 npt^3) per
+ * simplex; a simplex wholly below E counts 1, or the mean of its A'.
+ * source: ABZ_LTM_A_ONE (g, N: one component), ABZ_LTM_A_ENERGY (A = e, one component) or ABZ_LTM_A_ELEMENTS (the attached
+ * block).  what: ABZ_LTM_DOS or ABZ_LTM_STATES.  out [nE][ncomp] and the energy list as for abz_rule_ltm_weighted (any order,
+ * results in the caller's order).  N is n above all bands and exactly 0 below them; a flat band gives g = 0 and a unit step; two
+ * calls return the same bits.  The rule is a whole periodic 3-d grid; rules of abz_rule_ltm_unfold and of abz_rule_ltm_pairs are
+ * taken where abz_rule_ltm_weighted takes them.
+ * ABZ_ERR_ARG: NULL pointers, nE < 1, another `what` -- ABZ_LTM_STATES_CORRECTED too: this rule replaces the correction --,
+ * another `source`, ABZ_LTM_A_ELEMENTS with nothing attached, a rule without eigenvalues.  ABZ_ERR_UNSUPPORTED: d != 3, a slab
+ * (with or without its halo: the stencil needs three planes around it), a list of irreducible nodes.  A refusal launches nothing
+ * and leaves `out` and the rule as they were.  Not handled: d = 1, 2, slabs, Green's functions, node weights, occupied pair
+ * scans.  Kernels under ABZ_K_LTM.  Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_optimized(abz_rule* r, int source, const double* E, int nE, int what, double* out);
 /* Tetrahedron scans on a slab: attach the halo plane.  r: a rule of abz_ptr_rule_build_slab over [outer_begin, outer_end) that
  * holds eigenvalues (other `want` bits are fine).  The simplices of the cells of the slab's last plane reach into plane
  * outer_end mod npt; this builds that one plane, eigenvalues only, with the builder of the slab itself (1 / npt of the grid, no

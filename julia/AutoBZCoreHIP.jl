@@ -32,7 +32,7 @@ const WANT_HC = WANT_H | WANT_H_COMPACT
 const F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = Cint.(0:6)
 const LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = Cint(0), Cint(1), Cint(2), Cint(3)
 const LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = Cint(0), Cint(1), Cint(2)  # `what` of abz_rule_ltm / abz_rule_ltm_weighted
-const LTM_A_ELEMENTS, LTM_A_ENERGY, LTM_A_ONE = Cint(0), Cint(1), Cint(2)    # `source`; LTM_A_ONE: abz_rule_ltm_pairs_occupied only
+const LTM_A_ELEMENTS, LTM_A_ENERGY, LTM_A_ONE = Cint(0), Cint(1), Cint(2)    # `source`; LTM_A_ONE: abz_rule_ltm_pairs_occupied and abz_rule_ltm_optimized
 
 # (kind, lim_a, lim_b) of the reference's limits types for abz_iai_solve(_many); the SymmetryReduceBZ
 # extension's Polyhedron3 travels as packed faces [nv, x y z ...] with lim_b = [length(lim_a)]
@@ -475,6 +475,23 @@ function ltm_weighted(r::HIPRule, Es::Vector{Float64}; ncomp::Integer=1, energy:
     out = Matrix{Float64}(undef, energy ? 1 : ncomp, length(Es))
     check(ccall((:abz_rule_ltm_weighted, libabz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cint, Ptr{Float64}), r.h,
         energy ? 1 : 0, Es, length(Es), correction ? LTM_STATES_CORRECTED : (cumulative ? 1 : 0), out))
+    return out
+end
+
+"""
+    ltm_optimized(r, Es; ncomp=0, energy=false, cumulative=false)
+
+The sums of `ltm` / `ltm_weighted` by the optimized tetrahedron method of Kawamura, Gohda and Tsuneyuki, PRB 89, 094515
+(`abz_rule_ltm_optimized`, `d = 3`): every simplex takes the band and the elements at its 4 corners and 16 neighbouring grid
+points, and the closed forms run on the corner values of the linear function closest to the cubic through the 20 values.
+`ncomp = 0`: `g(E)` or `N(E)` (`LTM_A_ONE`); `energy`: `A = e`; `ncomp > 0`: the attached elements.  A matrix
+`[max(ncomp, 1), nE]`.  There is no correction: this rule replaces it.
+"""
+function ltm_optimized(r::HIPRule, Es::Vector{Float64}; ncomp::Integer=0, energy::Bool=false, cumulative::Bool=false)
+    source = energy ? LTM_A_ENERGY : (ncomp > 0 ? LTM_A_ELEMENTS : LTM_A_ONE)
+    out = Matrix{Float64}(undef, source == LTM_A_ELEMENTS ? ncomp : 1, length(Es))
+    check(ccall((:abz_rule_ltm_optimized, libabz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cint, Ptr{Float64}), r.h,
+        source, Es, length(Es), cumulative ? LTM_STATES : LTM_DOS, out))
     return out
 end
 
