@@ -102,6 +102,7 @@ F_ONE, F_LINEAR, F_LINEAR_X, F_DOS, F_TRGLOC, F_GLOC, F_DOS_EIG = range(7)
 LIMS_CUBIC, LIMS_TETRAHEDRAL, LIMS_POLYHEDRAL, LIMS_POLYGON = 0, 1, 2, 3
 K_CONTRACT, K_EVAL, K_REDUCE, K_GGR, K_EIG, K_GGRBUILD, K_LTM = range(7)
 K_EVAL_FUSED = 7  # launches only: the K_EVAL launches of the fused grid kernel
+K_EVAL_PASSWAVE = 8  # launches only: the K_EVAL_FUSED launches that ran one pass of a line pair per wave
 LTM_DOS, LTM_STATES, LTM_STATES_CORRECTED = 0, 1, 2
 LTM_A_ELEMENTS, LTM_A_ENERGY = 0, 1
 LTM_A_ONE = 2  # A = 1: the joint DOS of abz_rule_ltm_pairs_occupied, g and N of abz_rule_ltm_optimized

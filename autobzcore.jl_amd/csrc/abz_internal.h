@@ -82,6 +82,7 @@ enum Switch {
     SW_EVAL_FUSED,       // ABZ_EVAL_FUSED      3-D full grids, n <= 4: the grid kernel contracts variable 2 itself (0: level-1 sets in memory)
     SW_EVAL_PAIRS,       // ABZ_EVAL_PAIRS      fused grid kernel: one grid line per half-wave where that takes fewer lane-rounds (0: never, 2: wherever supported)
     SW_EVAL_MIRROR,      // ABZ_EVAL_MIRROR     3-D full grids, real Hermitian series: planes k3 <= npt/2 evaluated, H(-k) = conj H(k) stored with them, where the launch writes at most 600 MB (0: never, 2: wherever supported)
+    SW_EVAL_PASSWAVE,    // ABZ_EVAL_PASSWAVE   fused pair mapping, pairs of 2 or 4 passes: one pass of a pair per wave where the selection rule takes it (0: never, 2: wherever supported)
     SW_COUNT
 };
 int abz_switch(Switch s);  // the switch's integer value from the environment, or its default
@@ -178,7 +179,7 @@ struct abz_ctx {
     bool owns_stream = true;  // false: borrowed from the caller (abz_ctx_create_on_stream)
     unsigned prof = 0;  // bit k set: record HIP events around launches of kernel id k
     abz::ProfScope* prof_scope = nullptr;  // innermost active ProfScope: launch() binds its events
-    abz::ProfSlot prof_slots[ABZ_K_COUNT];
+    abz::ProfSlot prof_slots[ABZ_K_SLOTS];
     std::vector<hipEvent_t> event_pool;
     abz::DevBuf scratch[8];  // phases, partials, staging...
     void* pin = nullptr;     // pinned host staging buffer (hipHostMalloc), grown on demand
@@ -425,6 +426,9 @@ struct EvalSpec {
     // k3 <= npt / 2 are evaluated and every node of a plane that is not its own mirror image is stored a second time, conjugated,
     // at -k (eval_mirror_supported; the scalar fallback kernel evaluates every line as before)
     bool mirror = false;
+    // fused contraction (src2), pair mapping of a Hermitian series whose pairs take 2 or 4 passes: one pass of a pair per wave
+    // (eval_grid_kernel<..., PW>); elsewhere the flag changes nothing
+    bool passwave = false;
     // outputs (tiled planar views), base == nullptr when not wanted
     PlaneView H;
     PlaneView E;

@@ -92,6 +92,7 @@ const SwitchDef g_switches[SW_COUNT] = {
     {"ABZ_EVAL_FUSED", 1, "0: 3-D full-grid rules (n <= 4) build level-1 sets with contract_chain_kernel instead of contracting variable 2 inside the grid kernel"},
     {"ABZ_EVAL_PAIRS", 1, "fused grid kernel, one grid line per half-wave: 1 where it takes fewer lane-rounds per line (Hermitian series), 0 never, 2 wherever supported (tests: same values)"},
     {"ABZ_EVAL_MIRROR", 1, "3-D full-grid rules (n <= 4) of a real Hermitian series evaluate the planes k3 <= npt/2 and store H(-k) = conj H(k) beside them: 1 where the launch writes at most 600 MB, 0 never (every plane evaluated), 2 wherever supported"},
+    {"ABZ_EVAL_PASSWAVE", 1, "fused pair mapping of Hermitian series, pairs of 2 or 4 passes: one pass of a pair per wave instead of a pair per wave: 1 by the selection rule, 0 never, 2 wherever supported (tests: same values)"},
 };
 }  // namespace
 
@@ -411,7 +412,7 @@ ProfScope::~ProfScope() {
 }
 
 int prof_collect(abz_ctx* ctx) {
-    for (int i = 0; i < ABZ_K_COUNT; ++i) {
+    for (int i = 0; i < ABZ_K_SLOTS; ++i) {
         auto& sl = ctx->prof_slots[i];
         for (auto& pr : sl.pending) {
             ABZ_HIP(hipEventSynchronize(pr.second));
@@ -837,7 +838,7 @@ int abz_prof_reset(abz_ctx* ctx) try {
 } ABZ_CATCH_ALL
 
 int abz_prof_read(abz_ctx* ctx, int kernel_id, double* total_ms, int64_t* launches) try {
-    ABZ_REQUIRE(ctx && kernel_id >= 0 && kernel_id < ABZ_K_COUNT, "bad profile slot");
+    ABZ_REQUIRE(ctx && kernel_id >= 0 && kernel_id < ABZ_K_SLOTS, "bad profile slot");
     int rc = prof_collect(ctx);
     if (rc) return rc;
     if (total_ms) *total_ms = ctx->prof_slots[kernel_id].ms;
@@ -1221,6 +1222,16 @@ static int rule_fill(abz_rule* r) {
                                  (double)pv.row * (double)es.nlines;
         es.mirror = s->hermitian && s->real_coef && r->full && d == 3 && plan.outer_n == r->npt && !deriv && !Uout.base &&
                     !(r->want & ABZ_WANT_VEL) && (sw_mirror >= 2 || (sw_mirror == 1 && out_bytes <= 600e6));
+        // One pass of a line pair per wave in the fused pair mapping (launch_eval takes it where it runs pairs and the instance
+        // exists: Hermitian series, pairs of 2 or 4 passes).  Selection rule (DESIGN section 9 item 1,
+        // profiles/eval_passwave_trace_gaps.txt): pairs of two passes -- a pass is three rounds of 32 columns, two with 4 bands
+        // (launch_eval: kp), so 97 ... 192 points, with 4 bands 65 ... 128.  Every measured shape on which the launcher takes
+        // pairs by itself was faster than a pair per wave: SVO 129 ... 160 points 6-17 %, 4 bands real 70 ... 96 points 12-22 %,
+        // a complex Hermitian 3-band series at 150 points (not mirrored) 3.6 %.  Pairs of four passes (4 bands, 193 ... 256
+        // points) are not measured and run under ABZ_EVAL_PASSWAVE=2 only.
+        const int sw_passwave = abz_switch(SW_EVAL_PASSWAVE);
+        const int rounds = (r->npt + 31) / 32, per_pass = n < 4 ? 3 : 2;
+        es.passwave = sw_passwave >= 2 || (sw_passwave == 1 && rounds > per_pass && rounds <= 2 * per_pass);
         es.H = Hout;
         es.E = Eout;
         es.U = Uout;

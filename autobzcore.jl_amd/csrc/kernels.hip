@@ -969,13 +969,21 @@ __device__ __forceinline__ void contract_line_m(int M2, const double2* s2, const
 // MIR: the instance of a mirrored launch (EvalArgs::mirror, Hermitian series only).  A template parameter, so the instances of
 // every other launch hold none of its code: with a run-time flag alone the benchmark's instance measured 5 % slower with the
 // mirror switched off.
-template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false, bool PAIR = false, int KT = KPL, bool MIR = false>
+// PW (with PAIR, Hermitian series): one pass of one pair per wave.  The unit u = 4 seg + wave is pass u % npass of pair u / npass,
+// with npass = 2 or 4 (launch_eval), so the passes of a pair sit in one block: the two parts of a mirrored 128-B line at a pass
+// seam meet in one L2.  The wave contracts both lines of its pair as above -- each of a pair's npass waves does, the sums are the
+// same -- runs its pass, KPL rounds or the last pass's KT, stores and ends: no work loop, one LDS buffer per wave and nothing
+// contracted between the m-loop and the stores.  A template parameter as MIR is: other instances hold none of its code.
+template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false, bool PAIR = false, int KT = KPL, bool MIR = false,
+          bool PW = false>
 __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
     static_assert(!MIR || (HERM && !VEC), "mirrored launches: values and eigenvalues of a Hermitian series");
     static_assert(FUSE || !PAIR, "the pair mapping exists in the fused instance only");
     static_assert(KT >= 1 && KT <= KPL && (PAIR || KT == KPL), "a shorter last pass exists in the pair mapping only");
+    static_assert(!PW || (PAIR && HERM), "one pass per wave exists in the pair mapping of Hermitian series only");
     constexpr int LPU = PAIR ? 2 : 1;  // lines per unit of work
-    extern __shared__ double2 lds_c[];  // [4 waves][2 buffers][LPU][MNN], phase table [npt], FUSE: level-2 set [M2][MNN]
+    constexpr int NBUF = PW ? 1 : 2;   // LDS buffers per wave
+    extern __shared__ double2 lds_c[];  // [4 waves][NBUF buffers][LPU][MNN], phase table [npt], FUSE: level-2 set [M2][MNN]
     // the wave index is made an SGPR value: every per-line quantity (tile base, coefficient row) is
     // then scalar arithmetic
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -986,7 +994,7 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
         const double f = 6.283185307179586476925286766559 * (double)(a.first + idx / (N * N));
         return make_double2(-f * c.y, f * c.x);
     };
-    double2* const mybuf = lds_c + (size_t)wave * 2 * LPU * MNN;
+    double2* const mybuf = lds_c + (size_t)wave * NBUF * LPU * MNN;
     int fm = a.first % a.npt;
     if (fm < 0) fm += a.npt;
     // Every global load issued inside the work loop shares the in-order vmcnt with the stores, and a
@@ -996,7 +1004,7 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
     // come from an LDS copy of the table.  A unit of work is one pass (64 KPL nodes) of one line.
     constexpr int LW = 64 / LPU;  // lanes per line
     const int npass = (a.npt + LW * KPL - 1) / (LW * KPL);
-    double2* const tab_l = lds_c + (size_t)4 * 2 * LPU * MNN;  // LDS copy of the phase table, shared by the block
+    double2* const tab_l = lds_c + (size_t)4 * NBUF * LPU * MNN;  // LDS copy of the phase table, shared by the block
     if constexpr (FUSE) {
         static_assert(!VEC, "the fused instance stores values and eigenvalues only");
         const int k3 = blockIdx.y, seg = blockIdx.x;  // grid (bpk, outermost indices): both scalars
@@ -1009,6 +1017,12 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
         // reads row 0)
         const int kstride = 4 * a.bpk;
         int k2 = LPU * (4 * seg + wave);
+        int pw_pass = 0;  // PW: the wave's pass of its pair; npass is 2 or 4
+        if constexpr (PW) {
+            const int u = 4 * seg + wave;
+            pw_pass = u & (npass - 1);
+            k2 = 2 * (u >> (npass == 4 ? 2 : 1));
+        }
         LinePhases ph;
         load_line_phases(as_const(a.phs2 + (int64_t)(k2 < a.npt ? k2 : 0) * a.M2), ph);
         // phase table and level-2 set in one round trip: the loads are unconditional, from clamped 32-bit indices off
@@ -1037,6 +1051,28 @@ __global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
             // both lines of a pair, one after the other, lane = column as above; line k2 + 1 clamped to the last line
             load_line_phases(as_const(a.phs2 + (int64_t)min(k2 + 1, a.npt - 1) * a.M2), ph);
             contract_line_m(a.M2, s2, ph, mybuf + MNN, MNN, lane);
+            if constexpr (PW) {
+                // the wave's one unit; its seeds come from the column (two passes at least: the seeds of pass 0 are not read)
+                const int seeds[KPL] = {}, seeds_t[KT] = {};
+                const int64_t line = (int64_t)k3 * a.npt + k2;
+                MirrorTo mt;
+                if (mk3 >= 0) {
+                    mt.line = (int64_t)mk3 * a.npt;
+                    mt.t0 = k2 ? a.npt - k2 : 0;
+                    mt.t1 = k2 + 1 < a.npt ? a.npt - k2 - 1 : 0;  // (a half without a line: nothing is stored)
+                }
+                auto no_mid = []() {};
+                wave_lds_sync();
+                if (KT == KPL || pw_pass + 1 < npass)
+                    eval_unit<N, KPL, HERM, VEC, decltype(no_mid)&, PK, 32>(a, mybuf + (size_t)half * MNN, tab_l, fm, seeds, seeds, 2, pw_pass * (32 * KPL),
+                                                                            col, line, no_mid, half * (int)a.H.tile, half * (int)a.E.tile,
+                                                                            half == 0 || k2 + 1 < a.npt, mt);
+                else
+                    eval_unit<N, KT, HERM, VEC, decltype(no_mid)&, PK, 32>(a, mybuf + (size_t)half * MNN, tab_l, fm, seeds_t, seeds_t, 2, pw_pass * (32 * KPL),
+                                                                           col, line, no_mid, half * (int)a.H.tile, half * (int)a.E.tile,
+                                                                           half == 0 || k2 + 1 < a.npt, mt);
+                return;
+            }
             // seeds of pass 0, read when it is the only pass: then it is the last one, of KT rounds
             int iz0[KPL], iw0[KPL], izt[KT], iwt[KT];
 #pragma unroll
@@ -1418,7 +1454,17 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
                 const int64_t npairs = cdiv(es.npt, 2);
                 a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(npairs, 4), cdiv(blocks, gcnt)));
                 a.bpk = (int)cdiv(npairs, 4 * cdiv(npairs, 4 * a.bpk));
-                const size_t plds = flds + sizeof(double2) * 4 * 2 * (size_t)mnn;
+                size_t plds = flds + sizeof(double2) * 4 * 2 * (size_t)mnn;
+                // One pass of a pair per wave (eval_grid_kernel<..., PW>): Hermitian series whose pairs take 2 or 4 passes, so
+                // that a block holds whole pairs; one pass is the instance above as it is, three passes keep it.  The caller
+                // asks for it (EvalSpec::passwave; rule_fill holds the selection rule and ABZ_EVAL_PASSWAVE).
+                const int npass = (int)cdiv(rounds, kp);
+                const bool passwave = es.passwave && a.herm && (npass == 2 || npass == 4);
+                if (passwave) {
+                    a.bpk = (int)cdiv(npairs * npass, 4);
+                    plds = flds;  // one buffer of two line sets per wave: the room of the 64-lane mapping's two buffers
+                    if (ctx->prof & (1u << ABZ_K_EVAL_PASSWAVE)) ctx->prof_slots[ABZ_K_EVAL_PASSWAVE].launches += 1;
+                }
                 const dim3 grid((unsigned)a.bpk, grows);
 #define LKP(NN, KT)                                                                                                          \
     {                                                                                                                        \
@@ -1426,7 +1472,10 @@ int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
         constexpr int KH = NN < 4 ? 3 : 2, KG = NN < 4 ? 3 : 1; /* kp above */                                               \
         if (a.herm)                                                                                                          \
             with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                    \
-                launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, pk(), true, true, KT <= KH ? KT : KH, mir()>, grid, dim3(256), plds, a); \
+                if (passwave)                                                                                                \
+                    launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, pk(), true, true, KT <= KH ? KT : KH, mir(), true>, grid, dim3(256), plds, a); \
+                else                                                                                                         \
+                    launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, pk(), true, true, KT <= KH ? KT : KH, mir()>, grid, dim3(256), plds, a); \
             });                                                                                                              \
         else                                                                                                                 \
             launch(ctx, eval_grid_kernel<NN, KG, false, false, 2, false, true, true, KT <= KG ? KT : KG>, grid, dim3(256), plds, a); \

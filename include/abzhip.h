@@ -97,7 +97,9 @@ typedef struct abz_rule abz_rule;     /* device-resident cached rule values (Fou
 #define ABZ_K_GGRBUILD 5   /* fused GGR build: H, dH/dk, eig, velocities per node (get_ggr_data, ref src/dos_ggr.jl:14-44) */
 #define ABZ_K_LTM 6        /* linear tetrahedron scan over cached eigenvalues (abz_rule_ltm) */
 #define ABZ_K_EVAL_FUSED 7 /* launches only, no time: the ABZ_K_EVAL launches that contracted the last outer variable themselves */
-#define ABZ_K_COUNT 8
+#define ABZ_K_COUNT 8      /* the ids above: the timed kernels and the first launch counter */
+#define ABZ_K_EVAL_PASSWAVE 8 /* launches only, no time: the ABZ_K_EVAL_FUSED launches that ran one pass of a line pair per wave */
+#define ABZ_K_SLOTS 9      /* ids abz_prof_read takes: 0 ... ABZ_K_SLOTS - 1 */
 
 /* The library's own view of its memory, for leak checks and capacity planning (no reference counterpart):
  * info[0] device bytes handed out by its allocator and not yet returned (all contexts: coefficients, contracted
