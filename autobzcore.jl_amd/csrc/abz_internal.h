@@ -12,6 +12,7 @@
 
 #include "../../include/abzhip.h"
 #include "dev_buf.h"
+#include "eval_route.h"
 #include "ltm_block.h"
 #include "plane_view.h"
 
@@ -385,8 +386,8 @@ int launch_phases(abz_ctx* ctx, const PhaseSpec& ps, double2* phs);
 int launch_contract(abz_ctx* ctx, const double2* src, int64_t src_slot_elems, const int64_t* parents,
                     int64_t per_parent, const double2* phs, double2* out, int64_t B, int64_t L, int M);
 
-// full-grid contraction: out[(parent*npt + gi)][l], parents 0..nparents-1, all gi, phases from tab
-constexpr int ABZ_CONTRACT_GRID_MAXM = 16;
+// full-grid contraction: out[(parent*npt + gi)][l], parents 0..nparents-1, all gi, phases from tab; M <= ABZ_CONTRACT_GRID_MAXM
+// (eval_route.h)
 int launch_contract_grid(abz_ctx* ctx, const double2* src, int64_t src_slot_elems, int64_t nparents, const double2* tab,
                          double2* out, int64_t L, int M, int first, int npt, bool deriv, int gbeg, int gcnt,
                          const double2* phs_table = nullptr);  // phs_table [npt][M]: scalar-phase kernel (no derivative)
@@ -422,23 +423,16 @@ struct EvalSpec {
     const double2* src2 = nullptr;
     const double2* phs2 = nullptr;
     int M2 = 0;
-    // grid mode, nlines == npt * npt (a whole 3-D grid) of a real Hermitian series, no eigenvectors: the lines of the planes
-    // k3 <= npt / 2 are evaluated and every node of a plane that is not its own mirror image is stored a second time, conjugated,
-    // at -k (eval_mirror_supported; the scalar fallback kernel evaluates every line as before)
-    bool mirror = false;
-    // fused contraction (src2), pair mapping of a Hermitian series whose pairs take 2 or 4 passes: one pass of a pair per wave
-    // (eval_grid_kernel<..., PW>); elsewhere the flag changes nothing
-    bool passwave = false;
+    // grid mode, the caller's facts that the route reads (eval_route.h: EvalShape): H_R is real, the lines are a whole 3-D
+    // grid, the rule wants velocities
+    bool real_coef = false, whole_grid3 = false, velocity = false;
     // outputs (tiled planar views), base == nullptr when not wanted
     PlaneView H;
     PlaneView E;
     PlaneView U;  // eigenvector planes 2*(a + n*b) + {re, im}: component a of vector b
 };
-int launch_eval(abz_ctx* ctx, const EvalSpec& es);
-bool eval_packed_supported(int n, int M, int npt);
-bool eval_mirror_supported(const EvalSpec& es);
-// mnn: numbers per line (packed_row_elems or M n n); pairs: the LDS of the pair mapping (one grid line per half-wave)
-bool eval_fused_supported(int n, int64_t mnn, int M2, int npt, bool pairs = false);
+int launch_eval(abz_ctx* ctx, const EvalSpec& es);  // grid mode: by eval_route (eval_route.h)
+EvalSwitches eval_switches();  // the ABZ_EVAL_* switches that eval_route.h reads, from abz_switch
 // rows [nrows][M n n] of full coefficients (innermost variable fastest) -> packed rows [nrows][P] (packed_herm.h)
 int launch_pack_rows(abz_ctx* ctx, int n, int M, const double2* src, int64_t nrows, double2* out);
 size_t packed_row_elems(int n, int M);

@@ -1180,7 +1180,7 @@ static int rule_fill(abz_rule* r) {
         Dv.base = rp->tmpD.as<double>();
     }
     // full grids of a Hermitian series (n <= 4, values / eigenvalues only): the chain and the grid kernel work on packed sets
-    const bool packed_chain = r->full && s->hermitian && !(r->want & ABZ_WANT_VEL) && eval_packed_supported(n, s->dims[0], r->npt);
+    const bool packed_chain = r->full && s->hermitian && !(r->want & ABZ_WANT_VEL) && eval_packed_supported(n, s->dims[0], r->npt, eval_switches());
     // level2: the grid kernel contracts variable 2 itself from these level-2 sets (EvalSpec::src2); level1 is not read then
     auto run_eval = [&](const double2* level1, bool deriv, PlaneView Hout, PlaneView Eout, PlaneView Uout,
                         const double2* level2 = nullptr) -> int {
@@ -1210,28 +1210,10 @@ static int rule_fill(abz_rule* r) {
         es.deriv = deriv;
         es.herm = s->hermitian;
         es.packed = packed_chain && !deriv && !Uout.base;
-        // whole 3-D grids of a real Hermitian series, values / eigenvalues only (a slab's mirror planes belong to another rank).
-        // Size rule (profiles/eval_mirror_trace_gaps.txt): by the bytes the launch writes, padding
-        // included.  Every measured shape up to 597 MB was faster mirrored (3 and 4 bands, both layouts: 3-32 %), 605 MB tied
-        // (+2 %) and 665 MB and more lost 9-50 % with 3 bands -- the mirrored stores are temporal, and beyond that they no
-        // longer leave L2 as whole lines.  (4 bands still won 15 % at 814 MB and lost at 1331 MB; the limit is not tuned per
-        // band count.)  ABZ_EVAL_MIRROR=2 takes the route wherever it is supported.
-        const int sw_mirror = abz_switch(SW_EVAL_MIRROR);
-        const PlaneView& pv = Hout.base ? Hout : Eout;
-        const double out_bytes = 8.0 * ((Hout.base ? (Hout.compact ? 1.0 : 2.0) * n * n : 0.0) + (Eout.base ? (double)n : 0.0)) *
-                                 (double)pv.row * (double)es.nlines;
-        es.mirror = s->hermitian && s->real_coef && r->full && d == 3 && plan.outer_n == r->npt && !deriv && !Uout.base &&
-                    !(r->want & ABZ_WANT_VEL) && (sw_mirror >= 2 || (sw_mirror == 1 && out_bytes <= 600e6));
-        // One pass of a line pair per wave in the fused pair mapping (launch_eval takes it where it runs pairs and the instance
-        // exists: Hermitian series, pairs of 2 or 4 passes).  Selection rule (DESIGN section 9 item 1,
-        // profiles/eval_passwave_trace_gaps.txt): pairs of two passes -- a pass is three rounds of 32 columns, two with 4 bands
-        // (launch_eval: kp), so 97 ... 192 points, with 4 bands 65 ... 128.  Every measured shape on which the launcher takes
-        // pairs by itself was faster than a pair per wave: SVO 129 ... 160 points 6-17 %, 4 bands real 70 ... 96 points 12-22 %,
-        // a complex Hermitian 3-band series at 150 points (not mirrored) 3.6 %.  Pairs of four passes (4 bands, 193 ... 256
-        // points) are not measured and run under ABZ_EVAL_PASSWAVE=2 only.
-        const int sw_passwave = abz_switch(SW_EVAL_PASSWAVE);
-        const int rounds = (r->npt + 31) / 32, per_pass = n < 4 ? 3 : 2;
-        es.passwave = sw_passwave >= 2 || (sw_passwave == 1 && rounds > per_pass && rounds <= 2 * per_pass);
+        // what the route reads beyond the launch itself (eval_route.h holds the mirror and pass-per-wave rules)
+        es.real_coef = s->real_coef;
+        es.whole_grid3 = r->full && d == 3 && plan.outer_n == r->npt;
+        es.velocity = (r->want & ABZ_WANT_VEL) != 0;
         es.H = Hout;
         es.E = Eout;
         es.U = Uout;

@@ -4,12 +4,8 @@
 //   contract_grid_s_kernel  full-grid contraction of the outermost remaining variable, phases as scalars
 //   contract_grid_kernel    the same with LDS-staged phases (derivative builds); contract_kernel: node lists
 //                           = workspace_contract!  (ref src/fourier.jl:152,158,242,252,468,478)
-//   eval_grid_kernel        innermost 1-D series on a full PTR grid: one wavefront per pass of a line (i2,i3),
-//                           KPL nodes per lane, the line's coefficients in a wave-private double-buffered LDS
-//                           slot, one load group and one wait per unit of work (in-order vmcnt), fused
-//                           Hermitian eigensolve, tiled-planar stores (H first, non-temporal on large rules)
-//                           = workspace_evaluate! in fourier_ptr!  (ref src/fourier.jl:132-147)
-//   eval_node_kernel        the series at explicit nodes (symmetric rules, abz_eval_nodes)
+//   (eval_grid_kernel, eval_node_kernel: the innermost 1-D series on a full PTR grid and at explicit nodes,
+//                           kernels_eval.hip; the device code shared with the kernels below, eval_device.h)
 //   reduce_kernel           sum_k w_k f(H(k); omega_i) for all omega_i of a sweep in one pass over the cached
 //                           rule = quadsum (ref src/fourier.jl:204-207,289-292); Hermitian rules: real
 //                           characteristic polynomial / adjugate forms
@@ -19,6 +15,7 @@
 //   (generic n: kernels_generic.hip; symmetric-rule tables: kernels_symptr.hip)
 #include "abz_internal.h"
 #include "device_math.h"
+#include "eval_device.h"
 #include "gk15.h"
 #include "inner_adapt.h"
 #include "packed_herm.h"
@@ -32,14 +29,6 @@
 namespace abz {
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-struct cplx_pod {
-    double x, y;
-};
-typedef const cplx_pod __attribute__((address_space(4))) * cptr_t;
-__device__ __forceinline__ cptr_t as_const(const double2* p) {
-    return (cptr_t)(unsigned long long)p;
-}
 
 // ------------------------------------------------------------------------------------------
 // phases
@@ -415,872 +404,8 @@ int launch_contract_chain(abz_ctx* ctx, const double2* src, const double2* phs3,
 }
 
 // ------------------------------------------------------------------------------------------
-// innermost evaluation
+// stand-alone eigensolve on planes, velocities
 // ------------------------------------------------------------------------------------------
-// Constant-address-space view of read-only coefficient sets: a wave-uniform address in this address
-// space is fetched through the scalar cache (s_load_dwordx4/x8) and reaches v_fma_f64 as an SGPR
-// operand; a divergent address still becomes an ordinary global_load.  Legal because the sets are
-// written by an EARLIER kernel on the same stream and never inside the kernel that reads them.
-// (cplx_pod / cptr_t / as_const are defined at the top of this file)
-
-// H = sum_m c1[m] * (w z^m)  (optionally times i 2 pi f_m).
-template <int N>
-__device__ __forceinline__ void series_lane(cptr_t c1, int M, int first, double zr,
-                                            double zi, double wr, double wi, bool deriv, CMat<N>& H) {
-#pragma unroll
-    for (int a = 0; a < N; ++a) {
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-            H.re[a][b] = 0.0;
-            H.im[a][b] = 0.0;
-        }
-    }
-    double pr = wr, pi = wi;
-    for (int m = 0; m < M; ++m) {
-        double qr = pr, qi = pi;
-        if (deriv) {
-            const double f = 6.283185307179586476925286766559 * (double)(first + m);
-            qr = -f * pi;
-            qi = f * pr;
-        }
-        cptr_t cm = c1 + (int64_t)m * (N * N);
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-#pragma unroll
-            for (int a = 0; a < N; ++a) {
-                const double cx = cm[a + N * b].x, cy = cm[a + N * b].y;  // column-major block
-                H.re[a][b] = fma(cx, qr, H.re[a][b]);
-                H.re[a][b] = fma(-cy, qi, H.re[a][b]);
-                H.im[a][b] = fma(cx, qi, H.im[a][b]);
-                H.im[a][b] = fma(cy, qr, H.im[a][b]);
-            }
-        }
-        const double nr = pr * zr - pi * zi;
-        const double ni = pr * zi + pi * zr;
-        pr = nr;
-        pi = ni;
-    }
-}
-
-// offset of (node k, plane 0) in a tiled planar view
-__device__ __forceinline__ int64_t view_off(const PlaneView& v, int64_t k) {
-    const int64_t line = k / v.line_len;
-    return line * v.tile + (k - line * v.line_len);
-}
-
-// Plane of Re H[a][b], a <= b, in a view (Im is the next plane).  Full layout, the reference's SMatrix order:
-// 2 (a + N b).  Hermitian-compact layout (PlaneView::compact, ABZ_WANT_H_COMPACT in abzhip.h): the upper triangle column
-// by column, b^2 + 2 a; the real diagonal entry H[b][b] is the single plane b^2 + 2 b.
-template <int N>
-__device__ __forceinline__ int hplane(const PlaneView& v, int a, int b) {
-    return v.compact ? b * b + 2 * a : 2 * (a + N * b);
-}
-
-template <int N>
-__device__ __forceinline__ void store_planes(const CMat<N>& H, const PlaneView& v, int64_t off) {
-    double* __restrict__ out = v.base + off;
-    if (v.compact) {
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-#pragma unroll
-            for (int a = 0; a <= b; ++a) {
-                out[(int64_t)(b * b + 2 * a) * v.pitch] = H.re[a][b];
-                if (a < b) out[(int64_t)(b * b + 2 * a + 1) * v.pitch] = H.im[a][b];
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int b = 0; b < N; ++b) {
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            out[(int64_t)(2 * (a + N * b)) * v.pitch] = H.re[a][b];
-            out[(int64_t)(2 * (a + N * b) + 1) * v.pitch] = H.im[a][b];
-        }
-    }
-}
-
-// Hermitian values: the upper triangle's planes only (n^2 loads instead of 2 n^2), the rest mirrored in registers
-template <int N>
-__device__ __forceinline__ void load_planes_herm(CMat<N>& H, const PlaneView& v, int64_t off) {
-    const double* __restrict__ in = v.base + off;
-#pragma unroll
-    for (int b = 0; b < N; ++b) {
-#pragma unroll
-        for (int a = 0; a <= b; ++a) {
-            const int pl = hplane<N>(v, a, b);
-            H.re[a][b] = in[(int64_t)pl * v.pitch];
-            H.im[a][b] = (a == b) ? 0.0 : in[(int64_t)(pl + 1) * v.pitch];
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < N; ++b) {
-#pragma unroll
-        for (int a = b + 1; a < N; ++a) {
-            H.re[a][b] = H.re[b][a];
-            H.im[a][b] = -H.im[b][a];
-        }
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void load_planes(CMat<N>& H, const PlaneView& v, int64_t off) {
-    if (v.compact) {  // only the upper triangle exists
-        load_planes_herm<N>(H, v, off);
-        return;
-    }
-    const double* __restrict__ in = v.base + off;
-#pragma unroll
-    for (int b = 0; b < N; ++b) {
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            H.re[a][b] = in[(int64_t)(2 * (a + N * b)) * v.pitch];
-            H.im[a][b] = in[(int64_t)(2 * (a + N * b) + 1) * v.pitch];
-        }
-    }
-}
-
-struct EvalArgs {
-    const double2* src;
-    const double2* tab;
-    const int64_t* parents;
-    const int32_t* gi;
-    const double* x;
-    PlaneView H, E, U;
-    int64_t nlines, nk;
-    int64_t line0;  // store-free sums on a slab: global index of line 0 (for node coordinates)
-    int M, first, npt, deriv, herm;
-    int nt;  // non-temporal stores (rule values larger than the Infinity Cache)
-    int pk;    // the level-1 sets are PACKED Hermitian sets (packed_herm.h): Pk<N>::size((M - 1) / 2) numbers per line
-    double inv_period;
-    // fused last contraction (eval_grid_kernel<..., FUSE>): level-2 sets [nlines / npt][M2][numbers per line], the
-    // phase table [npt][M2] of variable 2, blocks per outermost index
-    const double2* src2 = nullptr;
-    const double2* phs2 = nullptr;
-    int M2 = 0, bpk = 0;
-    // nlines == npt^2, real Hermitian series: the lines of planes k3 <= npt / 2 are evaluated, the rest stored as their mirror
-    // images (eval_unit_store)
-    int mirror = 0;
-};
-
-// planes of one node at column i1 of tile `line`; with a wave-uniform line every plane row is a scalar
-// base and the lane offset i1 is the same 32-bit register for all of them.  NT: non-temporal stores
-// (streaming: the values are not re-read by this kernel and a large rule does not fit the caches anyway).
-template <bool NT>
-__device__ __forceinline__ void store_f64(double* p, double v) {
-    if constexpr (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-// CONJ: the conjugate is stored (the imaginary planes with their sign flipped; the diagonal's stay as they are, +0.0 in
-// Hermitian instances either way)
-template <int N, bool NT = false, bool HC = false, bool CONJ = false>
-__device__ __forceinline__ void store_planes_at(const CMat<N>& H, const PlaneView& v, int64_t line, int i1) {
-    double* __restrict__ row = v.base + line * v.tile;
-    const unsigned u = (unsigned)i1;
-    if constexpr (HC) {  // Hermitian-compact planes: the upper triangle
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-#pragma unroll
-            for (int a = 0; a <= b; ++a) {
-                store_f64<NT>((row + (int64_t)(b * b + 2 * a) * v.pitch) + u, H.re[a][b]);
-                if (a < b) store_f64<NT>((row + (int64_t)(b * b + 2 * a + 1) * v.pitch) + u, CONJ ? -H.im[a][b] : H.im[a][b]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-#pragma unroll
-            for (int a = 0; a < N; ++a) {
-                store_f64<NT>((row + (int64_t)(2 * (a + N * b)) * v.pitch) + u, H.re[a][b]);
-                store_f64<NT>((row + (int64_t)(2 * (a + N * b) + 1) * v.pitch) + u, (CONJ && a != b) ? -H.im[a][b] : H.im[a][b]);
-            }
-        }
-    }
-}
-
-template <int N, bool VEC = true>
-__device__ __forceinline__ void eval_epilogue(const EvalArgs& a, CMat<N>& H, int64_t line, int i1) {
-    if (a.H.base) {
-        if (a.H.compact)
-            store_planes_at<N, false, true>(H, a.H, line, i1);
-        else
-            store_planes_at<N>(H, a.H, line, i1);
-    }
-    if (a.E.base || (VEC && a.U.base)) {
-        double e[N];
-        CMat<N> V;
-        if (VEC && a.U.base) {
-            herm_eig<N, true>(H, e, V);
-            store_planes_at<N>(V, a.U, line, i1);
-        } else {
-            herm_eig_values<N>(H, e);
-        }
-        if (a.E.base) {
-            double* __restrict__ row = a.E.base + line * a.E.tile;
-            const unsigned u = (unsigned)i1;
-#pragma unroll
-            for (int b = 0; b < N; ++b) (row + (int64_t)b * a.E.pitch)[u] = e[b];
-        }
-    }
-}
-
-// One wavefront per line (i2,i3); each lane owns KPL nodes i1 = i0 + lane + 64 j of that line.
-// The line's coefficients c1[M][N*N] are staged in a wave-private LDS buffer (double-buffered: the
-// next line's set is fetched into registers while the current one is consumed), read back with
-// broadcast ds_read_b128 and reused for the KPL nodes of every lane; phases w z^m by recurrence.
-// No block-level barrier: a wave only ever reads the LDS bytes it wrote itself.
-constexpr int EVAL_MAX_MNN = 256;  // complex coefficients per line held in LDS (M * N * N)
-
-// Phase recurrence of the grid kernels, p <- p z.  The roundings are spelled out: written as p.x z.x - p.y z.y and
-// p.x z.y + p.y z.x, the compiler chose which product to fuse per instance (one column per lane: fma(p.y, z.x, p.x z.y);
-// three: fma(p.x, z.y, p.y z.x)), so two work mappings of one grid agreed only by chance.  This is the form of the
-// three-column instances (the 150^3 grid), now the same in every instance.
-__device__ __forceinline__ void phase_step(double& pr, double& pi, double zr, double zi) {
-    const double nr = fma(pr, zr, -(pi * zi));
-    const double ni = fma(pr, zi, pi * zr);
-    pr = nr;
-    pi = ni;
-}
-
-// One unit of work of the grid kernels: pass `pass` (64 KPL nodes starting at i0) of line `line`, from the
-// line's coefficients c1 (LDS).  `mid` runs between the m-loop and the stores: the place where the next
-// unit's coefficients are handed to the other LDS buffer.
-// LW = 32 (pair mapping of the fused instance): a unit is a pass of TWO lines, one per half-wave; `lane` is then the
-// lane's index within its half, c1 its half's set, and a lane owns the columns i0 + lane + 32 j.  Per node the
-// arithmetic is the same either way.
-template <int N, int KPL, bool HERM, class MID, bool PK = false, int LW = 64>
-__device__ __forceinline__ void eval_unit_core(const EvalArgs& a, const double2* __restrict__ c1, const double2* tab_l, int fm,
-                                               const int (&iz0)[KPL], const int (&iw0)[KPL], int npass, int i0, int lane,
-                                               MID&& mid, CMat<N> (&H)[KPL]) {
-    if constexpr (PK) {
-        // packed Hermitian set (packed_herm.h): +f and -f in one FMA group, phases z^f from z alone -- half the Fourier
-        // work of the loop over 2 F + 1 terms below
-        static_assert(HERM, "packed sets exist for Hermitian series only");
-        const int F = (a.M - 1) / 2;
-        double zr[KPL], zi[KPL], pr[KPL], pi[KPL];
-#pragma unroll
-        for (int j = 0; j < KPL; ++j) {
-            int ic = iz0[j];
-            if (npass > 1) {
-                const int i1 = i0 + lane + LW * j;
-                ic = i1 < a.npt ? i1 : 0;
-            }
-            const double2 z = tab_l[ic];
-            zr[j] = z.x;
-            zi[j] = z.y;
-            pr[j] = 1.0;
-            pi[j] = 0.0;
-        }
-#pragma unroll
-        for (int bb = 0; bb < N; ++bb) {
-#pragma unroll
-            for (int aa = 0; aa <= bb; ++aa) {
-                const double2 c = c1[Pk<N>::tri(aa, bb)];
-#pragma unroll
-                for (int j = 0; j < KPL; ++j) {
-                    H[j].re[aa][bb] = c.x;
-                    H[j].im[aa][bb] = (aa == bb) ? 0.0 : c.y;
-                }
-            }
-        }
-        for (int f = 1; f <= F; ++f) {
-#pragma unroll
-            for (int j = 0; j < KPL; ++j) {
-                phase_step(pr[j], pi[j], zr[j], zi[j]);
-            }
-            const double2* __restrict__ cf = c1 + Pk<N>::blk(1) + (f - 1) * (N * N);
-#pragma unroll
-            for (int aa = 0; aa < N; ++aa) {
-                const double2 dd = cf[aa];
-#pragma unroll
-                for (int j = 0; j < KPL; ++j) {
-                    H[j].re[aa][aa] = fma(dd.x, pr[j], H[j].re[aa][aa]);
-                    H[j].re[aa][aa] = fma(-dd.y, pi[j], H[j].re[aa][aa]);
-                }
-            }
-#pragma unroll
-            for (int bb = 1; bb < N; ++bb) {
-#pragma unroll
-                for (int aa = 0; aa < bb; ++aa) {
-                    const double2 sv = cf[N + 2 * Pk<N>::pair(aa, bb)];
-                    const double2 tv = cf[N + 2 * Pk<N>::pair(aa, bb) + 1];
-#pragma unroll
-                    for (int j = 0; j < KPL; ++j) {
-                        H[j].re[aa][bb] = fma(sv.x, pr[j], H[j].re[aa][bb]);
-                        H[j].re[aa][bb] = fma(-sv.y, pi[j], H[j].re[aa][bb]);
-                        H[j].im[aa][bb] = fma(tv.x, pi[j], H[j].im[aa][bb]);
-                        H[j].im[aa][bb] = fma(tv.y, pr[j], H[j].im[aa][bb]);
-                    }
-                }
-            }
-        }
-        mid();
-#pragma unroll
-        for (int j = 0; j < KPL; ++j) {
-#pragma unroll
-            for (int bb = 0; bb < N; ++bb) {
-#pragma unroll
-                for (int aa = bb + 1; aa < N; ++aa) {
-                    H[j].re[aa][bb] = H[j].re[bb][aa];
-                    H[j].im[aa][bb] = -H[j].im[bb][aa];
-                }
-            }
-        }
-        return;
-    }
-    double zr[KPL], zi[KPL], pr[KPL], pi[KPL];
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-        int ic = iz0[j], iw = iw0[j];
-        if (npass > 1) {
-            const int i1 = i0 + lane + LW * j;
-            ic = i1 < a.npt ? i1 : 0;
-            iw = (int)(((unsigned)fm * (unsigned)ic) % (unsigned)a.npt);
-        }
-        const double2 z = tab_l[ic];
-        const double2 w = tab_l[iw];
-        zr[j] = z.x;
-        zi[j] = z.y;
-        pr[j] = w.x;
-        pi[j] = w.y;
-#pragma unroll
-        for (int aa = 0; aa < N; ++aa) {
-#pragma unroll
-            for (int bb = 0; bb < N; ++bb) {
-                H[j].re[aa][bb] = 0.0;
-                H[j].im[aa][bb] = 0.0;
-            }
-        }
-    }
-    for (int m = 0; m < a.M; ++m) {
-        const double2* __restrict__ cm = c1 + m * (N * N);
-#pragma unroll
-        for (int bb = 0; bb < N; ++bb) {
-#pragma unroll
-            for (int aa = 0; aa < N; ++aa) {
-                if (HERM && aa > bb) continue;  // upper triangle only; mirrored below
-                const double2 c = cm[aa + N * bb];
-#pragma unroll
-                for (int j = 0; j < KPL; ++j) {
-                    H[j].re[aa][bb] = fma(c.x, pr[j], H[j].re[aa][bb]);
-                    H[j].re[aa][bb] = fma(-c.y, pi[j], H[j].re[aa][bb]);
-                    if (!(HERM && aa == bb)) {
-                        H[j].im[aa][bb] = fma(c.x, pi[j], H[j].im[aa][bb]);
-                        H[j].im[aa][bb] = fma(c.y, pr[j], H[j].im[aa][bb]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KPL; ++j) phase_step(pr[j], pi[j], zr[j], zi[j]);
-    }
-    mid();
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-        if constexpr (HERM) {
-#pragma unroll
-            for (int bb = 0; bb < N; ++bb) {
-#pragma unroll
-                for (int aa = bb + 1; aa < N; ++aa) {
-                    H[j].re[aa][bb] = H[j].re[bb][aa];
-                    H[j].im[aa][bb] = -H[j].im[bb][aa];
-                }
-            }
-        }
-    }
-}
-
-// Where a unit's values go a second time when the rule is built from the planes k3 <= npt / 2 alone (EvalArgs::mirror): the
-// row of -k.  `line` is a line of the mirrored plane and t0 / t1 the offset from it in tiles for the lanes of the first and
-// of the second half-wave (the pair mapping: line = first line of the mirrored plane, t0 / t1 = the mirrored k2 of the half's
-// line; the two are not neighbours at k2 = 0).  All three are scalars.
-// line < 0: nothing is mirrored (the unit's plane is its own mirror image, or the launch evaluates every plane).
-struct MirrorTo {
-    int64_t line = -1;
-    int t0 = 0, t1 = 0;
-};
-
-// The store epilogue of a unit: values of its 64 KPL nodes into the tiled-planar rule arrays.
-// Pair mapping (LW = 32): `line` is the pair's first line and the second half-wave adds one tile to its lane offset
-// (off_h, off_e: 0 or the tile of the H and of the eigenvalue planes), so every plane row keeps its scalar base; a
-// half without a line of its own (odd npt) has `on` false and stores nothing.
-// Mirror (mt.line >= 0): H(-k) = conj H(k) of a real Hermitian series, from the same registers -- column i1 of the row goes
-// to column (npt - i1) % npt of the mirrored row, padding columns to themselves, with the sign of the off-diagonal imaginary
-// planes flipped and the same eigenvalues.  Every column of the mirrored tile is written exactly once, like the unit's own.
-// A half-wave's mirrored run is contiguous but descends with the lane and starts off a 128-B line ((npt - 32 j - 31) 8 B:
-// 56 B off at 150 points), so it leaves lines partial until the next round or, across a pass seam, the next pass fills them.
-// These stores are therefore always temporal, so that L2 merges the parts before the line goes out: with the unit's own
-// non-temporal policy the 150^3 launch took 141 us instead of 62 (every line written to memory twice, in parts).
-template <int N, int KPL, bool VEC, int LW = 64>
-__device__ __forceinline__ void eval_unit_store(const EvalArgs& a, CMat<N> (&H)[KPL], int i0, int lane, int64_t line, int off_h = 0,
-                                                int off_e = 0, bool on = true, const MirrorTo mt = MirrorTo()) {
-    if constexpr (VEC) {
-        static_assert(LW == 64, "the pair mapping stores values and eigenvalues only");
-#pragma unroll
-        for (int j = 0; j < KPL; ++j) {
-            const int i1 = i0 + lane + 64 * j;
-            const int pitch = a.H.base ? a.H.row : a.E.row;
-            if (i1 < pitch) eval_epilogue<N, VEC>(a, H[j], line, i1);
-        }
-    }
-    if constexpr (!VEC) {
-        // columns npt..pitch-1 are padding: written (finite filler) so every 128-B line of the
-        // tile leaves the CU whole; never read back (leaving them unwritten measured 17 % slower: partial lines).
-        // Order: ALL H(k) stores of the unit first, then the eigensolves (they overlap the drain of those
-        // stores), then the eigenvalue stores.  With non-temporal stores on rules larger than the Infinity
-        // Cache this is worth 19 % at 150^3 (neither change alone is: the interleaved order leaves the
-        // store queue empty during every eigensolve, and temporal stores make the 605 MB fight for L2/MALL).
-        const int pitch = a.H.base ? a.H.row : a.E.row;
-        const bool mir = mt.line >= 0;  // wave-uniform
-        // the lane's offset in the mirrored row for its column j, formed where it is used from a thread index the compiler
-        // cannot see through: hoisted out of the work loop (one register per column and pass) these offsets were spilled to
-        // scratch at three waves per SIMD (the benchmark's instance, <3, 3, true, false, 3, true, true, true, 2>: 168 VGPRs and
-        // 12 B of scratch per lane, reloaded in the work loop; formed here: 168 VGPRs, no scratch, three waves per SIMD).
-        // This relies on what every caller passes: lane == threadIdx.x & (LW - 1), and with LW == 32 bit 5 of threadIdx.x
-        // is the lane's half (eval_grid_kernel: lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5).
-        auto moffset = [&](int j, int64_t tile) {
-            int tx = threadIdx.x;
-            asm volatile("" : "+v"(tx));
-            const int i1 = i0 + (tx & (LW - 1)) + LW * j;
-            const int mc = (i1 == 0 || i1 >= a.npt) ? i1 : a.npt - i1;
-            return mc + (LW == 32 && (tx & 32) ? mt.t1 : mt.t0) * (int)tile;
-        };
-        auto epilogue = [&](auto nt, auto hc) {
-            constexpr bool NT = decltype(nt)::value;
-            constexpr bool HC = decltype(hc)::value;
-            if (a.H.base) {
-#pragma unroll
-                for (int j = 0; j < KPL; ++j) {
-                    const int i1 = i0 + lane + LW * j;
-                    if (i1 < pitch && on) store_planes_at<N, NT, HC>(H[j], a.H, line, i1 + off_h);
-                }
-                if (mir) {
-#pragma unroll
-                    for (int j = 0; j < KPL; ++j) {
-                        const int i1 = i0 + lane + LW * j;
-                        if (i1 < pitch && on) store_planes_at<N, false, HC, true>(H[j], a.H, mt.line, moffset(j, a.H.tile));
-                    }
-                }
-            }
-            if (a.E.base) {
-#pragma unroll
-                for (int j = 0; j < KPL; ++j) {
-                    const int i1 = i0 + lane + LW * j;
-                    if (i1 < pitch && on) {
-                        double e[N];
-                        herm_eig_values<N>(H[j], e);
-                        double* __restrict__ row = a.E.base + line * a.E.tile;
-                        const unsigned u = (unsigned)(i1 + off_e);
-#pragma unroll
-                        for (int b = 0; b < N; ++b) store_f64<NT>((row + (int64_t)b * a.E.pitch) + u, e[b]);
-                        if (mir) {
-                            double* __restrict__ mrow = a.E.base + mt.line * a.E.tile;
-                            const unsigned mu = (unsigned)moffset(j, a.E.tile);
-#pragma unroll
-                            for (int b = 0; b < N; ++b) store_f64<false>((mrow + (int64_t)b * a.E.pitch) + mu, e[b]);
-                        }
-                    }
-                }
-            }
-        };
-        if (a.H.compact) {
-            if (a.nt)
-                epilogue(std::true_type{}, std::true_type{});
-            else
-                epilogue(std::false_type{}, std::true_type{});
-        } else if (a.nt)
-            epilogue(std::true_type{}, std::false_type{});
-        else
-            epilogue(std::false_type{}, std::false_type{});
-    }
-}
-
-template <int N, int KPL, bool HERM, bool VEC, class MID, bool PK = false, int LW = 64>
-__device__ __forceinline__ void eval_unit(const EvalArgs& a, const double2* __restrict__ c1, const double2* tab_l, int fm,
-                                          const int (&iz0)[KPL], const int (&iw0)[KPL], int npass, int i0, int lane,
-                                          int64_t line, MID&& mid, int off_h = 0, int off_e = 0, bool on = true,
-                                          const MirrorTo mt = MirrorTo()) {
-    CMat<N> H[KPL];
-    eval_unit_core<N, KPL, HERM, MID&, PK, LW>(a, c1, tab_l, fm, iz0, iw0, npass, i0, lane, mid, H);
-    eval_unit_store<N, KPL, VEC, LW>(a, H, i0, lane, line, off_h, off_e, on, mt);
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Fused last contraction (eval_grid_kernel<..., FUSE>): one line's level-1 set from the level-2 set s2[M2][MNN] of its
-// outermost index (LDS) and the phases of its k2 (wave-uniform address: scalar loads), lane = column, with the very fma
-// sequence of contract_grid_s_kernel / contract_chain_kernel for m ascending -- the sums are theirs bit for bit.
-// The phases are fetched as a fixed group of ABZ_CONTRACT_GRID_MAXM, whatever M2 is (straight-line scalar loads that can
-// be issued ahead of the block's barrier): the table is readable that far past the start of any row (EvalSpec::phs2).
-struct LinePhases {
-    double x[ABZ_CONTRACT_GRID_MAXM], y[ABZ_CONTRACT_GRID_MAXM];
-};
-__device__ __forceinline__ void load_line_phases(cptr_t p, LinePhases& ph) {
-#pragma unroll
-    for (int m = 0; m < ABZ_CONTRACT_GRID_MAXM; ++m) {
-        ph.x[m] = p[m].x;
-        ph.y[m] = p[m].y;
-    }
-}
-
-template <int M2>
-__device__ __forceinline__ void contract_line(const double2* s2, const LinePhases& ph, double2* dst, int MNN, int lane) {
-    for (int l = lane; l < MNN; l += 64) {
-        double ar = 0.0, ai = 0.0;
-#pragma unroll
-        for (int m = 0; m < M2; ++m) {
-            const double2 c = s2[m * MNN + l];
-            ar = fma(c.x, ph.x[m], ar);
-            ar = fma(-c.y, ph.y[m], ar);
-            ai = fma(c.x, ph.y[m], ai);
-            ai = fma(c.y, ph.x[m], ai);
-        }
-        dst[l] = make_double2(ar, ai);
-    }
-}
-
-__device__ __forceinline__ void contract_line_m(int M2, const double2* s2, const LinePhases& ph, double2* dst, int MNN, int lane) {
-#define CL(MM) case MM: contract_line<MM>(s2, ph, dst, MNN, lane); break;
-    switch (M2) {  // exact coefficient count: straight-line code
-        CL(1) CL(2) CL(3) CL(4) CL(5) CL(6) CL(7) CL(8) CL(9) CL(10) CL(11) CL(12) CL(13) CL(14) CL(15) CL(16)
-        default: break;  // launch_eval admits 1 ... ABZ_CONTRACT_GRID_MAXM only
-    }
-#undef CL
-}
-
-// FUSE: the level-1 sets never exist in memory.  A block owns one outermost index k3 and the lines k2 = 4 seg + wave,
-// stepping by 4 bpk, of that index; it stages the level-2 set of k3 next to the phase table (one round trip) and
-// every wave contracts its next line into its other LDS buffer where the plain kernel hands over prefetched
-// registers: the work loop holds no vector load at all.
-// PAIR (with FUSE): one grid line per half-wave.  A wave's unit is the pair of lines (k2, k2 + 1), k2 = 2 (4 seg + wave)
-// stepping by 8 bpk: lanes 0-31 own line k2, lanes 32-63 line k2 + 1, a lane the columns (lane & 31) + 32 j.  Five
-// rounds cover a 160-double row exactly where the 64-lane mapping issues 3 x 64 = 192 slots per line.  The rounds of
-// a pair, ceil(npt / 32), are run as passes of KPL with a last pass of KT <= KPL (150 points: 3 + 2; five rounds in one
-// pass spill at three waves per SIMD), so no round is idle.  Both lines'
-// level-1 sets lie side by side in the wave's LDS room, [buffer][half][MNN]; k3, the pair and the pass stay scalars,
-// only the half is per lane (the set's address and one tile added to the store offset).  The last pair of an odd npt
-// has one line: its second half evaluates line npt - 1 again and stores nothing.
-// MIR: the instance of a mirrored launch (EvalArgs::mirror, Hermitian series only).  A template parameter, so the instances of
-// every other launch hold none of its code: with a run-time flag alone the benchmark's instance measured 5 % slower with the
-// mirror switched off.
-// PW (with PAIR, Hermitian series): one pass of one pair per wave.  The unit u = 4 seg + wave is pass u % npass of pair u / npass,
-// with npass = 2 or 4 (launch_eval), so the passes of a pair sit in one block: the two parts of a mirrored 128-B line at a pass
-// seam meet in one L2.  The wave contracts both lines of its pair as above -- each of a pair's npass waves does, the sums are the
-// same -- runs its pass, KPL rounds or the last pass's KT, stores and ends: no work loop, one LDS buffer per wave and nothing
-// contracted between the m-loop and the stores.  A template parameter as MIR is: other instances hold none of its code.
-template <int N, int KPL, bool HERM, bool VEC, int OCC, bool PK = false, bool FUSE = false, bool PAIR = false, int KT = KPL, bool MIR = false,
-          bool PW = false>
-__global__ __launch_bounds__(256, OCC) void eval_grid_kernel(EvalArgs a) {
-    static_assert(!MIR || (HERM && !VEC), "mirrored launches: values and eigenvalues of a Hermitian series");
-    static_assert(FUSE || !PAIR, "the pair mapping exists in the fused instance only");
-    static_assert(KT >= 1 && KT <= KPL && (PAIR || KT == KPL), "a shorter last pass exists in the pair mapping only");
-    static_assert(!PW || (PAIR && HERM), "one pass per wave exists in the pair mapping of Hermitian series only");
-    constexpr int LPU = PAIR ? 2 : 1;  // lines per unit of work
-    constexpr int NBUF = PW ? 1 : 2;   // LDS buffers per wave
-    extern __shared__ double2 lds_c[];  // [4 waves][NBUF buffers][LPU][MNN], phase table [npt], FUSE: level-2 set [M2][MNN]
-    // the wave index is made an SGPR value: every per-line quantity (tile base, coefficient row) is
-    // then scalar arithmetic
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int MNN = PK ? Pk<N>::size((a.M - 1) / 2) : a.M * N * N;  // numbers per line
-    // derivative series: coefficient m is scaled by 2 pi i (first + m) once, on its way into LDS
-    auto stage = [&](double2 c, int idx) -> double2 {
-        if (!a.deriv) return c;
-        const double f = 6.283185307179586476925286766559 * (double)(a.first + idx / (N * N));
-        return make_double2(-f * c.y, f * c.x);
-    };
-    double2* const mybuf = lds_c + (size_t)wave * NBUF * LPU * MNN;
-    int fm = a.first % a.npt;
-    if (fm < 0) fm += a.npt;
-    // Every global load issued inside the work loop shares the in-order vmcnt with the stores, and a
-    // wait on any of them is a wait on every older store of the wave.  So the loop body is straight
-    // line code with exactly one group of loads (the next unit's coefficients) and one wait, placed
-    // right after the m-loop when the previous unit's stores are a whole m-loop old; phase seeds
-    // come from an LDS copy of the table.  A unit of work is one pass (64 KPL nodes) of one line.
-    constexpr int LW = 64 / LPU;  // lanes per line
-    const int npass = (a.npt + LW * KPL - 1) / (LW * KPL);
-    double2* const tab_l = lds_c + (size_t)4 * NBUF * LPU * MNN;  // LDS copy of the phase table, shared by the block
-    if constexpr (FUSE) {
-        static_assert(!VEC, "the fused instance stores values and eigenvalues only");
-        const int k3 = blockIdx.y, seg = blockIdx.x;  // grid (bpk, outermost indices): both scalars
-        // mirror: the grid's rows are the planes k3 <= npt / 2; the plane of -k3, or -1 where k3 is its own (0 and npt / 2)
-        const int mk3 = (MIR && k3 != 0 && 2 * k3 != a.npt) ? a.npt - k3 : -1;
-        const int L2 = a.M2 * MNN;
-        const double2* __restrict__ src2 = a.src2 + (int64_t)k3 * L2;
-        double2* const s2 = tab_l + a.npt;
-        // the phases of the wave's first line: in flight across the copy and the barrier (a wave beyond the last line
-        // reads row 0)
-        const int kstride = 4 * a.bpk;
-        int k2 = LPU * (4 * seg + wave);
-        int pw_pass = 0;  // PW: the wave's pass of its pair; npass is 2 or 4
-        if constexpr (PW) {
-            const int u = 4 * seg + wave;
-            pw_pass = u & (npass - 1);
-            k2 = 2 * (u >> (npass == 4 ? 2 : 1));
-        }
-        LinePhases ph;
-        load_line_phases(as_const(a.phs2 + (int64_t)(k2 < a.npt ? k2 : 0) * a.M2), ph);
-        // phase table and level-2 set in one round trip: the loads are unconditional, from clamped 32-bit indices off
-        // scalar bases, and the asm keeps the stores' bounds checks from being hoisted above them
-        {
-            const int it = threadIdx.x;
-            double2 vt = a.tab[min(it, a.npt - 1)];
-            double2 v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = src2[min(it + 256 * j, L2 - 1)];
-            asm volatile("" : "+v"(vt.x), "+v"(vt.y));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(v[j].x), "+v"(v[j].y));
-            if (it < a.npt) tab_l[it] = vt;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (it + 256 * j < L2) s2[it + 256 * j] = v[j];
-            for (int i = it + 256; i < a.npt; i += 256) tab_l[i] = a.tab[i];       // (more than 256 points)
-            for (int i = it + 4 * 256; i < L2; i += 256) s2[i] = src2[i];          // (more than 1024 numbers)
-        }
-        __syncthreads();
-        if (k2 >= a.npt) return;
-        contract_line_m(a.M2, s2, ph, mybuf, MNN, lane);
-        if constexpr (PAIR) {
-            const int half = lane >> 5, col = lane & 31;
-            // both lines of a pair, one after the other, lane = column as above; line k2 + 1 clamped to the last line
-            load_line_phases(as_const(a.phs2 + (int64_t)min(k2 + 1, a.npt - 1) * a.M2), ph);
-            contract_line_m(a.M2, s2, ph, mybuf + MNN, MNN, lane);
-            if constexpr (PW) {
-                // the wave's one unit; its seeds come from the column (two passes at least: the seeds of pass 0 are not read)
-                const int seeds[KPL] = {}, seeds_t[KT] = {};
-                const int64_t line = (int64_t)k3 * a.npt + k2;
-                MirrorTo mt;
-                if (mk3 >= 0) {
-                    mt.line = (int64_t)mk3 * a.npt;
-                    mt.t0 = k2 ? a.npt - k2 : 0;
-                    mt.t1 = k2 + 1 < a.npt ? a.npt - k2 - 1 : 0;  // (a half without a line: nothing is stored)
-                }
-                auto no_mid = []() {};
-                wave_lds_sync();
-                if (KT == KPL || pw_pass + 1 < npass)
-                    eval_unit<N, KPL, HERM, VEC, decltype(no_mid)&, PK, 32>(a, mybuf + (size_t)half * MNN, tab_l, fm, seeds, seeds, 2, pw_pass * (32 * KPL),
-                                                                            col, line, no_mid, half * (int)a.H.tile, half * (int)a.E.tile,
-                                                                            half == 0 || k2 + 1 < a.npt, mt);
-                else
-                    eval_unit<N, KT, HERM, VEC, decltype(no_mid)&, PK, 32>(a, mybuf + (size_t)half * MNN, tab_l, fm, seeds_t, seeds_t, 2, pw_pass * (32 * KPL),
-                                                                           col, line, no_mid, half * (int)a.H.tile, half * (int)a.E.tile,
-                                                                           half == 0 || k2 + 1 < a.npt, mt);
-                return;
-            }
-            // seeds of pass 0, read when it is the only pass: then it is the last one, of KT rounds
-            int iz0[KPL], iw0[KPL], izt[KT], iwt[KT];
-#pragma unroll
-            for (int j = 0; j < KPL; ++j) {
-                const int i1 = col + 32 * j;
-                iz0[j] = i1 < a.npt ? i1 : 0;
-                iw0[j] = (int)(((unsigned)fm * (unsigned)iz0[j]) % (unsigned)a.npt);
-                if (j < KT) {
-                    izt[j] = iz0[j];
-                    iwt[j] = iw0[j];
-                }
-            }
-            const int off_h = half * (int)a.H.tile, off_e = half * (int)a.E.tile;  // launch_eval: the tiles fit 31 bits
-            int cur = 0, pass = 0;
-            while (k2 < a.npt) {
-                // the next unit is the same pair again (its sets stay where they are) or the wave's next pair
-                const bool last_pass = pass + 1 >= npass;
-                const int nk2 = last_pass ? k2 + 2 * kstride : k2;
-                const bool contract_next = last_pass && nk2 < a.npt;
-                wave_lds_sync();
-                // (kept inline, so the phases stay in registers)
-                auto mid_fn = [&]() __attribute__((always_inline)) {
-                    if (contract_next) {
-                        // the LDS addresses of the contraction are formed here, from a lane index the compiler cannot see
-                        // through: hoisted out of the work loop they were spilled to scratch at three waves per SIMD
-                        int ln = lane;
-                        asm volatile("" : "+v"(ln));
-                        double2* const dst = mybuf + (size_t)(cur ^ 1) * 2 * MNN;
-                        load_line_phases(as_const(a.phs2 + (int64_t)nk2 * a.M2), ph);
-                        contract_line_m(a.M2, s2, ph, dst, MNN, ln);
-                        load_line_phases(as_const(a.phs2 + (int64_t)min(nk2 + 1, a.npt - 1) * a.M2), ph);
-                        contract_line_m(a.M2, s2, ph, dst + MNN, MNN, ln);
-                    }
-                };
-                const double2* const c1 = mybuf + (size_t)(2 * cur + half) * MNN;
-                const int64_t line = (int64_t)k3 * a.npt + k2;
-                const bool on = half == 0 || k2 + 1 < a.npt;
-                MirrorTo mt;
-                if (mk3 >= 0) {
-                    mt.line = (int64_t)mk3 * a.npt;
-                    mt.t0 = k2 ? a.npt - k2 : 0;
-                    mt.t1 = k2 + 1 < a.npt ? a.npt - k2 - 1 : 0;  // (a half without a line: nothing is stored)
-                }
-                if constexpr (KT == KPL) {
-                    eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK, 32>(a, c1, tab_l, fm, iz0, iw0, npass, pass * (32 * KPL), col, line, mid_fn,
-                                                                            off_h, off_e, on, mt);
-                } else if (!last_pass) {  // nothing to contract before the pair's last pass
-                    auto no_mid = []() {};
-                    eval_unit<N, KPL, HERM, VEC, decltype(no_mid)&, PK, 32>(a, c1, tab_l, fm, iz0, iw0, npass, pass * (32 * KPL), col, line, no_mid,
-                                                                            off_h, off_e, on, mt);
-                } else {
-                    eval_unit<N, KT, HERM, VEC, decltype(mid_fn)&, PK, 32>(a, c1, tab_l, fm, izt, iwt, npass, pass * (32 * KPL), col, line, mid_fn,
-                                                                           off_h, off_e, on, mt);
-                }
-                if (last_pass) cur ^= 1;
-                pass = last_pass ? 0 : pass + 1;
-                k2 = nk2;
-            }
-            return;
-        }
-        int iz0[KPL], iw0[KPL];
-#pragma unroll
-        for (int j = 0; j < KPL; ++j) {
-            const int i1 = lane + 64 * j;
-            iz0[j] = i1 < a.npt ? i1 : 0;
-            iw0[j] = (int)(((unsigned)fm * (unsigned)iz0[j]) % (unsigned)a.npt);
-        }
-        int cur = 0, pass = 0;
-        while (k2 < a.npt) {
-            // the next unit is the same line again (its set stays where it is) or the wave's next line
-            const bool last_pass = pass + 1 >= npass;
-            const int nk2 = last_pass ? k2 + kstride : k2;
-            const bool contract_next = last_pass && nk2 < a.npt;
-            wave_lds_sync();
-            auto mid_fn = [&]() {
-                if (contract_next) {
-                    load_line_phases(as_const(a.phs2 + (int64_t)nk2 * a.M2), ph);
-                    contract_line_m(a.M2, s2, ph, mybuf + (size_t)(cur ^ 1) * MNN, MNN, lane);
-                }
-            };
-            MirrorTo mt;
-            if (mk3 >= 0) mt.line = (int64_t)mk3 * a.npt + (k2 ? a.npt - k2 : 0);
-            eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK>(a, mybuf + (size_t)cur * MNN, tab_l, fm, iz0, iw0, npass, pass * (64 * KPL), lane,
-                                                                (int64_t)k3 * a.npt + k2, mid_fn, 0, 0, true, mt);
-            if (last_pass) cur ^= 1;
-            pass = last_pass ? 0 : pass + 1;
-            k2 = nk2;
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < a.npt; i += 256) tab_l[i] = a.tab[i];
-    __syncthreads();
-    const int64_t lstride = (int64_t)gridDim.x * 4;
-    int64_t line = (int64_t)blockIdx.x * 4 + wave;
-    if (line >= a.nlines) return;
-    // stage the first line
-    {
-        const double2* __restrict__ src = a.src + line * MNN;
-#pragma unroll
-        for (int t = 0; t < EVAL_MAX_MNN / 64; ++t) {
-            const int idx = lane + 64 * t;
-            if (idx < MNN) mybuf[idx] = stage(src[idx], idx);
-        }
-    }
-    // table indices of z and of the seed w = z^first for the nodes of pass 0
-    int iz0[KPL], iw0[KPL];
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-        const int i1 = lane + 64 * j;
-        iz0[j] = i1 < a.npt ? i1 : 0;
-        iw0[j] = (int)(((unsigned)fm * (unsigned)iz0[j]) % (unsigned)a.npt);
-    }
-    int cur = 0, pass = 0;
-    while (line < a.nlines) {
-        // fetch the next unit's coefficients into registers (the same line again if it has more passes)
-        const bool last_pass = pass + 1 >= npass;
-        const int64_t nline = last_pass ? line + lstride : line;
-        const bool have_next = nline < a.nlines;
-        double2 pre[EVAL_MAX_MNN / 64];
-        {
-            const double2* __restrict__ src = a.src + (have_next ? nline : line) * MNN;
-#pragma unroll
-            for (int t = 0; t < EVAL_MAX_MNN / 64; ++t) {
-                const int idx = lane + 64 * t;
-                pre[t] = src[idx < MNN ? idx : MNN - 1];  // unconditional: no select waits on the data
-            }
-        }
-        wave_lds_sync();
-        auto mid_fn = [&]() {
-            // The one wait of the loop body: the fetched registers are consumed here, unconditionally and
-            // before this unit's stores are issued (the asm pins the point; nothing is hoisted above it).
-#pragma unroll
-            for (int t = 0; t < EVAL_MAX_MNN / 64; ++t) asm volatile("" : "+v"(pre[t].x), "+v"(pre[t].y));
-            if (have_next) {
-                double2* dst = mybuf + (size_t)(cur ^ 1) * MNN;
-#pragma unroll
-                for (int t = 0; t < EVAL_MAX_MNN / 64; ++t) {
-                    const int idx = lane + 64 * t;
-                    if (idx < MNN) dst[idx] = stage(pre[t], idx);
-                }
-            }
-        };
-        MirrorTo mt;
-        if constexpr (MIR) {  // a.nlines: the lines of the planes k3 <= npt / 2, fewer than 2^31 (eval_mirror_supported)
-            const unsigned k3 = (unsigned)line / (unsigned)a.npt, k2 = (unsigned)line - k3 * (unsigned)a.npt;
-            if (k3 != 0 && 2 * (int)k3 != a.npt) mt.line = (int64_t)(a.npt - (int)k3) * a.npt + (k2 ? a.npt - (int)k2 : 0);
-        }
-        eval_unit<N, KPL, HERM, VEC, decltype(mid_fn)&, PK>(a, mybuf + (size_t)cur * MNN, tab_l, fm, iz0, iw0, npass, pass * (64 * KPL), lane, line,
-                                                            mid_fn, 0, 0, true, mt);
-        cur ^= 1;
-        pass = last_pass ? 0 : pass + 1;
-        line = nline;
-    }
-}
-
-// Fallback for coefficient sets too large for the LDS staging above: wave-uniform scalar loads.
-template <int N>
-__global__ __launch_bounds__(256) void eval_grid_kernel_scalar(EvalArgs a) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int fm = a.first % a.npt;
-    if (fm < 0) fm += a.npt;
-    for (int64_t line = (int64_t)blockIdx.x * 4 + wave; line < a.nlines; line += (int64_t)gridDim.x * 4) {
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(line & 0xffffffffu));
-        const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)line >> 32));
-        const int64_t line_u = (int64_t)(((unsigned long long)hi << 32) | lo);
-        cptr_t c1 = as_const(a.src + line_u * ((int64_t)a.M * N * N));
-        for (int i0 = 0; i0 < a.npt; i0 += 64) {
-            const int i1 = i0 + lane;
-            if (i1 < a.npt) {
-                const double2 z = a.tab[i1];
-                const double2 w = a.tab[(int)(((int64_t)fm * i1) % a.npt)];
-                CMat<N> H;
-                series_lane<N>(c1, a.M, a.first, z.x, z.y, w.x, w.y, a.deriv != 0, H);
-                eval_epilogue<N>(a, H, line_u, i1);
-            }
-        }
-    }
-}
-
-template <int N>
-__global__ __launch_bounds__(256) void eval_node_kernel(EvalArgs a) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.nk) return;
-    const int64_t slot = a.parents ? a.parents[k] : 0;
-    cptr_t c1 = as_const(a.src + slot * ((int64_t)a.M * N * N));
-    double zr, zi, wr, wi;
-    if (a.x == nullptr) {
-        const int i1 = a.gi[k];
-        int fm = a.first % a.npt;
-        if (fm < 0) fm += a.npt;
-        const double2 z = a.tab[i1];
-        const double2 w = a.tab[(int)(((int64_t)fm * i1) % a.npt)];
-        zr = z.x;
-        zi = z.y;
-        wr = w.x;
-        wi = w.y;
-    } else {
-        const double xx = a.x[k] * a.inv_period;
-        sincospi(2.0 * xx, &zi, &zr);
-        sincospi(2.0 * ((double)a.first * xx), &wi, &wr);
-    }
-    CMat<N> H;
-    series_lane<N>(c1, a.M, a.first, zr, zi, wr, wi, a.deriv != 0, H);
-    const int ll = a.H.base ? a.H.line_len : (a.E.base ? a.E.line_len : a.U.line_len);
-    const int64_t line = k / ll;
-    eval_epilogue<N>(a, H, line, (int)(k - line * ll));
-}
-
 #define ABZ_DISPATCH_N(n, FN)                                       \
     switch (n) {                                                    \
         case 1: FN(1); break;                                       \
@@ -1292,273 +417,6 @@ __global__ __launch_bounds__(256) void eval_node_kernel(EvalArgs a) {
             return ABZ_ERR_UNSUPPORTED;                             \
     }
 
-// Can the grid kernel take packed Hermitian level-1 sets (packed_herm.h)?  Same limits as its LDS-staged path.
-bool eval_packed_supported(int n, int M, int npt) {
-    if (!abz_switch(SW_EVAL_PACKED) || n < 1 || n > 4 || (M & 1) == 0) return false;
-    const size_t P = packed_row_elems(n, M);
-    return P <= (size_t)EVAL_MAX_MNN && npt < 65536 && sizeof(double2) * (4 * 2 * P + (size_t)npt) <= 64 * 1024;
-}
-
-// Can the grid kernel contract variable 2 itself (EvalSpec::src2)?  Its LDS-staged path with the level-2 set of one
-// outermost index next to the four waves' double buffers and the phase table; `mnn` numbers per line.
-// `pairs`: the pair mapping (one line per half-wave), whose waves hold two lines' sets in each buffer.
-bool eval_fused_supported(int n, int64_t mnn, int M2, int npt, bool pairs) {
-    const size_t lpu = pairs ? 2 : 1;
-    return n >= 1 && n <= 4 && mnn >= 1 && mnn <= EVAL_MAX_MNN && M2 >= 1 && M2 <= ABZ_CONTRACT_GRID_MAXM && npt >= 1 &&
-           npt < 65536 && sizeof(double2) * ((size_t)M2 * mnn + 4 * 2 * lpu * (size_t)mnn + (size_t)npt) <= 64 * 1024;
-}
-
-// f(std::bool_constant<p>{}, std::bool_constant<q>{}): the template flags of the launch ladders below from run-time values
-template <class F>
-static void with_flags(bool p, bool q, F&& f) {
-    if (p)
-        q ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
-    else
-        q ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
-}
-
-// Can a launch evaluate the planes k3 <= npt / 2 alone and store the rest as their mirror images (EvalSpec::mirror)?  A whole
-// 3-D grid, values / eigenvalues of a Hermitian series; the mirrored row is addressed from the first line of its plane by a
-// 32-bit lane offset.
-bool eval_mirror_supported(const EvalSpec& es) {
-    if (!es.mirror || !es.grid || !es.herm || es.deriv || es.U.base || es.n < 1 || es.n > 4 || es.npt < 1 || es.npt >= 65536 ||
-        es.nlines != (int64_t)es.npt * es.npt || es.nlines >= INT32_MAX)
-        return false;
-    for (const PlaneView* v : {&es.H, &es.E})
-        if (v->base && ((int64_t)es.npt * v->tile + v->row >= INT32_MAX || v->tile < 0)) return false;
-    return true;
-}
-
-int launch_eval(abz_ctx* ctx, const EvalSpec& es) {
-    if (es.n > 4) {
-        GenSpec gs;
-        gs.Uplanes = es.U;
-        gs.herm = es.herm && !es.deriv;
-        gs.n = es.n;
-        gs.M = es.M;
-        gs.first = es.first;
-        gs.npt = es.npt;
-        gs.d = 0;
-        gs.period = es.period;
-        gs.src = es.src;
-        gs.grid = es.grid;
-        gs.parents = es.parents;
-        gs.run_start = es.run_start;
-        gs.nruns = es.nruns;
-        gs.gi = es.gi;
-        gs.x = es.x;
-        gs.tab = es.tab;
-        gs.deriv = es.deriv;
-        gs.nnodes = es.grid ? es.nlines * es.npt : es.nk;
-        gs.Hplanes = es.H;
-        gs.Eplanes = es.E;
-        gs.Haos = nullptr;
-        gs.Eaos = nullptr;
-        gs.integrand = ABZ_F_ONE;
-        for (int i = 0; i < 4; ++i) gs.params[i] = 0.0;
-        gs.sweep_dev = nullptr;
-        gs.sweep0 = 0.0;
-        gs.n_sweep = 0;
-        gs.values = nullptr;
-        return launch_gen_nodes(ctx, gs);
-    }
-    EvalArgs a;
-    a.src = es.src;
-    a.tab = es.tab;
-    a.parents = es.parents;
-    a.gi = es.gi;
-    a.x = es.x;
-    a.H = es.H;
-    a.E = es.E;
-    a.U = es.U;
-    a.nlines = es.nlines;
-    a.nk = es.nk;
-    a.line0 = 0;
-    a.M = es.M;
-    a.first = es.first;
-    a.npt = es.npt > 0 ? es.npt : 1;
-    a.deriv = es.deriv ? 1 : 0;
-    a.herm = (es.herm && !es.deriv) ? 1 : 0;
-    a.inv_period = 1.0 / es.period;
-    {
-        // streaming stores once the values written by this launch exceed the 256 MB Infinity Cache
-        // (npt = 100, 168 MB: 7 % slower with them; 150, 605 MB: 19 % faster)
-        const PlaneView& pv = es.H.base ? es.H : es.E;
-        const double planes_out = (es.H.base ? (es.H.compact ? 1.0 : 2.0) * es.n * es.n : 0.0) + (es.E.base ? (double)es.n : 0.0) + (es.U.base ? 2.0 * es.n * es.n : 0.0);
-        const double bytes = 8.0 * planes_out * (double)pv.row * (double)(es.grid ? es.nlines : (es.nk + 63) / 64);
-        a.nt = bytes > 256.0 * 1024 * 1024 ? 1 : 0;
-    }
-    a.pk = (es.packed && a.herm && !es.U.base && es.grid) ? 1 : 0;
-    ProfScope ps(ctx, ABZ_K_EVAL);
-    if (es.grid) {
-        if (es.nlines == 0) return ABZ_OK;
-        // Workgroups: 8 per CU up to ~140^3, 16 per CU beyond (3 bands: npt 150 0.1133 -> 0.1101 ms on a fast box,
-        // 0.1234 -> 0.1175 on a slow one; 200 -6 %, 250 -15 %, 300 -3 %, 500 -6 %; 110 / 128 are 3-5 % better with 8 per
-        // CU, 180 and 400 lose 2-3 % with 16); compact H planes: 24 per CU -- at 150^3 one line per wave -- measured
-        // 1.5 % better than 16, the same at 200^3
-        const int64_t quads = cdiv(es.nlines, 4);
-        const int64_t blocks = std::min<int64_t>(quads, quads < 5000 ? 256 * 8 : (es.H.compact ? 256 * 24 : 256 * 16));
-        const int mnn = a.pk ? es.n * (es.n + 1) / 2 + ((es.M - 1) / 2) * es.n * es.n : es.M * es.n * es.n;  // numbers per line (packed_herm.h)
-        // nodes per lane: minimise lane-rounds per line, ceil(npt / (64 kpl)) * kpl, weighted by the LDS
-        // operand reads that are shared by the kpl nodes of a lane (200 points: 2 x 2 rounds, not 2 x 3)
-        int kpl = 1;
-        {
-            double best = 1e30;
-            for (int k = 1; k <= 3; ++k) {
-                const double cost = (double)(cdiv(es.npt, 64 * k) * k) * (1.0 + 0.3 / k);
-                if (cost < best - 1e-12) {
-                    best = cost;
-                    kpl = k;
-                }
-            }
-        }
-        // + an LDS copy of the phase table (fm * i1 < npt^2 must fit 32 bits)
-        const size_t lds = sizeof(double2) * (4 * 2 * (size_t)mnn + (size_t)a.npt);
-        if (es.src2) {
-            // fused last contraction: whole blocks per outermost index, about the block count chosen above (150^3: one
-            // line per wave, 38 blocks for each of the 150 indices)
-            if (es.deriv || es.U.base || !eval_fused_supported(es.n, mnn, es.M2, es.npt) || es.nlines % es.npt != 0 ||
-                es.nlines / es.npt > 65535) {
-                set_error("eval: fused contraction unsupported (n = %d, %d numbers per line, M2 = %d, npt = %d)", es.n, mnn, es.M2, es.npt);
-                return ABZ_ERR_UNSUPPORTED;
-            }
-            const int64_t gcnt = es.nlines / es.npt;
-            // mirror: the launch grid's rows are the planes k3 <= npt / 2; blocks per plane as for the whole grid
-            a.mirror = eval_mirror_supported(es) ? 1 : 0;
-            const unsigned grows = a.mirror ? (unsigned)(es.npt / 2 + 1) : (unsigned)gcnt;
-            a.src2 = es.src2;
-            a.phs2 = es.phs2;
-            a.M2 = es.M2;
-            if (ctx->prof & (1u << ABZ_K_EVAL_FUSED)) ctx->prof_slots[ABZ_K_EVAL_FUSED].launches += 1;
-            // ... then the fewest blocks with the same number of lines per wave: every wave of an index gets its share
-            // (100 points: 21 blocks would give 16 of 84 waves a second line; 13 give 48 of 52 two)
-            a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(es.npt, 4), cdiv(blocks, gcnt)));
-            a.bpk = (int)cdiv(es.npt, 4 * cdiv(es.npt, 4 * a.bpk));
-            const size_t flds = lds + sizeof(double2) * (size_t)es.M2 * mnn;
-            // Pair mapping (one line per half-wave): the same count over rounds of 32 lanes, for two lines at once.  Its
-            // passes are of KP rounds -- the most the instance holds without scratch in its work loop: 3, with 4 bands 2,
-            // non-Hermitian 1 -- and the last pass of the rest, kt, so a pair costs ceil(npt / 32) lane-rounds.  It is taken
-            // where that is fewer than two lines of the 64-lane mapping cost (150 points: 5 against 2 x 3); ties keep the
-            // 64-lane mapping (measured slower or equal there: +6 % at 64 and 250 points), and so do non-Hermitian series
-            // (3 bands: +7 % at 80 points, +4 % at 200, -2 % at 150).  ABZ_EVAL_PAIRS: 0 never,
-            // 2 wherever the kernel supports it.
-            const int sw_pairs = abz_switch(SW_EVAL_PAIRS);
-            const int rounds = (int)cdiv(es.npt, 32);
-            const bool pairs = sw_pairs != 0 && eval_fused_supported(es.n, mnn, es.M2, es.npt, true) && es.H.tile < INT32_MAX &&
-                               es.E.tile < INT32_MAX && (sw_pairs >= 2 || (a.herm && rounds < 2 * cdiv(es.npt, 64 * kpl) * kpl));
-            if (pairs) {
-                const int kp = es.n < 4 ? 3 : (a.herm ? 2 : 1);
-                const int kt = rounds - (int)(cdiv(rounds, kp) - 1) * kp;  // 1 ... kp
-                // blocks per index by the rule above, counted in pairs (150 points: 19 blocks, one pair per wave; two pairs
-                // per wave measured 9 % slower there and 7 % at 200 points)
-                const int64_t npairs = cdiv(es.npt, 2);
-                a.bpk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(npairs, 4), cdiv(blocks, gcnt)));
-                a.bpk = (int)cdiv(npairs, 4 * cdiv(npairs, 4 * a.bpk));
-                size_t plds = flds + sizeof(double2) * 4 * 2 * (size_t)mnn;
-                // One pass of a pair per wave (eval_grid_kernel<..., PW>): Hermitian series whose pairs take 2 or 4 passes, so
-                // that a block holds whole pairs; one pass is the instance above as it is, three passes keep it.  The caller
-                // asks for it (EvalSpec::passwave; rule_fill holds the selection rule and ABZ_EVAL_PASSWAVE).
-                const int npass = (int)cdiv(rounds, kp);
-                const bool passwave = es.passwave && a.herm && (npass == 2 || npass == 4);
-                if (passwave) {
-                    a.bpk = (int)cdiv(npairs * npass, 4);
-                    plds = flds;  // one buffer of two line sets per wave: the room of the 64-lane mapping's two buffers
-                    if (ctx->prof & (1u << ABZ_K_EVAL_PASSWAVE)) ctx->prof_slots[ABZ_K_EVAL_PASSWAVE].launches += 1;
-                }
-                const dim3 grid((unsigned)a.bpk, grows);
-#define LKP(NN, KT)                                                                                                          \
-    {                                                                                                                        \
-        constexpr int OO = NN == 3 ? 3 : 2;                                                                                  \
-        constexpr int KH = NN < 4 ? 3 : 2, KG = NN < 4 ? 3 : 1; /* kp above */                                               \
-        if (a.herm)                                                                                                          \
-            with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                    \
-                if (passwave)                                                                                                \
-                    launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, pk(), true, true, KT <= KH ? KT : KH, mir(), true>, grid, dim3(256), plds, a); \
-                else                                                                                                         \
-                    launch(ctx, eval_grid_kernel<NN, KH, true, false, OO, pk(), true, true, KT <= KH ? KT : KH, mir()>, grid, dim3(256), plds, a); \
-            });                                                                                                              \
-        else                                                                                                                 \
-            launch(ctx, eval_grid_kernel<NN, KG, false, false, 2, false, true, true, KT <= KG ? KT : KG>, grid, dim3(256), plds, a); \
-    }
-#define FN(NN)                     \
-    switch (kt) {                  \
-        case 1: LKP(NN, 1) break;  \
-        case 2: LKP(NN, 2) break;  \
-        default: LKP(NN, 3) break; \
-    }
-                ABZ_DISPATCH_N(es.n, FN)
-#undef FN
-#undef LKP
-            } else {
-#define LK(NN, KK)                                                                                                                         \
-    {                                                                                                                                      \
-        constexpr int OO = NN == 3 ? 3 : 2;                                                                                                \
-        if (a.herm)                                                                                                                        \
-            with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                                  \
-                launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, pk(), true, false, KK, mir()>, dim3((unsigned)a.bpk, grows), dim3(256), flds, a); \
-            });                                                                                                                            \
-        else                                                                                                                               \
-            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2, false, true>, dim3((unsigned)a.bpk, grows), dim3(256), flds, a); \
-    }
-#define FN(NN)                    \
-    switch (kpl) {                \
-        case 1: LK(NN, 1) break;  \
-        case 2: LK(NN, 2) break;  \
-        default: LK(NN, 3) break; \
-    }
-            ABZ_DISPATCH_N(es.n, FN)
-#undef FN
-#undef LK
-            }
-        } else if (mnn <= EVAL_MAX_MNN && lds <= 64 * 1024 && a.npt < 65536) {
-            // waves per SIMD the register allocator is asked for: 3 on the Hermitian 3-band paths (2 and 4 measured
-            // slower there), 2 elsewhere
-            // mirror: the lines of the planes k3 <= npt / 2, which come first
-            if (eval_mirror_supported(es)) {
-                a.mirror = 1;
-                a.nlines = (int64_t)(es.npt / 2 + 1) * es.npt;
-            }
-            const unsigned lblocks = (unsigned)std::min<int64_t>(blocks, cdiv(a.nlines, 4));
-#define LK(NN, KK)                                                                                                             \
-    {                                                                                                                          \
-        constexpr int OO = NN == 3 ? 3 : 2;                                                                                    \
-        if (a.U.base && !a.pk)                                                                                                 \
-            launch(ctx, eval_grid_kernel<NN, KK, false, true, 2>, dim3(lblocks), dim3(256), lds, a);                           \
-        else if (a.herm)                                                                                                       \
-            with_flags(a.pk != 0, a.mirror != 0, [&](auto pk, auto mir) {                                                      \
-                launch(ctx, eval_grid_kernel<NN, KK, true, false, OO, pk(), false, false, KK, mir()>, dim3(lblocks), dim3(256), lds, a); \
-            });                                                                                                                \
-        else                                                                                                                   \
-            launch(ctx, eval_grid_kernel<NN, KK, false, false, 2>, dim3(lblocks), dim3(256), lds, a);                          \
-    }
-#define FN(NN)                    \
-    switch (kpl) {                \
-        case 1: LK(NN, 1) break;  \
-        case 2: LK(NN, 2) break;  \
-        default: LK(NN, 3) break; \
-    }
-            ABZ_DISPATCH_N(es.n, FN)
-#undef FN
-#undef LK
-        } else {
-#define FN(NN) launch(ctx, eval_grid_kernel_scalar<NN>, dim3((unsigned)blocks), dim3(256), 0, a)
-            ABZ_DISPATCH_N(es.n, FN)
-#undef FN
-        }
-    } else {
-        if (es.nk == 0) return ABZ_OK;
-        const int64_t blocks = cdiv(es.nk, 256);
-#define FN(NN) launch(ctx, eval_node_kernel<NN>, dim3((unsigned)blocks), dim3(256), 0, a)
-        ABZ_DISPATCH_N(es.n, FN)
-#undef FN
-    }
-    ABZ_HIP(hipGetLastError());
-    return ABZ_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// stand-alone eigensolve on planes, velocities
-// ------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(256) void eig_planes_kernel(PlaneView Hv, PlaneView Ev, PlaneView Uv, int64_t nk) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2384,17 +1242,7 @@ int launch_eval_sum(abz_ctx* ctx, const SumSpec& ss) {
     a.herm = 1;
     a.nt = 0;
     a.inv_period = 1.0;
-    int kpl = 2;
-    {
-        double best = 1e30;
-        for (int k = 2; k <= 3; ++k) {
-            const double cost = (double)(cdiv(ss.npt, 64 * k) * k) * (1.0 + 0.3 / k);
-            if (cost < best - 1e-12) {
-                best = cost;
-                kpl = k;
-            }
-        }
-    }
+    const int kpl = eval_kpl(ss.npt, 2);  // (its instances are built for 2 and 3 nodes per lane)
     const int mnn = (int)packed_row_elems(ss.n, ss.M);  // packed Hermitian level-1 sets (packed_herm.h)
     const size_t lds = sizeof(double2) * (4 * 2 * (size_t)mnn + (size_t)ss.npt);
     const int64_t blocks = std::min<int64_t>(cdiv(ss.nlines, 4), 256 * 8);

@@ -645,7 +645,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const double2* __restric
     out[t] = pk_from_full<N>(src + row * ((int64_t)M * N * N), F, e);
 }
 
-size_t packed_row_elems(int n, int M) { return (size_t)(n * (n + 1) / 2 + ((M - 1) / 2) * n * n); }
+size_t packed_row_elems(int n, int M) { return (size_t)eval_line_elems(n, M, true); }
 
 int launch_pack_rows(abz_ctx* ctx, int n, int M, const double2* src, int64_t nrows, double2* out) {
     const int64_t tot = nrows * (int64_t)packed_row_elems(n, M);

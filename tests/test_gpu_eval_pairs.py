@@ -1,4 +1,4 @@
-"""Pair mapping of the fused grid kernel: one grid line per half-wave (eval_grid_kernel<..., FUSE, PAIR>).
+"""Pair mapping of the fused grid kernel: one grid line per half-wave (eval_grid_kernel, mapping fused_pairs).
 
 Per node the pair mapping runs the arithmetic of the 64-lane mapping on the same operands; only the lane a node sits in
 changes.  So three arms are compared bit for bit: ABZ_EVAL_PAIRS=2 (pairs wherever the kernel supports them: small grids

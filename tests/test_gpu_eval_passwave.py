@@ -1,4 +1,4 @@
-"""One pass of a line pair per wave in the fused pair mapping (eval_grid_kernel<..., PW>, ABZ_EVAL_PASSWAVE, DESIGN section 9
+"""One pass of a line pair per wave in the fused pair mapping (eval_grid_kernel, mapping fused_passwave, ABZ_EVAL_PASSWAVE, DESIGN section 9
 item 1).
 
 The instance changes which wave evaluates which nodes and nothing of the arithmetic per node, so its rules are compared bit for
