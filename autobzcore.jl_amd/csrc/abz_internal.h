@@ -543,6 +543,11 @@ int launch_ltm_weighted(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneV
 // A == nullptr: one component, A = 1 (g, N) or, with `energy`, A = e.  Under ABZ_K_LTM.
 int launch_ltm_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneView* A, bool energy, int ncomp, const double* Es_host, int nE,
                          bool states, double* out_host);
+// tr G(z) and G_A(z) by the optimized rule (kernels_ltm_green_opt.hip) over the planes of a whole periodic 3-d grid: the closed forms of
+// launch_ltm_green / launch_ltm_green_weighted on the effective corner values of every simplex.  z_host [nz][2] with Im z != 0, out_host
+// [nz][ncomp][2]; A == nullptr: one component, the trace or, with `energy`, A' = e'.  Under ABZ_K_LTM.
+int launch_ltm_green_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneView* A, bool energy, int ncomp, const double* z_host, int nz,
+                               double* out_host);
 // one component of host-ordered elements [nk][n] (on the device) into the planes plane0 ... plane0 + n - 1 of A
 // tr G(z) by the tetrahedron method on a whole grid (abz_rule_ltm_green): z_host [nz][2] with Im z != 0, out_host [nz][2]
 int launch_ltm_green(abz_ctx* ctx, int n, int d, int npt, PlaneView E, const double* z_host, int nz, double* out_host);

@@ -41,9 +41,6 @@ namespace {
 //  * Reduction.  Per z in a fixed order: a butterfly over the wave, lane 0 adds into the wave's LDS slot [nz][re, im] in
 //    program order, the four waves are summed in a fixed order into transposed partials and launch_ltm_final finishes.  No
 //    atomics: two calls return the same bits.
-constexpr int LTM_GREEN_CHUNK = 512;     // values of z per launch: 8 (2 + 4 x 2) B of LDS each
-static_assert(sizeof(double) * 10 * LTM_GREEN_CHUNK <= LTM_LDS_MAX, "the z list and the four waves' sums fit the scans' LDS");
-
 struct GreenArgs {
     PlaneView E;
     const double* z;  // device [nz][2]: re, im > 0
@@ -51,45 +48,6 @@ struct GreenArgs {
     int npt, nz;
     int zper;         // values of z per blockIdx.z
 };
-
-// J of three sorted corners from the J of its two pairs, which only a wide triple reads
-__device__ __forceinline__ Cx green_triple(const GreenCorner& a, const GreenCorner& b, const GreenCorner& c, Cx pab, Cx pbc, double zr,
-                                           double zi) {
-    const double u[3] = {zr - a.x, zr - b.x, zr - c.x};
-    const double w = c.x - a.x, ur = (u[0] + u[1] + u[2]) * (1.0 / 3.0), n2 = ur * ur + zi * zi;
-    if (w * w < GREEN_RHO2 * n2) return green_series<2>(u, ur, zi, n2);
-    const Cx t0 = cx_mul({u[0], zi}, pab), t1 = cx_mul({u[2], zi}, pbc);
-    const double f = 2.0 / w;
-    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
-}
-
-// J of a simplex with corners in any order
-__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, double zr, double zi) {
-    green_cx(a, b);
-    return green_pair(a, b, zr, zi);
-}
-__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenCorner c, double zr, double zi) {
-    green_cx(a, b);
-    green_cx(b, c);
-    green_cx(a, b);
-    return green_triple(a, b, c, green_pair(a, b, zr, zi), green_pair(b, c, zr, zi), zr, zi);
-}
-__device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenCorner c, GreenCorner d, double zr, double zi) {
-    green_cx(a, b);
-    green_cx(c, d);
-    green_cx(a, c);
-    green_cx(b, d);
-    green_cx(b, c);
-    const double u[4] = {zr - a.x, zr - b.x, zr - c.x, zr - d.x};
-    const double w = d.x - a.x, ur = 0.25 * ((u[0] + u[1]) + (u[2] + u[3])), n2 = ur * ur + zi * zi;
-    if (w * w < GREEN_RHO2 * n2) return green_series<3>(u, ur, zi, n2);
-    // the two triples share the middle pair
-    const Cx p01 = green_pair(a, b, zr, zi), p12 = green_pair(b, c, zr, zi), p23 = green_pair(c, d, zr, zi);
-    const Cx j0 = green_triple(a, b, c, p01, p12, zr, zi), j1 = green_triple(b, c, d, p12, p23, zr, zi);
-    const Cx t0 = cx_mul({u[0], zi}, j0), t1 = cx_mul({u[3], zi}, j1);
-    const double f = 1.5 / w;
-    return {(t0.re - t1.re) * f, (t0.im - t1.im) * f};
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Green's function with matrix elements at complex energies (abz_rule_ltm_green_weighted)
@@ -116,75 +74,11 @@ __device__ __forceinline__ Cx green_simplex(GreenCorner a, GreenCorner b, GreenC
 //    carries each corner's log and its NC elements, the m + 1 weights of a (simplex, z) are formed once and every component
 //    contracts with them.  Groups as in ltm_scan: 4s, a 2, a 1.  LDS: [zn][2] z | [4 waves][zn][NC][2] sums, so a launch takes
 //    green_w_chunk(NC) = 512 / 291 / 154 values of z.  1 / (m + 1) goes into the scale of launch_ltm_final.
-constexpr int green_w_chunk(int nc) {
-    const size_t fit = LTM_LDS_MAX / (sizeof(double) * (size_t)(2 + 8 * nc));
-    return fit < (size_t)LTM_GREEN_CHUNK ? (int)fit : LTM_GREEN_CHUNK;
-}
-static_assert(sizeof(double) * (2 + 8 * 1) * green_w_chunk(1) <= LTM_LDS_MAX && sizeof(double) * (2 + 8 * 2) * green_w_chunk(2) <= LTM_LDS_MAX &&
-                  sizeof(double) * (2 + 8 * 4) * green_w_chunk(4) <= LTM_LDS_MAX,
-              "the z list and the four waves' sums of every component group fit the scans' LDS");
-static_assert(green_w_chunk(1) == LTM_GREEN_CHUNK, "the trace is a group of one component");
-static_assert(green_w_chunk(4) >= 4 && green_w_chunk(4) <= green_w_chunk(2) && green_w_chunk(2) <= green_w_chunk(1), "chunks shrink with NC");
-
 struct GreenWArgs : GreenArgs {
     PlaneView A;
     int64_t acomp;  // doubles from a band's plane of one component to its plane of the next: n * A.pitch
     int aplane0;    // first element plane of this launch: (its first component) * n
 };
-
-// what the sort of a simplex carries per corner: the energy, log(z - energy) and the NC elements
-template <int NC>
-struct GreenWCorner {
-    GreenCorner g;
-    LtmVec<NC> a;
-};
-template <int NC>
-__device__ __forceinline__ GreenWCorner<NC> green_sel(bool first, const GreenWCorner<NC>& p, const GreenWCorner<NC>& q) {
-    GreenWCorner<NC> r;
-    r.g = green_sel(first, p.g, q.g);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) r.a.v[c] = first ? p.a.v[c] : q.a.v[c];
-    return r;
-}
-template <int NC>
-__device__ __forceinline__ void green_wcx(GreenWCorner<NC>& p, GreenWCorner<NC>& q) {
-    const bool sw = q.g.x < p.g.x;
-    const GreenWCorner<NC> lo = green_sel(sw, q, p), hi = green_sel(sw, p, q);
-    p = lo;
-    q = hi;
-}
-
-
-// sum_i A_{c,i} (m + 1) W_i of a simplex with corners in any order, added to (sr, si)[c]
-template <int NK, int NC>
-__device__ __forceinline__ void green_wsimplex(GreenWCorner<NC> (&q)[NK], double zr, double zi, double (&sr)[NC], double (&si)[NC]) {
-    if constexpr (NK == 2) {
-        green_wcx(q[0], q[1]);
-    } else if constexpr (NK == 3) {
-        green_wcx(q[0], q[1]);
-        green_wcx(q[1], q[2]);
-        green_wcx(q[0], q[1]);
-    } else {
-        green_wcx(q[0], q[1]);
-        green_wcx(q[2], q[3]);
-        green_wcx(q[0], q[2]);
-        green_wcx(q[1], q[3]);
-        green_wcx(q[1], q[2]);
-    }
-    GreenCorner g[NK];
-#pragma unroll
-    for (int l = 0; l < NK; ++l) g[l] = q[l].g;
-    Cx W[NK];
-    green_weights<NK>(g, zr, zi, W);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-        for (int l = 0; l < NK; ++l) {
-            sr[c] += q[l].a.v[c] * W[l].re;
-            si[c] += q[l].a.v[c] * W[l].im;
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The scan: one kernel, two payloads

@@ -10,7 +10,7 @@
 //      p17..p20 = v4 - v1 + v2,  v1 - v2 + v3,  v2 - v3 + v4,  v3 - v4 + v1,
 //    all inside i + [-1, 2]^3, every index wrapped mod npt (any npt >= 1; below 4 the stencil wraps onto itself).  The cubic through
 //    the 20 values is fitted, and the 4 corner values are replaced by those of the linear function closest to it in the
-//    least-squares sense over the simplex: x'_m = sum_j P[m][j] x(p_j), OPT_K = 1260 P below (rows sum to 1260; derived in exact
+//    least-squares sense over the simplex: x'_m = sum_j P[m][j] x(p_j), OPT_K = 1260 P in ltm_opt_device.h (rows sum to 1260; derived in exact
 //    rationals by tests/optltm_numpy.py, which does not read this table).  For band b, x is the b-th ascending eigenvalue at each
 //    point (no band unfolding); elements A_b take the same P at the same points.  Every closed form of the linear method
 //    (ltm_simplex_device.h) then applies unchanged to (e'_1..e'_4; A'_1..A'_4), with the weight 1 / (6 npt^3) per simplex; a simplex
@@ -41,49 +41,12 @@
 
 #include "abz_internal.h"
 #include "ltm_device.h"
+#include "ltm_opt_device.h"
 #include "ltm_simplex_device.h"
 
 namespace abz {
 
 namespace {
-
-// The 20 points in path coordinates: p = v1 + al e_a + be e_b + ga e_c.
-constexpr int OPT_NPT = 20;
-__device__ constexpr int OPT_PT[OPT_NPT][3] = {
-    {0, 0, 0},    {1, 0, 0},   {1, 1, 0},   {1, 1, 1},                                                   // v1 .. v4
-    {-1, 0, 0},   {1, -1, 0},  {1, 1, -1},  {2, 2, 2},                                                   // 2 v_i - v_j: (1,2) (2,3) (3,4) (4,1)
-    {-1, -1, 0},  {1, -1, -1}, {2, 2, 0},   {1, 2, 2},                                                   // (1,3) (2,4) (3,1) (4,2)
-    {-1, -1, -1}, {2, 0, 0},   {1, 2, 0},   {1, 1, 2},                                                   // (1,4) (2,1) (3,2) (4,3)
-    {2, 1, 1},    {0, 1, 0},   {1, 0, 1},   {0, 0, -1},                                                  // v4 - v1 + v2, ...
-};
-// 1260 P
-__device__ constexpr int OPT_K[4][OPT_NPT] = {
-    {1440, 0, 30, 0, -38, 7, 17, -28, -56, 9, -46, 9, -38, -28, 17, 7, -18, -18, 12, -18},
-    {0, 1440, 0, 30, -28, -38, 7, 17, 9, -56, 9, -46, 7, -38, -28, 17, -18, -18, -18, 12},
-    {30, 0, 1440, 0, 17, -28, -38, 7, -46, 9, -56, 9, 17, 7, -38, -28, 12, -18, -18, -18},
-    {0, 30, 0, 1440, 7, 17, -28, -38, 9, -46, 9, -56, -28, 17, 7, -38, -18, 12, -18, -18},
-};
-constexpr bool opt_rows_ok() {
-    for (int m = 0; m < 4; ++m) {
-        int s = 0;
-        for (int j = 0; j < OPT_NPT; ++j) s += OPT_K[m][j];
-        if (s != 1260) return false;
-    }
-    return true;
-}
-static_assert(opt_rows_ok(), "the rows of 1260 P sum to 1260");
-
-// x'_m = x_m + sum_{j != m} P[m][j] (x_j - x_m)
-__device__ __forceinline__ void opt_project(const double (&x)[OPT_NPT], double (&y)[4]) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < OPT_NPT; ++j)
-            if (j != m && OPT_K[m][j] != 0) s = fma((double)OPT_K[m][j] / 1260.0, x[j] - x[m], s);
-        y[m] = x[m] + s;
-    }
-}
 
 enum { OPT_ONE = 0, OPT_ENERGY = 1, OPT_ELEMS = 2 };
 
@@ -103,15 +66,6 @@ struct OptPayload {
     static constexpr int NC = NC_;
     static constexpr bool CORR = false;
 };
-
-// index i + o of a periodic axis of npt >= 1 points, o in -1 .. 2
-__device__ __forceinline__ int opt_wrap(int i, int o, int npt) {
-    int j = i + o;
-    j += j < 0 ? npt : 0;
-    j -= j >= npt ? npt : 0;
-    j -= j >= npt ? npt : 0;  // npt = 1: i + 2 is two periods away
-    return j;
-}
 
 // partial [(STATES ? 2 : 1) NC nE][nrows]: columns c nE + i the formula sums of component c, NC nE + c nE + i its steps
 template <bool STATES, int SRC, int NC>

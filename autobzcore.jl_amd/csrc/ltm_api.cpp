@@ -395,6 +395,31 @@ int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z, int nz
     return launch_ltm_green_weighted(ctx, rule_bands(r), r->s->d, r->npt, r->E, energy ? r->E : r->elems.view, energy ? 1 : r->elems.sets, z, nz, out);
 } ABZ_CATCH_ALL
 
+// The Green's functions of the optimized rule (kernels_ltm_green_opt.hip).  Every check comes before anything is reserved or launched.
+int abz_rule_ltm_green_optimized(abz_rule* r, int source, const double* z, int nz, double* out) try {
+    const char* const who = "abz_rule_ltm_green_optimized";
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(z && out && nz >= 1, "abz_rule_ltm_green_optimized: bad arguments");
+    ABZ_REQUIRE(source == ABZ_LTM_A_ONE || source == ABZ_LTM_A_ENERGY || source == ABZ_LTM_A_ELEMENTS,
+                "%s: source = %d is neither ABZ_LTM_A_ONE, ABZ_LTM_A_ENERGY nor ABZ_LTM_A_ELEMENTS", who, source);
+    if (r->s->d != 3) {
+        set_error("abz_rule_ltm_green_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if ((rc = refuse_pair_rule(r, who, "the effective corner values of e_c - e_v have not been looked at (abz_rule_ltm_green serves it)"))) return rc;
+    if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
+    ABZ_REQUIRE(source != ABZ_LTM_A_ELEMENTS || r->elems.buf.p,
+                "abz_rule_ltm_green_optimized: no matrix elements are attached (abz_rule_ltm_elements, abz_rule_ltm_orbitals; "
+                "abz_rule_rebuild drops them)");
+    if ((rc = ltm_check_zs(who, z, nz, source == ABZ_LTM_A_ONE ? "the trace is" : "G_A is"))) return rc;
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const bool elems = source == ABZ_LTM_A_ELEMENTS;
+    return launch_ltm_green_optimized(ctx, rule_bands(r), r->npt, r->E, elems ? &r->elems.view : nullptr, source == ABZ_LTM_A_ENERGY,
+                                      elems ? r->elems.sets : 1, z, nz, out);
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, double* N_F) try {
     int rc = check_rule(r);
     if (rc) return rc;

@@ -205,7 +205,8 @@ class LTM(DOSAlgorithm):
         if self.optimized and correction:
             raise ValueError("LTM: optimized=True replaces the curvature correction: it does not go with correction=True")
         if self.optimized and eta is not None:
-            raise ValueError("LTM: optimized=True does not go with eta (the Green's functions use the linear rule)")
+            raise ValueError("LTM: optimized=True does not go with eta (the solve path with eta is the linear rule's; the optimized Green's "
+                             "functions: dos.green_trace / dos.green_weighted with optimized=True, DeviceRule.ltm_green_optimized)")
         if self.optimized and pairs is not None:
             raise ValueError("LTM: optimized=True does not go with pairs (pair rules are scanned with the linear rule)")
         if pairs is not None and not isinstance(pairs, BandPairs):
@@ -491,9 +492,12 @@ def fermi_level(prob_or_cache, nstates, tol=1e-10, optimized=None):
     return c.cacheval.ltm_fermi(nstates, tol)
 
 
-def green_trace(prob_or_cache, zs):
+def green_trace(prob_or_cache, zs, optimized=False):
     """tr G(z) = sum_b int dk / (z - e_b(k)) at the complex energies `zs` (Im z != 0), per unit cell, complex128 [nz], from the
-    eigenvalues of an LTM cache or of a DOSProblem (solved with LTM()): DeviceRule.ltm_green on the cache's grid."""
+    eigenvalues of an LTM cache or of a DOSProblem (solved with LTM()): DeviceRule.ltm_green on the cache's grid.
+    `optimized=True`: the optimized tetrahedron rule instead (DeviceRule.ltm_green_optimized, d = 3), whose -Im / pi tends to the
+    DOS of LTM(optimized=True) as Im z -> 0.  The default is the linear rule whatever the cache's algorithm is; the solve path
+    LTM(eta=...) stays linear too (LTM(optimized=True, eta=...) is refused): this keyword is the way to the optimized trace."""
     H = getattr(prob_or_cache, "H", None)
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
         raise NotImplementedError("green_trace on a k-sharded series is not implemented: the trace of the Green's function is "
@@ -505,14 +509,19 @@ def green_trace(prob_or_cache, zs):
         c.cacheval = _init_cacheval(c.H, c.domain, c.p, c.alg)
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
+    if optimized:
+        return c.cacheval.ltm_green_optimized(zs)
     return c.cacheval.ltm_green(zs)
 
 
-def green_weighted(prob_or_cache, zs):
+def green_weighted(prob_or_cache, zs, optimized=False):
     """G_A(z) = sum_b int dk A_b(k) / (z - e_b(k)) at the complex energies `zs` (Im z != 0), per unit cell, complex128
     [nz, ncomp], with the elements of an LTM cache (`elements` = "energy", "orbitals" or a callable) or of a DOSProblem
     (solved with LTM(elements="energy")): DeviceRule.ltm_green with the cache's elements on the cache's grid.  With orbital
-    weights it is the diagonal G_aa(z) of the local Green's function."""
+    weights it is the diagonal G_aa(z) of the local Green's function.  `optimized=True`: the optimized tetrahedron rule instead
+    (DeviceRule.ltm_green_optimized, d = 3: elements and energies take the same 20-point fit per simplex).  The default is the
+    linear rule whatever the cache's algorithm is, and the solve path LTM(eta=...) stays linear (LTM(optimized=True, eta=...)
+    is refused): this keyword is the way to the optimized G_A."""
     H = getattr(prob_or_cache, "H", None)
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
         raise NotImplementedError("green_weighted on a k-sharded series is not implemented: the Green's function is computed on "
@@ -529,7 +538,8 @@ def green_weighted(prob_or_cache, zs):
     el = c.elements
     if not isinstance(el, str):
         _ltm_attach(c.cacheval, el)
-    return c.cacheval.ltm_green(zs, elements=el if isinstance(el, str) else "attached")
+    green = c.cacheval.ltm_green_optimized if optimized else c.cacheval.ltm_green
+    return green(zs, elements=el if isinstance(el, str) else "attached")
 
 
 def _green_local_check(c, who):

@@ -479,8 +479,8 @@ int abz_rule_ltm_bands(const abz_rule* r, int* nb);
  * ABZ_ERR_ARG: NULL pointers, nE < 1, another `what` -- ABZ_LTM_STATES_CORRECTED too: this rule replaces the correction --,
  * another `source`, ABZ_LTM_A_ELEMENTS with nothing attached, a rule without eigenvalues.  ABZ_ERR_UNSUPPORTED: d != 3, a slab
  * (with or without its halo: the stencil needs three planes around it), a list of irreducible nodes.  A refusal launches nothing
- * and leaves `out` and the rule as they were.  Not handled: d = 1, 2, slabs, Green's functions, node weights, occupied pair
- * scans.  Kernels under ABZ_K_LTM.  Entry point added without a change of ABZ_VERSION. */
+ * and leaves `out` and the rule as they were.  Not handled: d = 1, 2, slabs, node weights, occupied pair scans (the Green's
+ * functions: abz_rule_ltm_green_optimized below).  Kernels under ABZ_K_LTM.  Entry point added without a change of ABZ_VERSION. */
 int abz_rule_ltm_optimized(abz_rule* r, int source, const double* E, int nE, int what, double* out);
 /* Tetrahedron scans on a slab: attach the halo plane.  r: a rule of abz_ptr_rule_build_slab over [outer_begin, outer_end) that
  * holds eigenvalues (other `want` bits are fine).  The simplices of the cells of the slab's last plane reach into plane
@@ -530,6 +530,25 @@ int abz_rule_ltm_green(abz_rule* r, const double* z /* [nz][2]: re, im */, int n
  * eigenvalues, nz < 1, a NULL pointer, any Im z == 0 or non-finite z; nothing is reserved, launched or written then.
  * Entry point added without a change of ABZ_VERSION. */
 int abz_rule_ltm_green_weighted(abz_rule* r, int source, const double* z /* [nz][2] */, int nz, double* out /* [nz][ncomp][2] */);
+
+/* The Green's functions of the optimized tetrahedron method, d = 3: abz_rule_ltm_green and abz_rule_ltm_green_weighted on the
+ * effective corner values of abz_rule_ltm_optimized, so that -Im tr G(E + i eta) / pi tends to the g(E) of abz_rule_ltm_optimized as
+ * eta -> 0 and the error at npt compares with the linear rule's at 2 npt whatever eta is.  For every cell, Kuhn simplex and band b:
+ * e'_m = sum_j P[m][j] e_b(p_j) and A'_{c,m} = sum_j P[m][j] A_{c,b}(p_j) over the 20 stencil points (the same P, points and wrap
+ * mod npt, any npt >= 1; the band index is followed).  Then
+ *      tr G(z)  = w sum_{cells} sum_{6 simplices} sum_{bands} J[sort(e'_1 .. e'_4)](z),       w = 1 / (6 npt^3)
+ *      G_A,c(z) = w sum ... sum_{i=0..3} A'_{c,i} W_i(z),                                     W_i = J[x_0 .. x_3, x_i](z) / 4
+ * by the evaluation rule of abz_rule_ltm_green (rho = 1/2, Taylor series for narrow sub-ranges, principal logs of one half plane).
+ * source: ABZ_LTM_A_ONE (the trace, ncomp = 1, nothing loaded), ABZ_LTM_A_ENERGY (A' = e', one component: z tr G(z) - n) or
+ * ABZ_LTM_A_ELEMENTS (the attached block, in groups of 4, 2, 1 components).  out [nz][ncomp][2].  Im z < 0: the conjugate of the
+ * value at conj(z), to the bit.  No floating-point atomics: two calls return the same bits.  A flat band gives 1 / (z - e).
+ * Takes full-grid rules and rules of abz_rule_ltm_unfold.  ABZ_ERR_ARG: NULL pointers, nz < 1, any Im z == 0 or non-finite z,
+ * another `source`, ABZ_LTM_A_ELEMENTS with nothing attached, a rule without eigenvalues.  ABZ_ERR_UNSUPPORTED: d != 3; slabs, with
+ * or without a halo; lists of irreducible nodes; pair rules of abz_rule_ltm_pairs (e'_c - e'_v has not been looked at).  A refusal
+ * launches nothing and leaves `out` and the rule as they were.  Not handled: the node-weight forms W_b(k; z), the local matrix
+ * G_pq(z) other than through attached projectors, d < 3.  Kernels under ABZ_K_LTM.  Entry point added without a change of
+ * ABZ_VERSION. */
+int abz_rule_ltm_green_optimized(abz_rule* r, int source, const double* z /* [nz][2] */, int nz, double* out /* [nz][ncomp][2] */);
 
 /* Bloechl's integration weights themselves, per grid point and band: the numbers w_b(k; E) with
  *      N_A(E) = sum_k sum_b w_b(k; E) A_b(k)     (ABZ_LTM_STATES; likewise g_A with ABZ_LTM_DOS and the corrected N_A with

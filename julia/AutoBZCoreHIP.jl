@@ -644,6 +644,22 @@ function ltm_green_weighted(r::HIPRule, zs::Vector{ComplexF64}; ncomp::Integer=1
 end
 
 """
+    ltm_green_optimized(r, zs; ncomp=0, energy=false)   -> Matrix{ComplexF64} [max(ncomp, 1), nz]
+
+`ltm_green` / `ltm_green_weighted` by the optimized tetrahedron method (`abz_rule_ltm_green_optimized`, `d = 3`): the closed
+forms of the Green's function on the effective corner values of `ltm_optimized`, so that `-imag(G(E + im*eta)) / pi` tends to
+`ltm_optimized(r, [E])` as `eta -> 0`.  `ncomp = 0`: the trace (`LTM_A_ONE`); `energy`: `A = e`; `ncomp > 0`: the attached
+elements.
+"""
+function ltm_green_optimized(r::HIPRule, zs::Vector{ComplexF64}; ncomp::Integer=0, energy::Bool=false)
+    source = energy ? LTM_A_ENERGY : (ncomp > 0 ? LTM_A_ELEMENTS : LTM_A_ONE)
+    out = Matrix{ComplexF64}(undef, source == LTM_A_ELEMENTS ? ncomp : 1, length(zs))
+    check(ccall((:abz_rule_ltm_green_optimized, libabz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Float64}), r.h,
+        source, zs, length(zs), out))
+    return out
+end
+
+"""
     ltm_projectors!(r, pairs)                 -> number of components
 
 Attach the band projectors `P^b[p, q](k) = U[p, b] * conj(U[q, b])` of the orbital pairs `pairs` (1-based tuples `(p, q)`) as
