@@ -84,6 +84,7 @@ enum Switch {
     SW_EVAL_PAIRS,       // ABZ_EVAL_PAIRS      fused grid kernel: one grid line per half-wave where that takes fewer lane-rounds (0: never, 2: wherever supported)
     SW_EVAL_MIRROR,      // ABZ_EVAL_MIRROR     3-D full grids, real Hermitian series: planes k3 <= npt/2 evaluated, H(-k) = conj H(k) stored with them, where the launch writes at most 600 MB (0: never, 2: wherever supported)
     SW_EVAL_PASSWAVE,    // ABZ_EVAL_PASSWAVE   fused pair mapping, pairs of 2 or 4 passes: one pass of a pair per wave where the selection rule takes it (0: never, 2: wherever supported)
+    SW_LTM_OPTW_CHUNK_MB,  // ABZ_LTM_OPTW_CHUNK_MB  weights of the optimized tetrahedron rule: scratch for the corner weights of a slab of grid planes (0: 256 MB)
     SW_COUNT
 };
 int abz_switch(Switch s);  // the switch's integer value from the environment, or its default
@@ -605,6 +606,9 @@ int launch_ltm_unfold(abz_ctx* ctx, PlaneView src, PlaneView dst, const int32_t*
 // Integration weights per node and band (kernels_ltm_nodew.hip).  W: nE n planes tiled like the eigenvalue planes with pitch = row,
 // plane i n + b = w_b(k; Es_host[i]), padding columns zero; 1 <= nE <= ABZ_LTM_NODEW_MAX_E.  Launches only.
 int launch_ltm_node_weights(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView W, const double* Es_host, int nE, int what);
+// The weights of the optimized rule into the same kind of block (kernels_ltm_opt_nodew.hip), d = 3: corner weights of slabs of grid
+// planes in scratch[1] (ABZ_LTM_OPTW_CHUNK_MB), gathered with P transposed.  Launches only, under ABZ_K_LTM.
+int launch_ltm_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, PlaneView W, const double* Es_host, int nE, bool states);
 // out_host [nE][ncomp] = sum_k sum_b w_b(k; E_i) A_{c,b}(k), A an element block of ncomp components; one synchronisation
 // The complex weights of the Green's function (kernels_ltm_green_nodew.hip).  W: 2 nz n planes tiled like the eigenvalue planes with
 // pitch = row, plane (2 i + part) n + b; z_host [nz][2] with Im z != 0.  Launches only.

@@ -1,0 +1,330 @@
+// Optimized tetrahedron method (gfx950 only): the integration weights w_b(k; E) per grid point and band of the rule of
+// kernels_ltm_opt.hip, d = 3, written into a weight block laid out like that of kernels_ltm_nodew.hip.
+//
+// Kawamura, Gohda, Tsuneyuki, PRB 89, 094515 (2014) publish their method as such a set of weights.  The reference has no
+// counterpart (src/dos_algorithms.jl:1-7 plans "LTM").
+//
+//  * Definition.  For every Kuhn simplex T (path t, cell i) and band b the effective corner energies are e'_m = sum_j P[m][j] e_b(p_j)
+//    (ltm_opt_device.h; kernels_ltm_opt.hip has the derivation).  w'_m(T; E), m = 1..4, are the corner weights of the LINEAR rule on
+//    (e'_1..e'_4), in path order, unit = one simplex: the closed forms in the head of kernels_ltm_nodew.hip, half-open regions
+//    e'_1 <= E < e'_4 after sorting; a simplex with max e' <= E gives 1/4 to each corner under ABZ_LTM_STATES and nothing under
+//    ABZ_LTM_DOS, a flat one nothing under ABZ_LTM_DOS.  An element takes the same projection, A'_m = sum_j P[m][j] A(p_j), so the
+//    simplex's sum_m w'_m A'_m is sum_j (sum_m P[m][j] w'_m) A(p_j): the corner weights are scattered with P transposed onto the 20
+//    points, and
+//        w_b(k; E) = 1 / (6 npt^3) sum_t sum_{j = 1..20} sum_{m = 1..4} P[m][j] w'_m(T = (t, cell k - off_{t,j}); E),
+//    off_{t,j} the offset of stencil point j of path t from the cell's corner 0, inside [-1, 2]^3, every index wrapped mod npt
+//    (below npt = 4 a node receives from the same simplex more than once).  sum_k sum_b w A is then the N_A / g_A of
+//    abz_rule_ltm_optimized for ANY A.  The columns of P have negative sums away from the corners: these weights are NOT confined
+//    to [0, 1 / nk], and a node next to the Fermi surface can weigh negative (npt^3 w down to -0.12 has been seen).
+//  * Two kernels per group of NE = 1 or 4 energies (by value, as in ltm_nodew_kernel), no atomics anywhere:
+//    A. ltm_opt_cornerw_kernel<STATES, NE>: one cell per thread, its six simplices one after the other, blockIdx.y the band; the
+//       table and select addressing of ltm_opt_kernel (nothing indexed at run time, no scratch, a 32-bit line stride that the host
+//       checks).  Per simplex 20 loads, the product, a compare-exchange sort that carries each corner's path position along, the
+//       reciprocals once for the group.  It stores the four weights in PATH order for each energy into a workspace of 24 planes
+//       [t 4 + m] per band and energy, cell-contiguous (a wave's store is a run); a simplex outside its window stores 0.0, or
+//       0.25 when it lies wholly below E under STATES: the workspace needs no clearing.
+//    B. ltm_opt_nodew_gather_kernel<NE>: one thread per (column of a padded grid line, band); it sums the 6 x 20 x (the non-zero of
+//       4) terms P[m][j] C[t 4 + m][k - off_{t,j}] in ONE program order (t, then j, then m), multiplies by 1 / (6 npt^3) and
+//       writes plane iE n + b of the weight block; padding columns +0.0.  Consecutive lanes are consecutive i_1: every load is a
+//       shifted run of a line of the workspace.
+//  * Workspace and slabs.  The workspace is scratch of the context, bounded by ABZ_LTM_OPTW_CHUNK_MB (default 256 MB).  Node planes
+//    along axis 3 are taken in slabs of S planes; a slab needs the corner weights of the cells of the planes s - 2 .. s + S, wrapped:
+//    S + 3 planes, the overlap is computed again.  S is as large as the cap allows and at least 1; where S + 3 planes hold the whole
+//    grid there is one slab of npt planes whose plane indices wrap (this is every npt < 4, where wrapped planes coincide).  A
+//    node's sum has the same terms in the same order whatever S is: the block has the same bits for every cap.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "abz_internal.h"
+#include "ltm_device.h"
+#include "ltm_opt_device.h"
+
+namespace abz {
+
+namespace {
+
+struct OptWArgs {
+    PlaneView E, W;  // eigenvalue planes; the weight block (nE n planes per tile, pitch = row)
+    double* C;       // workspace [n][NE][24][nplanes npt^2]
+    int64_t wsplane; // cells of the workspace: nplanes npt^2
+    int npt;
+    int n;
+    int nplanes;     // cell planes in the workspace
+    int cell0;       // grid plane of the workspace's plane 0, inside 0 .. npt-1
+    int node0;       // first node plane of the slab (B)
+    int nnode;       // node planes of the slab (B)
+    int wrap3;       // B: the workspace holds the whole grid, plane = grid plane mod npt (else plane = grid plane - (node0 - 2))
+    int plane0;      // first weight plane of this launch: (its first energy) * n
+    double weight;   // 1 / (6 npt^3)
+    double Es[4];    // the launch's energies (NE of them)
+};
+
+// compare-exchange of two corners: the energies, and each corner's position in the path with them
+__device__ __forceinline__ void optw_cx(double& ea, double& eb, int& pa, int& pb) {
+    const bool sw = eb < ea;
+    const double lo = sw ? eb : ea, hi = sw ? ea : eb;
+    const int x = sw ? pb : pa, y = sw ? pa : pb;
+    ea = lo;
+    eb = hi;
+    pa = x;
+    pb = y;
+}
+
+// index i - o of a periodic axis of npt >= 1 points, o in -1 .. 2
+__device__ __forceinline__ int optw_wrap_back(int i, int o, int npt) {
+    int j = i - o;
+    j += j < 0 ? npt : 0;
+    j += j < 0 ? npt : 0;  // npt = 1: i - 2 is two periods away
+    j -= j >= npt ? npt : 0;
+    return j;
+}
+
+// The three select tables of a path, as in ltm_opt_kernel: what the step o - 1 along the path's first, second and third axis
+// adds to the column and to the line.  j1, j2: wrapped indices of the axes 1, 2; j3: of axis 3, times npt.
+#define OPTW_TABLES(t, j1, j2, j3)                                                  \
+    const int X = (t) >> 1, Y = (X + 1 + ((t) & 1)) % 3, Z = 3 - X - Y;             \
+    int col[3][4], line[3][4];                                                      \
+    _Pragma("unroll") for (int o = 0; o < 4; ++o) {                                 \
+        col[0][o] = X == 0 ? j1[o] : 0;                                             \
+        col[1][o] = Y == 0 ? j1[o] : 0;                                             \
+        col[2][o] = Z == 0 ? j1[o] : 0;                                             \
+        line[0][o] = X == 1 ? j2[o] : (X == 2 ? j3[o] : 0);                         \
+        line[1][o] = Y == 1 ? j2[o] : (Y == 2 ? j3[o] : 0);                         \
+        line[2][o] = Z == 1 ? j2[o] : (Z == 2 ? j3[o] : 0);                         \
+    }
+#define OPTW_COL(j) (col[0][OPT_PT[j][0] + 1] + col[1][OPT_PT[j][1] + 1] + col[2][OPT_PT[j][2] + 1])
+#define OPTW_LINE(j) (line[0][OPT_PT[j][0] + 1] + line[1][OPT_PT[j][1] + 1] + line[2][OPT_PT[j][2] + 1])
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A: corner weights of every simplex of the workspace's cells
+// ---------------------------------------------------------------------------------------------------------------------
+template <bool STATES, int NE>
+__global__ __launch_bounds__(256) void ltm_opt_cornerw_kernel(OptWArgs a) {
+    const int64_t kk = (int64_t)blockIdx.x * 256 + threadIdx.x;  // cell of the workspace: column i1 of line i2 of its plane q
+    if (kk >= a.wsplane) return;
+    const int npt = a.npt;
+    const LtmCell cell = ltm_cell<3>(kk, npt);
+    int i3 = a.cell0 + cell.i3;  // the grid plane of the workspace's plane
+    i3 -= i3 >= npt ? npt : 0;
+    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
+    const int tileE = (int)a.E.tile;  // (the host checks that it fits)
+    int j1[4], j2[4], j3[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        j1[o] = opt_wrap(cell.i1, o - 1, npt);
+        j2[o] = opt_wrap(cell.i2, o - 1, npt);
+        j3[o] = opt_wrap(i3, o - 1, npt) * npt;
+    }
+    double En[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i) En[i] = a.Es[i];
+    // plane [t 4 + m] of energy i of this band: out[(i 24 + t 4 + m) wsplane]
+    double* __restrict__ const out = a.C + (int64_t)blockIdx.y * NE * 24 * a.wsplane + kk;
+#pragma unroll 1
+    for (int t = 0; t < 6; ++t) {
+        OPTW_TABLES(t, j1, j2, j3)
+        double x[OPT_NPT], e[4];
+#pragma unroll
+        for (int j = 0; j < OPT_NPT; ++j) x[j] = Eb[(int64_t)OPTW_LINE(j) * tileE + OPTW_COL(j)];
+        opt_project(x, e);
+        double e1 = e[0], e2 = e[1], e3 = e[2], e4 = e[3];
+        int p1 = 0, p2 = 1, p3 = 2, p4 = 3;
+        optw_cx(e1, e2, p1, p2);
+        optw_cx(e3, e4, p3, p4);
+        optw_cx(e1, e3, p1, p3);
+        optw_cx(e2, e4, p2, p4);
+        optw_cx(e2, e3, p2, p3);
+        bool inside = false;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) inside = inside || (En[i] >= e1 && En[i] < e4);
+        // an unselected region may have zero width: its reciprocal is then inf and never read
+        double r21 = 0.0, r31 = 0.0, r41 = 0.0, r32 = 0.0, r42 = 0.0, r43 = 0.0;
+        if (inside) {
+            r21 = 1.0 / (e2 - e1);
+            r31 = 1.0 / (e3 - e1);
+            r41 = 1.0 / (e4 - e1);
+            r32 = 1.0 / (e3 - e2);
+            r42 = 1.0 / (e4 - e2);
+            r43 = 1.0 / (e4 - e3);
+        }
+        double* __restrict__ const ot = out + (int64_t)(t * 4) * a.wsplane;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) {
+            const double E = En[i];
+            // outside the window: nothing, or the whole simplex (a flat one included)
+            double w1 = STATES && !(E < e4) ? 0.25 : 0.0, w2 = w1, w3 = w1, w4 = w1;
+            if (E >= e1 && E < e4) {
+                if (E < e2) {
+                    const double xx = E - e1, t2 = xx * r21, t3 = xx * r31, t4 = xx * r41;
+                    const double q = STATES ? 0.25 * (t2 * t3 * t4) : t3 * t4 * r21;
+                    w2 = q * t2;
+                    w3 = q * t3;
+                    w4 = q * t4;
+                    w1 = (STATES ? 4.0 : 3.0) * q - (w2 + w3 + w4);
+                } else if (E < e3) {
+                    const double x1 = E - e1, x2 = E - e2;
+                    const double t13 = x1 * r31, t14 = x1 * r41, t23 = x2 * r32, t24 = x2 * r42;
+                    // shares of the vertices P13, P14, P23, P24 and of the corners 1, 2 themselves
+                    double p13, p14, p23, p24, c1, c2;
+                    if (STATES) {
+                        const double v1 = 0.25 * (t13 * t14), v2 = 0.25 * (t14 * t23 * (1.0 - t13)), v3 = 0.25 * ((1.0 - t14) * t23 * t24);
+                        p13 = v1 + v2;
+                        p14 = v1 + v2 + v3;
+                        p23 = v2 + v3;
+                        p24 = v3;
+                        c1 = v1;
+                        c2 = p14;
+                    } else {
+                        const double ga = t13 * (1.0 - t23) * r41, gb = t23 * (1.0 - t24) * r41;
+                        p13 = ga;
+                        p14 = ga + gb;
+                        p23 = p14;
+                        p24 = gb;
+                        c1 = 0.0;
+                        c2 = 0.0;
+                    }
+                    w1 = c1 + p13 * (1.0 - t13) + p14 * (1.0 - t14);
+                    w2 = c2 + p23 * (1.0 - t23) + p24 * (1.0 - t24);
+                    w3 = p13 * t13 + p23 * t23;
+                    w4 = p14 * t14 + p24 * t24;
+                } else {
+                    const double y = e4 - E, s1 = y * r41, s2 = y * r42, s3 = y * r43;
+                    const double q = STATES ? 0.25 * (s1 * s2 * s3) : s1 * s2 * r43;
+                    const double u1 = q * s1, u2 = q * s2, u3 = q * s3, u4 = (STATES ? 4.0 : 3.0) * q - (u1 + u2 + u3);
+                    w1 = STATES ? 0.25 - u1 : u1;
+                    w2 = STATES ? 0.25 - u2 : u2;
+                    w3 = STATES ? 0.25 - u3 : u3;
+                    w4 = STATES ? 0.25 - u4 : u4;
+                }
+            }
+            // back to path order: corner m of the path is the sorted corner whose position is m
+#pragma unroll
+            for (int m = 0; m < 4; ++m) ot[(int64_t)(i * 24 + m) * a.wsplane] = p1 == m ? w1 : (p2 == m ? w2 : (p3 == m ? w3 : w4));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// B: the node's weight, gathered from the corner weights of the simplices whose stencil holds it
+// ---------------------------------------------------------------------------------------------------------------------
+// Thread t of the launch is column t % row of line t / row of the slab's node planes, as in ltm_nodew_kernel.
+template <int NE>
+__global__ __launch_bounds__(256) void ltm_opt_nodew_gather_kernel(OptWArgs a) {
+    const int row = a.W.row, npt = a.npt;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)a.nnode * npt * row) return;
+    const int lline = (int)(t <= 0xffffffffll ? (int64_t)((uint32_t)t / (uint32_t)row) : t / row);  // line inside the slab (below npt^2)
+    const int i1 = (int)(t - (int64_t)lline * row);
+    const int l3 = (int)((uint32_t)lline / (uint32_t)npt);
+    const int i2 = lline - l3 * npt, i3 = a.node0 + l3;
+    const int64_t gline = (int64_t)i3 * npt + i2;
+    double* __restrict__ const out = a.W.base + gline * a.W.tile + (int64_t)(a.plane0 + (int)blockIdx.y) * a.W.pitch + i1;
+    const int64_t wstep = (int64_t)a.n * a.W.pitch;  // from an energy's plane of this band to the next energy's
+    if (i1 >= npt) {
+#pragma unroll
+        for (int i = 0; i < NE; ++i) out[i * wstep] = 0.0;
+        return;
+    }
+    // the cell k - o of every axis, o = -1 .. 2: a column, a line of the workspace's plane, a plane of the workspace (times npt)
+    int j1[4], j2[4], j3[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        j1[o] = optw_wrap_back(i1, o - 1, npt);
+        j2[o] = optw_wrap_back(i2, o - 1, npt);
+        j3[o] = (a.wrap3 ? optw_wrap_back(i3, o - 1, npt) : l3 + 2 - (o - 1)) * npt;
+    }
+    const double* __restrict__ const Cb = a.C + (int64_t)blockIdx.y * NE * 24 * a.wsplane;
+    double acc[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i) acc[i] = 0.0;
+#pragma unroll 1
+    for (int tt = 0; tt < 6; ++tt) {
+        OPTW_TABLES(tt, j1, j2, j3)
+        const double* __restrict__ const Ct = Cb + (int64_t)(tt * 4) * a.wsplane;
+#pragma unroll
+        for (int j = 0; j < OPT_NPT; ++j) {
+            const double* __restrict__ const Cj = Ct + ((int64_t)OPTW_LINE(j) * npt + OPTW_COL(j));
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                if (OPT_K[m][j] == 0) continue;
+#pragma unroll
+                for (int i = 0; i < NE; ++i) acc[i] = fma((double)OPT_K[m][j] / 1260.0, Cj[(int64_t)(i * 24 + m) * a.wsplane], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NE; ++i) out[i * wstep] = a.weight * acc[i];
+}
+
+#undef OPTW_TABLES
+#undef OPTW_COL
+#undef OPTW_LINE
+
+using OptWFn = void (*)(OptWArgs);
+// [states][NE == 4]
+constexpr OptWFn OPTW_CORNER[2][2] = {
+    {ltm_opt_cornerw_kernel<false, 1>, ltm_opt_cornerw_kernel<false, 4>},
+    {ltm_opt_cornerw_kernel<true, 1>, ltm_opt_cornerw_kernel<true, 4>},
+};
+constexpr OptWFn OPTW_GATHER[2] = {ltm_opt_nodew_gather_kernel<1>, ltm_opt_nodew_gather_kernel<4>};
+
+}  // namespace
+
+// The block W (nE n planes, tiled like the eigenvalue planes E with pitch = row, padding columns included) <- the weights of the
+// optimized rule at Es[i].  Launches only; groups of 4 energies, then single ones; per group the slabs one after the other.
+int launch_ltm_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, PlaneView W, const double* Es_host, int nE, bool states) {
+    if (E.tile > INT32_MAX || (int64_t)npt * npt > INT32_MAX) {
+        set_error("abz_rule_ltm_node_weights_optimized: a stride of %lld doubles between grid lines does not fit the kernel's 32-bit factor",
+                  (long long)E.tile);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    OptWArgs a;
+    a.E = E;
+    a.W = W;
+    a.npt = npt;
+    a.n = n;
+    a.weight = 1.0 / (6.0 * (double)npt * (double)npt * (double)npt);
+    const int64_t mb = abz_switch(SW_LTM_OPTW_CHUNK_MB) > 0 ? abz_switch(SW_LTM_OPTW_CHUNK_MB) : 256;
+    const int64_t cells = (int64_t)npt * npt;  // of a plane
+    // The slab height of a group of ne energies: S + 3 planes of 24 n ne doubles per cell within the cap, S >= 1.  One slab of npt
+    // wrapped planes where those S + 3 planes hold the whole grid.
+    auto slab = [&](int ne) {
+        const int64_t plane_bytes = (int64_t)sizeof(double) * 24 * n * ne * cells;
+        const int64_t fit = (mb << 20) / plane_bytes;
+        return (int)std::min<int64_t>(npt, std::max<int64_t>(1, fit - 3));
+    };
+    auto planes_of = [&](int S) { return S + 3 >= npt ? npt : S + 3; };
+    size_t need = 0;
+    for (int ne : {1, 4})
+        if (ne == 1 ? (nE % 4 != 0 || nE < 4) : nE >= 4)
+            need = std::max(need, sizeof(double) * 24 * (size_t)n * (size_t)ne * (size_t)planes_of(slab(ne)) * (size_t)cells);
+    const int rc = ctx->scratch[1].reserve(need);
+    if (rc) return rc;
+    a.C = ctx->scratch[1].as<double>();
+    ProfScope ps(ctx, ABZ_K_LTM);
+    for (int i0 = 0; i0 < nE;) {
+        const int ne = nE - i0 >= 4 ? 4 : 1;
+        for (int i = 0; i < 4; ++i) a.Es[i] = Es_host[i0 + std::min(i, ne - 1)];
+        a.plane0 = i0 * n;
+        const int S = slab(ne);
+        const bool whole = S + 3 >= npt;
+        for (int s0 = 0; s0 < npt; s0 += whole ? npt : S) {
+            a.node0 = s0;
+            a.nnode = whole ? npt : std::min(S, npt - s0);
+            a.nplanes = whole ? npt : a.nnode + 3;
+            a.wrap3 = whole;
+            a.cell0 = whole ? 0 : (s0 + npt - 2) % npt;  // (S + 3 < npt here: npt >= 5)
+            a.wsplane = (int64_t)a.nplanes * cells;
+            launch(ctx, OPTW_CORNER[states][ne == 4], dim3((unsigned)cdiv64(a.wsplane, 256), (unsigned)n), dim3(256), 0, a);
+            ABZ_HIP(hipGetLastError());
+            launch(ctx, OPTW_GATHER[ne == 4], dim3((unsigned)cdiv64((int64_t)a.nnode * npt * W.row, 256), (unsigned)n), dim3(256), 0, a);
+            ABZ_HIP(hipGetLastError());
+        }
+        i0 += ne;
+    }
+    return ABZ_OK;
+}
+
+}  // namespace abz

@@ -461,6 +461,41 @@ int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, do
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
+// The weights of the optimized rule into the same resident block (kernels_ltm_opt_nodew.hip).  Every check comes before anything is
+// reserved or launched; the block replaces the resident one as in abz_rule_ltm_node_weights.
+int abz_rule_ltm_node_weights_optimized(abz_rule* r, const double* E, int nE, int what, double* out) try {
+    const char* const who = "abz_rule_ltm_node_weights_optimized";
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(E, "abz_rule_ltm_node_weights_optimized: null energies");
+    ABZ_REQUIRE(nE >= 1 && nE <= ABZ_LTM_NODEW_MAX_E, "abz_rule_ltm_node_weights_optimized: nE = %d outside 1..%d", nE, ABZ_LTM_NODEW_MAX_E);
+    ABZ_REQUIRE(what != ABZ_LTM_STATES_CORRECTED, "abz_rule_ltm_node_weights_optimized: ABZ_LTM_STATES_CORRECTED: the optimized rule replaces the "
+                                                  "curvature correction (ask for ABZ_LTM_STATES)");
+    if ((rc = ltm_check_what(who, what, false))) return rc;
+    for (int i = 0; i < nE; ++i) ABZ_REQUIRE(std::isfinite(E[i]), "abz_rule_ltm_node_weights_optimized: E[%d] = %g is not finite", i, E[i]);
+    if (r->s->d != 3) {
+        set_error("abz_rule_ltm_node_weights_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = rule_bands(r);
+    LtmBlock block;
+    if ((rc = block.alloc(r->E, r->ntiles, n, nE))) return rc;
+    rc = launch_ltm_node_weights_optimized(ctx, n, r->npt, r->E, block.view, E, nE, what == ABZ_LTM_STATES);
+    // the block is complete before anything of it reaches `out`: a kernel that failed leaves `out` as it was
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_node_weights_optimized: the kernel failed");
+        rc = ABZ_ERR_HIP;
+    }
+    for (int i = 0; i < nE && !rc && out; ++i)  // one energy [nk][n] at a time, in the node and band order of abz_rule_export's eig
+        rc = export_planes(ctx, block.set_view(i, n), n, r->nk, out + (size_t)i * (size_t)r->nk * (size_t)n);  // (returns when the data has arrived)
+    if (rc) return rc;
+    r->nodew = std::move(block);  // (the previous weights go here)
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nE) try {
     return ltm_block_ptr(r, &abz_rule::nodew, 1, base, nbytes, nE);
 } ABZ_CATCH_ALL

@@ -649,7 +649,7 @@ def band_energy(prob_or_cache, nstates, tol=1e-10, correction=True):
     return float(u[0, 0]), E_F
 
 
-def integration_weights(prob_or_cache, E=None, nstates=None, kind="states", correction=False, fold=False):
+def integration_weights(prob_or_cache, E=None, nstates=None, kind="states", correction=False, fold=False, optimized=False):
     """(W, E): Bloechl's integration weights w_b(k; E) of the grid of an LTM cache, or of a DOSProblem (solved with LTM()), and
     the energies they belong to.  Exactly one of `E` (at most 16 energies; W is [nE, nk, n], [nk, n] for a scalar) and `nstates`
     (W [nk, n] at `fermi_level`'s energy on the same rule: the occupations of that filling) is given.  `kind`: "states"
@@ -657,14 +657,25 @@ def integration_weights(prob_or_cache, E=None, nstates=None, kind="states", corr
     sums at the grid's own Fermi level.  Nodes and bands are ordered like the eigenvalues of the cache's rule
     (`cache.cacheval.export(eig=True)`).  With `LTM(symmetric=True)` on a symmetric zone and `fold=True` the weights come back
     summed over orbits on the irreducible nodes that were solved, [.., nirr, n] in the order of
-    `cache.cacheval.source.export(eig=True)`; anywhere else `fold=True` raises ValueError."""
+    `cache.cacheval.source.export(eig=True)`; anywhere else `fold=True` raises ValueError.
+    `optimized=True` (d = 3): the weights of the optimized tetrahedron rule instead (DeviceRule.ltm_node_weights_optimized):
+    sum_k sum_b W A is the N_A / g_A of LTM(optimized=True) for any A, and with `nstates` the level is
+    `fermi_level(cache, nstates, optimized=True)`, so the occupations sum to `nstates`.  These weights are not confined to
+    [0, 1 / nk]: a node next to the Fermi surface can weigh negative.  It does not go with `correction` (ValueError); d < 3 and a
+    k-sharded series raise NotImplementedError.  The default is the linear rule whatever the cache's algorithm is (the
+    convention of `green_trace`): on an LTM(optimized=True) cache with `nstates` the default takes that cache's optimized level
+    and returns linear weights there, which do not sum to `nstates`."""
     if (E is None) == (nstates is None):
         raise ValueError("integration_weights: give exactly one of E and nstates")
+    if optimized and correction:
+        raise ValueError("integration_weights: optimized=True replaces the curvature correction: it does not go with correction=True")
     if kind not in ("states", "dos"):
         raise ValueError(f"integration_weights: kind = {kind!r} is neither 'states' nor 'dos'")
     if correction and kind != "states":
         raise ValueError("integration_weights: correction=True corrects the state sum: it needs kind='states' (the DOS has no correction)")
     H = getattr(prob_or_cache, "H", None)
+    if optimized and isinstance(H, FourierSeries) and H.d != 3:  # (before a device is asked for anything)
+        raise NotImplementedError(f"integration_weights: optimized=True is implemented for d = 3 (the series has d = {H.d})")
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
         raise NotImplementedError("integration_weights on a k-sharded series is not implemented: a node's weight needs its whole "
                                   "neighbourhood, which a slab with its halo plane does not hold")
@@ -679,14 +690,20 @@ def integration_weights(prob_or_cache, E=None, nstates=None, kind="states", corr
     if fold and not hasattr(rule, "ltm_node_weights_fold"):
         raise ValueError("integration_weights: fold=True needs an LTM(symmetric=True) cache on a symmetric zone (nothing was unfolded)")
     scalar = nstates is not None or np.ndim(E) == 0
-    Es = np.array([fermi_level(c, nstates)[0]]) if nstates is not None else np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
-    W = rule.ltm_node_weights(Es, states=kind == "states", correction=bool(correction), export=not fold)
+    if nstates is not None:
+        Es = np.array([(fermi_level(c, nstates, optimized=True) if optimized else fermi_level(c, nstates))[0]])
+    else:
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
+    if optimized:
+        W = rule.ltm_node_weights_optimized(Es, states=kind == "states", export=not fold)
+    else:
+        W = rule.ltm_node_weights(Es, states=kind == "states", correction=bool(correction), export=not fold)
     if fold:
         W = rule.ltm_node_weights_fold()
     return (W[0], float(Es[0])) if scalar else (W, Es)
 
 
-def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correction=False, orbitals=None):
+def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correction=False, orbitals=None, optimized=False):
     """(rho, E): the density matrix rho_pq(E) = sum_k sum_b w_b(k; E) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
     on the grid of an LTM cache or of a DOSProblem (solved with LTM()), and the energies it belongs to
     (DeviceRule.ltm_density_matrix: Bloechl's weights contracted with the eigenvectors inside one eigen-solve of the grid).
@@ -694,9 +711,15 @@ def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correctio
     `fermi_level`'s energy on the same rule: the occupation matrix of that filling, tr rho = nstates) is given.  `kind`:
     "states" (occupations) or "dos" (the spectral-density matrix, tr rho = g(E)); `correction=True` (with "states") adds
     Bloechl's curvature correction.  `orbitals` (None: all n) selects the sub-block.  The cache's attached elements stay as
-    they are; the rule's resident integration weights are replaced by those of E."""
+    they are; the rule's resident integration weights are replaced by those of E.
+    `optimized=True` (d = 3): the weights of the optimized tetrahedron rule instead (DeviceRule.ltm_node_weights_optimized), and
+    with `nstates` the level of `fermi_level(cache, nstates, optimized=True)`: tr rho = nstates on that rule.  It does not go with
+    `correction` (ValueError); d < 3 and a k-sharded series raise NotImplementedError.  The default is the linear rule whatever the
+    cache's algorithm is."""
     if (E is None) == (nstates is None):
         raise ValueError("density_matrix: give exactly one of E and nstates")
+    if optimized and correction:
+        raise ValueError("density_matrix: optimized=True replaces the curvature correction: it does not go with correction=True")
     if kind not in ("states", "dos"):
         raise ValueError(f"density_matrix: kind = {kind!r} is neither 'states' nor 'dos'")
     if correction and kind != "states":
@@ -704,6 +727,8 @@ def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correctio
     H = getattr(prob_or_cache, "H", None)
     if isinstance(H, FourierSeries):
         density_matrix_orbitals(orbitals, H.n, "density_matrix")
+        if optimized and H.d != 3:  # (before a device is asked for anything)
+            raise NotImplementedError(f"density_matrix: optimized=True is implemented for d = 3 (the series has d = {H.d})")
         if _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
             raise NotImplementedError("density_matrix on a k-sharded series is not implemented: a node's weight needs its whole "
                                       "neighbourhood, which a slab with its halo plane does not hold")
@@ -718,8 +743,11 @@ def density_matrix(prob_or_cache, E=None, nstates=None, kind="states", correctio
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     scalar = nstates is not None or np.ndim(E) == 0
-    Es = np.array([fermi_level(c, nstates)[0]]) if nstates is not None else np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
-    rho = c.cacheval.ltm_density_matrix(Es, states=kind == "states", correction=bool(correction), orbitals=orbitals)
+    if nstates is not None:
+        Es = np.array([(fermi_level(c, nstates, optimized=True) if optimized else fermi_level(c, nstates))[0]])
+    else:
+        Es = np.atleast_1d(np.asarray(E, dtype=np.float64)).reshape(-1)
+    rho = c.cacheval.ltm_density_matrix(Es, states=kind == "states", correction=bool(correction), orbitals=orbitals, optimized=bool(optimized))
     return (rho[0], float(Es[0])) if scalar else (rho, Es)
 
 

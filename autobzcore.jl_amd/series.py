@@ -1117,6 +1117,28 @@ class DeviceRule:
                                                   out.ctypes.data_as(L.c_f64p) if export else None))
         return out
 
+    def ltm_node_weights_optimized(self, Es, states=True, export=True):
+        """The integration weights w_b(k; E) of the optimized tetrahedron rule (abz_rule_ltm_node_weights_optimized; d = 3),
+        [nE, nk, n] in the node and band order of export()'s eig: sum_k sum_b w A is the N_A(E) (`states`, the default) or
+        g_A(E) (`states=False`) of `ltm_optimized` for ANY A; they sum to N(E) or g(E), and the occupations at
+        `ltm_fermi_optimized`'s level sum to its state count.  Every simplex scatters the corner weights of the linear rule
+        on its effective corner energies onto its 20 stencil points, so these weights are NOT confined to [0, 1 / nk]: a node
+        next to the Fermi surface can weigh negative (nk w down to -0.12 has been seen).  There is no `correction`: this
+        rule replaces it.  At most 16 energies per call, in any order.  The weights fill the same resident block as those of
+        `ltm_node_weights`: `ltm_node_weights_ptr`, `ltm_node_weights_dot`, `ltm_node_weights_fold` and `ltm_density_matrix`
+        (Es=None) work on them as they are; `export=False` (returns None) skips the copy to the host.  Two calls return the
+        same bits, whatever ABZ_LTM_OPTW_CHUNK_MB (the scratch of a slab of grid planes) is.  The rule must be a whole
+        periodic grid (an unfolded rule is one); NotImplementedError on a k-sharded rule and for d < 3."""
+        self._ltm_refuse_optimized("ltm_node_weights_optimized")
+        Es = np.ascontiguousarray(np.asarray(Es, dtype=np.float64).reshape(-1))
+        if not 1 <= len(Es) <= L.LTM_NODEW_MAX_E:
+            raise ValueError(f"ltm_node_weights_optimized: {len(Es)} energies, a call takes 1..{L.LTM_NODEW_MAX_E}")
+        h = self.h  # (a stale rule is refilled here, which drops the weights it held)
+        out = np.empty((len(Es), self.nk, self.nbands)) if export else None
+        L.check(L.lib().abz_rule_ltm_node_weights_optimized(h, Es.ctypes.data_as(L.c_f64p), len(Es), L.LTM_STATES if states else L.LTM_DOS,
+                                                            out.ctypes.data_as(L.c_f64p) if export else None))
+        return out
+
     def ltm_node_weights_ptr(self):
         """(device address, bytes, nE) of the resident weight block of `ltm_node_weights`; (0, 0, 0) when there is none."""
         self._ltm_refuse_shard("ltm_node_weights_ptr")
@@ -1150,7 +1172,7 @@ class DeviceRule:
         L.check(getattr(L.lib(), f"abz_rule_{weights}_dot")(h, out.view(np.float64).ctypes.data_as(L.c_f64p)))
         return out
 
-    def ltm_density_matrix(self, Es=None, states=True, correction=False, orbitals=None):
+    def ltm_density_matrix(self, Es=None, states=True, correction=False, orbitals=None, optimized=False):
         """The density matrix rho_pq(E) = sum_k sum_b w_b(k; E) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
         complex128 [nE, m, m] (abz_rule_ltm_density_matrix): the resident weights of `ltm_node_weights` contracted with the
         eigenvectors inside one eigen-solve of the grid; U(k) and the band projectors never reach memory.  With `Es` the
@@ -1159,11 +1181,20 @@ class DeviceRule:
         (`correction`) or the spectral-density matrix (`states=False`).  Hermitian to the bit; tr rho is N(E) or g(E); two
         calls return the same bits.  `orbitals` (None: all n) selects the sub-block rho[orbitals][:, orbitals] on the host.
         Nothing is attached: elements and weights stay as they were.  1...32 bands, a whole periodic grid with H(k) (not an
-        unfolded rule); a k-sharded rule raises NotImplementedError."""
+        unfolded rule); a k-sharded rule raises NotImplementedError.  `optimized=True` (d = 3, with `Es`): the weights are
+        those of the optimized tetrahedron rule (`ltm_node_weights_optimized`), tr rho the N(E) or g(E) of `ltm_optimized`;
+        it does not go with `correction`."""
         self._ltm_refuse_shard("ltm_density_matrix")
+        if optimized and correction:
+            raise ValueError("ltm_density_matrix: optimized=True replaces the curvature correction: it does not go with correction=True")
+        if optimized and Es is None:
+            raise ValueError("ltm_density_matrix: optimized=True makes the weights of Es (the resident ones are what the call that made "
+                             "them says: give Es, or leave optimized out)")
         n = self.dev.s.n
         orb = density_matrix_orbitals(orbitals, n)
-        if Es is not None:
+        if Es is not None and optimized:
+            self.ltm_node_weights_optimized(Es, states=states, export=False)
+        elif Es is not None:
             self.ltm_node_weights(Es, states=states, correction=correction, export=False)
         h = self.h  # (a stale rule is refilled here, which drops the weights it held)
         _, _, nE = self.ltm_node_weights_ptr()

@@ -588,6 +588,26 @@ int abz_rule_ltm_node_weights_dot(abz_rule* r, double* out /* [nE][ncomp] */);
  * map is made at the first call and kept (8 B per node, 4 B per grid point, counted by abz_mem_info).  No floating-point atomics:
  * two calls return the same bits.  ABZ_ERR_ARG: a rule that was not unfolded, no resident weights, out == NULL. */
 int abz_rule_ltm_node_weights_fold(abz_rule* r, double* out /* [nE][nirr][n] */);
+/* The integration weights of the OPTIMIZED tetrahedron rule (abz_rule_ltm_optimized; Kawamura, Gohda, Tsuneyuki, who publish the
+ * method in this form), d = 3: the numbers w_b(k; E) with
+ *      sum_k sum_b w_b(k; E) A_b(k) = the N_A(E) (ABZ_LTM_STATES) or g_A(E) (ABZ_LTM_DOS) of abz_rule_ltm_optimized
+ * for ANY A; sum w = N(E) or g(E), sum w e = the ABZ_LTM_A_ENERGY sums.  Every Kuhn simplex forms the corner weights of the
+ * linear rule on its effective corner energies e' = P e and scatters them with P transposed onto its 20 stencil points:
+ *      w_b(k; E) = 1 / (6 npt^3) sum_t sum_j sum_m P[m][j] w'_m(simplex t of the cell k - off_{t,j}; E),
+ * every index wrapped mod npt (any npt >= 1).  Half-open regions e'_1 <= E < e'_4; a simplex with max e' <= E gives 1/4 to each
+ * corner under ABZ_LTM_STATES, a flat one nothing under ABZ_LTM_DOS.  The columns of P have negative sums away from the corners:
+ * these weights are NOT confined to [0, 1 / nk], and a node next to the Fermi surface can weigh negative (nk w down to -0.12 has
+ * been seen).  Where every e' lies above E the weights are 0.0 exactly; where every e' lies below E they are 1 / nk to rounding.
+ * Arguments, order of `out` and limits are those of abz_rule_ltm_node_weights, and the weights fill the SAME resident block:
+ * abz_rule_ltm_node_weights_ptr, _dot, _fold and abz_rule_ltm_density_matrix then work on the optimized weights as they are.
+ * No atomics: two calls write the same bits, and so does every value of the switch ABZ_LTM_OPTW_CHUNK_MB, which bounds the
+ * scratch the corner weights of a slab of grid planes take (not part of the rule, not resident).
+ * Takes full-grid rules and rules of abz_rule_ltm_unfold.  ABZ_ERR_ARG: a rule without eigenvalues, E == NULL, nE outside
+ * 1..ABZ_LTM_NODEW_MAX_E, a non-finite energy, a `what` that is neither ABZ_LTM_DOS nor ABZ_LTM_STATES
+ * (ABZ_LTM_STATES_CORRECTED is refused: this rule replaces the correction).  ABZ_ERR_UNSUPPORTED: d != 3, slabs with or without
+ * a halo, lists of irreducible nodes, a stride between grid lines beyond 2^31 doubles.  A refusal or failure leaves the resident
+ * weights as they were; a refusal, or a failure of the kernels (the copy to `out` starts after they have finished), `out` too.  Entry point added without a change of ABZ_VERSION. */
+int abz_rule_ltm_node_weights_optimized(abz_rule* r, const double* E, int nE, int what, double* out /* [nE][nk][n] or NULL */);
 /* The density matrix in the orbital basis from the resident weights and the eigenvectors U(k) of Hermitian(H(k)), bands ascending:
  *      rho_pq(E_i) = sum_k sum_b w_b(k; E_i) U_pb(k) conj(U_qb(k)),      out [nE][n][n][2], per unit cell,
  * for the nE energies of the last abz_rule_ltm_node_weights call, whose `what` says what rho is: the occupation matrix

@@ -715,6 +715,23 @@ function ltm_green_matrix(r::HIPRule, zs::Vector{ComplexF64}, n::Integer; orbita
 end
 
 """
+    ltm_node_weights_optimized(r, Es, n; cumulative=true, export_weights=true)  -> Array{Float64,3} [n, nk, nE] or nothing
+
+The integration weights `W[b, k, i] = w_b(k; E_i)` of the optimized tetrahedron rule on an `n`-band whole-grid rule, `d = 3`
+(`abz_rule_ltm_node_weights_optimized`): `sum_k sum_b w_b(k; E) A_b(k)` is the `N_A` (`cumulative`) or `g_A` of `ltm_optimized`
+for any `A`.  Every simplex scatters the corner weights of the linear rule on its effective corner energies onto its 20 stencil
+points, so the weights are not confined to `[0, 1 / nk]`: a node next to the Fermi surface can weigh negative.  At most 16
+energies.  The weights stay resident on the rule, in the block that `ltm_density_matrix` reads.
+"""
+function ltm_node_weights_optimized(r::HIPRule, Es::Vector{Float64}, n::Integer; cumulative::Bool=true, export_weights::Bool=true)
+    1 <= length(Es) <= 16 || throw(ArgumentError("ltm_node_weights_optimized: $(length(Es)) energies, a call takes 1..16"))
+    out = export_weights ? Array{Float64}(undef, n, r.nk, length(Es)) : nothing
+    GC.@preserve Es out check(ccall((:abz_rule_ltm_node_weights_optimized, libabz), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Float64}),
+                                    r.h, Es, length(Es), cumulative ? LTM_STATES : LTM_DOS, export_weights ? pointer(out) : C_NULL))
+    return out
+end
+
+"""
     ltm_density_matrix(r, n; orbitals=1:n)     -> Array{ComplexF64,3} [m, m, nE]
 
 The density matrix `rho[p, q](E) = sum_k sum_b w_b(k; E) U[p, b](k) conj(U[q, b](k))` on the listed orbitals of an `n`-band rule,
