@@ -75,6 +75,7 @@ PROTOTYPES = {
     "abz_rule_ltm_node_weights_fold": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_rule_ltm_density_matrix": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_rule_ltm_green_node_weights": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
+    "abz_rule_ltm_green_node_weights_optimized": (C.c_int, [C.c_void_p, c_f64p, C.c_int, c_f64p]),
     "abz_rule_ltm_green_node_weights_ptr": (C.c_int, [C.c_void_p, c_vpp, c_i64p, c_ip]),
     "abz_rule_ltm_green_node_weights_dot": (C.c_int, [C.c_void_p, c_f64p]),
     "abz_rule_ltm_green_node_weights_fold": (C.c_int, [C.c_void_p, c_f64p]),

@@ -613,6 +613,10 @@ int launch_ltm_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneView E,
 // The complex weights of the Green's function (kernels_ltm_green_nodew.hip).  W: 2 nz n planes tiled like the eigenvalue planes with
 // pitch = row, plane (2 i + part) n + b; z_host [nz][2] with Im z != 0.  Launches only.
 int launch_ltm_green_node_weights(abz_ctx* ctx, int n, int d, int npt, PlaneView E, PlaneView W, const double* z_host, int nz);
+// The complex weights W_b(k; z) of the optimized rule into the same kind of block, d = 3 (kernels_ltm_green_opt_nodew.hip): complex
+// corner weights of slabs of grid planes in scratch[1] (ABZ_LTM_OPTW_CHUNK_MB), gathered with P transposed by the gather kernel of
+// the real weights.  Launches only, under ABZ_K_LTM.
+int launch_ltm_green_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, PlaneView W, const double* z_host, int nz);
 int launch_ltm_node_weights_dot(abz_ctx* ctx, int n, int npt, int64_t nlines, PlaneView W, int nE, PlaneView A, int ncomp, double* out_host);
 // host: the inverse of an orbit map node_of [N] with entries inside 0 .. nirr-1: start [nirr + 1], member [N] (ascending per orbit)
 void ltm_orbit_inverse(const int32_t* node_of, int64_t N, int64_t nirr, std::vector<int64_t>& start, std::vector<int32_t>& member);

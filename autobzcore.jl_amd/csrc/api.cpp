@@ -93,7 +93,7 @@ const SwitchDef g_switches[SW_COUNT] = {
     {"ABZ_EVAL_PAIRS", 1, "fused grid kernel, one grid line per half-wave: 1 where it takes fewer lane-rounds per line (Hermitian series), 0 never, 2 wherever supported (tests: same values)"},
     {"ABZ_EVAL_MIRROR", 1, "3-D full-grid rules (n <= 4) of a real Hermitian series evaluate the planes k3 <= npt/2 and store H(-k) = conj H(k) beside them: 1 where the launch writes at most 600 MB, 0 never (every plane evaluated), 2 wherever supported"},
     {"ABZ_EVAL_PASSWAVE", 1, "fused pair mapping of Hermitian series, pairs of 2 or 4 passes: one pass of a pair per wave instead of a pair per wave: 1 by the selection rule, 0 never, 2 wherever supported (tests: same values)"},
-    {"ABZ_LTM_OPTW_CHUNK_MB", 0, "abz_rule_ltm_node_weights_optimized: MB of scratch for the corner weights of a slab of grid planes (0: 256; every value gives the same bits; tests set 1 to walk many slabs)"},
+    {"ABZ_LTM_OPTW_CHUNK_MB", 0, "abz_rule_ltm_node_weights_optimized, abz_rule_ltm_green_node_weights_optimized: MB of scratch for the corner weights of a slab of grid planes (0: 256; every value gives the same bits; tests set 1 to walk many slabs)"},
 };
 }  // namespace
 

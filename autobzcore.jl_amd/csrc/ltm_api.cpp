@@ -631,6 +631,47 @@ int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z, int nz, double
     return ABZ_OK;
 } ABZ_CATCH_ALL
 
+// The complex weights of the optimized rule into the same resident block (kernels_ltm_green_opt_nodew.hip).  Every check comes
+// before anything is reserved or launched; the block is complete before anything of it reaches `out` and before it replaces the
+// resident one.
+int abz_rule_ltm_green_node_weights_optimized(abz_rule* r, const double* z, int nz, double* out) try {
+    const char* const who = "abz_rule_ltm_green_node_weights_optimized";
+    int rc = check_rule(r);
+    if (rc) return rc;
+    ABZ_REQUIRE(z, "abz_rule_ltm_green_node_weights_optimized: null z");
+    ABZ_REQUIRE(nz >= 1 && nz <= ABZ_LTM_GREEN_NODEW_MAX_Z, "abz_rule_ltm_green_node_weights_optimized: nz = %d outside 1..%d", nz,
+                ABZ_LTM_GREEN_NODEW_MAX_Z);
+    if ((rc = ltm_check_zs(who, z, nz, "G is"))) return rc;
+    if (r->s->d != 3) {
+        set_error("abz_rule_ltm_green_node_weights_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = rule_bands(r);
+    LtmBlock block;
+    if ((rc = block.alloc(r->E, r->ntiles, n, 2 * nz))) return rc;
+    rc = launch_ltm_green_node_weights_optimized(ctx, n, r->npt, r->E, block.view, z, nz);
+    // the block is complete before anything of it reaches `out`: a kernel that failed leaves `out` as it was
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("abz_rule_ltm_green_node_weights_optimized: the kernel failed");
+        rc = ABZ_ERR_HIP;
+    }
+    if (!rc && out) {
+        // the two real sets [nk][n] of one z at a time through the staging of the export, interleaved on the host
+        const size_t per = (size_t)r->nk * (size_t)n;
+        std::vector<double> pair(2 * per);
+        for (int i = 0; i < 2 * nz && !rc; ++i) {
+            rc = export_planes(ctx, block.set_view(i, n), n, r->nk, pair.data() + (size_t)(i & 1) * per);  // (returns when the data has arrived)
+            if (!rc && (i & 1)) interleave_sets(pair.data(), 1, per, out + (size_t)(i >> 1) * per * 2);
+        }
+    }
+    if (rc) return rc;
+    r->gnodew = std::move(block);  // (the previous complex weights go here)
+    return ABZ_OK;
+} ABZ_CATCH_ALL
+
 int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nz) try {
     return ltm_block_ptr(r, &abz_rule::gnodew, 2, base, nbytes, nz);
 } ABZ_CATCH_ALL

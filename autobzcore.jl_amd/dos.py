@@ -550,11 +550,13 @@ def _green_local_check(c, who):
                          "an unfolded rule stores no H(k))")
 
 
-def _green_local(prob_or_cache, zs, orbitals, fused):
+def _green_local(prob_or_cache, zs, orbitals, fused, optimized=False):
     who = "green_local_fused" if fused else "green_local"
     if fused and isinstance(prob_or_cache, DOSCache):  # (a cache says what it is without its series' device being asked)
         _green_local_check(prob_or_cache, who)
     H = getattr(prob_or_cache, "H", None)
+    if optimized and isinstance(H, FourierSeries) and H.d != 3:  # (before a device is asked for anything)
+        raise NotImplementedError(f"{who}: optimized=True is implemented for d = 3 (the series has d = {H.d})")
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
         raise NotImplementedError(f"{who} on a k-sharded series is not implemented: the Green's function is computed on "
                                   "whole grids")
@@ -565,7 +567,7 @@ def _green_local(prob_or_cache, zs, orbitals, fused):
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     if fused:
-        return c.cacheval.ltm_green_node_weights_matrix(zs, orbitals)
+        return c.cacheval.ltm_green_node_weights_matrix(zs, orbitals, optimized=bool(optimized))
     return c.cacheval.ltm_green_matrix(zs, orbitals)
 
 
@@ -583,7 +585,7 @@ def green_local(prob_or_cache, zs, orbitals=None):
     return _green_local(prob_or_cache, zs, orbitals, False)
 
 
-def green_local_fused(prob_or_cache, zs, orbitals=None):
+def green_local_fused(prob_or_cache, zs, orbitals=None, optimized=False):
     """`green_local` by the other route (DeviceRule.ltm_green_node_weights_matrix): the complex integration weights W_b(k; z)
     are gathered per node, 8 values of z at a time, and contracted with the eigenvectors by the kernel of `density_matrix`;
     no projector is attached and the cache's elements stay as they are.  Same solver, same basis, same arguments and refusals;
@@ -593,18 +595,27 @@ def green_local_fused(prob_or_cache, zs, orbitals=None):
     simplices of a scan, one series per simplex where it is narrow) and solves the grid once per 4 weight sets for 1...4 bands,
     twice per z for 5...32 bands.  Measured (profiles/ltm_green_node_weights.txt): 1.25 times faster than `green_local` for 3
     bands at one z and 1.05 times at 8 and 64; 16...26 times faster for 16 bands and 27...55 times for 32 bands at 64...1 values.
-    It holds a weight block of 16 nz n bytes per node (8 values at a time) that `green_local` does not need."""
-    return _green_local(prob_or_cache, zs, orbitals, True)
+    It holds a weight block of 16 nz n bytes per node (8 values at a time) that `green_local` does not need.
+    `optimized=True` (d = 3): the weights of the optimized tetrahedron rule instead
+    (DeviceRule.ltm_green_node_weights_optimized): tr G_pq(z) is then `green_trace(cache, zs, optimized=True)` and -Im G_pp / pi
+    tends to the projected DOS of LTM(optimized=True) as Im z -> 0.  The default is the linear rule whatever the cache's algorithm
+    is (the convention of `green_trace`); d < 3 and a k-sharded series raise NotImplementedError.  `green_local` has no such
+    keyword: its scan route serves the linear rule."""
+    return _green_local(prob_or_cache, zs, orbitals, True, optimized)
 
 
-def green_weights(prob_or_cache, zs, fold=False):
+def green_weights(prob_or_cache, zs, fold=False, optimized=False):
     """(W, zs): the complex integration weights W_b(k; z) of the Green's function on the grid of an LTM cache, or of a DOSProblem
     (solved with LTM()), and the values of z they belong to: G_A(z) = sum_k sum_b W_b(k; z) A_b(k) for ANY A, complex or
     matrix-valued (DeviceRule.ltm_green_node_weights).  At most 8 values, Im z != 0; W is complex128 [nz, nk, n], [nk, n] for a
     scalar z.  Nodes and bands are ordered like the eigenvalues of the cache's rule (`cache.cacheval.export(eig=True)`).  With
     `LTM(symmetric=True)` on a symmetric zone and `fold=True` the weights come back summed over orbits on the irreducible nodes
     that were solved, [.., nirr, n] in the order of `cache.cacheval.source.export(eig=True)`: G_loc(z) is then a sum over
-    those nodes followed by the caller's own symmetrisation; anywhere else `fold=True` raises ValueError."""
+    those nodes followed by the caller's own symmetrisation; anywhere else `fold=True` raises ValueError.
+    `optimized=True` (d = 3): the weights of the optimized tetrahedron rule instead (DeviceRule.ltm_green_node_weights_optimized):
+    sum_k sum_b W A is the G_A(z) of `green_weighted(..., optimized=True)` for any A and sum W is `green_trace(..., optimized=True)`.
+    The default is the linear rule whatever the cache's algorithm is (the convention of `green_trace`); d < 3 and a k-sharded
+    series raise NotImplementedError."""
     scalar = np.ndim(zs) == 0
     zs = green_node_weight_zs(zs, "green_weights")
 
@@ -620,6 +631,8 @@ def green_weights(prob_or_cache, zs, fold=False):
     else:
         check(LTM(), getattr(prob_or_cache, "p", None))
     H = getattr(prob_or_cache, "H", None)
+    if optimized and isinstance(H, FourierSeries) and H.d != 3:  # (before a device is asked for anything)
+        raise NotImplementedError(f"green_weights: optimized=True is implemented for d = 3 (the series has d = {H.d})")
     if isinstance(H, FourierSeries) and _ksharded(H.device()):  # (before a cache is made: nothing is built for the refusal)
         raise NotImplementedError("green_weights on a k-sharded series is not implemented: a node's weight needs its whole "
                                   "neighbourhood, which a slab with its halo plane does not hold")
@@ -629,7 +642,7 @@ def green_weights(prob_or_cache, zs, fold=False):
         c.elements = _ltm_elements(c.cacheval, c.alg)
         c.isfresh = False
     rule = c.cacheval
-    W = rule.ltm_green_node_weights(zs, export=not fold)
+    W = (rule.ltm_green_node_weights_optimized if optimized else rule.ltm_green_node_weights)(zs, export=not fold)
     if fold:
         W = rule.ltm_green_node_weights_fold()
     return (W[0], complex(zs[0])) if scalar else (W, zs)

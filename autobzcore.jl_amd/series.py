@@ -1223,6 +1223,25 @@ class DeviceRule:
                                                         out.view(np.float64).ctypes.data_as(L.c_f64p) if export else None))
         return out
 
+    def ltm_green_node_weights_optimized(self, zs, export=True):
+        """The complex integration weights W_b(k; z) of the optimized tetrahedron rule (abz_rule_ltm_green_node_weights_optimized;
+        d = 3), complex128 [nz, nk, n] in the node and band order of export()'s eig: sum_k sum_b W A is the G_A(z) of
+        `ltm_green_optimized` for ANY A, sum W its tr G(z), sum W e = z tr G(z) - n.  Every simplex scatters the complex corner
+        weights of the linear rule on its effective corner energies onto its 20 stencil points; the weights differ from those of
+        `ltm_green_node_weights` by O(1 / npt^2).  At most 8 values per call, Im z != 0, in any order; Im z < 0 gives the
+        conjugate of the weights at conj z, to the bit.  The weights fill the same resident block as those of
+        `ltm_green_node_weights`: `ltm_green_node_weights_ptr`, `_dot`, `_fold` and `_matrix` (zs=None) work on them as they
+        are, and the real weights of `ltm_node_weights` are untouched; `export=False` (returns None) skips the copy to the host.
+        Two calls return the same bits, whatever ABZ_LTM_OPTW_CHUNK_MB (the scratch of a slab of grid planes) is.  The rule
+        must be a whole periodic grid (an unfolded rule is one); NotImplementedError on a k-sharded rule and for d < 3."""
+        self._ltm_refuse_optimized("ltm_green_node_weights_optimized")
+        zs = green_node_weight_zs(zs, "ltm_green_node_weights_optimized")
+        h = self.h  # (a stale rule is refilled here, which drops the weights it held)
+        out = np.empty((len(zs), self.nk, self.nbands), dtype=np.complex128) if export else None
+        L.check(L.lib().abz_rule_ltm_green_node_weights_optimized(h, zs.view(np.float64).ctypes.data_as(L.c_f64p), len(zs),
+                                                                  out.view(np.float64).ctypes.data_as(L.c_f64p) if export else None))
+        return out
+
     def ltm_green_node_weights_ptr(self):
         """(device address, bytes, nz) of the resident block of `ltm_green_node_weights`; (0, 0, 0) when there is none."""
         self._ltm_refuse_shard("ltm_green_node_weights_ptr")
@@ -1235,7 +1254,7 @@ class DeviceRule:
         leaves the weights in place."""
         return self._node_weights_dot(True, elements)
 
-    def ltm_green_node_weights_matrix(self, zs=None, orbitals=None):
+    def ltm_green_node_weights_matrix(self, zs=None, orbitals=None, optimized=False):
         """The local Green's function G_pq(z) = sum_k sum_b W_b(k; z) U_pb(k) conj(U_qb(k)) in the orbital basis, per unit cell,
         complex128 [nz, m, m] (abz_rule_ltm_green_node_weights_matrix): the resident weights of `ltm_green_node_weights`
         contracted with the eigenvectors by the kernel of `ltm_density_matrix`; no projector is attached and attached elements
@@ -1245,8 +1264,15 @@ class DeviceRule:
         components and scans the simplices per group: this route gathers the weights once per z and solves the grid once per 4
         weight sets for 1...4 bands, twice per z for 5...32 (`abz.dos.green_local` has the measured crossover: the number of
         projector groups).  1...32 bands, a whole periodic grid with H(k)
-        (not an unfolded rule); a k-sharded rule raises NotImplementedError."""
+        (not an unfolded rule); a k-sharded rule raises NotImplementedError.  `optimized=True` (d = 3, with `zs`): the weights
+        are those of the optimized tetrahedron rule (`ltm_green_node_weights_optimized`), tr G the tr G(z) of
+        `ltm_green_optimized`."""
         self._ltm_refuse_shard("ltm_green_node_weights_matrix")
+        if optimized and zs is None:
+            raise ValueError("ltm_green_node_weights_matrix: optimized=True makes the weights of zs (the resident ones are what the "
+                             "call that made them says: give zs, or leave optimized out)")
+        if optimized:
+            self._ltm_refuse_optimized("ltm_green_node_weights_matrix")
         n = self.dev.s.n
         orb = density_matrix_orbitals(orbitals, n, "ltm_green_node_weights_matrix")
         if zs is None:
@@ -1257,7 +1283,9 @@ class DeviceRule:
             chunks = [green_node_weight_zs(zs[i:i + step], "ltm_green_node_weights_matrix") for i in range(0, max(len(zs), 1), step)]
         parts = []
         for chunk in chunks:
-            if chunk is not None:
+            if chunk is not None and optimized:
+                self.ltm_green_node_weights_optimized(chunk, export=False)
+            elif chunk is not None:
                 self.ltm_green_node_weights(chunk, export=False)
             h = self.h  # (a stale rule is refilled here, which drops the weights it held)
             _, _, nz = self.ltm_green_node_weights_ptr()

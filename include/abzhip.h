@@ -649,6 +649,25 @@ int abz_rule_ltm_density_matrix(abz_rule* r, double* out /* [nE][n][n][2] */);
  * elements as they were.  Entry points added without a change of ABZ_VERSION. */
 #define ABZ_LTM_GREEN_NODEW_MAX_Z 8   /* 2 nz real weight sets <= ABZ_LTM_NODEW_MAX_E */
 int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z /* [nz][2] */, int nz, double* out /* [nz][nk][n][2] or NULL */);
+/* The complex integration weights of the OPTIMIZED tetrahedron rule (abz_rule_ltm_green_optimized), d = 3: the numbers W_b(k; z)
+ * with
+ *      sum_k sum_b W_b(k; z) A_b(k) = the G_A(z) of abz_rule_ltm_green_optimized
+ * for ANY A; sum W = its tr G(z), sum W e = z tr G(z) - n.  Every Kuhn simplex forms the complex corner weights
+ * W'_m = J[sort(e'), e'_m](z) / 4 of the linear rule on its effective corner energies e' = P e (the evaluation rule of
+ * abz_rule_ltm_green_weighted) and scatters them with P transposed onto its 20 stencil points:
+ *      W_b(k; z) = 1 / (6 npt^3) sum_t sum_j sum_m P[m][j] W'_m(simplex t of the cell k - off_{t,j}; z),
+ * every index wrapped mod npt (any npt >= 1).  They differ from the weights of abz_rule_ltm_green_node_weights by O(1 / npt^2).
+ * Arguments, order of `out` and limits are those of abz_rule_ltm_green_node_weights, and the weights fill the SAME resident
+ * block: abz_rule_ltm_green_node_weights_ptr, _dot, _fold and _matrix then work on the optimized weights as they are; the real
+ * weights of abz_rule_ltm_node_weights and the attached elements are not touched.  Im z < 0: the conjugate of the value at
+ * conj(z), to the bit.  No atomics: two calls write the same bits, and so does every value of the switch
+ * ABZ_LTM_OPTW_CHUNK_MB, which bounds the scratch the corner weights of a slab of grid planes take.
+ * Takes full-grid rules and rules of abz_rule_ltm_unfold.  ABZ_ERR_ARG: a rule without eigenvalues, z == NULL, nz outside
+ * 1..ABZ_LTM_GREEN_NODEW_MAX_Z, any Im z == 0 or non-finite z.  ABZ_ERR_UNSUPPORTED: d != 3, slabs with or without a halo, lists
+ * of irreducible nodes, a stride between grid lines beyond 2^31 doubles.  A refusal or failure leaves both weight blocks, the
+ * attached elements and `out` as they were (the copy to `out` starts after the kernels have finished).  Entry point added
+ * without a change of ABZ_VERSION. */
+int abz_rule_ltm_green_node_weights_optimized(abz_rule* r, const double* z /* [nz][2] */, int nz, double* out /* [nz][nk][n][2] or NULL */);
 /* The resident complex weights: device address, bytes and values of z of the block; NULL, 0, 0 when the rule holds none (any of
  * the three pointers may be NULL). */
 int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nz);

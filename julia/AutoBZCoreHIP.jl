@@ -774,6 +774,22 @@ function ltm_green_node_weights!(r::HIPRule, zs::Vector{ComplexF64}, n::Integer;
 end
 
 """
+    ltm_green_node_weights_optimized(r, zs, n; export_weights=true)  -> Array{ComplexF64,3} [n, nk, nz] or nothing
+
+The complex integration weights of the optimized tetrahedron rule, `d = 3` (`abz_rule_ltm_green_node_weights_optimized`):
+`sum_k sum_b W_b(k; z) A_b(k)` is the `G_A(z)` of `abz_rule_ltm_green_optimized` for any `A`.  At most 8 values, `imag(z) != 0`.
+The weights fill the same resident block as those of `ltm_green_node_weights!`: `ltm_green_node_weights_dot`, `_fold` and
+`_matrix` work on them as they are.  (Written after the Python binding; not run.)
+"""
+function ltm_green_node_weights_optimized(r::HIPRule, zs::Vector{ComplexF64}, n::Integer; export_weights::Bool=true)
+    1 <= length(zs) <= 8 || throw(ArgumentError("ltm_green_node_weights_optimized: $(length(zs)) values of z, a call takes 1..8"))
+    out = export_weights ? Array{ComplexF64}(undef, n, r.nk, length(zs)) : nothing
+    GC.@preserve zs out check(ccall((:abz_rule_ltm_green_node_weights_optimized, libabz), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Cint, Ptr{ComplexF64}),
+                                    r.h, zs, length(zs), export_weights ? pointer(out) : C_NULL))
+    return out
+end
+
+"""
     ltm_green_node_weights_dot(r, ncomp)  -> Matrix{ComplexF64} [ncomp, nz]
 
 The resident complex weights against the `ncomp` attached element components (`abz_rule_ltm_green_node_weights_dot`).
