@@ -9,8 +9,9 @@
 //      G_A,c(z) = w sum ...                                  sum_{i=0..3} A'_{c,i} W_i(z),            W_i = J[x_0 .. x_3, x_i](z) / 4
 //    by the evaluation rule of ltm_green_device.h as it stands (rho = 1/2, the Taylor series of a narrow sub-range, principal logs
 //    of one half plane).  Im z < 0: the conjugate of the value at conj(z), to the bit.
-//  * Shape (ltm_green_opt_kernel<SRC, NC>).  The cell walk, the wrapped index tables and the compare-selected stencil are
-//    ltm_opt_kernel's: blocks of 256 cells, one cell per thread, blockIdx.y the band, nothing indexed by a run-time value.  The
+//  * Shape (ltm_green_opt_kernel<SRC, NC>).  The cell walk is ltm_opt_kernel's (blocks of 256 cells, one cell per thread,
+//    blockIdx.y the band); the wrapped index tables, the compare-selected stencil (OptPath), the band's planes and the effective
+//    elements (opt_elements, here before the z loop) are those of ltm_opt_device.h: nothing indexed by a run-time value.  The
 //    simplex loop is the outer one and the loop over z the inner one: the 20 loads and the 4 x 17 product of a simplex (and of
 //    each of its NC components) are made once per (cell, simplex, launch) and only the 4 e' and the 4 NC A' of ONE simplex live
 //    across the z loop -- 8 + 8 NC VGPRs, where the 24 e' of a cell would take 48 + 48 NC.  The price is that the wave butterfly
@@ -41,16 +42,10 @@ namespace abz {
 
 namespace {
 
-enum { OPT_ONE = 0, OPT_ENERGY = 1, OPT_ELEMS = 2 };
-
-struct GreenOptArgs {
-    PlaneView E, A;
+struct GreenOptArgs : OptScanArgs {
     const double* z;  // device [nz][2]: re, im > 0
-    int64_t ncell;    // npt^3
-    int64_t acomp;    // doubles from a band's plane of one component to its plane of the next: n * A.pitch
-    int npt, nz;
+    int nz;
     int zper;         // values of z per blockIdx.z
-    int aplane0;      // first element plane of this launch: (its first component) * n
 };
 
 // partial [2 NC nz][nrows]: column (i NC + c) 2 + {0, 1} the real and imaginary part of component c's sum at z_i
@@ -68,67 +63,21 @@ __global__ __launch_bounds__(256) void ltm_green_opt_kernel(GreenOptArgs a, doub
     for (int i = threadIdx.x; i < 8 * NC * zn; i += 256) ldsgo[2 * zn + i] = 0.0;
     __syncthreads();
     const int npt = a.npt;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const int tileE = (int)a.E.tile;  // 32-bit factors, checked by the host, as in ltm_opt_kernel
-    [[maybe_unused]] const double* __restrict__ Ab = nullptr;
-    [[maybe_unused]] int tileA = 0;
-    [[maybe_unused]] int64_t acomp = 0;
-    if constexpr (SRC == OPT_ELEMS) {
-        Ab = a.A.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.A.pitch;
-        tileA = (int)a.A.tile;
-        acomp = a.acomp;
-    }
+    const OptBand<SRC> band(a);
     for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
         const int64_t k = base + threadIdx.x;
         const bool active = k < a.ncell;  // (the whole wave takes part in every butterfly)
         const LtmCell cell = ltm_cell<3>(active ? k : 0, npt);
-        // the wrapped indices i - 1 .. i + 2 of every axis: a column (axis 1) or a line number (axis 2; axis 3 in units of npt lines)
         int j1[4], j2[4], j3[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            j1[o] = opt_wrap(cell.i1, o - 1, npt);
-            j2[o] = opt_wrap(cell.i2, o - 1, npt);
-            j3[o] = opt_wrap(cell.i3, o - 1, npt) * npt;
-        }
+        opt_tables(cell.i1, cell.i2, cell.i3, npt, j1, j2, j3);
 #pragma unroll 1
         for (int t = 0; t < 6; ++t) {
-            // the permutation (X, Y, Z) of the axes and the tables of a step along the path's axes, as in ltm_opt_kernel
-            const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3, Z = 3 - X - Y;
-            int col[3][4], line[3][4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                col[0][o] = X == 0 ? j1[o] : 0;
-                col[1][o] = Y == 0 ? j1[o] : 0;
-                col[2][o] = Z == 0 ? j1[o] : 0;
-                line[0][o] = X == 1 ? j2[o] : (X == 2 ? j3[o] : 0);
-                line[1][o] = Y == 1 ? j2[o] : (Y == 2 ? j3[o] : 0);
-                line[2][o] = Z == 1 ? j2[o] : (Z == 2 ? j3[o] : 0);
-            }
-            // point j of the stencil: column inside 0 .. npt-1, line inside 0 .. npt^2-1
-            auto at = [&](const double* __restrict__ planes, int tile, int j) -> double {
-                const int c = col[0][OPT_PT[j][0] + 1] + col[1][OPT_PT[j][1] + 1] + col[2][OPT_PT[j][2] + 1];
-                const int l = line[0][OPT_PT[j][0] + 1] + line[1][OPT_PT[j][1] + 1] + line[2][OPT_PT[j][2] + 1];
-                return planes[(int64_t)l * tile + c];
-            };
+            const OptPath path(t, j1, j2, j3);
             double x[OPT_NPT], e[4];
-#pragma unroll
-            for (int j = 0; j < OPT_NPT; ++j) x[j] = at(Eb, tileE, j);
+            path.load(band.Eb, band.tileE, x);
             opt_project(x, e);
-            [[maybe_unused]] LtmVec<NC> A[4];
-            if constexpr (SRC == OPT_ENERGY) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) A[m].v[0] = e[m];
-            } else if constexpr (SRC == OPT_ELEMS) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    double y[4];
-#pragma unroll
-                    for (int j = 0; j < OPT_NPT; ++j) x[j] = at(Ab + (int64_t)c * acomp, tileA, j);
-                    opt_project(x, y);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) A[m].v[c] = y[m];
-                }
-            }
+            [[maybe_unused]] LtmVec<NC> A[4];  // (the trace reads none)
+            opt_elements<SRC, NC>(path, band, e, A);
             for (int iz = 0; iz < zn; ++iz) {
                 const double zr = zl[2 * iz], zi = zl[2 * iz + 1];
                 // the 4 complex logs of z - e'_m: no two simplices of a cell share a corner value
@@ -201,21 +150,11 @@ GreenOptFn green_opt_fn(int src, int nc) {
 // [nz][ncomp][2].
 int launch_ltm_green_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneView* A, bool energy, int ncomp, const double* z_host, int nz,
                                double* out_host) {
-    const int src = A ? OPT_ELEMS : (energy ? OPT_ENERGY : OPT_ONE);
-    if (!A) ncomp = 1;
-    if (E.tile > INT32_MAX || (A && A->tile > INT32_MAX)) {
-        set_error("abz_rule_ltm_green_optimized: a stride of %lld doubles between grid lines does not fit the kernel's 32-bit factor",
-                  (long long)std::max(E.tile, A ? A->tile : 0));
-        return ABZ_ERR_UNSUPPORTED;
-    }
     GreenOptArgs a{};
-    a.E = E;
-    a.npt = npt;
-    a.ncell = (int64_t)npt * npt * npt;
-    if (A) {
-        a.A = *A;
-        a.acomp = (int64_t)n * A->pitch;
-    }
+    int src;
+    int64_t nblocks, nrows;
+    int rc = opt_scan_open("abz_rule_ltm_green_optimized", n, npt, E, A, energy, ncomp, a, src, nblocks, nrows);
+    if (rc) return rc;
     // of a simplex and, with elements, of its 4 corner weights the 1 / 4
     const double weight = 1.0 / (6.0 * (double)a.ncell * (src == OPT_ONE ? 1.0 : 4.0));
     std::vector<double> zup(2 * (size_t)nz);
@@ -223,13 +162,10 @@ int launch_ltm_green_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const 
         zup[2 * i] = z_host[2 * i];
         zup[2 * i + 1] = std::fabs(z_host[2 * i + 1]);
     }
-    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
-    const int64_t nrows = nblocks * n;
     size_t pmax = 0;
     for (int nc : {1, 2, 4})
         if (nc <= ncomp) pmax = std::max(pmax, (size_t)std::min(nz, green_w_chunk(nc)) * (size_t)(2 * nc));
-    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax);
-    if (rc) return rc;
+    if ((rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax))) return rc;
     double* partial = ctx->scratch[1].as<double>();
     const double* zdev = nullptr;
     if ((rc = sweep_to_device(ctx, zup.data(), 2 * nz, &zdev))) return rc;

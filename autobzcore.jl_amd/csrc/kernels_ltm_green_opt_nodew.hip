@@ -11,17 +11,17 @@
 //    sum W e = z tr G - n.  Im z < 0: computed at conj(z) and conjugated where the corner weights are stored: the conjugate of
 //    the weights at conj(z) to the bit.
 //  * Two kernels per group of NZ = 1 or 2 values of z (by value), no atomics anywhere:
-//    A'. ltm_green_opt_cornerw_kernel<NZ>: the cell walk and the table and select addressing of ltm_opt_cornerw_kernel (one cell
-//       per thread, blockIdx.y the band, the six simplices under unroll 1, nothing indexed at run time, a 32-bit line stride
-//       that the host checks).  Per simplex 20 loads, opt_project, the five-step compare-exchange sort that carries each corner's
-//       path position, the four corner logs (taken after the sort), green_weights<4> per z, and 8 NZ stores in path order into the
+//    A'. ltm_green_opt_cornerw_kernel<NZ>: the cell walk of ltm_opt_cornerw_kernel (optw_cell: one cell per thread, blockIdx.y the
+//       band) and the stencil addressing OptPath of ltm_opt_device.h (the six simplices under unroll 1, nothing indexed at run
+//       time, a 32-bit line stride that the host checks).  Per simplex 20 loads, opt_project, the five-step compare-exchange sort
+//       that carries each corner's path position (optw_sort), the four corner logs (taken after the sort), green_weights<4> per z, and 8 NZ stores in path order into the
 //       workspace [band][set][t 4 + m][cell] as 2 NZ real sets: set 2 iz = Re, set 2 iz + 1 = Im with the sign of Im z applied.
 //       Every simplex stores: the workspace needs no clearing.
 //    B. ltm_opt_nodew_gather_kernel<2 NZ> (ltm_opt_nodew_device.h), the gather of the real weights as it is: it sums the 432 terms
 //       of a node per set in one fixed order (t, j, m) and writes plane (plane0 / n + set) n + b, which is the layout of the complex
 //       block.  The host's scale is 1 / (24 npt^3): of a simplex, and of its corner weights the 1 / 4.
-//  * Workspace and slabs: scratch[1] under ABZ_LTM_OPTW_CHUNK_MB and the slab planner of the real weights (optw_slab) for 2 NZ
-//    sets.  A node's terms and their order do not depend on the slab height: the block has the same bits for every cap.
+//  * Workspace and slabs: scratch[1] under ABZ_LTM_OPTW_CHUNK_MB, the slab planner and the slab loop of the real weights
+//    (optw_need, optw_run_group of ltm_opt_nodew_device.h) for 2 NZ sets.  A node's terms and their order do not depend on the slab height: the block has the same bits for every cap.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,19 +45,7 @@ template <int NZ>
 __global__ __launch_bounds__(256) void ltm_green_opt_cornerw_kernel(OptWArgs a) {
     const int64_t kk = (int64_t)blockIdx.x * 256 + threadIdx.x;  // cell of the workspace: column i1 of line i2 of its plane q
     if (kk >= a.wsplane) return;
-    const int npt = a.npt;
-    const LtmCell cell = ltm_cell<3>(kk, npt);
-    int i3 = a.cell0 + cell.i3;  // the grid plane of the workspace's plane
-    i3 -= i3 >= npt ? npt : 0;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const int tileE = (int)a.E.tile;  // (the host checks that it fits)
-    int j1[4], j2[4], j3[4];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        j1[o] = opt_wrap(cell.i1, o - 1, npt);
-        j2[o] = opt_wrap(cell.i2, o - 1, npt);
-        j3[o] = opt_wrap(i3, o - 1, npt) * npt;
-    }
+    const OptWCell c = optw_cell(a, kk, 2 * NZ);  // (a value of z is two sets: Re, Im)
     double zr[NZ], zi[NZ];
     bool neg[NZ];
 #pragma unroll
@@ -66,23 +54,15 @@ __global__ __launch_bounds__(256) void ltm_green_opt_cornerw_kernel(OptWArgs a) 
         zi[i] = fabs(a.Es[2 * i + 1]);
         neg[i] = a.Es[2 * i + 1] < 0.0;
     }
-    // plane [t 4 + m] of set s of this band: out[(s 24 + t 4 + m) wsplane]
-    double* __restrict__ const out = a.C + (int64_t)blockIdx.y * (2 * NZ) * 24 * a.wsplane + kk;
 #pragma unroll 1
     for (int t = 0; t < 6; ++t) {
-        OPTW_TABLES(t, j1, j2, j3)
+        const OptPath path(t, c.j1, c.j2, c.j3);
         double x[OPT_NPT], e[4];
-#pragma unroll
-        for (int j = 0; j < OPT_NPT; ++j) x[j] = Eb[(int64_t)OPTW_LINE(j) * tileE + OPTW_COL(j)];
+        path.load(c.Eb, c.tileE, x);
         opt_project(x, e);
-        double e1 = e[0], e2 = e[1], e3 = e[2], e4 = e[3];
-        int p1 = 0, p2 = 1, p3 = 2, p4 = 3;
-        optw_cx(e1, e2, p1, p2);
-        optw_cx(e3, e4, p3, p4);
-        optw_cx(e1, e3, p1, p3);
-        optw_cx(e2, e4, p2, p4);
-        optw_cx(e2, e3, p2, p3);
-        double* __restrict__ const ot = out + (int64_t)(t * 4) * a.wsplane;
+        const OptWSorted s = optw_sort(e);
+        const double e1 = s.e1, e2 = s.e2, e3 = s.e3, e4 = s.e4;
+        double* __restrict__ const ot = c.out + (int64_t)(t * 4) * a.wsplane;
 #pragma unroll
         for (int i = 0; i < NZ; ++i) {
             const double u1 = zr[i] - e1, u2 = zr[i] - e2, u3 = zr[i] - e3, u4 = zr[i] - e4, y = zi[i];
@@ -92,21 +72,15 @@ __global__ __launch_bounds__(256) void ltm_green_opt_cornerw_kernel(OptWArgs a) 
                                       {e4, 0.5 * log(u4 * u4 + y * y), atan2(y, u4)}};
             Cx W[4];
             green_weights<4>(g, zr[i], y, W);
-            // back to path order: corner m of the path is the sorted corner whose position is m
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const double re = p1 == m ? W[0].re : (p2 == m ? W[1].re : (p3 == m ? W[2].re : W[3].re));
-                const double im = p1 == m ? W[0].im : (p2 == m ? W[1].im : (p3 == m ? W[2].im : W[3].im));
-                ot[(int64_t)((2 * i) * 24 + m) * a.wsplane] = re;
+                const double im = optw_of_path(s, m, W[0].im, W[1].im, W[2].im, W[3].im);
+                ot[(int64_t)((2 * i) * 24 + m) * a.wsplane] = optw_of_path(s, m, W[0].re, W[1].re, W[2].re, W[3].re);
                 ot[(int64_t)((2 * i + 1) * 24 + m) * a.wsplane] = neg[i] ? -im : im;
             }
         }
     }
 }
-
-#undef OPTW_TABLES
-#undef OPTW_COL
-#undef OPTW_LINE
 
 // Values of z per group where at least that many remain.  A' is the expensive kernel and the slab overlap (S + 3) / S multiplies
 // it: a pair takes 4 sets and gets shorter slabs under the cap than a single value's 2 sets.  Measured at SVO 150^3 under the default
@@ -117,7 +91,6 @@ __global__ __launch_bounds__(256) void ltm_green_opt_cornerw_kernel(OptWArgs a) 
 constexpr int green_opt_nodew_nz() { return ABZ_LTM_GREEN_OPTW_NZ; }
 static_assert(green_opt_nodew_nz() == 1 || green_opt_nodew_nz() == 2, "a group is one value of z or a pair");
 
-using OptWFn = void (*)(OptWArgs);
 // the pair's kernels exist only in a build that launches them
 template <int NZ>
 constexpr OptWFn green_optw_pair_corner() {
@@ -150,14 +123,11 @@ int launch_ltm_green_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneV
     a.npt = npt;
     a.n = n;
     a.weight = 1.0 / (24.0 * (double)npt * (double)npt * (double)npt);
-    const int64_t mb = abz_switch(SW_LTM_OPTW_CHUNK_MB) > 0 ? abz_switch(SW_LTM_OPTW_CHUNK_MB) : 256;
-    const int64_t cells = (int64_t)npt * npt;  // of a plane
     size_t need = 0;
     for (int cnt : {1, 2})
         if (cnt == 1 ? (green_opt_nodew_nz() == 1 || nz % 2 != 0) : (green_opt_nodew_nz() == 2 && nz >= 2))
-            need = std::max(need, sizeof(double) * 24 * (size_t)n * (size_t)(2 * cnt) *
-                                      (size_t)optw_planes_of(npt, optw_slab(npt, n, 2 * cnt, mb)) * (size_t)cells);
-    const int rc = ctx->scratch[1].reserve(need);
+            need = std::max(need, optw_need(npt, n, 2 * cnt));
+    int rc = ctx->scratch[1].reserve(need);
     if (rc) return rc;
     a.C = ctx->scratch[1].as<double>();
     ProfScope ps(ctx, ABZ_K_LTM);
@@ -169,20 +139,7 @@ int launch_ltm_green_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneV
             a.Es[2 * i + 1] = z_host[2 * k + 1];
         }
         a.plane0 = 2 * i0 * n;
-        const int S = optw_slab(npt, n, 2 * cnt, mb);
-        const bool whole = S + 3 >= npt;
-        for (int s0 = 0; s0 < npt; s0 += whole ? npt : S) {
-            a.node0 = s0;
-            a.nnode = whole ? npt : std::min(S, npt - s0);
-            a.nplanes = whole ? npt : a.nnode + 3;
-            a.wrap3 = whole;
-            a.cell0 = whole ? 0 : (s0 + npt - 2) % npt;  // (S + 3 < npt here: npt >= 5)
-            a.wsplane = (int64_t)a.nplanes * cells;
-            launch(ctx, GREEN_OPTW_CORNER[cnt == 2], dim3((unsigned)cdiv64(a.wsplane, 256), (unsigned)n), dim3(256), 0, a);
-            ABZ_HIP(hipGetLastError());
-            launch(ctx, GREEN_OPTW_GATHER[cnt == 2], dim3((unsigned)cdiv64((int64_t)a.nnode * npt * W.row, 256), (unsigned)n), dim3(256), 0, a);
-            ABZ_HIP(hipGetLastError());
-        }
+        if ((rc = optw_run_group(ctx, a, 2 * cnt, GREEN_OPTW_CORNER[cnt == 2], GREEN_OPTW_GATHER[cnt == 2]))) return rc;
         i0 += cnt;
     }
     return ABZ_OK;

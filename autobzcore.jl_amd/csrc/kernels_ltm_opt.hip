@@ -25,7 +25,10 @@
 //    shifted copies of the same run of a grid line (consecutive lanes, consecutive i_1), and the 4^3 neighbourhood that the six
 //    simplices and the neighbouring cells share is served by the caches.  Per axis the thread keeps the 4 wrapped indices
 //    i - 1 .. i + 2 as (column, line) contributions; a simplex picks its three tables by compares on the permutation and every
-//    point is three constant-index entries of them: nothing is indexed by a run-time value, nothing goes to scratch.
+//    point is three constant-index entries of them: nothing is indexed by a run-time value, nothing goes to scratch.  This
+//    addressing is OptPath of ltm_opt_device.h, which every kernel of the optimized rule uses; the header also has what this
+//    scan shares with ltm_green_opt_kernel: the sources, the shared arguments, the band's planes (OptBand), the effective
+//    elements of a simplex (opt_elements) and the opening of the launcher (opt_scan_open).
 //  * Window.  e' can leave the range of the cell's 8 corners (sum_j |P[m][j]| = 1836 / 1260), so the window [min e', max e') is
 //    that of the effective energies of each simplex, taken after the product.  A simplex with no energy at or above min e' is
 //    done; without STATES one with no energy below max e' too, before its elements are loaded.  Everything else goes to
@@ -48,15 +51,9 @@ namespace abz {
 
 namespace {
 
-enum { OPT_ONE = 0, OPT_ENERGY = 1, OPT_ELEMS = 2 };
-
-struct OptArgs {
-    PlaneView E, A;
+struct OptArgs : OptScanArgs {
     const double* Es;  // device, ascending
-    int64_t ncell;     // npt^3
-    int64_t acomp;     // doubles from a band's plane of one component to its plane of the next: n * A.pitch
-    int npt, nE;
-    int aplane0;       // first element plane of this launch: (its first component) * n
+    int nE;
     double inv_step = 0.0;
 };
 
@@ -85,77 +82,25 @@ __global__ __launch_bounds__(256) void ltm_opt_kernel(OptArgs a, double* __restr
     for (int i = threadIdx.x; i < NH * nE; i += 256) ldsl[nE + i] = 0.0;
     __syncthreads();
     const int npt = a.npt;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    // the strides between lines as 32-bit factors (the host checks them): line * tile is then ONE 32 x 32 -> 64 bit multiply-add per point,
-    // where the 64 x 64 bit product took three quarter-rate multiplies and set the kernel's time
-    const int tileE = (int)a.E.tile;
-    [[maybe_unused]] const double* __restrict__ Ab = nullptr;
-    [[maybe_unused]] int tileA = 0;
-    [[maybe_unused]] int64_t acomp = 0;
-    if constexpr (SRC == OPT_ELEMS) {
-        Ab = a.A.base + (int64_t)(a.aplane0 + (int)blockIdx.y) * a.A.pitch;
-        tileA = (int)a.A.tile;
-        acomp = a.acomp;
-    }
+    const OptBand<SRC> band(a);
     for (int64_t base = (int64_t)blockIdx.x * 256; base < a.ncell; base += (int64_t)gridDim.x * 256) {
         const int64_t k = base + threadIdx.x;
         if (k >= a.ncell) continue;  // (no barrier inside the walk)
         const LtmCell cell = ltm_cell<3>(k, npt);
-        // the wrapped indices i - 1 .. i + 2 of every axis: a column (axis 1) or a line number (axis 2; axis 3 in units of npt lines)
         int j1[4], j2[4], j3[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            j1[o] = opt_wrap(cell.i1, o - 1, npt);
-            j2[o] = opt_wrap(cell.i2, o - 1, npt);
-            j3[o] = opt_wrap(cell.i3, o - 1, npt) * npt;
-        }
+        opt_tables(cell.i1, cell.i2, cell.i3, npt, j1, j2, j3);
 #pragma unroll 1
         for (int t = 0; t < 6; ++t) {
-            // the permutation (X, Y, Z) of the axes, as in the queue of ltm_window_kernel: corners 0, e_X, e_X + e_Y, (1,1,1)
-            const int X = t >> 1, Y = (X + 1 + (t & 1)) % 3, Z = 3 - X - Y;
-            // what a step of o - 1 along the path's first, second and third axis adds to the column and to the line
-            int col[3][4], line[3][4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                col[0][o] = X == 0 ? j1[o] : 0;
-                col[1][o] = Y == 0 ? j1[o] : 0;
-                col[2][o] = Z == 0 ? j1[o] : 0;
-                line[0][o] = X == 1 ? j2[o] : (X == 2 ? j3[o] : 0);
-                line[1][o] = Y == 1 ? j2[o] : (Y == 2 ? j3[o] : 0);
-                line[2][o] = Z == 1 ? j2[o] : (Z == 2 ? j3[o] : 0);
-            }
-            // point j of the stencil: column and line inside 0 .. npt-1 and 0 .. npt^2-1, as for a corner of the linear scan
-            auto at = [&](const double* __restrict__ planes, int tile, int j) -> double {
-                const int c = col[0][OPT_PT[j][0] + 1] + col[1][OPT_PT[j][1] + 1] + col[2][OPT_PT[j][2] + 1];
-                const int l = line[0][OPT_PT[j][0] + 1] + line[1][OPT_PT[j][1] + 1] + line[2][OPT_PT[j][2] + 1];
-                return planes[(int64_t)l * tile + c];
-            };
+            const OptPath path(t, j1, j2, j3);
             double x[OPT_NPT], e[4];
-#pragma unroll
-            for (int j = 0; j < OPT_NPT; ++j) x[j] = at(Eb, tileE, j);
+            path.load(band.Eb, band.tileE, x);
             opt_project(x, e);
             const double emin = fmin(fmin(e[0], e[1]), fmin(e[2], e[3])), emax = fmax(fmax(e[0], e[1]), fmax(e[2], e[3]));
             const int i0 = ltm_first(Esl, nE, a.inv_step, emin);
             if (i0 >= nE) continue;                       // every energy lies below the simplex
             if (!STATES && !(Esl[i0] < emax)) continue;   // no energy inside the window: nothing for g
             Vec A[4];
-            if constexpr (SRC == OPT_ONE) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) A[m].v[0] = 1.0;
-            } else if constexpr (SRC == OPT_ENERGY) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) A[m].v[0] = e[m];
-            } else {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    double y[4];
-#pragma unroll
-                    for (int j = 0; j < OPT_NPT; ++j) x[j] = at(Ab + (int64_t)c * acomp, tileA, j);
-                    opt_project(x, y);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) A[m].v[c] = y[m];
-                }
-            }
+            opt_elements<SRC, NC>(path, band, e, A);
             ltm_simplex3<STATES, Pay>(e[0], e[1], e[2], e[3], A[0], A[1], A[2], A[3], Esl, nE, i0, hist, step);
         }
     }
@@ -194,21 +139,11 @@ OptFn opt_fn(bool states, int src, int nc) {
 // final and prefix kernels.  A == nullptr: one component, A = 1 (`energy` false) or A = e (`energy` true).
 int launch_ltm_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneView* A, bool energy, int ncomp, const double* Es_host, int nE,
                          bool states, double* out_host) {
-    const int src = A ? OPT_ELEMS : (energy ? OPT_ENERGY : OPT_ONE);
-    if (!A) ncomp = 1;
-    if (E.tile > INT32_MAX || (A && A->tile > INT32_MAX)) {
-        set_error("abz_rule_ltm_optimized: a stride of %lld doubles between grid lines does not fit the kernel's 32-bit factor",
-                  (long long)std::max(E.tile, A ? A->tile : 0));
-        return ABZ_ERR_UNSUPPORTED;
-    }
     OptArgs a;
-    a.E = E;
-    a.npt = npt;
-    a.ncell = (int64_t)npt * npt * npt;
-    if (A) {
-        a.A = *A;
-        a.acomp = (int64_t)n * A->pitch;
-    }
+    int src;
+    int64_t nblocks, nrows;
+    int rc = opt_scan_open("abz_rule_ltm_optimized", n, npt, E, A, energy, ncomp, a, src, nblocks, nrows);
+    if (rc) return rc;
     const double weight = 1.0 / (6.0 * (double)a.ncell);
     const int ncol = states ? 2 : 1;
     // energies per launch of NC components, as in ltm_scan: 8 (1 + 4 NC ncol) B of LDS each within LTM_LDS_MAX, at most 512 where
@@ -217,13 +152,10 @@ int launch_ltm_optimized(abz_ctx* ctx, int n, int npt, PlaneView E, const PlaneV
         const size_t fit = LTM_LDS_MAX / (sizeof(double) * (size_t)(1 + 4 * nc * ncol));
         return (int)std::min<size_t>(fit, states ? 512 : 1024);
     };
-    const int64_t nblocks = std::min<int64_t>(cdiv64(a.ncell, 256), std::max(64, std::min(2048, 8192 / n)));
-    const int64_t nrows = nblocks * n;
     size_t pmax = 0;
     for (int nc : {1, 2, 4})
         if (nc <= ncomp) pmax = std::max(pmax, (size_t)std::min(nE, chunk(nc)) * (size_t)(nc * ncol));
-    int rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax);
-    if (rc) return rc;
+    if ((rc = ctx->scratch[1].reserve(sizeof(double) * (size_t)nrows * pmax))) return rc;
     double* partial = ctx->scratch[1].as<double>();
     EnergyList el;
     // behind the energies: the column sums of a launch, [nc][cnt] sums | [nc][cnt] steps (states)

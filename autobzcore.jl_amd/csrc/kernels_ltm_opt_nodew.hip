@@ -18,9 +18,9 @@
 //    to [0, 1 / nk], and a node next to the Fermi surface can weigh negative (npt^3 w down to -0.12 has been seen).
 //  * Two kernels per group of NE = 1 or 4 energies (by value, as in ltm_nodew_kernel), no atomics anywhere:
 //    A. ltm_opt_cornerw_kernel<STATES, NE>: one cell per thread, its six simplices one after the other, blockIdx.y the band; the
-//       table and select addressing of ltm_opt_kernel (nothing indexed at run time, no scratch, a 32-bit line stride that the host
-//       checks).  Per simplex 20 loads, the product, a compare-exchange sort that carries each corner's path position along, the
-//       reciprocals once for the group.  It stores the four weights in PATH order for each energy into a workspace of 24 planes
+//       stencil addressing is OptPath of ltm_opt_device.h (nothing indexed at run time, no scratch, a 32-bit line stride that the
+//       host checks), the prologue optw_cell and the sort optw_sort of ltm_opt_nodew_device.h.  Per simplex 20 loads, the product,
+//       the compare-exchange sort that carries each corner's path position along, the reciprocals once for the group.  It stores the four weights in PATH order for each energy into a workspace of 24 planes
 //       [t 4 + m] per band and energy, cell-contiguous (a wave's store is a run); a simplex outside its window stores 0.0, or
 //       0.25 when it lies wholly below E under STATES: the workspace needs no clearing.
 //    B. ltm_opt_nodew_gather_kernel<NE> (ltm_opt_nodew_device.h, shared with kernels_ltm_green_opt_nodew.hip): one thread per (column of a padded grid line, band); it sums the 6 x 20 x (the non-zero of
@@ -31,7 +31,8 @@
 //    along axis 3 are taken in slabs of S planes; a slab needs the corner weights of the cells of the planes s - 2 .. s + S, wrapped:
 //    S + 3 planes, the overlap is computed again.  S is as large as the cap allows and at least 1; where S + 3 planes hold the whole
 //    grid there is one slab of npt planes whose plane indices wrap (this is every npt < 4, where wrapped planes coincide).  A
-//    node's sum has the same terms in the same order whatever S is: the block has the same bits for every cap.
+//    node's sum has the same terms in the same order whatever S is: the block has the same bits for every cap.  The planner
+//    (optw_slab, optw_need) and the slab loop (optw_run_group) stand in ltm_opt_nodew_device.h; this file groups the energies.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,38 +54,18 @@ template <bool STATES, int NE>
 __global__ __launch_bounds__(256) void ltm_opt_cornerw_kernel(OptWArgs a) {
     const int64_t kk = (int64_t)blockIdx.x * 256 + threadIdx.x;  // cell of the workspace: column i1 of line i2 of its plane q
     if (kk >= a.wsplane) return;
-    const int npt = a.npt;
-    const LtmCell cell = ltm_cell<3>(kk, npt);
-    int i3 = a.cell0 + cell.i3;  // the grid plane of the workspace's plane
-    i3 -= i3 >= npt ? npt : 0;
-    const double* __restrict__ const Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
-    const int tileE = (int)a.E.tile;  // (the host checks that it fits)
-    int j1[4], j2[4], j3[4];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        j1[o] = opt_wrap(cell.i1, o - 1, npt);
-        j2[o] = opt_wrap(cell.i2, o - 1, npt);
-        j3[o] = opt_wrap(i3, o - 1, npt) * npt;
-    }
+    const OptWCell c = optw_cell(a, kk, NE);  // (a set is an energy)
     double En[NE];
 #pragma unroll
     for (int i = 0; i < NE; ++i) En[i] = a.Es[i];
-    // plane [t 4 + m] of energy i of this band: out[(i 24 + t 4 + m) wsplane]
-    double* __restrict__ const out = a.C + (int64_t)blockIdx.y * NE * 24 * a.wsplane + kk;
 #pragma unroll 1
     for (int t = 0; t < 6; ++t) {
-        OPTW_TABLES(t, j1, j2, j3)
+        const OptPath path(t, c.j1, c.j2, c.j3);
         double x[OPT_NPT], e[4];
-#pragma unroll
-        for (int j = 0; j < OPT_NPT; ++j) x[j] = Eb[(int64_t)OPTW_LINE(j) * tileE + OPTW_COL(j)];
+        path.load(c.Eb, c.tileE, x);
         opt_project(x, e);
-        double e1 = e[0], e2 = e[1], e3 = e[2], e4 = e[3];
-        int p1 = 0, p2 = 1, p3 = 2, p4 = 3;
-        optw_cx(e1, e2, p1, p2);
-        optw_cx(e3, e4, p3, p4);
-        optw_cx(e1, e3, p1, p3);
-        optw_cx(e2, e4, p2, p4);
-        optw_cx(e2, e3, p2, p3);
+        const OptWSorted s = optw_sort(e);
+        const double e1 = s.e1, e2 = s.e2, e3 = s.e3, e4 = s.e4;
         bool inside = false;
 #pragma unroll
         for (int i = 0; i < NE; ++i) inside = inside || (En[i] >= e1 && En[i] < e4);
@@ -98,7 +79,7 @@ __global__ __launch_bounds__(256) void ltm_opt_cornerw_kernel(OptWArgs a) {
             r42 = 1.0 / (e4 - e2);
             r43 = 1.0 / (e4 - e3);
         }
-        double* __restrict__ const ot = out + (int64_t)(t * 4) * a.wsplane;
+        double* __restrict__ const ot = c.out + (int64_t)(t * 4) * a.wsplane;
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
             const double E = En[i];
@@ -148,18 +129,12 @@ __global__ __launch_bounds__(256) void ltm_opt_cornerw_kernel(OptWArgs a) {
                     w4 = STATES ? 0.25 - u4 : u4;
                 }
             }
-            // back to path order: corner m of the path is the sorted corner whose position is m
 #pragma unroll
-            for (int m = 0; m < 4; ++m) ot[(int64_t)(i * 24 + m) * a.wsplane] = p1 == m ? w1 : (p2 == m ? w2 : (p3 == m ? w3 : w4));
+            for (int m = 0; m < 4; ++m) ot[(int64_t)(i * 24 + m) * a.wsplane] = optw_of_path(s, m, w1, w2, w3, w4);
         }
     }
 }
 
-#undef OPTW_TABLES
-#undef OPTW_COL
-#undef OPTW_LINE
-
-using OptWFn = void (*)(OptWArgs);
 // [states][NE == 4]
 constexpr OptWFn OPTW_CORNER[2][2] = {
     {ltm_opt_cornerw_kernel<false, 1>, ltm_opt_cornerw_kernel<false, 4>},
@@ -183,16 +158,10 @@ int launch_ltm_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneView E,
     a.npt = npt;
     a.n = n;
     a.weight = 1.0 / (6.0 * (double)npt * (double)npt * (double)npt);
-    const int64_t mb = abz_switch(SW_LTM_OPTW_CHUNK_MB) > 0 ? abz_switch(SW_LTM_OPTW_CHUNK_MB) : 256;
-    const int64_t cells = (int64_t)npt * npt;  // of a plane
-    // the slab height of a group of ne energies and the cell planes it needs (ltm_opt_nodew_device.h)
-    auto slab = [&](int ne) { return optw_slab(npt, n, ne, mb); };
-    auto planes_of = [&](int S) { return optw_planes_of(npt, S); };
     size_t need = 0;
     for (int ne : {1, 4})
-        if (ne == 1 ? (nE % 4 != 0 || nE < 4) : nE >= 4)
-            need = std::max(need, sizeof(double) * 24 * (size_t)n * (size_t)ne * (size_t)planes_of(slab(ne)) * (size_t)cells);
-    const int rc = ctx->scratch[1].reserve(need);
+        if (ne == 1 ? (nE % 4 != 0 || nE < 4) : nE >= 4) need = std::max(need, optw_need(npt, n, ne));
+    int rc = ctx->scratch[1].reserve(need);
     if (rc) return rc;
     a.C = ctx->scratch[1].as<double>();
     ProfScope ps(ctx, ABZ_K_LTM);
@@ -200,20 +169,7 @@ int launch_ltm_node_weights_optimized(abz_ctx* ctx, int n, int npt, PlaneView E,
         const int ne = nE - i0 >= 4 ? 4 : 1;
         for (int i = 0; i < 4; ++i) a.Es[i] = Es_host[i0 + std::min(i, ne - 1)];
         a.plane0 = i0 * n;
-        const int S = slab(ne);
-        const bool whole = S + 3 >= npt;
-        for (int s0 = 0; s0 < npt; s0 += whole ? npt : S) {
-            a.node0 = s0;
-            a.nnode = whole ? npt : std::min(S, npt - s0);
-            a.nplanes = whole ? npt : a.nnode + 3;
-            a.wrap3 = whole;
-            a.cell0 = whole ? 0 : (s0 + npt - 2) % npt;  // (S + 3 < npt here: npt >= 5)
-            a.wsplane = (int64_t)a.nplanes * cells;
-            launch(ctx, OPTW_CORNER[states][ne == 4], dim3((unsigned)cdiv64(a.wsplane, 256), (unsigned)n), dim3(256), 0, a);
-            ABZ_HIP(hipGetLastError());
-            launch(ctx, OPTW_GATHER[ne == 4], dim3((unsigned)cdiv64((int64_t)a.nnode * npt * W.row, 256), (unsigned)n), dim3(256), 0, a);
-            ABZ_HIP(hipGetLastError());
-        }
+        if ((rc = optw_run_group(ctx, a, ne, OPTW_CORNER[states][ne == 4], OPTW_GATHER[ne == 4]))) return rc;
         i0 += ne;
     }
     return ABZ_OK;

@@ -55,6 +55,27 @@ static int ltm_check_source(const char* who, int source) {
     return ABZ_OK;
 }
 
+// the three checks that the entry points of the optimized rule repeat
+static int ltm_check_source3(const char* who, int source) {
+    ABZ_REQUIRE(source == ABZ_LTM_A_ONE || source == ABZ_LTM_A_ENERGY || source == ABZ_LTM_A_ELEMENTS,
+                "%s: source = %d is neither ABZ_LTM_A_ONE, ABZ_LTM_A_ENERGY nor ABZ_LTM_A_ELEMENTS", who, source);
+    return ABZ_OK;
+}
+
+static int ltm_refuse_corrected(const char* who, int what) {
+    ABZ_REQUIRE(what != ABZ_LTM_STATES_CORRECTED,
+                "%s: ABZ_LTM_STATES_CORRECTED: the optimized rule replaces the curvature correction (ask for ABZ_LTM_STATES)", who);
+    return ABZ_OK;
+}
+
+static int ltm_require_d3(const char* who, const abz_rule* r) {
+    if (r->s->d != 3) {
+        set_error("%s: d = %d; the optimized tetrahedron rule is implemented for d = 3", who, r->s->d);
+        return ABZ_ERR_UNSUPPORTED;
+    }
+    return ABZ_OK;
+}
+
 // z [nz][2]: finite and off the real axis; `what`: "the trace is" / "G_A is" / "G is"
 static int ltm_check_zs(const char* who, const double* z, int nz, const char* what) {
     for (int i = 0; i < nz; ++i) {
@@ -100,6 +121,37 @@ static void interleave_sets(const double* sets, int nz, size_t per, double* out)
         double* o = out + (size_t)(i >> 1) * per * 2 + (size_t)(i & 1);
         for (size_t x = 0; x < per; ++x) o[2 * x] = src[x];
     }
+}
+
+// THE path of the four producers of a resident weight block (the real and the complex weights of the linear and of the optimized
+// rule): a new block of `sets` real sets tiled like the eigenvalue planes, `fill(ctx, n, W)` launches into its view, one
+// synchronisation, then `out` if given -- set by set [sets][nk][n] in the node and band order of abz_rule_export's eig, or, `cplx`,
+// the sets 2 i and 2 i + 1 as Re and Im of [sets / 2][nk][n][2] -- and the block becomes r->*which.  The block is complete before
+// anything of it reaches `out` and before it replaces the resident one: a refusal or a failure leaves both as they were, and the
+// half-made block goes with its DevBuf.
+template <class Fill>
+static int ltm_weight_block(abz_rule* r, const char* who, LtmBlock abz_rule::*which, int sets, bool cplx, double* out, Fill&& fill) {
+    abz_ctx* ctx = r->s->ctx;
+    ABZ_HIP(hipSetDevice(ctx->device));
+    const int n = rule_bands(r);
+    LtmBlock block;
+    int rc = block.alloc(r->E, r->ntiles, n, sets);
+    if (rc) return rc;
+    rc = fill(ctx, n, block.view);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
+        set_error("%s: the kernel failed", who);
+        rc = ABZ_ERR_HIP;
+    }
+    const size_t per = (size_t)r->nk * (size_t)n;
+    // complex: the two real sets of one z at a time through the staging of the export, interleaved on the host
+    std::vector<double> pair(cplx && out && !rc ? 2 * per : 0);
+    for (int i = 0; i < sets && !rc && out; ++i) {
+        rc = export_planes(ctx, block.set_view(i, n), n, r->nk, cplx ? pair.data() + (size_t)(i & 1) * per : out + (size_t)i * per);  // (returns when the data has arrived)
+        if (cplx && !rc && (i & 1)) interleave_sets(pair.data(), 1, per, out + (size_t)(i >> 1) * per * 2);
+    }
+    if (rc) return rc;
+    r->*which = std::move(block);  // (the previous weights go here)
+    return ABZ_OK;
 }
 
 extern "C" {
@@ -360,15 +412,10 @@ int abz_rule_ltm_optimized(abz_rule* r, int source, const double* E, int nE, int
     int rc = check_rule(r);
     if (rc) return rc;
     ABZ_REQUIRE(E && out && nE >= 1, "abz_rule_ltm_optimized: bad arguments");
-    ABZ_REQUIRE(what != ABZ_LTM_STATES_CORRECTED,
-                "abz_rule_ltm_optimized: ABZ_LTM_STATES_CORRECTED: the optimized rule replaces the curvature correction (ask for ABZ_LTM_STATES)");
+    if ((rc = ltm_refuse_corrected(who, what))) return rc;
     if ((rc = ltm_check_what(who, what, false))) return rc;
-    ABZ_REQUIRE(source == ABZ_LTM_A_ONE || source == ABZ_LTM_A_ENERGY || source == ABZ_LTM_A_ELEMENTS,
-                "%s: source = %d is neither ABZ_LTM_A_ONE, ABZ_LTM_A_ENERGY nor ABZ_LTM_A_ELEMENTS", who, source);
-    if (r->s->d != 3) {
-        set_error("abz_rule_ltm_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
-        return ABZ_ERR_UNSUPPORTED;
-    }
+    if ((rc = ltm_check_source3(who, source))) return rc;
+    if ((rc = ltm_require_d3(who, r))) return rc;
     if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
     ABZ_REQUIRE(source != ABZ_LTM_A_ELEMENTS || r->elems.buf.p,
                 "abz_rule_ltm_optimized: no matrix elements are attached (abz_rule_ltm_elements; abz_rule_rebuild drops them)");
@@ -401,12 +448,8 @@ int abz_rule_ltm_green_optimized(abz_rule* r, int source, const double* z, int n
     int rc = check_rule(r);
     if (rc) return rc;
     ABZ_REQUIRE(z && out && nz >= 1, "abz_rule_ltm_green_optimized: bad arguments");
-    ABZ_REQUIRE(source == ABZ_LTM_A_ONE || source == ABZ_LTM_A_ENERGY || source == ABZ_LTM_A_ELEMENTS,
-                "%s: source = %d is neither ABZ_LTM_A_ONE, ABZ_LTM_A_ENERGY nor ABZ_LTM_A_ELEMENTS", who, source);
-    if (r->s->d != 3) {
-        set_error("abz_rule_ltm_green_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
-        return ABZ_ERR_UNSUPPORTED;
-    }
+    if ((rc = ltm_check_source3(who, source))) return rc;
+    if ((rc = ltm_require_d3(who, r))) return rc;
     if ((rc = refuse_pair_rule(r, who, "the effective corner values of e_c - e_v have not been looked at (abz_rule_ltm_green serves it)"))) return rc;
     if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
     ABZ_REQUIRE(source != ABZ_LTM_A_ELEMENTS || r->elems.buf.p,
@@ -432,8 +475,7 @@ int abz_rule_ltm_fermi(abz_rule* r, double nstates, double tol, double* E_F, dou
     return ltm_fermi(ctx, rule_bands(r), r->s->d, r->npt, r->E, r->nk, nstates, tol, E_F, N_F);
 } ABZ_CATCH_ALL
 
-// Integration weights w_b(k; E) per node and band (kernels_ltm_nodew.hip).  The new block is complete before it replaces the
-// resident one: a refusal or a failure leaves that one as it was, and the half-made block goes with its DevBuf.
+// Integration weights w_b(k; E) per node and band (kernels_ltm_nodew.hip), resident through ltm_weight_block.
 int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, double* out) try {
     int rc = check_rule(r);
     if (rc) return rc;
@@ -443,57 +485,27 @@ int abz_rule_ltm_node_weights(abz_rule* r, const double* E, int nE, int what, do
     for (int i = 0; i < nE; ++i) ABZ_REQUIRE(std::isfinite(E[i]), "abz_rule_ltm_node_weights: E[%d] = %g is not finite", i, E[i]);
     // (no slab_ok: a node needs the plane BEFORE it as well, which a halo does not give)
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_node_weights"))) return rc;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    LtmBlock block;
-    if ((rc = block.alloc(r->E, r->ntiles, n, nE))) return rc;
-    rc = launch_ltm_node_weights(ctx, n, r->s->d, r->npt, r->E, block.view, E, nE, what);
-    for (int i = 0; i < nE && !rc && out; ++i)  // one energy [nk][n] at a time, in the node and band order of abz_rule_export's eig
-        rc = export_planes(ctx, block.set_view(i, n), n, r->nk, out + (size_t)i * (size_t)r->nk * (size_t)n);
-    // the block is complete, and nothing reads the old one any more
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_node_weights: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) return rc;
-    r->nodew = std::move(block);  // (the previous weights go here)
-    return ABZ_OK;
+    return ltm_weight_block(r, "abz_rule_ltm_node_weights", &abz_rule::nodew, nE, false, out, [&](abz_ctx* ctx, int n, PlaneView W) {
+        return launch_ltm_node_weights(ctx, n, r->s->d, r->npt, r->E, W, E, nE, what);
+    });
 } ABZ_CATCH_ALL
 
 // The weights of the optimized rule into the same resident block (kernels_ltm_opt_nodew.hip).  Every check comes before anything is
-// reserved or launched; the block replaces the resident one as in abz_rule_ltm_node_weights.
+// reserved or launched.
 int abz_rule_ltm_node_weights_optimized(abz_rule* r, const double* E, int nE, int what, double* out) try {
     const char* const who = "abz_rule_ltm_node_weights_optimized";
     int rc = check_rule(r);
     if (rc) return rc;
     ABZ_REQUIRE(E, "abz_rule_ltm_node_weights_optimized: null energies");
     ABZ_REQUIRE(nE >= 1 && nE <= ABZ_LTM_NODEW_MAX_E, "abz_rule_ltm_node_weights_optimized: nE = %d outside 1..%d", nE, ABZ_LTM_NODEW_MAX_E);
-    ABZ_REQUIRE(what != ABZ_LTM_STATES_CORRECTED, "abz_rule_ltm_node_weights_optimized: ABZ_LTM_STATES_CORRECTED: the optimized rule replaces the "
-                                                  "curvature correction (ask for ABZ_LTM_STATES)");
+    if ((rc = ltm_refuse_corrected(who, what))) return rc;
     if ((rc = ltm_check_what(who, what, false))) return rc;
     for (int i = 0; i < nE; ++i) ABZ_REQUIRE(std::isfinite(E[i]), "abz_rule_ltm_node_weights_optimized: E[%d] = %g is not finite", i, E[i]);
-    if (r->s->d != 3) {
-        set_error("abz_rule_ltm_node_weights_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
-        return ABZ_ERR_UNSUPPORTED;
-    }
+    if ((rc = ltm_require_d3(who, r))) return rc;
     if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    LtmBlock block;
-    if ((rc = block.alloc(r->E, r->ntiles, n, nE))) return rc;
-    rc = launch_ltm_node_weights_optimized(ctx, n, r->npt, r->E, block.view, E, nE, what == ABZ_LTM_STATES);
-    // the block is complete before anything of it reaches `out`: a kernel that failed leaves `out` as it was
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_node_weights_optimized: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    for (int i = 0; i < nE && !rc && out; ++i)  // one energy [nk][n] at a time, in the node and band order of abz_rule_export's eig
-        rc = export_planes(ctx, block.set_view(i, n), n, r->nk, out + (size_t)i * (size_t)r->nk * (size_t)n);  // (returns when the data has arrived)
-    if (rc) return rc;
-    r->nodew = std::move(block);  // (the previous weights go here)
-    return ABZ_OK;
+    return ltm_weight_block(r, who, &abz_rule::nodew, nE, false, out, [&](abz_ctx* ctx, int n, PlaneView W) {
+        return launch_ltm_node_weights_optimized(ctx, n, r->npt, r->E, W, E, nE, what == ABZ_LTM_STATES);
+    });
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nE) try {
@@ -596,7 +608,7 @@ int abz_rule_ltm_green_node_weights_fold(abz_rule* r, double* out) try {
 
 // Complex integration weights W_b(k; z) of the Green's function per node and band (kernels_ltm_green_nodew.hip), resident in a
 // block of their own: 2 nz real weight sets to the dot, the fold and the density-matrix contraction, which are launched as they
-// are.  As for the real weights the new block is complete before it replaces the resident one.
+// are.  Resident through ltm_weight_block, as the real weights.
 int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z, int nz, double* out) try {
     int rc = check_rule(r);
     if (rc) return rc;
@@ -606,34 +618,13 @@ int abz_rule_ltm_green_node_weights(abz_rule* r, const double* z, int nz, double
     if ((rc = ltm_check_zs("abz_rule_ltm_green_node_weights", z, nz, "G is"))) return rc;
     // (no slab_ok: a node needs the plane BEFORE it as well, which a halo does not give)
     if ((rc = ltm_check_grid(r, "abz_rule_ltm_green_node_weights"))) return rc;
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    LtmBlock block;
-    if ((rc = block.alloc(r->E, r->ntiles, n, 2 * nz))) return rc;
-    rc = launch_ltm_green_node_weights(ctx, n, r->s->d, r->npt, r->E, block.view, z, nz);
-    if (!rc && out) {
-        // the two real sets [nk][n] of one z at a time through the staging of the export, interleaved on the host
-        const size_t per = (size_t)r->nk * (size_t)n;
-        std::vector<double> pair(2 * per);
-        for (int i = 0; i < 2 * nz && !rc; ++i) {
-            rc = export_planes(ctx, block.set_view(i, n), n, r->nk, pair.data() + (size_t)(i & 1) * per);
-            if (!rc && (i & 1)) interleave_sets(pair.data(), 1, per, out + (size_t)(i >> 1) * per * 2);
-        }
-    }
-    // the block is complete, and nothing reads the old one any more
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_green_node_weights: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (rc) return rc;
-    r->gnodew = std::move(block);  // (the previous complex weights go here)
-    return ABZ_OK;
+    return ltm_weight_block(r, "abz_rule_ltm_green_node_weights", &abz_rule::gnodew, 2 * nz, true, out, [&](abz_ctx* ctx, int n, PlaneView W) {
+        return launch_ltm_green_node_weights(ctx, n, r->s->d, r->npt, r->E, W, z, nz);
+    });
 } ABZ_CATCH_ALL
 
 // The complex weights of the optimized rule into the same resident block (kernels_ltm_green_opt_nodew.hip).  Every check comes
-// before anything is reserved or launched; the block is complete before anything of it reaches `out` and before it replaces the
-// resident one.
+// before anything is reserved or launched.
 int abz_rule_ltm_green_node_weights_optimized(abz_rule* r, const double* z, int nz, double* out) try {
     const char* const who = "abz_rule_ltm_green_node_weights_optimized";
     int rc = check_rule(r);
@@ -642,34 +633,11 @@ int abz_rule_ltm_green_node_weights_optimized(abz_rule* r, const double* z, int 
     ABZ_REQUIRE(nz >= 1 && nz <= ABZ_LTM_GREEN_NODEW_MAX_Z, "abz_rule_ltm_green_node_weights_optimized: nz = %d outside 1..%d", nz,
                 ABZ_LTM_GREEN_NODEW_MAX_Z);
     if ((rc = ltm_check_zs(who, z, nz, "G is"))) return rc;
-    if (r->s->d != 3) {
-        set_error("abz_rule_ltm_green_node_weights_optimized: d = %d; the optimized tetrahedron rule is implemented for d = 3", r->s->d);
-        return ABZ_ERR_UNSUPPORTED;
-    }
+    if ((rc = ltm_require_d3(who, r))) return rc;
     if ((rc = ltm_check_grid(r, who))) return rc;  // (no slab_ok: the stencil reaches one plane before the slab and two behind it)
-    abz_ctx* ctx = r->s->ctx;
-    ABZ_HIP(hipSetDevice(ctx->device));
-    const int n = rule_bands(r);
-    LtmBlock block;
-    if ((rc = block.alloc(r->E, r->ntiles, n, 2 * nz))) return rc;
-    rc = launch_ltm_green_node_weights_optimized(ctx, n, r->npt, r->E, block.view, z, nz);
-    // the block is complete before anything of it reaches `out`: a kernel that failed leaves `out` as it was
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        set_error("abz_rule_ltm_green_node_weights_optimized: the kernel failed");
-        rc = ABZ_ERR_HIP;
-    }
-    if (!rc && out) {
-        // the two real sets [nk][n] of one z at a time through the staging of the export, interleaved on the host
-        const size_t per = (size_t)r->nk * (size_t)n;
-        std::vector<double> pair(2 * per);
-        for (int i = 0; i < 2 * nz && !rc; ++i) {
-            rc = export_planes(ctx, block.set_view(i, n), n, r->nk, pair.data() + (size_t)(i & 1) * per);  // (returns when the data has arrived)
-            if (!rc && (i & 1)) interleave_sets(pair.data(), 1, per, out + (size_t)(i >> 1) * per * 2);
-        }
-    }
-    if (rc) return rc;
-    r->gnodew = std::move(block);  // (the previous complex weights go here)
-    return ABZ_OK;
+    return ltm_weight_block(r, who, &abz_rule::gnodew, 2 * nz, true, out, [&](abz_ctx* ctx, int n, PlaneView W) {
+        return launch_ltm_green_node_weights_optimized(ctx, n, r->npt, r->E, W, z, nz);
+    });
 } ABZ_CATCH_ALL
 
 int abz_rule_ltm_green_node_weights_ptr(const abz_rule* r, void** base, int64_t* nbytes, int* nz) try {

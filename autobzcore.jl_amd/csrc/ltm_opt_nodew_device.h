@@ -1,9 +1,10 @@
 // Optimized tetrahedron method (gfx950 only): what the two producers of node weights of the optimized rule share -- the real
 // weights w_b(k; E) of kernels_ltm_opt_nodew.hip and the complex weights W_b(k; z) of kernels_ltm_green_opt_nodew.hip.  Each
-// file has its own corner-weight kernel (A); the arguments, the sort step that carries a corner's path position, the select
-// tables of a path, the gather kernel (B: it sums any NE real sets of corner weights in one fixed order) and the slab planner of
-// the workspace are the same and stand here.  kernels_ltm_opt_nodew.hip has the definition, the layout of the workspace and
-// the reasoning about slabs.
+// file has its own corner-weight kernel (A) and its own grouping of energies or values of z; the arguments, the prologue of a
+// corner-weight kernel, the sort that carries a corner's path position and the select back to path order, the gather kernel (B:
+// it sums any NE real sets of corner weights in one fixed order), the slab planner of the workspace and the slab loop of the
+// host are the same and stand here.  The stencil addressing is OptPath of ltm_opt_device.h.  kernels_ltm_opt_nodew.hip has the
+// definition, the layout of the workspace and the reasoning about slabs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,6 +46,25 @@ __device__ __forceinline__ void optw_cx(double& ea, double& eb, int& pa, int& pb
     pb = y;
 }
 
+// the four effective corner energies of a simplex ascending, e1 <= .. <= e4, and the position in the path of each: p1 .. p4
+struct OptWSorted {
+    double e1, e2, e3, e4;
+    int p1, p2, p3, p4;
+};
+__device__ __forceinline__ OptWSorted optw_sort(const double (&e)[4]) {
+    OptWSorted s = {e[0], e[1], e[2], e[3], 0, 1, 2, 3};
+    optw_cx(s.e1, s.e2, s.p1, s.p2);
+    optw_cx(s.e3, s.e4, s.p3, s.p4);
+    optw_cx(s.e1, s.e3, s.p1, s.p3);
+    optw_cx(s.e2, s.e4, s.p2, s.p4);
+    optw_cx(s.e2, s.e3, s.p2, s.p3);
+    return s;
+}
+// back to path order: corner m of the path is the sorted corner whose position is m
+__device__ __forceinline__ double optw_of_path(const OptWSorted& s, int m, double w1, double w2, double w3, double w4) {
+    return s.p1 == m ? w1 : (s.p2 == m ? w2 : (s.p3 == m ? w3 : w4));
+}
+
 // index i - o of a periodic axis of npt >= 1 points, o in -1 .. 2
 __device__ __forceinline__ int optw_wrap_back(int i, int o, int npt) {
     int j = i - o;
@@ -54,21 +74,28 @@ __device__ __forceinline__ int optw_wrap_back(int i, int o, int npt) {
     return j;
 }
 
-// The three select tables of a path, as in ltm_opt_kernel: what the step o - 1 along the path's first, second and third axis
-// adds to the column and to the line.  j1, j2: wrapped indices of the axes 1, 2; j3: of axis 3, times npt.
-#define OPTW_TABLES(t, j1, j2, j3)                                                  \
-    const int X = (t) >> 1, Y = (X + 1 + ((t) & 1)) % 3, Z = 3 - X - Y;             \
-    int col[3][4], line[3][4];                                                      \
-    _Pragma("unroll") for (int o = 0; o < 4; ++o) {                                 \
-        col[0][o] = X == 0 ? j1[o] : 0;                                             \
-        col[1][o] = Y == 0 ? j1[o] : 0;                                             \
-        col[2][o] = Z == 0 ? j1[o] : 0;                                             \
-        line[0][o] = X == 1 ? j2[o] : (X == 2 ? j3[o] : 0);                         \
-        line[1][o] = Y == 1 ? j2[o] : (Y == 2 ? j3[o] : 0);                         \
-        line[2][o] = Z == 1 ? j2[o] : (Z == 2 ? j3[o] : 0);                         \
-    }
-#define OPTW_COL(j) (col[0][OPT_PT[j][0] + 1] + col[1][OPT_PT[j][1] + 1] + col[2][OPT_PT[j][2] + 1])
-#define OPTW_LINE(j) (line[0][OPT_PT[j][0] + 1] + line[1][OPT_PT[j][1] + 1] + line[2][OPT_PT[j][2] + 1])
+// What a thread of a corner-weight kernel (A) starts from: cell kk < a.wsplane of the workspace (column i1 of line i2 of its
+// plane q, which is grid plane cell0 + q wrapped) -> the index tables of its stencil on the grid, the eigenvalue planes of band
+// blockIdx.y (a 32-bit line stride: the host checks that it fits) and where its corner weights go: plane [t 4 + m] of set s of
+// this band is out[(s 24 + t 4 + m) wsplane], `sets` sets per band.  The arguments come by value: by reference
+// ltm_green_opt_cornerw_kernel<1> compiles to 34 SGPR spills instead of 26 (profiles/ltm_opt_shared_stencil_isa_vs_parent.txt).
+struct OptWCell {
+    int j1[4], j2[4], j3[4];
+    const double* Eb;
+    int tileE;
+    double* out;
+};
+__device__ __forceinline__ OptWCell optw_cell(OptWArgs a, int64_t kk, int sets) {
+    const LtmCell cell = ltm_cell<3>(kk, a.npt);
+    int i3 = a.cell0 + cell.i3;
+    i3 -= i3 >= a.npt ? a.npt : 0;
+    OptWCell c;
+    opt_tables(cell.i1, cell.i2, i3, a.npt, c.j1, c.j2, c.j3);
+    c.Eb = a.E.base + (int64_t)blockIdx.y * a.E.pitch;
+    c.tileE = (int)a.E.tile;
+    c.out = a.C + (int64_t)blockIdx.y * sets * 24 * a.wsplane + kk;
+    return c;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // B: the node's weight, gathered from the corner weights of the simplices whose stencil holds it
@@ -105,11 +132,11 @@ __global__ __launch_bounds__(256) void ltm_opt_nodew_gather_kernel(OptWArgs a) {
     for (int i = 0; i < NE; ++i) acc[i] = 0.0;
 #pragma unroll 1
     for (int tt = 0; tt < 6; ++tt) {
-        OPTW_TABLES(tt, j1, j2, j3)
+        const OptPath path(tt, j1, j2, j3);
         const double* __restrict__ const Ct = Cb + (int64_t)(tt * 4) * a.wsplane;
 #pragma unroll
         for (int j = 0; j < OPT_NPT; ++j) {
-            const double* __restrict__ const Cj = Ct + ((int64_t)OPTW_LINE(j) * npt + OPTW_COL(j));
+            const double* __restrict__ const Cj = Ct + ((int64_t)path.line_of(j) * npt + path.col_of(j));
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 if (OPT_K[m][j] == 0) continue;
@@ -131,6 +158,36 @@ inline int optw_slab(int npt, int n, int sets, int64_t mb) {
 }
 // cell planes in the workspace of a slab of S node planes
 inline int optw_planes_of(int npt, int S) { return S + 3 >= npt ? npt : S + 3; }
+// the cap of the workspace, MB
+inline int64_t optw_cap_mb() { return abz_switch(SW_LTM_OPTW_CHUNK_MB) > 0 ? abz_switch(SW_LTM_OPTW_CHUNK_MB) : 256; }
+// bytes of workspace that a group of `sets` real weight sets asks for
+inline size_t optw_need(int npt, int n, int sets) {
+    return sizeof(double) * 24 * (size_t)n * (size_t)sets * (size_t)optw_planes_of(npt, optw_slab(npt, n, sets, optw_cap_mb())) * (size_t)npt * (size_t)npt;
+}
+
+// THE slab loop: one group of `sets` real weight sets, slab after slab -- the corner weights of a slab's cells into the workspace
+// a.C (at least optw_need(npt, n, sets) bytes), then the gather into the slab's node planes of a.W.  Of `a` everything but the
+// slab's own fields is set by the caller: E, W, C, npt, n, weight, and of the group Es and plane0.  Launches only.
+using OptWFn = void (*)(OptWArgs);
+inline int optw_run_group(abz_ctx* ctx, OptWArgs& a, int sets, OptWFn corner, OptWFn gather) {
+    const int npt = a.npt;
+    const int64_t cells = (int64_t)npt * npt;  // of a plane
+    const int S = optw_slab(npt, a.n, sets, optw_cap_mb());
+    const bool whole = S + 3 >= npt;
+    for (int s0 = 0; s0 < npt; s0 += whole ? npt : S) {
+        a.node0 = s0;
+        a.nnode = whole ? npt : std::min(S, npt - s0);
+        a.nplanes = whole ? npt : a.nnode + 3;
+        a.wrap3 = whole;
+        a.cell0 = whole ? 0 : (s0 + npt - 2) % npt;  // (S + 3 < npt here: npt >= 5)
+        a.wsplane = (int64_t)a.nplanes * cells;
+        launch(ctx, corner, dim3((unsigned)cdiv64(a.wsplane, 256), (unsigned)a.n), dim3(256), 0, a);
+        ABZ_HIP(hipGetLastError());
+        launch(ctx, gather, dim3((unsigned)cdiv64((int64_t)a.nnode * npt * a.W.row, 256), (unsigned)a.n), dim3(256), 0, a);
+        ABZ_HIP(hipGetLastError());
+    }
+    return ABZ_OK;
+}
 
 }  // namespace
 

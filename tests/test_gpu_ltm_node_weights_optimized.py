@@ -1,5 +1,5 @@
 """Integration weights of the optimized tetrahedron method on the device (abz_rule_ltm_node_weights_optimized;
-ltm_opt_cornerw_kernel and ltm_opt_nodew_gather_kernel of kernels_ltm_opt_nodew.hip) against the scatter-form restatement of
+ltm_opt_cornerw_kernel of kernels_ltm_opt_nodew.hip, ltm_opt_nodew_gather_kernel of ltm_opt_nodew_device.h) against the scatter-form restatement of
 tests/optnodew_numpy.py, against the shipped scans of abz_rule_ltm_optimized, and their exact values, repeatability, slabs,
 consumers (dot, fold, density matrix), lifetime and refusals.
 
